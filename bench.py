@@ -18,7 +18,20 @@ external launcher it checks that WORLD_SIZE == --gpus.
     64 x 11 lnZ_* units (64 x 18 scenarios) are dealt to the ranks by cost (LPT), every rank draws
     and evaluates its own units, ONE all_gather assembles all tables (strong scaling).
 
-One JSON line on rank 0 (contract in the task statement) with these extra objects:
+A plain run sets up, warms up, times the --steps steps and prints one JSON line on rank 0: metric, value,
+unit, higher_is_better, dtype, ms_per_step (wall-clock of one timed step), config, and a `roofline` object
+priced from the timed launches alone (one model evaluation per cell: a lower bound).  --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy (float64; inputs are seeded, so two builds
+can be compared output for output):
+  grid   lnZ.npy       the lnZ vector the step returns (18 families per rank, gathered over the ranks)
+         halfchi2.npy  (18, n_samples) chi^2/2 of rank 0's rows, one row per family (past 60 MB of data: a
+                       fixed sample of the columns, their indices in halfchi2_columns.npy)
+  batch  lnZ.npy, prob.npy  every target's scenario evidences and probabilities, concatenated in target order
+         FPP.npy, NFPP.npy  one value per target
+Every file holds finite numbers: an output with non-finite entries (halfchi2: +inf for the rows lnL_EB_p's
+secondary-eclipse rule excludes) has them as 0, and <name>_nonfinite.npy says which and what they were
+
+--full adds everything else the line can carry, measured after the timed steps (grid mode):
   roofline     dominant kernel = the fused likelihood kernel; it is fp64-VALU bound, not HBM/MFMA
                (SURVEY.md 8d).  achieved = EXECUTED model evaluations (the kernel's own census,
                measured in this run) x the plain operation count of one evaluation / mean launch
@@ -41,6 +54,8 @@ One JSON line on rank 0 (contract in the task statement) with these extra object
   e2e          end-to-end calc_probs() wall-clock (the second half of the BASELINE metric) on
                TOI-465.01 (BASELINE configs[2]: real light curve + contrast curve, 1 + 20 stars,
                75 scenarios, N = 1e6): the default sampling mode (device) first, then the validation modes.
+  batch        the configs[3] step (see --mode batch) at --tois x --batch-n, timed in the same job.
+The --no-* and --pmc options switch single legs of --full off.
 """
 import argparse
 import csv
@@ -99,6 +114,11 @@ def parse():
                     help="switch the reduced-node exposure average off for the timed steps")
     ap.add_argument("--fp32-model", action="store_true",
                     help="BASELINE config 5: fp32 Mandel-Agol arithmetic, fp64 orbit/chi^2/log-mean-exp")
+    ap.add_argument("--full", action="store_true",
+                    help="grid mode: also measure the legs beside the headline (PMC traffic, census, shapes, HBM kernels, "
+                         "the `batch` object, CPU baseline, e2e); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, rank 0)")
     return ap.parse_args()
 
 
@@ -196,6 +216,41 @@ def collect_pmc(args):
                       "bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 (gfx950 read-side factor, MI355X_MICROARCH.md)"}
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6         # array data: with the .npy headers, under 64 MB in all
+
+
+def _finite_parts(name, a):
+    """{name: a} when every entry is finite, else {name: a with its non-finite entries as 0, name_nonfinite: 0 where a is
+    finite, +1 / -1 where it is +inf / -inf (a row excluded by lnL_EB_p's secondary-eclipse rule, a scenario without
+    evidence), 2 where it is NaN}: every file a dump writes holds finite numbers, and nothing of the output is lost"""
+    fin = np.isfinite(a)
+    if fin.all():
+        return {name: a}
+    return {name: np.where(fin, a, 0.0), name + "_nonfinite": np.where(fin, 0.0, np.where(np.isnan(a), 2.0, np.sign(a)))}
+
+
+def dump_outputs(dirname, arrays, wide_name=None, wide=None):
+    """--dump-outputs: DIR/<name>.npy in float64 for every array (non-finite entries: _finite_parts).  `wide` (rows x
+    columns) is written whole while all files fit in DUMP_LIMIT_BYTES, otherwise as a fixed, seeded sample of its
+    columns (sorted; their indices in DIR/<wide_name>_columns.npy): the same arguments give the same columns"""
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for k, v in arrays.items():
+        out.update(_finite_parts(k, np.asarray(v, dtype=np.float64)))
+    if wide is not None:
+        wide = np.asarray(wide, dtype=np.float64)
+        copies = 1 if np.isfinite(wide).all() else 2          # the values and their _nonfinite companion
+        room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values())
+        if copies * wide.nbytes > room:
+            cols = np.sort(np.random.default_rng(0).choice(wide.shape[1], room // (8 * (copies * wide.shape[0] + 1)),
+                                                           replace=False))
+            out[wide_name + "_columns"] = cols.astype(np.float64)
+            wide = wide[:, cols]
+        out.update(_finite_parts(wide_name, wide))
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def committed_traffic(n_time, n_rows):
     path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
     if not os.path.exists(path):
@@ -217,7 +272,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
     traffic = None
     if world == 1 and args.mode == "grid" and extras and args.pmc == "auto":
         try:
@@ -451,13 +506,15 @@ def run_grid(ctx):
     elapsed = _max_over_ranks(ctx, time.perf_counter() - t0)
 
     lnz_host = lnz_all.cpu().numpy()
+    if args.dump_outputs and rank == 0:          # before the --full legs, which reuse h_d and lnz_all
+        dump_outputs(args.dump_outputs, {"lnZ": lnz_host}, "halfchi2", np.stack([h.cpu().numpy() for h in h_d]))
     evals_per_step_per_gpu = float(n_time) * n_rows * len(fams)
     value = evals_per_step_per_gpu * world * args.steps / elapsed
     kern_ms = np.array([[a.elapsed_time(b) for (a, b) in ev[s]] for s in range(args.steps)])
     mean_launch_s = float(kern_ms.mean()) * 1e-3
     # the configs[3] step in the same job, on every rank count (collective inside: all ranks take part)
     batch = None
-    if not args.no_batch_leg:
+    if args.full and not args.no_batch_leg:
         try:
             batch = batch_object(ctx)
         except Exception as exc:                  # the grid line stands on its own (a failure here is the same on
@@ -541,7 +598,7 @@ def run_grid(ctx):
                     % (int(F_ORBIT + F_MA), synth.NSAMPLES))
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(t, flux, rows_h, fams, args.cpu_seconds)
     e2e = None
     if ctx["extras"] and not args.no_e2e and world == 1:
@@ -760,6 +817,10 @@ def run_batch(ctx):
 
     elapsed, out, jobs, timing = batch_leg(ctx, args.tois, args.batch_n, args.n_time, args.steps, args.warmup,
                                            before_timed=clear_counters)
+    if args.dump_outputs and rank == 0:          # before the traced step below, which updates the targets in place
+        dump_outputs(args.dump_outputs, {"lnZ": np.concatenate([tg.lnZ for tg in out]),
+                                         "prob": np.concatenate([tg.probs["prob"].to_numpy() for tg in out]),
+                                         "FPP": [float(tg.FPP) for tg in out], "NFPP": [float(tg.NFPP) for tg in out]})
 
     def step(js, seed):
         np.random.seed(seed)

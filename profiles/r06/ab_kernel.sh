@@ -7,7 +7,7 @@ T=$1; shift
 for rep in 1 2; do
 for L in "$@"; do
   P=$R/profiles/ab_libs/$L; [ "$L" = tree ] && P=$R/triceratops_amd/libtrx.so
-  TRX_LIB=$P python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-e2e --no-batch-leg --pmc off 2>/dev/null | tail -1 > $O/ab_${T}_${L}_$rep.json
+  TRX_LIB=$P python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-e2e --no-batch-leg --pmc off 2>/dev/null | tail -1 > $O/ab_${T}_${L}_$rep.json
   python - <<PY
 import json
 d=json.load(open("$O/ab_${T}_${L}_$rep.json"))

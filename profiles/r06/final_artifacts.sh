@@ -5,11 +5,11 @@ T=$1
 O=$R/gpurun_out/r06
 mkdir -p $O
 cd $R
-python bench.py > $O/${T}_bench.out 2> $O/${T}_bench.err; tail -1 $O/${T}_bench.out > $O/${T}_bench.json
-python bench.py --fp32-model --no-cpu-baseline --no-e2e 2>> $O/${T}_bench.err | tail -1 > $O/${T}_bench_fp32.json
+python bench.py --full > $O/${T}_bench.out 2> $O/${T}_bench.err; tail -1 $O/${T}_bench.out > $O/${T}_bench.json
+python bench.py --full --fp32-model --no-cpu-baseline --no-e2e 2>> $O/${T}_bench.err | tail -1 > $O/${T}_bench_fp32.json
 python bench.py --mode batch 2>> $O/${T}_bench.err | tail -1 > $O/${T}_bench_batch.json
 # the same line under an external launcher with ONE rank (the RCCL group of torchrun's environment)
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --pmc off 2>> $O/${T}_bench.err | grep '^{' | tail -1 > $O/${T}_bench_torchrun1.json
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 3 --warmup 1 --full --no-cpu-baseline --no-e2e --pmc off 2>> $O/${T}_bench.err | grep '^{' | tail -1 > $O/${T}_bench_torchrun1.json
 export TRX_TESTING=1      # the scripts below drive switches of include/trx_debug.h: the testing library
 python profiles/r05/batch_timing.py > $O/${T}_batch_timing.txt 2>&1
 python profiles/r05/e2e_timing.py > $O/${T}_e2e_timing.txt 2>&1

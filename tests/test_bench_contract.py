@@ -8,10 +8,11 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--n-samples", "2048", "--n-time", "256", "--steps", "2", "--warmup", "1", "--no-e2e",
+SMALL = ["--full", "--n-samples", "2048", "--n-time", "256", "--steps", "2", "--warmup", "1", "--no-e2e",
          "--tois", "4", "--batch-n", "50000"]          # (the `batch` object of the line at a reduced size)
 
 
@@ -39,6 +40,37 @@ def _check_common(d, n_gpus):
     assert b["n_gpus"] == n_gpus and b["scaling"] == "strong" and b["ms_per_step"] > 0
     for k in ("prepare_s", "enqueue_s", "wait_s", "gather_s", "finish_s", "other_s", "host_path_s"):
         assert len(b["per_rank"][k]) == n_gpus, k
+
+
+def test_dump_outputs_keeps_a_fixed_sample_past_the_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files; a wide output past the cap is cut to the same seeded columns in every run"""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8000)
+    wide = np.arange(18 * 1000, dtype=np.float32).reshape(18, 1000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"lnZ": np.ones(18)}, "halfchi2", wide)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["halfchi2.npy", "halfchi2_columns.npy", "lnZ.npy"]
+    got = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 8000
+    cols = got["halfchi2_columns.npy"]
+    assert cols.size > 0 and np.all(np.diff(cols) > 0)
+    assert np.array_equal(got["halfchi2.npy"], wide[:, cols.astype(np.int64)])
+    assert np.array_equal(cols, np.load(tmp_path / "b" / "halfchi2_columns.npy"))
+    bench.dump_outputs(str(tmp_path / "c"), {}, "halfchi2", wide[:, :10])       # under the cap: written whole
+    assert os.listdir(tmp_path / "c") == ["halfchi2.npy"]
+    assert np.array_equal(np.load(tmp_path / "c" / "halfchi2.npy"), wide[:, :10])
+    # non-finite entries: every file finite, the output recoverable from the value and its _nonfinite companion
+    odd = np.array([[1.5, np.inf, -np.inf], [np.nan, 0.25, np.inf]])
+    bench.dump_outputs(str(tmp_path / "d"), {"lnZ": [-2.0, -np.inf]}, "halfchi2", odd)
+    got = {n[:-4]: np.load(tmp_path / "d" / n) for n in os.listdir(tmp_path / "d")}
+    assert sorted(got) == ["halfchi2", "halfchi2_nonfinite", "lnZ", "lnZ_nonfinite"]
+    assert all(np.isfinite(a).all() and a.dtype == np.float64 for a in got.values())
+    kind = {0.0: np.nan, 1.0: np.inf, -1.0: -np.inf, 2.0: np.nan}
+    for name, want in (("halfchi2", odd), ("lnZ", np.array([-2.0, -np.inf]))):
+        back = np.where(got[name + "_nonfinite"] == 0, got[name], np.vectorize(kind.get)(got[name + "_nonfinite"]))
+        assert np.array_equal(back, want, equal_nan=True), name
 
 
 def test_gpus_flag_must_agree_with_the_launcher():
@@ -85,6 +117,37 @@ def test_single_gpu_line():
         assert r["traffic"] > 0.5 * r["algorithmic_bytes_per_launch"]
     for k in ("chi2_grid_kernel", "lme_partial_kernel"):
         assert 0 < d["kernels"][k]["frac"] < 1
+
+
+@pytest.mark.gpu
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """without --full: the headline of the timed steps and nothing measured beside it; --dump-outputs writes what the
+    last timed step computed"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n-samples", "2048", "--n-time", "256",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _last_json(p.stdout)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["unit"] == "evals/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 256 * 2048 * 18 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-9
+    for k in ("batch", "cpu_baseline", "e2e", "shapes"):
+        assert d[k] is None, k
+    assert d["kernels"] == {} and d["roofline"]["traffic"] is None
+    names = sorted(os.listdir(tmp_path))
+    assert {"halfchi2.npy", "lnZ.npy"} <= set(names) <= {"halfchi2.npy", "halfchi2_nonfinite.npy", "lnZ.npy",
+                                                         "lnZ_nonfinite.npy"}
+    got = {n[:-4]: np.load(tmp_path / n) for n in names}
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in got.values()), names
+    lnz, h = got["lnZ"], got["halfchi2"]
+    lnz_fin = got.get("lnZ_nonfinite", np.zeros_like(lnz)) == 0
+    h_kind = got.get("halfchi2_nonfinite", np.zeros_like(h))
+    assert lnz.shape == (18,) and lnz_fin.any()
+    assert d["lnZ_checksum"] == float(np.nansum(lnz[lnz_fin]))
+    assert h.shape == h_kind.shape == (18, 2048)
+    # chi^2 / 2 of every row the step evaluated; +inf (kind 1) only where lnL_EB_p's secondary-eclipse rule excludes
+    assert set(np.unique(h_kind)) <= {0.0, 1.0} and (h_kind == 0).mean() > 0.5 and np.all(h[h_kind == 0] >= 0.0)
+    assert np.all(h[h_kind != 0] == 0.0)
 
 
 @pytest.mark.gpu

@@ -100,7 +100,7 @@ def test_bench_under_an_external_launcher_with_one_rank():
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port),
                         os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--n-samples", "4000",
-                        "--no-cpu-baseline", "--no-extras", "--pmc", "off", "--tois", "4", "--batch-n", "50000"],
+                        "--full", "--no-cpu-baseline", "--no-extras", "--pmc", "off", "--tois", "4", "--batch-n", "50000"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
