@@ -94,6 +94,13 @@ extern "C" {
                                         light curves of fewer than 48 points are always evaluated in full;
                                         trx_pruned_rows counts the abandoned draws.  The per-row entry points
                                         (trx_lnl_batch, trx_lnz_scenario ...) always return the full chi^2. */
+#define TRX_FLAG_WEIGHT_MOMENTS    256 /* trx_scenario_enqueue / trx_scenario_evidence / trx_star_enqueue: a branch record
+                                        is TRX_SCENARIO_OUT_MOMENTS doubles wide -- the TRX_SCENARIO_OUT of today, then
+                                        [18] lnM2 and [19] lnWmax of the evidence's weights (the definitions and special
+                                        cases of trx_lnz_moments_from_halfchi2; both NaN when [17] status is 1) -- and
+                                        the record of a call 2 * TRX_SCENARIO_OUT_MOMENTS + 1 doubles.  Every other slot,
+                                        lnZ and the best draw are the same bits with and without the flag.  Calls with
+                                        and without it may share a launch chain (each keeps its own record width). */
 
 /* parameter-block rows, SoA [n_param][n] contiguous fp64 (reference argument order):
  *   TP  (10): R_p[R_earth] P_orb[d] inc[deg] a[cm] R_s[R_sun] u1 u2 ecc argp[deg] companion_fluxratio
@@ -138,7 +145,7 @@ int trx_flux_grid(int model, int flags,
 int trx_chi2_grid(const double* flux, const double* model_grid, int n_time, long n, double sigma,
                   double* out_halfchi2, void* stream);
 
-/* Bytes of device scratch the reductions below need (a small constant). */
+/* Bytes of device scratch the reductions below need (a small constant: 64 KiB). */
 size_t trx_workspace_bytes(void);
 
 /* Replaces _log_mean_exp(logw, N_total=...) (_numerics.py:12-51): log(mean(exp(logw))) with
@@ -166,6 +173,19 @@ int trx_lnz_scenario(int model, int flags,
 int trx_lnz_from_halfchi2(const double* halfchi2, const double* lnprior, long n, long n_total,
                           double lnsigma, double* out_lnz,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* trx_lnz_from_halfchi2 with the Monte-Carlo moments of the same weights w_i = exp(lnL_i [+ lnprior_i]), one pass:
+ *   out[0]  lnZ    = log(sum w / n_total): trx_lnz_from_halfchi2's value bit for bit (same partition, same fold)
+ *   out[1]  lnM2   = log(sum w^2 / n_total), the log of the mean squared weight (the zero weights count in n_total)
+ *   out[2]  lnWmax = log(max w / sum w), the largest single weight's share of the evidence (<= 0)
+ * so that the effective sample size is (sum w)^2 / sum w^2 = n_total * exp(2 lnZ - lnM2) and the standard error of lnZ
+ * sqrt(1 / ess - 1 / n_total).  Special cases: any +inf term -> lnZ = +inf, lnM2 = lnWmax = NaN; no finite term (or
+ * n = 0) -> lnZ = lnM2 = -inf, lnWmax = NaN.  (In a record of TRX_FLAG_WEIGHT_MOMENTS a branch whose status is 1 --
+ * a row no pass wrote -- has lnZ = lnM2 = lnWmax = NaN.)  Terms more than 80 below the largest are left out of both
+ * sums, as of lnZ's.  out: 3 doubles (device). */
+int trx_lnz_moments_from_halfchi2(const double* halfchi2, const double* lnprior, long n, long n_total,
+                                  double lnsigma, double* out, void* workspace, size_t workspace_bytes,
+                                  void* stream);
 
 /* Host-pointer conveniences: stage host buffers to the current device, run the kernels above,
  * copy back and synchronise.  For callers without a device allocator (a ctypes binding on
@@ -303,7 +323,8 @@ size_t trx_draw_args_size(void);   /* sizeof(trx_draw_args): lets a foreign bind
  * scenarios two (q < 0.95 at P_orb, q >= 0.95 at 2 P_orb).
  *   draw      as for trx_draw_scenario; its output pointers (cols, mask, mask_twin, lnprior, flag,
  *             dump) are ignored: the buffers are stream-ordered scratch of the call
- *   out       HOST, [branches][TRX_SCENARIO_OUT]: the best draw's columns (11 or 14, the layout
+ *   out       HOST, [branches][TRX_SCENARIO_OUT] ([branches][TRX_SCENARIO_OUT_MOMENTS] with TRX_FLAG_WEIGHT_MOMENTS):
+ *             the best draw's columns (11 or 14, the layout
  *             of trx_draw_args.cols; draw 0 when no draw passes the mask), then lnZ, then the
  *             number of draws that passed the mask; [16] the number of masked draws that hold the smallest
  *             chi^2 (> 1: the best draw is the FIRST of an exact tie -- numpy's argmin; the reference's
@@ -315,6 +336,7 @@ size_t trx_draw_args_size(void);   /* sizeof(trx_draw_args): lets a foreign bind
  * read them from device memory and their grids are sized for a guess), so trx_scenario_evidence is the
  * enqueue below followed by ONE hipStreamSynchronize, after which `out` is filled. */
 #define TRX_SCENARIO_OUT 18
+#define TRX_SCENARIO_OUT_MOMENTS 20  /* with TRX_FLAG_WEIGHT_MOMENTS: + [18] lnM2, [19] lnWmax */
 typedef struct {
     const trx_draw_args* draw;
     const double* time;          /* [n_time] device */
@@ -345,7 +367,8 @@ typedef struct {
 int trx_scenario_evidence(const trx_scenario_args* args, void* stream);
 /* The same call without the final synchronisation: everything is enqueued on `stream` and the function
  * returns.  args->out / args->out_flag are ignored; the record arrives in
- *   out   HOST, [2 * TRX_SCENARIO_OUT + 1] doubles: the branch records as above, then the flag as a double.
+ *   out   HOST, [2 * TRX_SCENARIO_OUT + 1] doubles: the branch records as above, then the flag as a double
+ *         ([2 * TRX_SCENARIO_OUT_MOMENTS + 1] with TRX_FLAG_WEIGHT_MOMENTS in args->flags).
  * Give pinned memory (hipHostMalloc / torch pin_memory) so that the copy is asynchronous; `out` is valid once
  * the stream has passed the call (hipStreamSynchronize, an event).  `args` and everything it points to on the
  * host may be reused as soon as the function returns; the device tables it names must stay alive until the
@@ -359,7 +382,8 @@ size_t trx_scenario_args_size(void);
  * trx_scenario_enqueue(&calls[i], out[i], streams[i]) for i = 0 .. n_calls - 1, in that order.  A host binding
  * builds the argument blocks of a star once and crosses the FFI once instead of ten times.
  *   calls    HOST, [n_calls]
- *   out      HOST, [n_calls] pointers to pinned records of 2 * TRX_SCENARIO_OUT + 1 doubles
+ *   out      HOST, [n_calls] pointers to pinned records of 2 * TRX_SCENARIO_OUT + 1 doubles (of
+ *            2 * TRX_SCENARIO_OUT_MOMENTS + 1 for a call with TRX_FLAG_WEIGHT_MOMENTS)
  *   streams  HOST, [n_calls] hipStream_t handles (they may repeat; calls on one stream run in order)
  * Returns the status of the first call that failed (the later ones are not enqueued; *n_done, if given, receives
  * the number of calls that were). */

@@ -22,13 +22,16 @@ MODEL_TP, MODEL_EB, MODEL_EB_TWIN, MODEL_RAW = 0, 1, 2, 3
 FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, FLAG_FP32_MODEL, FLAG_EVALUATE_EXCLUDED = 1, 2, 4, 8
 # result-neutral per-call choices (include/trx.h)
 FLAG_ALL_SUBEXPOSURES, FLAG_NO_STENCIL, FLAG_COUNT_EVALUATIONS, FLAG_FULL_EVALUATION = 16, 32, 64, 128
+# scenario records carry lnM2 and lnWmax of the evidence's weights (include/trx.h)
+FLAG_WEIGHT_MOMENTS = 256
 N_PARAM = {MODEL_TP: 10, MODEL_EB: 11, MODEL_EB_TWIN: 11, MODEL_RAW: 9}
 ERR_NTOTAL = 4
 
 # every symbol include/trx.h declares (tests check that libtrx.so exports all of them and nothing of trx_debug.h)
 ABI_SYMBOLS = (
     "trx_lnl_batch", "trx_flux_grid", "trx_chi2_grid", "trx_workspace_bytes",
-    "trx_log_mean_exp", "trx_lnz_scenario", "trx_lnz_from_halfchi2", "trx_lnl_batch_host", "trx_flux_grid_host",
+    "trx_log_mean_exp", "trx_lnz_scenario", "trx_lnz_from_halfchi2", "trx_lnz_moments_from_halfchi2",
+    "trx_lnl_batch_host", "trx_flux_grid_host",
     "trx_log_mean_exp_host", "trx_skipped_rows", "trx_pruned_rows",
     "trx_draw_scenario", "trx_draw_args_size", "trx_scenario_evidence", "trx_scenario_enqueue", "trx_star_enqueue",
     "trx_scenario_args_size", "trx_release_scratch", "trx_version", "trx_last_error", "trx_device_count",
@@ -155,6 +158,8 @@ def _load(path, testing):
                                    c_int, _vp, c_long, c_double, _vp, _vp, _vp, c_size_t, _vp]
     L.trx_lnz_from_halfchi2.restype = c_int
     L.trx_lnz_from_halfchi2.argtypes = [_vp, _vp, c_long, c_long, c_double, _vp, _vp, c_size_t, _vp]
+    L.trx_lnz_moments_from_halfchi2.restype = c_int
+    L.trx_lnz_moments_from_halfchi2.argtypes = [_vp, _vp, c_long, c_long, c_double, _vp, _vp, c_size_t, _vp]
     L.trx_lnl_batch_host.restype = c_int
     L.trx_lnl_batch_host.argtypes = [c_int, c_int, _vp, _vp, c_int, c_double, _vp, c_long,
                                      c_double, c_int, _vp]
@@ -456,3 +461,56 @@ def lnz_from_halfchi2(h_d, lnprior_d, n_total, lnsigma):
                                           out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
                                           _stream(h_d)))
     return out
+
+
+def lnz_moments_from_halfchi2(h_d, lnprior_d, n_total, lnsigma):
+    """(lnZ, lnM2, lnWmax) as a 3-element device tensor from device chi^2/2 values of the masked draws
+    (trx_lnz_moments_from_halfchi2: lnZ is lnz_from_halfchi2's value bit for bit)."""
+    require_gpu()
+    device = h_d.device
+    out = torch.empty(3, dtype=torch.float64, device=device)
+    ws = workspace(device)
+    with torch.cuda.device(device):
+        check(lib().trx_lnz_moments_from_halfchi2(h_d.data_ptr() if h_d.numel() else None,
+                                                  lnprior_d.data_ptr() if lnprior_d is not None else None,
+                                                  h_d.numel(), int(n_total), float(lnsigma),
+                                                  out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                                  _stream(h_d)))
+    return out
+
+
+# The Monte-Carlo moments (lnM2, lnWmax) of the branches a lnZ_* call evaluates, on their way to sharding.run_units
+# without entering the call's result dicts: run_units opens a sink on each thread that evaluates its units (when
+# fused.MOMENTS is on), the evidence paths that are not the library's deferred records (the numpy mode, the operator
+# chain, a call resolved at once) append one pair per branch, in branch order, and run_units takes a unit's pairs as
+# the part of the list its call appended (moments_mark / moments_since).  An open sink is also what makes a native call
+# ask the library for the moments.  Thread-local: the worker threads of run_units each have their own.
+_moments_tls = threading.local()
+
+
+def moments_swap(sink):
+    """opens ([]) or closes (None) this thread's sink; returns the one it replaces"""
+    old = getattr(_moments_tls, "sink", None)
+    _moments_tls.sink = sink
+    return old
+
+
+def moments_mark():
+    sink = getattr(_moments_tls, "sink", None)
+    return None if sink is None else len(sink)
+
+
+def moments_since(mark):
+    """the pairs appended since moments_mark() returned `mark`"""
+    sink = getattr(_moments_tls, "sink", None)
+    return [] if sink is None or mark is None else sink[mark:]
+
+
+def moments_wanted():
+    return getattr(_moments_tls, "sink", None) is not None
+
+
+def moments_emit(lnm2, lnwmax):
+    sink = getattr(_moments_tls, "sink", None)
+    if sink is not None:
+        sink.append((float(lnm2), float(lnwmax)))

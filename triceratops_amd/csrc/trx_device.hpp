@@ -1101,21 +1101,46 @@ __device__ __forceinline__ double exposure_flux(const RowC& c, const Limb& L, do
 }
 
 // ---------------------------------------------------------------------------------------
-// log-mean-exp partial state: running max m (finite or -inf), s = sum exp(x - m), pinf = saw +inf.
-// NaN and -inf carry zero weight (_numerics.py:48).
+// log-mean-exp partial state: running max m (finite or -inf), s = sum exp(x - m), pinf = saw +inf,
+// s2 = sum exp(2 (x - m)) over the same terms (the second moment of the weights: TRX_FLAG_WEIGHT_MOMENTS).
+// NaN and -inf carry zero weight (_numerics.py:48).  s2 rides along: nothing that produces m or s reads it.
 struct Lme {
     double m, s;
     int pinf;
+    double s2;
 };
 
 __device__ __forceinline__ void lme_merge(Lme& a, const Lme& b)
 {
     a.pinf |= b.pinf;
     if (b.m == -INFINITY) return;
-    if (a.m == -INFINITY) { a.m = b.m; a.s = b.s; return; }
-    if (b.m > a.m) { a.s = fma(a.s, exp(a.m - b.m), b.s); a.m = b.m; }
-    else           { a.s = fma(b.s, exp(b.m - a.m), a.s); }
+    if (a.m == -INFINITY) { a.m = b.m; a.s = b.s; a.s2 = b.s2; return; }
+    if (b.m > a.m) { const double e = exp(a.m - b.m); a.s = fma(a.s, e, b.s); a.s2 = fma(a.s2, e * e, b.s2); a.m = b.m; }
+    else           { const double e = exp(b.m - a.m); a.s = fma(b.s, e, a.s); a.s2 = fma(b.s2, e * e, a.s2); }
 }
+
+// the shuffle of a whole state (the butterflies of the wave combines)
+__device__ __forceinline__ Lme lme_shfl_xor(const Lme& t, int o)
+{
+    Lme r;
+    r.m = __shfl_xor(t.m, o, 64);
+    r.s = __shfl_xor(t.s, o, 64);
+    r.pinf = __shfl_xor(t.pinf, o, 64);
+    r.s2 = __shfl_xor(t.s2, o, 64);
+    return r;
+}
+
+// the moments of a finished state over n_total draws (include/trx.h, trx_lnz_moments_from_halfchi2):
+// lnM2 = log(mean of the squared weights) = log(s2) + 2 m - log(n_total), lnWmax = -log(s) (the largest term's share)
+__device__ __forceinline__ void lme_moments(const Lme& t, long n_total, double& lnm2, double& lnwmax)
+{
+    if (t.pinf) { lnm2 = NAN; lnwmax = NAN; }
+    else if (t.m == -INFINITY) { lnm2 = -INFINITY; lnwmax = NAN; }
+    else { lnm2 = log(t.s2) + 2.0 * t.m - log((double)n_total); lnwmax = -log(t.s); }
+}
+
+// doubles per block partial in the reduction workspace: m, s, pinf, s2
+constexpr int kLmePart = 4;
 
 // blocks a vector of n log-weights is reduced by (the partition decides the bits of the sum)
 __host__ __device__ inline int lme_blocks(long n)
@@ -1142,12 +1167,14 @@ __device__ __forceinline__ bool argmin_before(double a, long ia, double b, long 
 //     res[ncol]       lnZ          res[ncol + 1]  the masked count
 //     res[16]         rows that hold the smallest chi^2 (> 1: the best draw is the first of an exact tie)
 //     res[17]         status: 1 = a row of the branch was never written by any likelihood pass (lnZ is NaN then)
+//     res[18], [19]   lnM2, lnWmax (f.stride == kScenRecordMoments: TRX_FLAG_WEIGHT_MOMENTS; NaN with status 1)
 //     flag_out[0]     the limb-darkening flag of the draw kernel (branch 0 writes it)
 // `res` may be pinned host memory (the record then needs no copy).  `state` is the persistent block at the head of
 // the stream's scenario scratch: [0] the counter of finished blocks, [1] the draw kernel's flag -- both are left at
 // zero for the next call (the last branch of a call clears the flag).
 constexpr int kScenRecord = 18;       // TRX_SCENARIO_OUT
-constexpr int kScenTies = 16, kScenStatus = 17;
+constexpr int kScenRecordMoments = 20;  // TRX_SCENARIO_OUT_MOMENTS
+constexpr int kScenTies = 16, kScenStatus = 17, kScenLnM2 = 18, kScenLnWmax = 19;
 struct ScenFinal {
     const int* idx;                   // the branch's list of masked draws
     const double* cols;               // [ncol][N]
@@ -1157,6 +1184,7 @@ struct ScenFinal {
                                       // position r (branch 1: N - 1 - r); 0: at their draw index idx[r]
     long N, n_total;
     int ncol, branch, last_branch;
+    int stride;                       // doubles per branch record: kScenRecord, or kScenRecordMoments (+ lnM2, lnWmax)
     double* res;                      // this branch's record
     double* flag_out;                 // where the flag goes (as a double), or null: branch 0 reads it and clears it
     unsigned* state;                  // persistent: [0] finished blocks of THIS branch, [1] the call's flag (branch 0's block)
@@ -1167,12 +1195,12 @@ __device__ __forceinline__ void scenario_final(const ScenFinal& f, const double*
                                                const long* __restrict__ pc, const long n, const int lane)
 {
     const int nparts = lme_blocks(n);
-    Lme t{-INFINITY, 0.0, 0};
+    Lme t{-INFINITY, 0.0, 0, 0.0};
     double bv = INFINITY;
     long bi = -1, bc = 0;
     if (n > 0) {
         for (int i = lane; i < nparts; i += 64) {
-            Lme o{w[3 * i], w[3 * i + 1], (int)w[3 * i + 2]};
+            Lme o{w[kLmePart * i], w[kLmePart * i + 1], (int)w[kLmePart * i + 2], w[kLmePart * i + 3]};
             lme_merge(t, o);
             const long oi = pi[i];
             if (oi >= 0) {
@@ -1184,11 +1212,7 @@ __device__ __forceinline__ void scenario_final(const ScenFinal& f, const double*
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        Lme other;
-        other.m = __shfl_xor(t.m, o, 64);
-        other.s = __shfl_xor(t.s, o, 64);
-        other.pinf = __shfl_xor(t.pinf, o, 64);
-        lme_merge(t, other);
+        lme_merge(t, lme_shfl_xor(t, o));
         const double ov = __shfl_xor(bv, o, 64);
         const long oi = __shfl_xor(bi, o, 64);
         const long oc = __shfl_xor(bc, o, 64);
@@ -1216,6 +1240,12 @@ __device__ __forceinline__ void scenario_final(const ScenFinal& f, const double*
     if (lane == 62) {
         f.res[kScenTies] = (double)bc;
         f.res[kScenStatus] = unwritten ? 1.0 : 0.0;
+    }
+    if (lane == 61 && f.stride == kScenRecordMoments) {
+        double lnm2, lnwmax;
+        lme_moments(t, f.n_total, lnm2, lnwmax);
+        f.res[kScenLnM2] = unwritten ? NAN : lnm2;
+        f.res[kScenLnWmax] = unwritten ? NAN : lnwmax;
     }
     if (lane == 63) {
         // (the flag belongs to the call: the branch that reports it -- branch 0 -- also clears it; with the branches of a

@@ -57,7 +57,7 @@ int lnl_draws(int model, int flags, const double* time, const double* flux, int 
               double lnsigma, const double** bounds_base, hipStream_t st);
 
 // First pass of the evidence and of the best-draw search over those chi^2/2 values: per-block
-// (max, sum exp, saw +inf) partials in ws[3 * 2048] and (value, position) argmin partials in
+// (max, sum exp, saw +inf, sum exp^2) partials in ws[kLmePart * 2048] and (value, position) argmin partials in
 // amin_pv / amin_pi [2048]; lme_blocks(*n_dev) of them are valid.
 // fin.state != null: the block that finishes last also folds the partials into the branch's record
 // (scenario_final, trx_device.hpp).
@@ -68,7 +68,7 @@ int lme_draws(const double* halfchi2, const double* lnprior, double lnsigma, lon
 // ---- one launch chain for several lnZ_* calls (trx_star_enqueue) -------------------------------------------------
 // A branch of a chain: what lnl_draws + lme_draws take for one branch of one call, with the branch's own scratch
 // (chain_branch_scratch_bytes(N) bytes; `scan_count` = 8 bytes that are zero before the chain's first use of them and
-// at a place nothing else ever occupies) and reduction buffers (ws [3 * 2048], amin_pv [2048], amin_pi [2 * 2048]).
+// at a place nothing else ever occupies) and reduction buffers (ws [4 * 2048], amin_pv [2048], amin_pi [2 * 2048]).
 struct ChainBranch {
     int model, flags, twin;
     const double* flux;

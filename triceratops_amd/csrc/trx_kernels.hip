@@ -570,7 +570,7 @@ int launch_rows(const RowsArgs& a0, hipStream_t st)
 }
 
 int launch_lme(const double* logw, const double* h, const double* lnprior, double c0, long n,
-               long n_total, double* out, void* workspace, size_t workspace_bytes, hipStream_t st)
+               long n_total, double* out, void* workspace, size_t workspace_bytes, hipStream_t st, int moments = 0)
 {
     if (workspace_bytes < trx_workspace_bytes() || !workspace)
         return fail(TRX_ERR_WORKSPACE, "workspace too small%s (need %ld bytes)", "", (long)trx_workspace_bytes());
@@ -583,7 +583,7 @@ int launch_lme(const double* logw, const double* h, const double* lnprior, doubl
                        vec_ok, ws, (const long*)nullptr, (const int*)nullptr, (double*)nullptr, (long*)nullptr,
                        (const double*)nullptr, ScenFinal{});
     TRX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(lme_final_kernel, dim3(1), dim3(64), 0, st, ws, blocks, n_total, out);
+    hipLaunchKernelGGL(lme_final_kernel, dim3(1), dim3(64), 0, st, ws, blocks, n_total, out, moments);
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }
@@ -990,7 +990,7 @@ int trx_chi2_grid(const double* flux, const double* model_grid, int n_time, long
     return TRX_OK;
 }
 
-size_t trx_workspace_bytes(void) { return (size_t)kLmeMaxBlocks * 3 * sizeof(double); }
+size_t trx_workspace_bytes(void) { return (size_t)kLmeMaxBlocks * kLmePart * sizeof(double); }
 
 int trx_log_mean_exp(const double* logw, long n, long n_total, double* out, void* workspace,
                      size_t workspace_bytes, void* stream)
@@ -1011,6 +1011,17 @@ int trx_lnz_from_halfchi2(const double* halfchi2, const double* lnprior, long n,
     const double c0 = -0.5 * log(kTwoPi) - lnsigma;   // marginal_likelihoods.py:130 etc.
     return launch_lme(nullptr, halfchi2, lnprior, c0, n, n_total, out_lnz, workspace,
                       workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int trx_lnz_moments_from_halfchi2(const double* halfchi2, const double* lnprior, long n, long n_total,
+                                  double lnsigma, double* out, void* workspace, size_t workspace_bytes,
+                                  void* stream)
+{
+    if (!out || n < 0 || (n > 0 && !halfchi2)) return fail(TRX_ERR_ARG, "bad argument%s", "", 0);
+    if (n_total < n || n_total < 1) return fail(TRX_ERR_NTOTAL, "n_total must be >= n%s (n=%ld)", "", n);
+    const double c0 = -0.5 * log(kTwoPi) - lnsigma;   // (the partition and the fold of trx_lnz_from_halfchi2)
+    return launch_lme(nullptr, halfchi2, lnprior, c0, n, n_total, out, workspace, workspace_bytes,
+                      static_cast<hipStream_t>(stream), 1);
 }
 
 int trx_lnz_scenario(int model, int flags, const double* time, const double* flux, int n_time,

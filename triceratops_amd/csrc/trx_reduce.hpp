@@ -60,7 +60,8 @@ __device__ __forceinline__ double lme_value(const double* logw, const double* h,
 
 // fold four values into the running (max, sum) state: one rescale, exps only for terms that can
 // reach the sum: s >= 1 always (the max contributes exp(0)), so a term with d = x - max < -80
-// is < 1.8e-35 and even 2^60 of them stay below fp64 resolution of s (also covers -inf)
+// is < 1.8e-35 and even 2^60 of them stay below fp64 resolution of s (also covers -inf).
+// s2 takes the squares of the same terms (e * e of the exp already computed; the rescale squared)
 __device__ __forceinline__ void lme_fold4(Lme& st, double x0, double x1, double x2, double x3)
 {
     double x[4] = {x0, x1, x2, x3};
@@ -76,13 +77,19 @@ __device__ __forceinline__ void lme_fold4(Lme& st, double x0, double x1, double 
     if (cm == -INFINITY) return;
     if (cm > st.m) {
         const double d = st.m - cm;
-        st.s = (d > -80.0) ? st.s * exp(d) : 0.0;
+        const double e = exp(d);
+        st.s = (d > -80.0) ? st.s * e : 0.0;
+        st.s2 = (d > -80.0) ? st.s2 * (e * e) : 0.0;
         st.m = cm;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const double d = x[u] - st.m;
-        if (d > -80.0) st.s += exp(d);
+        if (d > -80.0) {
+            const double e = exp(d);
+            st.s += e;
+            st.s2 = fma(e, e, st.s2);
+        }
     }
 }
 
@@ -103,7 +110,7 @@ __device__ __forceinline__ void lme_fold4(Lme& st, double x0, double x1, double 
 // SCEN (trx_scenario_evidence): the element count comes from the device (n_dev; the grid was sized for
 // its upper bound and the blocks beyond lme_blocks(n) leave at once), lnprior is indexed by the draw
 // (src_idx: the masked draws are not gathered), and the pass also finds the first minimum of h
-// (argmin partials behind the 3 * 2048 sums of the workspace).
+// (argmin partials in buffers of their own next to the kLmePart * 2048 partials of the sums).
 constexpr int kLmeMaxBlocks = 2048;
 // same value for the search of the smallest chi^2 (NaN equals NaN there: torch.argmin's order)
 __device__ __forceinline__ bool argmin_same(double a, double b) { return a == b || (a != a && b != b); }
@@ -129,7 +136,7 @@ __device__ __forceinline__ void lme_partial_body(const double* __restrict__ logw
                                                  const double* __restrict__ bounds_base, const ScenFinal& fin)
 {
     typedef double dvec2 __attribute__((ext_vector_type(2)));
-    Lme st{-INFINITY, 0.0, 0};
+    Lme st{-INFINITY, 0.0, 0, 0.0};
     unsigned nblocks = gridDim.x;
     // SCEN after a bounded evaluation (cells_kernel<PRUNE>): the launch header holds the largest log-weight M
     // of the call, and every term below M - 90 is taken as -inf.  Such a term carries no weight either way;
@@ -179,7 +186,11 @@ __device__ __forceinline__ void lme_partial_body(const double* __restrict__ logw
             for (int i = 0; i < kQ; ++i) {
                 if (i < qc) {
                     const double d = qbuf[i][threadIdx.x] - st.m;
-                    if (d > -80.0) st.s += exp(d);
+                    if (d > -80.0) {
+                        const double e = exp(d);
+                        st.s += e;
+                        st.s2 = fma(e, e, st.s2);
+                    }
                 }
             }
             qc = 0;
@@ -243,7 +254,9 @@ __device__ __forceinline__ void lme_partial_body(const double* __restrict__ logw
             for (int u = 1; u < kV; ++u) cm = fmax(cm, x[u]);
             if (cm > st.m) {
                 const double d = st.m - cm;
-                st.s = (d > -80.0) ? st.s * exp(d) : 0.0;
+                const double e = exp(d);
+                st.s = (d > -80.0) ? st.s * e : 0.0;
+                st.s2 = (d > -80.0) ? st.s2 * (e * e) : 0.0;
                 st.m = cm;
             }
             bool live[kV];
@@ -259,7 +272,11 @@ __device__ __forceinline__ void lme_partial_body(const double* __restrict__ logw
                 // a narrow distribution: most terms count, nothing to gain from parking them
 #pragma unroll
                 for (int u = 0; u < kV; ++u)
-                    if (live[u]) st.s += exp(x[u] - st.m);
+                    if (live[u]) {
+                        const double e = exp(x[u] - st.m);
+                        st.s += e;
+                        st.s2 = fma(e, e, st.s2);
+                    }
             } else {
                 if (__any(qc > kQ - kV)) flush();
 #pragma unroll
@@ -278,7 +295,7 @@ __device__ __forceinline__ void lme_partial_body(const double* __restrict__ logw
             }
         }
         flush();
-        if (st.m == INFINITY) { st.pinf = 1; st.m = -INFINITY; st.s = 0.0; }
+        if (st.m == INFINITY) { st.pinf = 1; st.m = -INFINITY; st.s = 0.0; st.s2 = 0.0; }
         if ((n & 1) && tid == 0) {
             if (SCEN) {
                 const double hv = h[n - 1];
@@ -304,14 +321,8 @@ __device__ __forceinline__ void lme_partial_body(const double* __restrict__ logw
     if (SCEN && unwritten) st.pinf |= 2;           // (bit 1 of the flag word travels with the partials: lme_merge ORs it)
     // wave combine (fixed butterfly order => deterministic)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        Lme other;
-        other.m = __shfl_xor(st.m, o, 64);
-        other.s = __shfl_xor(st.s, o, 64);
-        other.pinf = __shfl_xor(st.pinf, o, 64);
-        lme_merge(st, other);
-    }
-    __shared__ double sm[4], ss[4];
+    for (int o = 32; o > 0; o >>= 1) lme_merge(st, lme_shfl_xor(st, o));
+    __shared__ double sm[4], ss[4], ss2[4];
     __shared__ int sp[4];
     __shared__ double av[4];
     __shared__ long ai[4], ac[4];
@@ -326,16 +337,17 @@ __device__ __forceinline__ void lme_partial_body(const double* __restrict__ logw
         }
     }
     if ((threadIdx.x & 63) == 0) {
-        sm[wave] = st.m; ss[wave] = st.s; sp[wave] = st.pinf;
+        sm[wave] = st.m; ss[wave] = st.s; sp[wave] = st.pinf; ss2[wave] = st.s2;
         if (SCEN) { av[wave] = amin_v; ai[wave] = amin_i; ac[wave] = amin_c; }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        Lme t{sm[0], ss[0], sp[0]};
-        for (int w = 1; w < 4; ++w) { Lme o{sm[w], ss[w], sp[w]}; lme_merge(t, o); }
-        ws[3 * blockIdx.x + 0] = t.m;
-        ws[3 * blockIdx.x + 1] = t.s;
-        ws[3 * blockIdx.x + 2] = (double)t.pinf;
+        Lme t{sm[0], ss[0], sp[0], ss2[0]};
+        for (int w = 1; w < 4; ++w) { Lme o{sm[w], ss[w], sp[w], ss2[w]}; lme_merge(t, o); }
+        ws[kLmePart * blockIdx.x + 0] = t.m;
+        ws[kLmePart * blockIdx.x + 1] = t.s;
+        ws[kLmePart * blockIdx.x + 2] = (double)t.pinf;
+        ws[kLmePart * blockIdx.x + 3] = t.s2;
         if (SCEN) {
             double bv = av[0];
             long bi = ai[0], bc = ac[0];
@@ -400,29 +412,25 @@ __global__ __launch_bounds__(256) void lme_partial_kernel_star(LmeTab tab, long 
                            b.bounds_base, b.fin);
 }
 
+// moments != 0: out[1] = lnM2, out[2] = lnWmax as well (trx_lnz_moments_from_halfchi2)
 __global__ __launch_bounds__(64) void lme_final_kernel(const double* __restrict__ ws, int nparts,
-                                                       long n_total, double* __restrict__ out)
+                                                       long n_total, double* __restrict__ out, int moments)
 {
     // lane l folds partials l, l+64, ... in order, then a fixed butterfly: deterministic
-    Lme t{-INFINITY, 0.0, 0};
+    Lme t{-INFINITY, 0.0, 0, 0.0};
     for (int i = threadIdx.x; i < nparts; i += 64) {
-        Lme o{ws[3 * i], ws[3 * i + 1], ws[3 * i + 2] != 0.0};
+        Lme o{ws[kLmePart * i], ws[kLmePart * i + 1], ws[kLmePart * i + 2] != 0.0, ws[kLmePart * i + 3]};
         lme_merge(t, o);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        Lme other;
-        other.m = __shfl_xor(t.m, o, 64);
-        other.s = __shfl_xor(t.s, o, 64);
-        other.pinf = __shfl_xor(t.pinf, o, 64);
-        lme_merge(t, other);
-    }
+    for (int o = 32; o > 0; o >>= 1) lme_merge(t, lme_shfl_xor(t, o));
     if (threadIdx.x != 0) return;
     double r;
     if (t.pinf) r = INFINITY;                                   // _numerics.py:46-47
     else if (t.m == -INFINITY) r = -INFINITY;                   // :49-50
     else r = log(t.s) + t.m - log((double)n_total);             // :51
     out[0] = r;
+    if (moments) lme_moments(t, n_total, out[1], out[2]);
 }
 
 }  // namespace

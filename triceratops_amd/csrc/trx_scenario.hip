@@ -153,6 +153,9 @@ __global__ __launch_bounds__(256) void table_kernel(TableArgs t)
     }
 }
 
+// doubles per branch record: TRX_SCENARIO_OUT, or TRX_SCENARIO_OUT_MOMENTS with TRX_FLAG_WEIGHT_MOMENTS
+int record_stride(int flags) { return (flags & TRX_FLAG_WEIGHT_MOMENTS) ? TRX_SCENARIO_OUT_MOMENTS : TRX_SCENARIO_OUT; }
+
 int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
 {
     trx_draw_args d = *s->draw;
@@ -165,6 +168,7 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
     if (K > TRX_TABLE_MAX_ROWS || (K && !s->table)) return TRX_ERR_ARG;
     const int n_pad = K ? K : 1;
     const int flags = s->flags | (K ? TRX_FLAG_FULL_EVALUATION : 0);
+    const int stride = record_stride(s->flags);
     trx::StreamLock turn(st);              // the whole call is enqueued back to back on the stream's scratch
 
     // Where the record goes: straight into the caller's buffer when the device can write there (pinned host memory:
@@ -184,8 +188,8 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
                  o_prior = A.reserve(s->want_prior ? sizeof(double) * N : 0),
                  o_n = A.reserve(2 * sizeof(long)), o_cols0 = A.reserve(sizeof(double) * 16 * n_pad),
                  o_table = A.reserve(K ? sizeof(double) * 2 * TRX_TABLE_BRANCH(K) : 0),
-                 o_res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT + 1)),
-                 o_ws = A.reserve(sizeof(double) * 2 * 3 * kLmeParts), o_pv = A.reserve(sizeof(double) * 2 * kLmeParts),
+                 o_res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1)),
+                 o_ws = A.reserve(sizeof(double) * 2 * trx::kLmePart * kLmeParts), o_pv = A.reserve(sizeof(double) * 2 * kLmeParts),
                  o_pi = A.reserve(sizeof(long) * 2 * 2 * kLmeParts), o_cnt = A.reserve(sizeof(int) * 2 * trx::kDrawMaxGroups),
                  o_idx0 = A.reserve(sizeof(int) * N), o_idx1 = A.reserve(planet ? 0 : sizeof(int) * N),
                  o_h0 = A.reserve(sizeof(double) * N), o_h1 = A.reserve(planet ? 0 : sizeof(double) * N);
@@ -239,11 +243,12 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
         fin.ncol = ncol;
         fin.branch = b;
         fin.last_branch = (b == nbr - 1) ? 1 : 0;
-        fin.res = res + (size_t)b * TRX_SCENARIO_OUT;
-        fin.flag_out = (b == 0) ? res + 2 * TRX_SCENARIO_OUT : nullptr;
+        fin.stride = stride;
+        fin.res = res + (size_t)b * stride;
+        fin.flag_out = (b == 0) ? res + 2 * stride : nullptr;
         fin.state = state;
         if (int rc = trx::lme_draws(h[b], d.lnprior, s->lnsigma, N, n_dev + b, idx[b],
-                                    A.at<double>(o_ws) + (size_t)b * 3 * kLmeParts, A.at<double>(o_pv) + (size_t)b * kLmeParts,
+                                    A.at<double>(o_ws) + (size_t)b * trx::kLmePart * kLmeParts, A.at<double>(o_pv) + (size_t)b * kLmeParts,
                                     A.at<long>(o_pi) + (size_t)b * 2 * kLmeParts, bounds, fin, st))
             return bail(rc);
         if (K) {
@@ -259,7 +264,7 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
         TRXS_HIP(hipMemcpyAsync(s->table, A.at<double>(o_table), sizeof(double) * (size_t)nbr * TRX_TABLE_BRANCH(K),
                                 hipMemcpyDefault, st));
     if (!rec_dev)
-        TRXS_HIP(hipMemcpyAsync(out_host, res, sizeof(double) * (2 * TRX_SCENARIO_OUT + 1), hipMemcpyDeviceToHost, st));
+        TRXS_HIP(hipMemcpyAsync(out_host, res, sizeof(double) * (2 * stride + 1), hipMemcpyDeviceToHost, st));
     return TRX_OK;
 }
 
@@ -303,8 +308,8 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
         co[i].mask2 = A.reserve(planet ? 0 : N);
         co[i].prior = A.reserve(s.want_prior ? sizeof(double) * N : 0);
         co[i].n = A.reserve(2 * sizeof(long));
-        co[i].res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT + 1));
-        co[i].ws = A.reserve(sizeof(double) * 2 * 3 * kLmeParts);
+        co[i].res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1));
+        co[i].ws = A.reserve(sizeof(double) * 2 * trx::kLmePart * kLmeParts);
         co[i].pv = A.reserve(sizeof(double) * 2 * kLmeParts);
         co[i].pi = A.reserve(sizeof(long) * 2 * 2 * kLmeParts);
         co[i].idx[0] = A.reserve(sizeof(int) * N);
@@ -368,7 +373,7 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
             c.lnprior = d.lnprior;
             c.scratch = reinterpret_cast<double*>(A.base + o_branch + branch_bytes * (size_t)b_at);
             c.scan_count = reinterpret_cast<unsigned long long*>(head);
-            c.ws = A.at<double>(co[i].ws) + (size_t)b * 3 * kLmeParts;
+            c.ws = A.at<double>(co[i].ws) + (size_t)b * trx::kLmePart * kLmeParts;
             c.amin_pv = A.at<double>(co[i].pv) + (size_t)b * kLmeParts;
             c.amin_pi = A.at<long>(co[i].pi) + (size_t)b * 2 * kLmeParts;
             trx::ScenFinal& f = fin[b_at];
@@ -383,8 +388,9 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
             f.ncol = ncol;
             f.branch = b;
             f.last_branch = (b == nbr - 1) ? 1 : 0;
-            f.res = res + (size_t)b * TRX_SCENARIO_OUT;
-            f.flag_out = (b == 0) ? res + 2 * TRX_SCENARIO_OUT : nullptr;
+            f.stride = record_stride(s.flags);           // (per call: a chain may mix calls with and without moments)
+            f.res = res + (size_t)b * f.stride;
+            f.flag_out = (b == 0) ? res + 2 * f.stride : nullptr;
             f.state = reinterpret_cast<unsigned*>(head + 8);      // (branch 0: == state0, whose word 1 is the call's flag)
             c.fin = &f;
         }
@@ -413,7 +419,8 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
     }
     for (int i = 0; i < n; ++i)
         if (copy_back[i])
-            TRXS_HIP(hipMemcpyAsync(out[which[i]], res_of[i], sizeof(double) * (2 * TRX_SCENARIO_OUT + 1), hipMemcpyDeviceToHost, st));
+            TRXS_HIP(hipMemcpyAsync(out[which[i]], res_of[i], sizeof(double) * (2 * record_stride(calls[which[i]].flags) + 1),
+                                    hipMemcpyDeviceToHost, st));
     return TRX_OK;
 }
 
@@ -489,12 +496,12 @@ extern "C" int trx_scenario_evidence(const trx_scenario_args* s, void* stream)
     hipStream_t st = static_cast<hipStream_t>(stream);
     trx::StreamLock turn(st);              // the pinned staging record is the stream's, too
     double* pinned = nullptr;              // pinned, so that the copy is asynchronous
-    TRXS_HIP(trx::stream_scratch(st, 3, sizeof(double) * (2 * TRX_SCENARIO_OUT + 1), reinterpret_cast<void**>(&pinned)));
+    TRXS_HIP(trx::stream_scratch(st, 3, sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1), reinterpret_cast<void**>(&pinned)));
     if (int rc = enqueue(s, pinned, st)) return rc;
     TRXS_HIP(hipStreamSynchronize(st));
-    const int nbr = s->draw->planet ? 1 : 2;
-    memcpy(s->out, pinned, (size_t)nbr * TRX_SCENARIO_OUT * sizeof(double));
-    *s->out_flag = (int)pinned[2 * TRX_SCENARIO_OUT];
+    const int nbr = s->draw->planet ? 1 : 2, stride = record_stride(s->flags);
+    memcpy(s->out, pinned, (size_t)nbr * stride * sizeof(double));
+    *s->out_flag = (int)pinned[2 * stride];
     return TRX_OK;
 }
 

@@ -118,6 +118,8 @@ def _table_branch(K):
 
 SCENARIO_OUT = 18      # TRX_SCENARIO_OUT
 SCEN_TIES, SCEN_STATUS = 16, 17      # record slots: rows holding the smallest chi^2; 1 = a row was never written
+SCENARIO_OUT_MOMENTS = 20            # TRX_SCENARIO_OUT_MOMENTS: a record of TRX_FLAG_WEIGHT_MOMENTS ...
+SCEN_LNM2, SCEN_LNWMAX = 18, 19      # ... + the log mean squared weight and the largest weight's share
 # True: a lnZ_* call that only has to return its best draw (calc_probs: TABLE_ROWS == 1, device
 # generator) is ONE library call, trx_scenario_evidence; False: the chain of torch operators around
 # trx_draw_scenario / trx_lnz_scenario below (the path of the 100-row table; kept as cross-check)
@@ -125,6 +127,11 @@ NATIVE = os.environ.get("TRX_NATIVE", "1") != "0"      # TRX_NATIVE=0: A/B runs 
 # the draw kernel's fp32 pre-test of the geometry (csrc/trx_draw.hip, may_transit): the fp64 mask is evaluated
 # only for the draws it lets through.  Same masks; TRX_PRETEST=0 / PRETEST = False evaluates every draw (tests)
 PRETEST = os.environ.get("TRX_PRETEST", "1") != "0"
+# the native calls of calc_probs / calc_probs_many (sharding.run_units: a moments sink is open, _lib.moments_begin) ask
+# the library for the Monte-Carlo moments of every evidence as well (TRX_FLAG_WEIGHT_MOMENTS: records of
+# SCENARIO_OUT_MOMENTS doubles; lnZ and the best draw are the same bits either way).  False: records as before, and
+# the target's error attributes are NaN (tests)
+MOMENTS = True
 
 
 def _fn_scenario():
@@ -152,24 +159,28 @@ def _fn_scenario():
 # back: between begin_deferred() and end_deferred() a native call returns a Pending instead of its
 # result dicts, and sharding.run_units resolves them after one synchronisation per stream.
 RECORD = 2 * SCENARIO_OUT + 1      # doubles per call: two branch records + the limb-darkening flag
+RECORD_MOMENTS = 2 * SCENARIO_OUT_MOMENTS + 1      # ... of a call with TRX_FLAG_WEIGHT_MOMENTS (the slots' size)
 
 
 class Pending:
     """one trx_scenario_enqueue call whose record has not been read yet"""
 
-    def __init__(self, scen, out, stream, keep, ncol, n_time, is_host=False, table=None, table_rows=0):
+    def __init__(self, scen, out, stream, keep, ncol, n_time, is_host=False, table=None, table_rows=0,
+                 stride=SCENARIO_OUT):
         self.scen, self.out, self.stream, self.keep, self.ncol, self.n_time = scen, out, stream, keep, ncol, n_time
         self.is_host = is_host
+        self.stride = stride                                   # doubles per branch record (SCENARIO_OUT[_MOMENTS])
         self.table, self.table_rows = table, table_rows        # pinned [2][15][K + 1] block of a call with a table
 
     def result(self):
         """the call's result dict(s); the stream must have been synchronised"""
         rec = self.out.numpy()
-        if rec[2 * SCENARIO_OUT] != 0.0:
+        W = self.stride
+        if rec[2 * W] != 0.0:
             self.keep = None
             raise ValueError("can only convert an array of size 1 to a Python scalar")
         planet, ncol = bool(self.scen.a.planet), self.ncol
-        _check_status(rec[None, :], [planet])
+        _check_status(rec[None, :], [planet], W)
         with _stats_lock:
             _lib.STATS["native_calls"] += 1
         if self.replay_for_ties(rec):
@@ -178,7 +189,9 @@ class Pending:
         res = []
         K = self.table_rows
         for b in range(1 if planet else 2):
-            row = rec[b * SCENARIO_OUT:(b + 1) * SCENARIO_OUT]
+            row = rec[b * W:(b + 1) * W]
+            if W == SCENARIO_OUT_MOMENTS:
+                _lib.moments_emit(row[SCEN_LNM2], row[SCEN_LNWMAX])
             n = int(row[ncol + 1])
             with _stats_lock:
                 _lib.count_launch(n, self.n_time)
@@ -201,24 +214,25 @@ class Pending:
             return False
         nbr = 1 if self.scen.a.planet else 2
         K = self.table_rows
+        W = self.stride
         if K > 1:
             # a table of the K best draws: the reference's order needs the K + 1 smallest chi^2 to be finite and
             # strictly increasing, and more than K masked draws (the operator chain's own rule, _best below: anything
             # else goes through numpy's argsort on the host)
             for b in range(nbr):
-                n = int(rec[b * SCENARIO_OUT + self.ncol + 1])
+                n = int(rec[b * W + self.ncol + 1])
                 hv = self.table.numpy()[b].reshape(15, K + 1)[14]
                 if n <= K or not (np.isfinite(hv[-1]) and np.all(hv[1:] > hv[:-1])):
                     return True
             return False
-        return any(rec[b * SCENARIO_OUT + SCEN_TIES] > 1.0 for b in range(nbr))
+        return any(rec[b * W + SCEN_TIES] > 1.0 for b in range(nbr))
 
 
-def _check_status(recs, planet):
+def _check_status(recs, planet, stride=SCENARIO_OUT):
     """raises when a record says that a masked draw's chi^2 was never written (an internal error of the passes of the
     bounded evaluation: round 4 shipped two such bugs, and a stale value read as a result gave FPP = 1)"""
     for b in range(2):
-        bad = recs[:, b * SCENARIO_OUT + SCEN_STATUS] != 0.0
+        bad = recs[:, b * stride + SCEN_STATUS] != 0.0
         if b == 1:
             bad = bad & ~np.asarray(planet, dtype=bool)
         if np.any(bad):
@@ -231,30 +245,48 @@ def _check_status(recs, planet):
 _stats_lock = threading.Lock()
 
 
+def _widen(rec, stride):
+    """a call's record in the layout of TRX_FLAG_WEIGHT_MOMENTS (moments NaN where the call did not ask for them)"""
+    if stride == SCENARIO_OUT_MOMENTS:
+        return rec[:RECORD_MOMENTS]
+    W = SCENARIO_OUT_MOMENTS
+    out = np.full(RECORD_MOMENTS, np.nan)
+    out[:SCENARIO_OUT] = rec[:SCENARIO_OUT]
+    out[W:W + SCENARIO_OUT] = rec[SCENARIO_OUT:2 * SCENARIO_OUT]
+    out[2 * W] = rec[2 * SCENARIO_OUT]
+    return out
+
+
 def records_to_rows(pending):
-    """The calls of a pass in one go: [(unit, Pending)] -> {unit: (branches, 15) array in sharding.RECORD_COLS order
-    (M_s R_s u1 u2 P_orb inc b R_p ecc argp M_EB R_EB fluxratio_EB fluxratio_comp lnZ)}, what Pending.result() +
-    sharding._record give call by call (768 calls of a 64-target step: 12 ms of dict building; here a few array
-    expressions).  The streams must have been synchronised."""
+    """The calls of a pass in one go: [(unit, Pending)] -> {unit: (branches, 17) array in sharding.RECORD_COLS order
+    (M_s R_s u1 u2 P_orb inc b R_p ecc argp M_EB R_EB fluxratio_EB fluxratio_comp lnZ), then sharding.MOMENT_COLS
+    (lnM2 lnWmax: NaN where the call did not ask for them)}, what Pending.result() + sharding._record give call by call
+    (768 calls of a 64-target step: 12 ms of dict building; here a few array expressions).  The streams must have been
+    synchronised."""
     if not pending:
         return {}
-    recs = np.stack([p.out.numpy() for _, p in pending])                 # [calls][37]
-    if np.any(recs[:, 2 * SCENARIO_OUT] != 0.0):
+    W = SCENARIO_OUT_MOMENTS
+    recs = np.stack([_widen(p.out.numpy(), p.stride) for _, p in pending])      # [calls][41]
+    if np.any(recs[:, 2 * W] != 0.0):
         raise ValueError("can only convert an array of size 1 to a Python scalar")
     planet = np.array([bool(p.scen.a.planet) for _, p in pending])
-    _check_status(recs, planet)
-    replay = [i for i, (_, p) in enumerate(pending) if p.replay_for_ties(recs[i])]
+    _check_status(recs, planet, W)
+    # (on the record as the library wrote it: replay_for_ties reads it at the call's own stride)
+    replay = [i for i, (_, p) in enumerate(pending) if p.replay_for_ties(p.out.numpy())]
     if replay:
         # (seeded numpy modes only: the reference's own order among exactly tied best draws, see Pending.replay_for_ties)
         redo = {}
         for i in replay:
             k, p = pending[i]
+            p.scen.want_moments = p.stride == SCENARIO_OUT_MOMENTS
             with torch.cuda.stream(p.stream):
                 res = p.scen.run_operator_chain(p.is_host, p.ncol)
             p.stream.synchronize()
             dicts = res if isinstance(res, tuple) else (res,)
             from .sharding import RECORD_COLS
-            redo[k] = np.array([[d[c] if c == "lnZ" else d[c][0] for c in RECORD_COLS] for d in dicts])
+            mom = p.scen.moments or [(np.nan, np.nan)] * len(dicts)
+            redo[k] = np.array([[d[c] if c == "lnZ" else d[c][0] for c in RECORD_COLS] + list(m)
+                                for d, m in zip(dicts, mom)])
         with _stats_lock:
             _lib.STATS["native_calls"] += len(replay)
         rest = [kp for i, kp in enumerate(pending) if i not in set(replay)]
@@ -273,8 +305,10 @@ def records_to_rows(pending):
     if planet.any():
         r = recs[planet]
         rp, P, inc, sm, Rh, u1, u2, ecc, w, frc, Mh, lnz, n = (r[:, j] for j in range(13))
+        lnm2, lnwmax = r[:, SCEN_LNM2], r[:, SCEN_LNWMAX]
         z = np.zeros(r.shape[0])
-        block = np.stack([Mh, Rh, u1, u2, P, inc, impact(sm, ecc, w, inc, Rh), rp, ecc, w, z, z, z, frc, lnz], axis=1)
+        block = np.stack([Mh, Rh, u1, u2, P, inc, impact(sm, ecc, w, inc, Rh), rp, ecc, w, z, z, z, frc, lnz,
+                          lnm2, lnwmax], axis=1)
         for row, (k, _) in zip(block, [kp for kp, pl in zip(pending, planet) if pl]):
             out[k] = row[None, :]
         rows_total += int(n.sum())
@@ -284,16 +318,18 @@ def records_to_rows(pending):
         r = recs[~planet]
         blocks = []
         for b in range(2):
-            q = r[:, b * SCENARIO_OUT:(b + 1) * SCENARIO_OUT]
+            q = r[:, b * W:(b + 1) * W]
             rr, fr, P, inc, sm, Rh, u1, u2, ecc, w, frc, sm2, m, Mh, lnz, n = (q[:, j] for j in range(16))
+            lnm2, lnwmax = q[:, SCEN_LNM2], q[:, SCEN_LNWMAX]
             if b == 1:
                 P, sm = 2 * P, sm2
             z = np.zeros(q.shape[0])
-            blocks.append(np.stack([Mh, Rh, u1, u2, P, inc, impact(sm, ecc, w, inc, Rh), z, ecc, w, m, rr, fr, frc, lnz], axis=1))
+            blocks.append(np.stack([Mh, Rh, u1, u2, P, inc, impact(sm, ecc, w, inc, Rh), z, ecc, w, m, rr, fr, frc, lnz,
+                                    lnm2, lnwmax], axis=1))
             rows_total += int(n.sum())
             cells_total += int((n * n_time[~planet]).sum())
             launches += q.shape[0]
-        both = np.stack(blocks, axis=1)                                   # [calls][2][15]
+        both = np.stack(blocks, axis=1)                                   # [calls][2][17]
         for row, (k, _) in zip(both, [kp for kp, pl in zip(pending, planet) if not pl]):
             out[k] = row
     with _stats_lock:
@@ -311,7 +347,7 @@ def begin_deferred(n_calls):
     their number (one pinned block holds all their records).  The calls are not handed to the library one by
     one: they collect in a list that flush() passes on in ONE call (trx_star_enqueue) -- sharding.run_units
     flushes at the end of every star's units."""
-    _tls.records = torch.empty((max(int(n_calls), 1), RECORD), dtype=F64, pin_memory=True)
+    _tls.records = torch.empty((max(int(n_calls), 1), RECORD_MOMENTS), dtype=F64, pin_memory=True)
     _tls.next_record = 0
     _tls.batch = []
 
@@ -354,7 +390,7 @@ def _record_slot():
         return recs[_tls.next_record - 1], True
     one = getattr(_tls, "one_record", None)
     if one is None:
-        one = _tls.one_record = torch.empty(RECORD, dtype=F64).pin_memory()
+        one = _tls.one_record = torch.empty(RECORD_MOMENTS, dtype=F64).pin_memory()
     return one, False
 
 
@@ -727,6 +763,8 @@ class _Scenario:
     want_prior = False
     band = "TESS"
     cc_nonmono = False
+    want_moments = False
+    moments = None
 
     def _replay_interp(self, ncol):
         """The reference interpolates the contrast curve with np.interp (funcs.py:222-238), and on a curve whose contrasts
@@ -802,6 +840,10 @@ class _Scenario:
             raise _lib.TrxError("trx_draw_scenario failed with status %d" % rc)
         self.keep = []
         out = []
+        # the Monte-Carlo moments of each branch's evidence (calc_probs: _lib.moments_wanted; a replay of a record that
+        # carried them: want_moments), from the chi^2/2 values already on the device
+        moments = MOMENTS and (_lib.moments_wanted() or self.want_moments)
+        self.moments = [] if moments else None
         flags = (FLAG_COMPANION_IS_HOST if is_host else 0) | (0 if self.parallel else FLAG_SCALAR_K)
         branches = ((MODEL_TP, mask, False),) if a.planet else ((MODEL_EB, mask, False), (MODEL_EB_TWIN, mask2, True))
         for model, m, twin in branches:
@@ -815,6 +857,10 @@ class _Scenario:
             lp = None if lnprior is None else lnprior.index_select(0, idx)
             h, lnz = _lib.lnz_scenario(model, flags, self.time, self.flux, self.sigma, block, self.exptime,
                                        self.nsamples, lp, N, float(np.log(self.sigma)))
+            if moments:
+                mom = _lib.lnz_moments_from_halfchi2(h, lp, N, float(np.log(self.sigma))).cpu().numpy()
+                self.moments.append((float(mom[1]), float(mom[2])))
+                _lib.moments_emit(mom[1], mom[2])
             best = self._best(h, idx, n)
             out.append((best, lnz, twin))
         # one device -> host copy per branch: the N_BEST x ncol table, lnZ and (once) the flag
@@ -838,6 +884,11 @@ class _Scenario:
         sa.sigma, sa.lnsigma, sa.exptime = float(self.sigma), float(np.log(self.sigma)), float(self.exptime)
         sa.flags = ((FLAG_COMPANION_IS_HOST if is_host else 0) | (0 if self.parallel else FLAG_SCALAR_K)
                     | _lib.EXTRA_FLAGS)
+        # (calc_probs / calc_probs_many: records with the moments of the evidence; a direct lnZ_* call keeps today's)
+        stride = SCENARIO_OUT
+        if MOMENTS and _lib.moments_wanted():
+            sa.flags |= _lib.FLAG_WEIGHT_MOMENTS
+            stride = SCENARIO_OUT_MOMENTS
         sa.want_prior = int(self.want_prior)
         out, deferred = _record_slot()
         stream = torch.cuda.current_stream(dev)
@@ -845,7 +896,8 @@ class _Scenario:
         if K > 1:
             table = torch.empty((2, _table_branch(K)), dtype=F64).pin_memory()
             sa.table_rows, sa.table = K, table.data_ptr()
-        pend = Pending(self, out, stream, self.keep + [self.time, self.flux], ncol, sa.n_time, is_host, table, K if K > 1 else 0)
+        pend = Pending(self, out, stream, self.keep + [self.time, self.flux], ncol, sa.n_time, is_host, table, K if K > 1 else 0,
+                       stride)
         self.keep = []
         if deferred and getattr(_tls, "batch", None) is not None:
             _tls.batch.append((sa, out, stream, dev))      # (sa.draw points at self.a: alive in the Pending)

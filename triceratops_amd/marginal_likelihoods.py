@@ -287,6 +287,10 @@ def _evidence(model, is_host, parallel, time, flux, sigma, cols, mask, lnprior, 
     lp = None if lnprior is None else _lib.dev(lnprior[idx])
     h, lnz = _lib.lnz_scenario(model, flags, _lib.dev(time), _lib.dev(flux), sigma,
                                _lib.dev(block), exptime, nsamples, lp, N, lnsigma)
+    if _lib.moments_wanted() and h.is_cuda:
+        # calc_probs: the Monte-Carlo moments of this evidence, from the same chi^2/2 values (sharding.run_units)
+        mom = _lib.lnz_moments_from_halfchi2(h, lp, N, lnsigma).cpu().numpy()
+        _lib.moments_emit(mom[1], mom[2])
     # best draws = smallest chi^2/2.  With >= N_BEST finite values only their order matters and a
     # device top-k gives it; otherwise fall back to the reference's full argsort so that the
     # (arbitrary) order of the -inf ties is the reference's too.

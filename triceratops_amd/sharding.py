@@ -25,8 +25,14 @@ import os
 
 import numpy as np
 
+from . import _lib
+
 RECORD_COLS = ("M_s", "R_s", "u1", "u2", "P_orb", "inc", "b", "R_p", "ecc", "argp", "M_EB",
                "R_EB", "fluxratio_EB", "fluxratio_comp", "lnZ")
+# run_units' table carries the Monte-Carlo moments of every evidence behind RECORD_COLS (NaN where a path gave none):
+# lnM2 = log of the mean squared weight, lnWmax = log of the largest weight's share (include/trx.h,
+# trx_lnz_moments_from_halfchi2).  They never enter a result dict; target._finish reads them from the rows.
+MOMENT_COLS = ("lnM2", "lnWmax")
 per_unit_seed = False
 # Host threads that evaluate this rank's units side by side, each on its own HIP stream
 # (set_sampling("device") with the kernel's own random numbers only).  A lnZ_* call is ~25 small
@@ -172,6 +178,15 @@ def schedule(costs, world, groups=None):
     return owner
 
 
+# fields of a work unit (run_units' docstring) read by name elsewhere
+UNIT_DRAWS = 7          # N: the Monte-Carlo draws of the unit's lnZ_* call (units of target._prepare)
+
+
+def unit_draws(u):
+    """N of the unit's lnZ_* call, or None when the unit does not say (units built by hand)"""
+    return u[UNIT_DRAWS] if len(u) > UNIT_DRAWS else None
+
+
 def _record(res):
     """(res,) or (res, res_twin) -> (n, 15) array of the best row + lnZ of each dict"""
     dicts = res if isinstance(res, tuple) else (res,)
@@ -193,9 +208,9 @@ def run_units(units, verbose=0, as_rows=False, job_done=None):
     the scenario cost of `key` in the schedule (units of differently sized jobs, calc_probs_many), (job, star) lets
     the schedule deal whole TOIs and whole stars.
     Returns, per unit, None (dropped scenario) or a tuple of per-scenario dicts
-    {column: best value, 'lnZ': float} -- with as_rows, the (branches, 15) array of RECORD_COLS instead (what
-    target._finish reads: building a dict per scenario and taking it apart again cost 4 ms of a 64-target step, on
-    every rank).
+    {column: best value, 'lnZ': float} -- with as_rows, the (branches, 17) array of RECORD_COLS + MOMENT_COLS instead
+    (what target._finish reads: building a dict per scenario and taking it apart again cost 4 ms of a 64-target step,
+    on every rank).
     job_done(job, results_of_its_units): called as soon as every unit of a job (the first element of a unit's
     (job, star)) has its records -- while the GPU still works on later jobs -- on one rank with the calls enqueued
     from one host thread; elsewhere never (the caller finishes what is left)."""
@@ -228,9 +243,12 @@ def run_units(units, verbose=0, as_rows=False, job_done=None):
         # (threads only apply to the device generator: the numpy modes keep consuming the caller's stream)
         base = _draw_base()
     _fused.TABLE_ROWS = 1
+    # (this thread's moments sink for the pass: the evidences report lnM2 / lnWmax, see _lib.moments_swap)
+    prev_sink = _lib.moments_swap([] if _fused.MOMENTS else None)
     try:
         return _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows, job_done if not dist else None)
     finally:
+        _lib.moments_swap(prev_sink)
         _fused.TABLE_ROWS = _fused.N_BEST
 
 
@@ -298,7 +316,8 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
     for k in live:
         offs[k] = total
         total += rows[k]
-    table = np.full((total, len(RECORD_COLS)), np.nan)
+    table = np.full((total, len(RECORD_COLS) + len(MOMENT_COLS)), np.nan)
+    ncol = len(RECORD_COLS)
     from . import fused as _fused
     mine_k = [k for k in live if owner[k] == rank]
 
@@ -317,14 +336,18 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
                 np.random.seed(unit_seed)            # the numpy sampling modes
                 import torch
                 torch.manual_seed(unit_seed)         # staged draws from torch's generator
+        mark = _lib.moments_mark()                   # (the moments this unit's evidences report: fused / ml)
         try:
             res = fn()
         finally:
             _fused.set_thread_seed(None)
+        mom = _lib.moments_since(mark)
         if isinstance(res, _fused.Pending):
             pending.append((k, res))                 # list.append is atomic: worker threads share it
         else:
-            table[offs[k]:offs[k] + rows[k]] = _record(res)
+            table[offs[k]:offs[k] + rows[k], :ncol] = _record(res)
+            if len(mom) == rows[k]:
+                table[offs[k]:offs[k] + rows[k], ncol:] = mom
 
     def resolve():
         for k, rec in _fused.records_to_rows(pending).items():
@@ -454,6 +477,7 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
         pool_streams = _worker_streams(device, n_threads)
 
         def worker(stream):
+            _lib.moments_swap([] if _fused.MOMENTS else None)
             try:
                 torch.cuda.set_device(device)        # the current device is thread-local
                 _fused.begin_deferred(len(mine_k))
@@ -470,6 +494,7 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
             finally:
                 stream.synchronize()                  # (also after an error: calls enqueued before it are in flight)
                 _fused.end_deferred()
+                _lib.moments_swap(None)
 
         torch.cuda.current_stream().synchronize()    # inputs staged on the caller's stream
         pool = [threading.Thread(target=worker, args=(pool_streams[i],)) for i in range(n_threads)]
@@ -484,15 +509,15 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
 
     if dist:
         # ONE collective: every rank contributes the records of its own units (in unit order, padded to the
-        # largest share) behind one header row that carries its seed base -- 15 doubles per scenario, a few KB
-        # per rank, latency-bound: a direct all_gather, no ring, no bucketing
+        # largest share) behind one header row that carries its seed base -- 17 doubles per scenario (RECORD_COLS and
+        # MOMENT_COLS), a few KB per rank, latency-bound: a direct all_gather, no ring, no bucketing
         import time
         import torch
         t_g = time.perf_counter()
         dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
-        ncol = len(RECORD_COLS)
+        width = table.shape[1]
         share = [sum(rows[k] for k in live if owner[k] == r) for r in range(world)]
-        chunk = np.full((1 + max(share + [0]), ncol), np.nan)
+        chunk = np.full((1 + max(share + [0]), width), np.nan)
         chunk[0, 0] = float(base)
         at = 1
         for k in mine_k:

@@ -25,7 +25,7 @@ from pandas import DataFrame
 from scipy.special import ndtr
 
 from . import _lib
-from ._numerics import _normalize_probabilities
+from ._numerics import _mc_errors, _normalize_probabilities
 from .constants import G, Msun, pi
 from .funcs import renorm_flux
 from .marginal_likelihoods import *  # noqa: F401,F403  (reference re-exports the lnZ_* names)
@@ -202,6 +202,41 @@ class target:
         self._finish(units, sharding.run_units(units, verbose=verbose, as_rows=True), book)
         return
 
+    def calc_probs_runs(self, time, flux_0, flux_err_0: float, P_orb, n_runs: int = 20, **calc_probs_kwargs):
+        """n_runs independent calc_probs of this target in ONE sharded pass: the mean and the scatter of FPP and NFPP that
+        the reference's tutorial asks for before a result is quoted (its loop of `.calc_probs()` calls), with the
+        streams, launch chains, host threads and ranks seeing the units of all runs at once.
+
+        calc_probs_kwargs: the other arguments of calc_probs (verbose defaults to 0 here).  On one rank, one host thread
+        and without sharding.per_unit_seed, run r is the r-th of n_runs consecutive calc_probs calls from the same seed,
+        bit for bit.  Returns a dict of numpy arrays: FPP, NFPP, FPP_err, NFPP_err [n_runs]; lnZ, prob [n_runs][n_scen];
+        FPP_mean, FPP_std, NFPP_mean, NFPP_std (np.std, ddof = 0).  Afterwards the target holds the table of the last
+        run, as the loop leaves it."""
+        n_runs = int(n_runs)
+        if n_runs < 1:
+            raise ValueError("n_runs must be >= 1")
+        kw = dict(calc_probs_kwargs)
+        verbose = kw.pop("verbose", 0)
+        prepared = [self._prepare(time, flux_0, flux_err_0, P_orb, job=r, **kw) for r in range(n_runs)]
+        flat = [u for units, _ in prepared for u in units]
+        results = sharding.run_units(flat, verbose=verbose, as_rows=True)
+        keys = ("FPP", "NFPP", "FPP_err", "NFPP_err")
+        out = {k: np.empty(n_runs) for k in keys}
+        lnZ, prob = [], []
+        at = 0
+        for r, (units, n_scen) in enumerate(prepared):
+            self._finish(units, results[at:at + len(units)], n_scen)
+            at += len(units)
+            for k in keys:
+                out[k][r] = getattr(self, k)
+            lnZ.append(self.lnZ)
+            prob.append(self._probs_columns["prob"])
+        out["lnZ"], out["prob"] = np.array(lnZ), np.array(prob)
+        for k in ("FPP", "NFPP"):
+            out[k + "_mean"] = float(np.mean(out[k]))
+            out[k + "_std"] = float(np.std(out[k]))
+        return out
+
     def _prepare(self, time, flux_0, flux_err_0, P_orb, contrast_curve_file=None, filt="TESS",
                  N=1000000, parallel=False, drop_scenario=[], flatpriors=False, exptime=0.00139,
                  nsamples=20, molusc_file=None, job=0):
@@ -254,17 +289,27 @@ class target:
         best = {c: np.zeros(n_scen) for c in _COLS}
         lnZ = np.zeros(n_scen)
         rec_tab = None
+        ncol = len(sharding.RECORD_COLS)
+        lnM2 = np.full(n_scen, np.nan)               # the evidences' moments (sharding.MOMENT_COLS), NaN = unknown
+        lnWmax = np.full(n_scen, np.nan)
+        n_draws = np.full(n_scen, np.nan)            # N of each row's lnZ_* call (units of target._prepare)
         for u, res in zip(units, results):
             j0, names, snum, ID = u[:4]
+            draws = sharding.unit_draws(u)
+            if draws is not None:
+                n_draws[j0:j0 + len(names)] = draws
             if isinstance(res, np.ndarray):
-                # (sharding.run_units(as_rows=True): the unit's (branches, 15) block of sharding.RECORD_COLS)
+                # (sharding.run_units(as_rows=True): the unit's (branches, 15) block of sharding.RECORD_COLS, + the
+                # two of sharding.MOMENT_COLS when the run gave them)
                 if rec_tab is None:
-                    rec_tab = np.zeros((n_scen, len(sharding.RECORD_COLS)))
+                    rec_tab = np.zeros((n_scen, ncol))
                 nb = len(names)
-                rec_tab[j0:j0 + nb] = res
+                rec_tab[j0:j0 + nb] = res[:, :ncol]
                 targets[j0:j0 + nb], star_num[j0:j0 + nb] = ID, snum
                 scenarios[j0:j0 + nb] = names
-                lnZ[j0:j0 + nb] = res[:, -1]
+                lnZ[j0:j0 + nb] = res[:, ncol - 1]
+                if res.shape[1] >= ncol + 2:
+                    lnM2[j0:j0 + nb], lnWmax[j0:j0 + nb] = res[:, ncol], res[:, ncol + 1]
                 continue
             for off, name in enumerate(names):
                 j = j0 + off
@@ -300,7 +345,33 @@ class target:
         prob = relative_probs
         self.FPP = 1 - (prob[0] + prob[3] + prob[9])
         self.NFPP = np.sum(prob[15:]) if len(prob) > 15 else 0.0
+        # what the Monte-Carlo error of this table is made from; the error attributes below are
+        # computed when one of them is first read, like .probs (a 64-target step reads none of them)
+        self._mc_inputs = (lnZ, lnM2, lnWmax, n_draws, status)
+        self._mc = None
         return
+
+    def _mc_attr(self, name):
+        d = self.__dict__
+        inputs = d.get("_mc_inputs")
+        if inputs is None:
+            # (no table yet, or a deferred one: target.__getattr__ fills it and reads again)
+            raise AttributeError("'%s' object has no attribute '%s'" % (type(self).__name__, name))
+        if d.get("_mc") is None:
+            lnZ, lnM2, lnWmax, n_draws, status = inputs
+            mc = _mc_errors(lnZ, lnM2, n_draws, status)
+            mc["w_max_frac"] = np.exp(lnWmax)
+            d["_mc"] = mc
+        return d["_mc"][name]
+
+    # The Monte-Carlo error of the last calc_probs table: per scenario row the effective sample size ess (0 where
+    # lnZ = -inf), the standard error of lnZ (NaN where lnZ is not finite) and the largest draw's share of the evidence;
+    # per target the delta-method errors of FPP and NFPP.  NaN where the run gave no moments.
+    ess = property(lambda self: self._mc_attr("ess"))
+    lnZ_err = property(lambda self: self._mc_attr("lnZ_err"))
+    w_max_frac = property(lambda self: self._mc_attr("w_max_frac"))
+    FPP_err = property(lambda self: self._mc_attr("FPP_err"))
+    NFPP_err = property(lambda self: self._mc_attr("NFPP_err"))
 
     @staticmethod
     def _warn_status(status, stacklevel):
@@ -319,7 +390,7 @@ class target:
 
     # what _finish sets: a target whose table is still to be filled (calc_probs_many on several ranks) has none of them
     _RESULTS = ("lnZ", "star_num", "u1", "u2", "fluxratio_EB", "fluxratio_comp", "FPP", "NFPP", "FPP_degenerate",
-                "_probs_columns", "_probs")
+                "_probs_columns", "_probs", "ess", "lnZ_err", "w_max_frac", "FPP_err", "NFPP_err", "_mc_inputs", "_mc")
 
     def _defer_finish(self, units, results, n_scen):
         """The table of this target is filled when one of its results is first read (calc_probs_many on several
@@ -331,7 +402,9 @@ class target:
         d = self.__dict__
         for name in self._RESULTS:
             d.pop(name, None)                # (results of an earlier calc_probs must not be read as this one's)
-        slim = [tuple(u[:4]) for u in units]
+        # (the unit's layout with its thunk dropped: the other fields are plain data, and the error attributes need
+        # sharding.unit_draws)
+        slim = [tuple(u[:4]) + (None,) + tuple(u[5:]) for u in units]
         kept = [None if r is None else (np.array(r, copy=True) if isinstance(r, np.ndarray) else r) for r in results]
         d["_pending_finish"] = (slim, kept, n_scen)
         lnz = np.full(n_scen, 0.0)
@@ -339,7 +412,7 @@ class target:
             if r is None:
                 lnz[u[0]:u[0] + len(u[1])] = -np.inf
             elif isinstance(r, np.ndarray):
-                lnz[u[0]:u[0] + len(u[1])] = r[:, -1]
+                lnz[u[0]:u[0] + len(u[1])] = r[:, len(sharding.RECORD_COLS) - 1]
             else:
                 lnz[u[0]:u[0] + len(u[1])] = [x["lnZ"] for x in r]
         if not np.all(np.isfinite(lnz)):      # (the common case costs one pass over ~20 numbers)
