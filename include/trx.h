@@ -187,6 +187,18 @@ int trx_lnz_moments_from_halfchi2(const double* halfchi2, const double* lnprior,
                                   double lnsigma, double* out, void* workspace, size_t workspace_bytes,
                                   void* stream);
 
+/* The selection of trx_scenario_args.post_rows on its own, on chi^2/2 values already on the device (the counterpart of
+ * trx_lnz_moments_from_halfchi2): post_rows = M systematic-resampling draws from the weights of the n rows.
+ *   out_pos [M] (device)  the sampled list positions r_j, non-decreasing; -1 where there is none
+ *   out_hdr [4] (device)  u, X, ln S, the number of rows with positive weight (0: no sample; also when a +inf term
+ *                         makes the evidence +inf)
+ *   workspace             trx_workspace_bytes() bytes of device scratch
+ * M < 0, M > TRX_POST_MAX_ROWS, n < 0, NULL outputs: TRX_ERR_ARG; workspace too small: TRX_ERR_WORKSPACE; nothing is
+ * enqueued then. */
+int trx_posterior_from_halfchi2(const double* halfchi2, const double* lnprior, long n, double lnsigma,
+                                int post_rows, unsigned long long post_seed, long* out_pos, double* out_hdr,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* Host-pointer conveniences: stage host buffers to the current device, run the kernels above,
  * copy back and synchronise.  For callers without a device allocator (a ctypes binding on
  * numpy arrays).  They are GPU paths, not CPU fallbacks. */
@@ -361,9 +373,32 @@ typedef struct {
      * or device memory.  K <= TRX_TABLE_MAX_ROWS. */
     int table_rows;
     double* table;
+    /* Posterior samples: post_rows = M > 0 draws M of the branch's masked draws in proportion to their weight in the
+     * evidence, w_i = exp(x_i - X) with x_i = -ln(sigma) - 0.5 ln(2 pi) - chi2half_i (+ lnprior_i), X = max x_i, and
+     * w_i = 0 where x_i - X <= -80 (the evidence's own cut; NaN and -inf: 0) -- by systematic resampling: S = sum w_i,
+     * C_i = w_0 + ... + w_i over the masked draws in list order, one uniform u in [0, 1), and sample j = the first list
+     * position r_j with C_{r_j} > (u + j) / M * S.  The r_j come out in non-decreasing order; draw i appears
+     * floor(M w_i / S) or ceil(M w_i / S) times; a draw of zero weight never appears.  The sums are taken in 128-bit fixed
+     * point (w 2^96), so S and C are exact to n 2^-96 S and the result repeats bit for bit.  `post` receives, per branch
+     * b, TRX_POST_BRANCH(M) doubles at post + b * TRX_POST_BRANCH(M):
+     *   [0] u  [1] X  [2] ln S  [3] the number of rows with w > 0  [4..7] 0
+     *   [8 + c * M, 8 + (c + 1) * M)  row c: column c of trx_draw_args.cols at the sampled draws for c < 11 (planet) or
+     *                                 14 (binary), 0 for the rows up to 13; row 14 the list positions r_j; row 15 the
+     *                                 log-weights x_{r_j}
+     * A branch without a positive weight (lnZ = -inf), or with lnZ = +inf / NaN: [3] = 0 and every one of the 16 rows NaN.
+     * u is Philox4x32-10 with key post_seed and counter (b, 0, 0x504f5354, 0): no random stream of the draws is touched.
+     * Such a call keeps the bounded evaluation (an abandoned draw lies more than 90 below X: weight 0 either way), is
+     * enqueued on its own, not in a launch chain, and may be combined with table_rows and TRX_FLAG_WEIGHT_MOMENTS; its
+     * record is bit for bit that of the call without post_rows.  `post`: pinned host or device memory, as `table`.
+     * M <= TRX_POST_MAX_ROWS.  post_rows = 0: no posterior. */
+    int post_rows;
+    double* post;
+    unsigned long long post_seed;
 } trx_scenario_args;
 #define TRX_TABLE_MAX_ROWS 127
 #define TRX_TABLE_BRANCH(K) (15 * ((K) + 1))
+#define TRX_POST_MAX_ROWS 4096
+#define TRX_POST_BRANCH(M) (8 + 16 * (M))
 int trx_scenario_evidence(const trx_scenario_args* args, void* stream);
 /* The same call without the final synchronisation: everything is enqueued on `stream` and the function
  * returns.  args->out / args->out_flag are ignored; the record arrives in

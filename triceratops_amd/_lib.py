@@ -31,6 +31,7 @@ ERR_NTOTAL = 4
 ABI_SYMBOLS = (
     "trx_lnl_batch", "trx_flux_grid", "trx_chi2_grid", "trx_workspace_bytes",
     "trx_log_mean_exp", "trx_lnz_scenario", "trx_lnz_from_halfchi2", "trx_lnz_moments_from_halfchi2",
+    "trx_posterior_from_halfchi2",
     "trx_lnl_batch_host", "trx_flux_grid_host",
     "trx_log_mean_exp_host", "trx_skipped_rows", "trx_pruned_rows",
     "trx_draw_scenario", "trx_draw_args_size", "trx_scenario_evidence", "trx_scenario_enqueue", "trx_star_enqueue",
@@ -160,6 +161,9 @@ def _load(path, testing):
     L.trx_lnz_from_halfchi2.argtypes = [_vp, _vp, c_long, c_long, c_double, _vp, _vp, c_size_t, _vp]
     L.trx_lnz_moments_from_halfchi2.restype = c_int
     L.trx_lnz_moments_from_halfchi2.argtypes = [_vp, _vp, c_long, c_long, c_double, _vp, _vp, c_size_t, _vp]
+    L.trx_posterior_from_halfchi2.restype = c_int
+    L.trx_posterior_from_halfchi2.argtypes = [_vp, _vp, c_long, c_double, c_int, ctypes.c_ulonglong, _vp, _vp, _vp,
+                                              c_size_t, _vp]
     L.trx_lnl_batch_host.restype = c_int
     L.trx_lnl_batch_host.argtypes = [c_int, c_int, _vp, _vp, c_int, c_double, _vp, c_long,
                                      c_double, c_int, _vp]
@@ -477,6 +481,27 @@ def lnz_moments_from_halfchi2(h_d, lnprior_d, n_total, lnsigma):
                                                   out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
                                                   _stream(h_d)))
     return out
+
+
+POST_MAX_ROWS = 4096       # TRX_POST_MAX_ROWS (include/trx.h)
+
+
+def posterior_from_halfchi2(h_d, lnprior_d, lnsigma, rows, seed):
+    """Systematic resampling of the weights exp(-ln sigma - 0.5 ln 2 pi - h [+ lnprior]) on the device
+    (trx_posterior_from_halfchi2): (positions, header) as device tensors -- `rows` list positions (int64, non-decreasing;
+    -1 where no row carries weight) and the header (u, X, ln S, rows with positive weight)."""
+    require_gpu()
+    device = h_d.device
+    pos = torch.empty(int(rows), dtype=torch.int64, device=device)
+    hdr = torch.empty(4, dtype=torch.float64, device=device)
+    ws = workspace(device)
+    with torch.cuda.device(device):
+        check(lib().trx_posterior_from_halfchi2(h_d.data_ptr() if h_d.numel() else None,
+                                                lnprior_d.data_ptr() if lnprior_d is not None else None,
+                                                h_d.numel(), float(lnsigma), int(rows), int(seed),
+                                                pos.data_ptr() if rows else None, hdr.data_ptr(),
+                                                ws.data_ptr(), ws.numel() * 8, _stream(h_d)))
+    return pos, hdr
 
 
 # The Monte-Carlo moments (lnM2, lnWmax) of the branches a lnZ_* call evaluates, on their way to sharding.run_units

@@ -1188,6 +1188,9 @@ struct ScenFinal {
     double* res;                      // this branch's record
     double* flag_out;                 // where the flag goes (as a double), or null: branch 0 reads it and clears it
     unsigned* state;                  // persistent: [0] finished blocks of THIS branch, [1] the call's flag (branch 0's block)
+    double* post_x;                   // null, or [1] in the call's scratch: the largest log-weight of the branch (the merged
+                                      // state's m) for the posterior resampler (trx_posterior.hpp); NaN where the branch
+                                      // has no posterior (lnZ = +inf or NaN), -inf where no draw carries weight
 };
 
 __device__ __forceinline__ void scenario_final(const ScenFinal& f, const double* __restrict__ w,
@@ -1247,6 +1250,7 @@ __device__ __forceinline__ void scenario_final(const ScenFinal& f, const double*
         f.res[kScenLnM2] = unwritten ? NAN : lnm2;
         f.res[kScenLnWmax] = unwritten ? NAN : lnwmax;
     }
+    if (lane == 60 && f.post_x) f.post_x[0] = (unwritten || t.pinf) ? NAN : t.m;
     if (lane == 63) {
         // (the flag belongs to the call: the branch that reports it -- branch 0 -- also clears it; with the branches of a
         // call reduced side by side in one launch the other branch must not touch it)

@@ -39,6 +39,7 @@
 #include "trx_device.hpp"
 #include "trx_internal.hpp"
 #include "trx_knobs.hpp"
+#include "trx_posterior.hpp"
 
 namespace {
 
@@ -166,6 +167,9 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
     // a table of the K best draws (include/trx.h): every masked draw evaluated to the end, K stand-in draws
     const int K = s->table_rows > 1 ? s->table_rows : 0;
     if (K > TRX_TABLE_MAX_ROWS || (K && !s->table)) return TRX_ERR_ARG;
+    // posterior rows (include/trx.h): M draws per branch in proportion to their weight, selected behind the evidence
+    const int M = s->post_rows;
+    if (M < 0 || M > TRX_POST_MAX_ROWS || (M && !s->post)) return TRX_ERR_ARG;
     const int n_pad = K ? K : 1;
     const int flags = s->flags | (K ? TRX_FLAG_FULL_EVALUATION : 0);
     const int stride = record_stride(s->flags);
@@ -188,6 +192,8 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
                  o_prior = A.reserve(s->want_prior ? sizeof(double) * N : 0),
                  o_n = A.reserve(2 * sizeof(long)), o_cols0 = A.reserve(sizeof(double) * 16 * n_pad),
                  o_table = A.reserve(K ? sizeof(double) * 2 * TRX_TABLE_BRANCH(K) : 0),
+                 o_post_ws = A.reserve(M ? 2 * trx::kPostWsBytes : 0),
+                 o_post = A.reserve(M ? sizeof(double) * 2 * TRX_POST_BRANCH(M) : 0),
                  o_res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1)),
                  o_ws = A.reserve(sizeof(double) * 2 * trx::kLmePart * kLmeParts), o_pv = A.reserve(sizeof(double) * 2 * kLmeParts),
                  o_pi = A.reserve(sizeof(long) * 2 * 2 * kLmeParts), o_cnt = A.reserve(sizeof(int) * 2 * trx::kDrawMaxGroups),
@@ -224,6 +230,15 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
         else
             (void)hipGetLastError();
     }
+    double* post_dev = nullptr;            // ... and the posterior block
+    if (M) {
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, s->post) == hipSuccess && attr.devicePointer &&
+            (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice))
+            post_dev = static_cast<double*>(attr.devicePointer);
+        else
+            (void)hipGetLastError();
+    }
     if (trx::knob_poison())          // tests: an unwritten row must show (include/trx_debug.h)
         for (int b = 0; b < nbr; ++b) TRXS_HIP(hipMemsetAsync(h[b], 0, sizeof(double) * (size_t)N, st));
     for (int b = 0; b < nbr; ++b) {
@@ -247,6 +262,8 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
         fin.res = res + (size_t)b * stride;
         fin.flag_out = (b == 0) ? res + 2 * stride : nullptr;
         fin.state = state;
+        char* post_ws = M ? A.at<char>(o_post_ws) + (size_t)b * trx::kPostWsBytes : nullptr;
+        if (M) fin.post_x = reinterpret_cast<double*>(post_ws + trx::kPostWsSums + trx::kPostWsCounts);
         if (int rc = trx::lme_draws(h[b], d.lnprior, s->lnsigma, N, n_dev + b, idx[b],
                                     A.at<double>(o_ws) + (size_t)b * trx::kLmePart * kLmeParts, A.at<double>(o_pv) + (size_t)b * kLmeParts,
                                     A.at<long>(o_pi) + (size_t)b * 2 * kLmeParts, bounds, fin, st))
@@ -259,7 +276,24 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
             hipLaunchKernelGGL(table_kernel, dim3(1), dim3(256), 0, st, t);
             if (hipGetLastError() != hipSuccess) return bail(TRX_ERR_HIP);
         }
+        if (M) {
+            // the weights are the evidence's own (its largest log-weight is in the scratch: fin.post_x); rows the
+            // bounded evaluation abandoned report a bound more than 90 below it and fall to the cut at -80
+            trx::PostArgs p{};
+            p.h = h[b]; p.lnprior = d.lnprior; p.n_dev = n_dev + b; p.n = N; p.N = N; p.twin = b;
+            p.c0 = -0.5 * log(trx::kTwoPi) - s->lnsigma;      // (lme_draws' constant)
+            p.M = M; p.branch = b; p.seed = s->post_seed;
+            p.xmax = fin.post_x;
+            p.tile_q = reinterpret_cast<trx::u128*>(post_ws);
+            p.tile_cnt = reinterpret_cast<long*>(post_ws + trx::kPostWsSums);
+            p.cols = d.cols; p.ncol = ncol;
+            p.block = (post_dev ? post_dev : A.at<double>(o_post)) + (size_t)b * TRX_POST_BRANCH(M);
+            if (trx::post_launch(p, false, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
+        }
     }
+    if (M && !post_dev)
+        TRXS_HIP(hipMemcpyAsync(s->post, A.at<double>(o_post), sizeof(double) * (size_t)nbr * TRX_POST_BRANCH(M),
+                                hipMemcpyDefault, st));
     if (K && !table_dev)
         TRXS_HIP(hipMemcpyAsync(s->table, A.at<double>(o_table), sizeof(double) * (size_t)nbr * TRX_TABLE_BRANCH(K),
                                 hipMemcpyDefault, st));
@@ -459,10 +493,11 @@ extern "C" int trx_star_enqueue(const trx_scenario_args* calls, int n_calls, dou
         hipStream_t st = static_cast<hipStream_t>(streams[i]);
         int which[trx::kChainMaxCalls];
         int n = 0, nbr = 0;
-        if (chain_enabled() && calls[i].table_rows <= 1 &&
+        if (chain_enabled() && calls[i].table_rows <= 1 && calls[i].post_rows <= 0 &&
             trx::lnl_chain_applicable(calls[i].flags, calls[i].n_time, calls[i].draw->N, calls[i].nsupersample)) {
             for (int j = i; j < n_calls && n < trx::kChainMaxCalls; ++j) {
-                if (streams[j] != streams[i] || calls[j].table_rows > 1 || !chain_compatible(calls[i], calls[j])) break;
+                if (streams[j] != streams[i] || calls[j].table_rows > 1 || calls[j].post_rows > 0 ||
+                    !chain_compatible(calls[i], calls[j])) break;
                 const int add = calls[j].draw->planet ? 1 : 2;
                 if (nbr + add > trx::kChainMaxBranchesHost) break;
                 if ((double)(n + 1) * (double)calls[i].draw->N > draw_budget && n > 0) break;
@@ -506,6 +541,30 @@ extern "C" int trx_scenario_evidence(const trx_scenario_args* s, void* stream)
 }
 
 extern "C" size_t trx_scenario_args_size(void) { return sizeof(trx_scenario_args); }
+
+extern "C" int trx_posterior_from_halfchi2(const double* halfchi2, const double* lnprior, long n, double lnsigma,
+                                           int post_rows, unsigned long long post_seed, long* out_pos, double* out_hdr,
+                                           void* workspace, size_t workspace_bytes, void* stream)
+{
+    static_assert(trx::kPostWsBytes <= 65536, "the reductions' workspace (trx_workspace_bytes) serves");
+    if (n < 0 || n > 0x7fffffffL || (n > 0 && !halfchi2) || post_rows < 0 || post_rows > TRX_POST_MAX_ROWS || !out_hdr ||
+        (post_rows > 0 && !out_pos))
+        return TRX_ERR_ARG;
+    if (!workspace || workspace_bytes < trx_workspace_bytes() || trx_workspace_bytes() < trx::kPostWsBytes)
+        return TRX_ERR_WORKSPACE;
+    char* ws = static_cast<char*>(workspace);
+    trx::PostArgs p{};
+    p.h = halfchi2; p.lnprior = lnprior; p.n = n; p.N = n;
+    p.c0 = -0.5 * log(trx::kTwoPi) - lnsigma;
+    p.M = post_rows; p.seed = post_seed;
+    p.tile_q = reinterpret_cast<trx::u128*>(ws);
+    p.tile_cnt = reinterpret_cast<long*>(ws + trx::kPostWsSums);
+    p.tile_max = reinterpret_cast<double*>(ws + trx::kPostWsSums);
+    p.xmax = reinterpret_cast<double*>(ws + trx::kPostWsSums + trx::kPostWsCounts);
+    p.out_pos = out_pos; p.out_hdr = out_hdr;
+    if (trx::post_launch(p, true, static_cast<hipStream_t>(stream)) != TRX_OK) return trx::fail_hip(hipErrorLaunchFailure);
+    return TRX_OK;
+}
 
 #ifdef TRX_TESTING
 extern "C" int trx_set_debug_poison(int on)

@@ -108,7 +108,13 @@ class ScenarioArgs(ctypes.Structure):
                 ("sigma", ctypes.c_double), ("lnsigma", ctypes.c_double), ("exptime", ctypes.c_double),
                 ("flags", ctypes.c_int), ("want_prior", ctypes.c_int),
                 ("out", ctypes.POINTER(ctypes.c_double)), ("out_flag", ctypes.POINTER(ctypes.c_int)),
-                ("table_rows", ctypes.c_int), ("table", _vp)]
+                ("table_rows", ctypes.c_int), ("table", _vp),
+                ("post_rows", ctypes.c_int), ("post", _vp), ("post_seed", ctypes.c_ulonglong)]
+
+
+def _post_branch(M):
+    """TRX_POST_BRANCH(M): doubles of one branch's posterior block (include/trx.h)"""
+    return 8 + 16 * M
 
 
 def _table_branch(K):
@@ -132,6 +138,34 @@ PRETEST = os.environ.get("TRX_PRETEST", "1") != "0"
 # SCENARIO_OUT_MOMENTS doubles; lnZ and the best draw are the same bits either way).  False: records as before, and
 # the target's error attributes are NaN (tests)
 MOMENTS = True
+# Posterior samples per scenario: M > 0 makes a native lnZ_* call ask the library for M draws of
+# each branch in proportion to their weight in the evidence (trx_scenario_args.post_rows: systematic resampling on the
+# device); every result dict gains "posterior" -- a dict of [M] arrays under the dict's own keys plus "lnw" (the sampled
+# draws' log-weights) and "row" (their positions in the branch's list of masked draws), or None where no draw carries
+# weight.  The operator chain produces the same key through trx_posterior_from_halfchi2.  Every other key: same bits.
+POSTERIOR_ROWS = 0
+POST_MAX_ROWS = _lib.POST_MAX_ROWS
+POSTERIOR_KEYS = ("M_s", "R_s", "u1", "u2", "P_orb", "inc", "b", "R_p", "ecc", "argp", "M_EB", "R_EB", "fluxratio_EB",
+                  "fluxratio_comp", "lnw", "row")
+_POST_SALT = 0x706F7374       # post_seed = _mix(the call's draw seed, this): no generator is advanced
+
+
+def posterior_to_flat(post, M):
+    """a "posterior" dict (or None) as 16 * M doubles, POSTERIOR_KEYS order, NaN where absent: the extra columns of
+    sharding.run_units' table"""
+    if post is None:
+        return np.full(16 * M, np.nan)
+    return np.concatenate([np.asarray(post[k], dtype=np.float64) for k in POSTERIOR_KEYS])
+
+
+def posterior_from_flat(flat, M):
+    """the inverse of posterior_to_flat (None for a row of NaN)"""
+    flat = np.asarray(flat, dtype=np.float64)
+    if flat.size != 16 * M or M == 0 or np.isnan(flat[14 * M]):
+        return None
+    post = {k: flat[i * M:(i + 1) * M].copy() for i, k in enumerate(POSTERIOR_KEYS)}
+    post["row"] = post["row"].astype(np.int64)
+    return post
 
 
 def _fn_scenario():
@@ -166,7 +200,8 @@ class Pending:
     """one trx_scenario_enqueue call whose record has not been read yet"""
 
     def __init__(self, scen, out, stream, keep, ncol, n_time, is_host=False, table=None, table_rows=0,
-                 stride=SCENARIO_OUT):
+                 stride=SCENARIO_OUT, post=None, post_rows=0):
+        self.post, self.post_rows = post, post_rows            # pinned [2][8 + 16 M] block of a call with posterior rows
         self.scen, self.out, self.stream, self.keep, self.ncol, self.n_time = scen, out, stream, keep, ncol, n_time
         self.is_host = is_host
         self.stride = stride                                   # doubles per branch record (SCENARIO_OUT[_MOMENTS])
@@ -200,7 +235,13 @@ class Pending:
                 res.append(self.scen._table(blk[:ncol, :K].copy(), float(row[ncol]), b == 1))
             else:
                 res.append(self.scen._table(row[:ncol].reshape(ncol, 1).copy(), float(row[ncol]), b == 1))
+            if self.post_rows:
+                res[-1]["posterior"] = self.posterior(b)
         return res[0] if planet else (res[0], res[1])
+
+    def posterior(self, b):
+        """branch b's "posterior" dict from the library's block (None: no draw carries weight)"""
+        return self.scen._posterior(self.post.numpy()[b], self.ncol, b == 1)
 
 
     def replay_for_ties(self, rec):
@@ -286,6 +327,7 @@ def records_to_rows(pending):
             from .sharding import RECORD_COLS
             mom = p.scen.moments or [(np.nan, np.nan)] * len(dicts)
             redo[k] = np.array([[d[c] if c == "lnZ" else d[c][0] for c in RECORD_COLS] + list(m)
+                                + (list(posterior_to_flat(d.get("posterior"), p.post_rows)) if p.post_rows else [])
                                 for d, m in zip(dicts, mom)])
         with _stats_lock:
             _lib.STATS["native_calls"] += len(replay)
@@ -297,6 +339,19 @@ def records_to_rows(pending):
         return out
     n_time = np.array([p.n_time for _, p in pending])
     out = {}
+    _rows_fill(pending, recs, planet, n_time, out)
+    # (calls with posterior rows: 16 M more columns per branch, sharding.run_units' wide table)
+    for k, p in pending:
+        if p.post_rows:
+            flat = [posterior_to_flat(p.posterior(b), p.post_rows) for b in range(out[k].shape[0])]
+            out[k] = np.concatenate([out[k], np.stack(flat)], axis=1)
+    for _, p in pending:
+        p.keep = None
+    return out
+
+
+def _rows_fill(pending, recs, planet, n_time, out):
+    W = SCENARIO_OUT_MOMENTS
 
     def impact(sm, ecc, w, inc, Rh):
         return sm * (1 - ecc ** 2) / (1 + ecc * np.sin(w * pi / 180)) * np.cos(inc * pi / 180) / (Rh * Rsun)
@@ -337,9 +392,6 @@ def records_to_rows(pending):
         _lib.STATS["cells"] += cells_total
         _lib.STATS["launches"] += launches
         _lib.STATS["native_calls"] += len(pending)
-    for _, p in pending:
-        p.keep = None
-    return out
 
 
 def begin_deferred(n_calls):
@@ -862,14 +914,28 @@ class _Scenario:
                 self.moments.append((float(mom[1]), float(mom[2])))
                 _lib.moments_emit(mom[1], mom[2])
             best = self._best(h, idx, n)
-            out.append((best, lnz, twin))
+            post = None
+            if POSTERIOR_ROWS:
+                # the same selection on this chain's chi^2/2 values (trx_posterior_from_halfchi2; the twin branch draws
+                # its uniform from a key of its own: the export has no branch counter)
+                M = int(POSTERIOR_ROWS)
+                pos, hdr = _lib.posterior_from_halfchi2(h, lp, float(np.log(self.sigma)), M,
+                                                        _mix(self.post_seed(), 1) if twin else self.post_seed())
+                if float(hdr[3]) > 0:
+                    x = (-0.5 * np.log(2 * pi) - float(np.log(self.sigma))) - h.index_select(0, pos)
+                    if lp is not None:
+                        x = x + lp.index_select(0, pos)
+                    post = torch.cat([cols.index_select(1, idx.index_select(0, pos)), pos.to(F64)[None, :], x[None, :]])
+            out.append((best, lnz, twin, post))
         # one device -> host copy per branch: the N_BEST x ncol table, lnZ and (once) the flag
         res = []
-        for best, lnz, twin in out:
+        for best, lnz, twin, post in out:
             tabl = torch.cat([cols.index_select(1, best).reshape(-1), lnz, flag.to(F64)]).cpu().numpy()
             if tabl[-1] != 0.0:
                 raise ValueError("can only convert an array of size 1 to a Python scalar")
             res.append(self._table(tabl[:-2].reshape(ncol, -1), float(tabl[-2]), twin))
+            if POSTERIOR_ROWS:
+                res[-1]["posterior"] = None if post is None else self._posterior_dict(post.cpu().numpy(), ncol, twin)
         return res[0] if a.planet else (res[0], res[1])
 
     def _run_native(self, is_host, ncol):
@@ -896,8 +962,14 @@ class _Scenario:
         if K > 1:
             table = torch.empty((2, _table_branch(K)), dtype=F64).pin_memory()
             sa.table_rows, sa.table = K, table.data_ptr()
+        post, M = None, int(POSTERIOR_ROWS)
+        if M < 0 or M > POST_MAX_ROWS:
+            raise ValueError("fused.POSTERIOR_ROWS must lie in [0, %d]" % POST_MAX_ROWS)
+        if M:
+            post = torch.empty((2, _post_branch(M)), dtype=F64).pin_memory()
+            sa.post_rows, sa.post, sa.post_seed = M, post.data_ptr(), self.post_seed()
         pend = Pending(self, out, stream, self.keep + [self.time, self.flux], ncol, sa.n_time, is_host, table, K if K > 1 else 0,
-                       stride)
+                       stride, post, M)
         self.keep = []
         if deferred and getattr(_tls, "batch", None) is not None:
             _tls.batch.append((sa, out, stream, dev))      # (sa.draw points at self.a: alive in the Pending)
@@ -936,6 +1008,25 @@ class _Scenario:
             lnL[idx.cpu().numpy()] = -0.5 * np.log(2 * pi) - np.log(self.sigma) - h.cpu().numpy()
             best = torch.as_tensor((-lnL).argsort()[:N_BEST]).to(dev)
         return best
+
+    def post_seed(self):
+        """key of the resampler's uniform: from the call's draw seed, no generator is advanced"""
+        return _mix(int(self.a.seed), _POST_SALT)
+
+    def _posterior(self, block, ncol, twin):
+        """a branch's TRX_POST_BRANCH(M) block (include/trx.h) -> its "posterior" dict, or None without weight"""
+        M = (block.size - 8) // 16
+        if block[3] == 0.0:
+            return None
+        rows = block[8:].reshape(16, M)
+        return self._posterior_dict(np.concatenate([rows[:ncol], rows[14:16]]), ncol, twin)
+
+    def _posterior_dict(self, t, ncol, twin):
+        """[ncol + 2][M]: the sampled draws' columns, their list positions and log-weights"""
+        d = self._table(t[:ncol].copy(), 0.0, twin)
+        del d["lnZ"]
+        d["lnw"], d["row"] = t[ncol + 1].copy(), t[ncol].astype(np.int64)
+        return d
 
     def _table(self, t, lnZ, twin):
         """the reference's result dict from the gathered columns (marginal_likelihoods.py:152-171)"""

@@ -198,7 +198,14 @@ def _record(res):
 
 
 def _as_dicts(rec):
-    return tuple({c: rec[i, j] for j, c in enumerate(RECORD_COLS)} for i in range(rec.shape[0]))
+    out = tuple({c: rec[i, j] for j, c in enumerate(RECORD_COLS)} for i in range(rec.shape[0]))
+    wide = rec.shape[1] - len(RECORD_COLS) - len(MOMENT_COLS)
+    if wide > 0:
+        # (a pass with fused.POSTERIOR_ROWS = M: 16 M more columns per scenario row)
+        from . import fused as _fused
+        for i, d in enumerate(out):
+            d["posterior"] = _fused.posterior_from_flat(rec[i, rec.shape[1] - wide:], wide // 16)
+    return out
 
 
 def run_units(units, verbose=0, as_rows=False, job_done=None):
@@ -316,9 +323,13 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
     for k in live:
         offs[k] = total
         total += rows[k]
-    table = np.full((total, len(RECORD_COLS) + len(MOMENT_COLS)), np.nan)
-    ncol = len(RECORD_COLS)
     from . import fused as _fused
+    # with posterior rows (fused.POSTERIOR_ROWS = M > 0) a scenario row carries its samples as 16 M more columns
+    # (fused.POSTERIOR_KEYS order, NaN where the row has none): they ride in the ONE all_gather below
+    post_rows = int(_fused.POSTERIOR_ROWS)
+    narrow = len(RECORD_COLS) + len(MOMENT_COLS)
+    table = np.full((total, narrow + 16 * post_rows), np.nan)
+    ncol = len(RECORD_COLS)
     mine_k = [k for k in live if owner[k] == rank]
 
     pending = []                                  # (unit, fused.Pending): calls in flight
@@ -347,11 +358,14 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
         else:
             table[offs[k]:offs[k] + rows[k], :ncol] = _record(res)
             if len(mom) == rows[k]:
-                table[offs[k]:offs[k] + rows[k], ncol:] = mom
+                table[offs[k]:offs[k] + rows[k], ncol:narrow] = mom
+            if post_rows:
+                for i, d in enumerate(res if isinstance(res, tuple) else (res,)):
+                    table[offs[k] + i, narrow:] = _fused.posterior_to_flat(d.get("posterior"), post_rows)
 
     def resolve():
         for k, rec in _fused.records_to_rows(pending).items():
-            table[offs[k]:offs[k] + rows[k]] = rec
+            table[offs[k]:offs[k] + rows[k], :rec.shape[1]] = rec
 
     on_device = _fused.threadable() or _fused.staged_native()
     if on_device:
@@ -436,7 +450,7 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
                 if upto > at:
                     got = _fused.records_to_rows(pending[at:upto])
                     for k, rec in got.items():
-                        table[offs[k]:offs[k] + rows[k]] = rec
+                        table[offs[k]:offs[k] + rows[k], :rec.shape[1]] = rec
                     at = upto
                     if job_done is not None:
                         for k in got:
@@ -452,7 +466,7 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
             timing["wait_s"] = t_wait
             if at < len(pending):
                 for k, rec in _fused.records_to_rows(pending[at:]).items():
-                    table[offs[k]:offs[k] + rows[k]] = rec
+                    table[offs[k]:offs[k] + rows[k], :rec.shape[1]] = rec
         finally:
             if not drained:
                 # a call failed after others were enqueued: their kernels and record copies still use the

@@ -35,6 +35,7 @@ from . import sharding
 
 _COLS = ("M_s", "R_s", "u1", "u2", "P_orb", "inc", "b", "R_p", "ecc", "argp", "M_EB", "R_EB",
          "fluxratio_EB", "fluxratio_comp")
+_POSTERIOR_PARAMS = _COLS        # the physical columns of a scenario's posterior samples (fused.POSTERIOR_KEYS less lnw, row)
 
 # (drop key, scenario names, first row index, star_num) of the nine target-star calls, in the
 # reference's order (triceratops.py:784-1340)
@@ -202,6 +203,73 @@ class target:
         self._finish(units, sharding.run_units(units, verbose=verbose, as_rows=True), book)
         return
 
+    def calc_posteriors(self, time, flux_0, flux_err_0: float, P_orb, n_samples: int = 1000, **calc_probs_kwargs):
+        """calc_probs with posterior samples: the same pass -- from the same seed `.probs`, `.lnZ`, `.FPP`, `.NFPP`, the
+        best-draw columns and the error attributes are bit for bit those of calc_probs -- in which every lnZ_* call also
+        draws n_samples of its draws in proportion to their weight in the evidence (systematic resampling on the
+        device).  Fills `.posterior`: a list with one entry per scenario row -- a dict of
+        [n_samples] arrays (M_s R_s u1 u2 P_orb inc b R_p ecc argp M_EB R_EB fluxratio_EB fluxratio_comp, "lnw" the
+        draws' log-weights, "row" their positions among the call's masked draws), or None for a dropped scenario or one
+        none of whose draws carries weight.  The samples of a row are equally weighted.  Needs a device sampling mode
+        (set_sampling("device") or "numpy-device")."""
+        from . import fused
+        n_samples = int(n_samples)
+        if not 1 <= n_samples <= fused.POST_MAX_ROWS:
+            raise ValueError("n_samples must lie in [1, %d]" % fused.POST_MAX_ROWS)
+        saved = fused.POSTERIOR_ROWS
+        fused.POSTERIOR_ROWS = n_samples
+        try:
+            self.calc_probs(time, flux_0, flux_err_0, P_orb, **calc_probs_kwargs)
+        finally:
+            fused.POSTERIOR_ROWS = saved
+        if all(p is None for p in self.posterior) and np.isfinite(self.lnZ).any():
+            raise NotImplementedError("calc_posteriors needs the device paths (set_sampling('device') or "
+                                      "'numpy-device'): this sampling mode returns no posterior rows")
+        return
+
+    def posterior_summary(self, q=(0.16, 0.5, 0.84)):
+        """Quantiles of every scenario's posterior samples (calc_posteriors): a DataFrame with one row per scenario
+        that has samples -- ID, scenario, prob, then <param>_q<100 q> for every physical column.  The samples are
+        equally weighted, so these are plain np.quantile values."""
+        post = self.__dict__.get("posterior")
+        if post is None:
+            raise ValueError("no posterior samples: run calc_posteriors first")
+        cols = self._probs_columns
+        out = []
+        for j, p in enumerate(post):
+            if p is None:
+                continue
+            row = {"ID": cols["ID"][j], "scenario": cols["scenario"][j], "prob": cols["prob"][j]}
+            for c in _POSTERIOR_PARAMS:
+                for qq, v in zip(q, np.quantile(p[c], q)):
+                    row["%s_q%g" % (c, 100 * qq)] = v
+            out.append(row)
+        return DataFrame(out)
+
+    def posterior_samples(self, n, rng=None):
+        """n draws from the model-averaged posterior: a scenario in proportion to its `prob`, then one of its
+        (equally weighted) samples.  DataFrame of n rows: `scenario`, `ID`, and the physical columns.  Scenarios
+        without samples contribute nothing (their probability is zero or was dropped).  Host side, numpy only."""
+        post = self.__dict__.get("posterior")
+        if post is None:
+            raise ValueError("no posterior samples: run calc_posteriors first")
+        rng = np.random.default_rng() if rng is None else rng
+        cols = self._probs_columns
+        have = np.array([p is not None for p in post])
+        w = np.where(have, np.nan_to_num(np.asarray(cols["prob"], dtype=np.float64)), 0.0)
+        if not w.sum() > 0:
+            raise ValueError("no scenario with posterior samples carries probability")
+        which = rng.choice(len(post), size=int(n), p=w / w.sum())
+        out = {"scenario": np.asarray(cols["scenario"])[which], "ID": np.asarray(cols["ID"])[which]}
+        for c in _POSTERIOR_PARAMS:
+            out[c] = np.empty(int(n))
+        for j in np.unique(which):
+            sel = which == j
+            pick = rng.integers(0, len(post[j]["lnw"]), size=int(sel.sum()))
+            for c in _POSTERIOR_PARAMS:
+                out[c][sel] = np.asarray(post[j][c])[pick]
+        return DataFrame(out)
+
     def calc_probs_runs(self, time, flux_0, flux_err_0: float, P_orb, n_runs: int = 20, **calc_probs_kwargs):
         """n_runs independent calc_probs of this target in ONE sharded pass: the mean and the scatter of FPP and NFPP that
         the reference's tutorial asks for before a result is quoted (its loop of `.calc_probs()` calls), with the
@@ -215,6 +283,9 @@ class target:
         n_runs = int(n_runs)
         if n_runs < 1:
             raise ValueError("n_runs must be >= 1")
+        from . import fused
+        if fused.POSTERIOR_ROWS:
+            raise NotImplementedError("posterior rows are not available in calc_probs_runs: use calc_posteriors")
         kw = dict(calc_probs_kwargs)
         verbose = kw.pop("verbose", 0)
         prepared = [self._prepare(time, flux_0, flux_err_0, P_orb, job=r, **kw) for r in range(n_runs)]
@@ -291,6 +362,7 @@ class target:
         rec_tab = None
         ncol = len(sharding.RECORD_COLS)
         lnM2 = np.full(n_scen, np.nan)               # the evidences' moments (sharding.MOMENT_COLS), NaN = unknown
+        posterior = [None] * n_scen                  # calc_posteriors: the samples of every scenario row
         lnWmax = np.full(n_scen, np.nan)
         n_draws = np.full(n_scen, np.nan)            # N of each row's lnZ_* call (units of target._prepare)
         for u, res in zip(units, results):
@@ -310,6 +382,11 @@ class target:
                 lnZ[j0:j0 + nb] = res[:, ncol - 1]
                 if res.shape[1] >= ncol + 2:
                     lnM2[j0:j0 + nb], lnWmax[j0:j0 + nb] = res[:, ncol], res[:, ncol + 1]
+                if res.shape[1] > ncol + 2:
+                    # (16 M more columns: the row's posterior samples, fused.POSTERIOR_KEYS order)
+                    from . import fused
+                    for i in range(nb):
+                        posterior[j0 + i] = fused.posterior_from_flat(res[i, ncol + 2:], (res.shape[1] - ncol - 2) // 16)
                 continue
             for off, name in enumerate(names):
                 j = j0 + off
@@ -321,6 +398,7 @@ class target:
                 for c in _COLS:
                     best[c][j] = r[c]
                 lnZ[j] = r["lnZ"]
+                posterior[j] = r.get("posterior") if isinstance(r, dict) else None
         if rec_tab is not None:
             for i, c in enumerate(sharding.RECORD_COLS[:-1]):
                 best[c] = best[c] + rec_tab[:, i]         # (rows of dict-valued or dropped units stay as filled above)
@@ -337,6 +415,7 @@ class target:
             "prob": relative_probs}
         self._probs = None
         self.lnZ = lnZ
+        self.posterior = posterior
         self.star_num = star_num
         self.u1 = best["u1"]
         self.u2 = best["u2"]
@@ -390,7 +469,8 @@ class target:
 
     # what _finish sets: a target whose table is still to be filled (calc_probs_many on several ranks) has none of them
     _RESULTS = ("lnZ", "star_num", "u1", "u2", "fluxratio_EB", "fluxratio_comp", "FPP", "NFPP", "FPP_degenerate",
-                "_probs_columns", "_probs", "ess", "lnZ_err", "w_max_frac", "FPP_err", "NFPP_err", "_mc_inputs", "_mc")
+                "_probs_columns", "_probs", "ess", "lnZ_err", "w_max_frac", "FPP_err", "NFPP_err", "_mc_inputs", "_mc",
+                "posterior")
 
     def _defer_finish(self, units, results, n_scen):
         """The table of this target is filled when one of its results is first read (calc_probs_many on several
@@ -511,6 +591,9 @@ def calc_probs_many(jobs, verbose: int = 0):
     without per-unit seeding this is the jobs' calc_probs calls one after the other on one random
     stream."""
     import time as _time
+    from . import fused
+    if fused.POSTERIOR_ROWS:
+        raise NotImplementedError("posterior rows are not available in calc_probs_many: use target.calc_posteriors")
     t0 = _time.perf_counter()
     prepared = []
     for job, (tg, kw) in enumerate(jobs):
