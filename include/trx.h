@@ -387,9 +387,12 @@ typedef struct {
      *                                 log-weights x_{r_j}
      * A branch without a positive weight (lnZ = -inf), or with lnZ = +inf / NaN: [3] = 0 and every one of the 16 rows NaN.
      * u is Philox4x32-10 with key post_seed and counter (b, 0, 0x504f5354, 0): no random stream of the draws is touched.
-     * Such a call keeps the bounded evaluation (an abandoned draw lies more than 90 below X: weight 0 either way), is
-     * enqueued on its own, not in a launch chain, and may be combined with table_rows and TRX_FLAG_WEIGHT_MOMENTS; its
-     * record is bit for bit that of the call without post_rows.  `post`: pinned host or device memory, as `table`.
+     * Such a call keeps the bounded evaluation (an abandoned draw lies more than 90 below X: weight 0 either way) and
+     * may be combined with table_rows and TRX_FLAG_WEIGHT_MOMENTS; its record is bit for bit that of the call without
+     * post_rows.  In trx_star_enqueue it joins a launch chain like a call without post_rows (the calls of a chain may
+     * ask for different M, 0 included, and name different `post` blocks; the block is that of the call enqueued on its
+     * own, bit for bit: key and counter are the call's own) -- unless it also asks for a table: table_rows > 1 takes a
+     * call out of the chains, with or without post_rows.  `post`: pinned host or device memory, as `table`.
      * M <= TRX_POST_MAX_ROWS.  post_rows = 0: no posterior. */
     int post_rows;
     double* post;
@@ -427,8 +430,10 @@ int trx_star_enqueue(const trx_scenario_args* calls, int n_calls, double* const*
 /* Consecutive calls of a trx_star_enqueue that sit on ONE stream and share N, the time stamps (pointer and length),
  * exptime, nsupersample and the precision flag are enqueued as one LAUNCH CHAIN: every kernel of the path once, with
  * the call / branch as a further grid dimension (up to 16 calls or 24 branches per chain; ~11 launches instead of
- * 9-17 per call).  Same records, bit for bit.  The calls of a chain run side by side: `out` of all of them is valid
- * once the stream has passed the call.  (The testing library can switch chains off: trx_debug.h.) */
+ * 9-17 per call, and two more for all the posterior rows of a chain's calls together).  A call with a table
+ * (table_rows > 1) is enqueued on its own and splits the chain there; post_rows does not.  Same records and posterior
+ * blocks, bit for bit.  The calls of a chain run side by side: `out` (and `post`) of all of them is valid once the
+ * stream has passed the call.  (The testing library can switch chains off: trx_debug.h.) */
 
 /* Frees the per-stream scratch described above (every device); all streams must be idle. */
 int trx_release_scratch(void);

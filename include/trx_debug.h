@@ -60,6 +60,10 @@ int trx_set_debug_bug(int on);
 int trx_set_probe_rows(int rows);
 /* 0: trx_star_enqueue enqueues its calls one by one instead of in launch chains (same records, bit for bit) */
 int trx_set_star_chain(int on);
+/* what trx_star_enqueue has put into launch chains since the library was loaded (or since the last call with
+ * reset != 0, which returns the counts and then zeroes them): chains, the calls in them, and those of these calls that
+ * had post_rows > 0.  Host counters; they cannot change a result.  Any pointer may be NULL. */
+int trx_debug_chain_counts(long* chains, long* calls_in_chains, long* posterior_calls_in_chains, int reset);
 
 /* scratch buffers of calls captured into hipGraphs: how many a live graph still owns, how many wait in the library's
  * pool for reuse (trx_release_scratch frees those) */

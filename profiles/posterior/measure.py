@@ -1,5 +1,6 @@
 """calc_probs against calc_posteriors(n_samples=1000) on TOI-465.01 (15 and 75 scenarios, N = 1e6, device sampling):
-wall-clock per pass, median and spread of REPS passes after a warm-up.  Prints the lines of results.txt."""
+wall-clock per pass, median and spread of REPS passes after a warm-up.  Prints the lines of results.txt.  Where the
+tree has calc_posteriors_many: the same pair for a batch of 16 synthetic TOIs (synth.toi_jobs, N = 2e5)."""
 import os
 import sys
 import time
@@ -49,3 +50,14 @@ for tag in ("real", "blend"):
         med, lo, hi = timed(fn)
         print("%-5s %2d scenarios  %-22s median %7.2f ms  (min %7.2f, max %7.2f, %d passes)"
               % (tag, len(tg.lnZ), label, med, lo, hi, REPS), flush=True)
+
+if hasattr(triceratops_amd, "calc_posteriors_many"):
+    from triceratops_amd import synth  # noqa: E402
+    jobs = synth.toi_jobs(16, n_time=200, N=200000, seed=synth.SEED, trilegal_fname=os.path.join(GOLD, "trilegal_synth.csv"),
+                          contrast_curve_file=os.path.join(GOLD, "contrast_curve_synth.csv"))
+    for label, fn in (("calc_probs_many", lambda: triceratops_amd.calc_probs_many(jobs)),
+                      ("calc_posteriors_many(1000)", lambda: triceratops_amd.calc_posteriors_many(jobs, n_samples=1000)),
+                      ("... keep='summary'", lambda: triceratops_amd.calc_posteriors_many(jobs, n_samples=1000, keep="summary"))):
+        med, lo, hi = timed(fn)
+        print("batch %d TOIs x %d rows  %-26s median %7.2f ms  (min %7.2f, max %7.2f, %d passes)"
+              % (len(jobs), len(jobs[0][0].lnZ), label, med, lo, hi, REPS), flush=True)

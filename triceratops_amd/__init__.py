@@ -94,3 +94,9 @@ def calc_probs_many(jobs, verbose: int = 0):
     """calc_probs for several targets in one sharded pass (see triceratops.calc_probs_many)."""
     from .triceratops import calc_probs_many as _many
     return _many(jobs, verbose=verbose)
+
+
+def calc_posteriors_many(jobs, n_samples: int = 1000, keep: str = "samples", q=(0.16, 0.5, 0.84), verbose: int = 0):
+    """calc_probs_many with posterior samples for every target (see triceratops.calc_posteriors_many)."""
+    from .triceratops import calc_posteriors_many as _many
+    return _many(jobs, n_samples=n_samples, keep=keep, q=q, verbose=verbose)

@@ -28,6 +28,11 @@
 //                       a binary search over the 256 thread totals and a step through that thread's 8 rows for every
 //                       target, and the gather of the chosen draw's columns from the dense column block into the
 //                       caller's block.  Tile 0 writes the header (and the NaN rows of a branch without weight).
+//   post_sum_chain_kernel, post_select_chain_kernel
+//                       the same two for every branch of a launch chain that wants samples (trx_star_enqueue,
+//                       enqueue_chain): the branch is the grid's second dimension and picks its PostArgs from a table in
+//                       the chain's arena.  The bodies are the single-call kernels' (post_sum_body, post_select_body), so
+//                       a block from a chain is the block of the call on its own, bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -144,6 +149,16 @@ __device__ __forceinline__ u128 post_block_sum(u128 v, u64 (*stage)[2])
     return t;
 }
 
+// the masked count is the same on every lane: kept in scalar registers (the compiler cannot know that the earlier
+// kernels' store is done, so it loads per lane, and the tile geometry that follows from it would sit in VGPRs)
+__device__ __forceinline__ long post_rows_of(const PostArgs& a)
+{
+    const long n = a.n_dev ? *a.n_dev : a.n;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)n);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)n >> 32));
+    return (long)(((unsigned long long)hi << 32) | lo);
+}
+
 __device__ __forceinline__ bool post_live(double X) { return X == X && X != INFINITY && X != -INFINITY; }
 
 // target j of M on a total of Q (Qd = Q as a double): floor((u + j) / M * Q), below Q; non-decreasing in j
@@ -206,17 +221,16 @@ __global__ __launch_bounds__(256) void post_x_kernel(PostArgs a)
     }
 }
 
-__global__ __launch_bounds__(256) void post_sum_kernel(PostArgs a)
+__device__ __forceinline__ void post_sum_body(const PostArgs& a, const int tile, u64 (*stage)[2])
 {
-    __shared__ u64 stage[4][2];
-    const long n = a.n_dev ? *a.n_dev : a.n;
+    const long n = post_rows_of(a);
     int tiles, per_tile;
     post_geometry(n < a.n ? n : a.n, a.n, tiles, per_tile);
-    if ((int)blockIdx.x >= tiles) return;
+    if (tile >= tiles) return;
     const double X = a.xmax[0];
     u128 q = 0, cnt = 0;
     if (post_live(X)) {
-        const long lo = (long)blockIdx.x * per_tile * kPostChunk;
+        const long lo = (long)tile * per_tile * kPostChunk;
         long hi = lo + (long)per_tile * kPostChunk;
         if (hi > n) hi = n;
         for (long r = lo + threadIdx.x; r < hi; r += 256) {
@@ -228,9 +242,24 @@ __global__ __launch_bounds__(256) void post_sum_kernel(PostArgs a)
     q = post_block_sum(q, stage);
     cnt = post_block_sum(cnt, stage);
     if (threadIdx.x == 0) {
-        a.tile_q[blockIdx.x] = q;
-        a.tile_cnt[blockIdx.x] = (long)(u64)cnt;
+        a.tile_q[tile] = q;
+        a.tile_cnt[tile] = (long)(u64)cnt;
     }
+}
+
+__global__ __launch_bounds__(256) void post_sum_kernel(PostArgs a)
+{
+    __shared__ u64 stage[4][2];
+    post_sum_body(a, (int)blockIdx.x, stage);
+}
+
+// the branches of a launch chain that want samples: slot blockIdx.y of `tab` (the grid's first dimension is sized for the
+// bound N the chain's calls share; a workgroup beyond its branch's tiles in use leaves at once, as in the single call)
+__global__ __launch_bounds__(256) void post_sum_chain_kernel(const PostArgs* __restrict__ tab)
+{
+    __shared__ u64 stage[4][2];
+    const PostArgs a = tab[blockIdx.y];
+    post_sum_body(a, (int)blockIdx.x, stage);
 }
 
 __device__ __forceinline__ void post_emit(const PostArgs& a, int j, long r)
@@ -244,14 +273,13 @@ __device__ __forceinline__ void post_emit(const PostArgs& a, int j, long r)
     rows[15 * M + j] = post_x(a, r);
 }
 
-__global__ __launch_bounds__(256) void post_select_kernel(PostArgs a)
+// c_lo / c_hi: inclusive sums of the chunk, [8][256]: row 8 t + k at k * 256 + t
+__device__ __forceinline__ void post_select_body(const PostArgs& a, const int tile, u64 (*stage)[2], u64* c_lo, u64* c_hi)
 {
-    __shared__ u64 stage[4][2];
-    __shared__ u64 c_lo[kPostChunk], c_hi[kPostChunk];       // inclusive sums of the chunk, [8][256]: row 8 t + k at k * 256 + t
-    const long n = a.n_dev ? *a.n_dev : a.n;
+    const long n = post_rows_of(a);
     int tiles, per_tile;
     post_geometry(n < a.n ? n : a.n, a.n, tiles, per_tile);
-    const int tile = (int)blockIdx.x, tid = (int)threadIdx.x, M = a.M;
+    const int tid = (int)threadIdx.x, M = a.M;
     if (tile >= tiles) return;
     const double X = a.xmax[0];
     // the tiles before this one, all of them, and the rows that carry weight
@@ -350,6 +378,21 @@ __global__ __launch_bounds__(256) void post_select_kernel(PostArgs a)
     }
 }
 
+__global__ __launch_bounds__(256) void post_select_kernel(PostArgs a)
+{
+    __shared__ u64 stage[4][2];
+    __shared__ u64 c_lo[kPostChunk], c_hi[kPostChunk];
+    post_select_body(a, (int)blockIdx.x, stage, c_lo, c_hi);
+}
+
+__global__ __launch_bounds__(256) void post_select_chain_kernel(const PostArgs* __restrict__ tab)
+{
+    __shared__ u64 stage[4][2];
+    __shared__ u64 c_lo[kPostChunk], c_hi[kPostChunk];
+    const PostArgs a = tab[blockIdx.y];
+    post_select_body(a, (int)blockIdx.x, stage, c_lo, c_hi);
+}
+
 // the passes of one branch behind its evidence (X already in a.xmax) -- or, standalone, behind the search for X
 int post_launch(const PostArgs& a, bool find_x, hipStream_t st)
 {
@@ -361,6 +404,17 @@ int post_launch(const PostArgs& a, bool find_x, hipStream_t st)
     }
     hipLaunchKernelGGL(post_sum_kernel, dim3(tiles), dim3(256), 0, st, a);
     hipLaunchKernelGGL(post_select_kernel, dim3(tiles), dim3(256), 0, st, a);
+    return hipGetLastError() == hipSuccess ? TRX_OK : TRX_ERR_HIP;
+}
+
+// ... and of the `slots` branches of a launch chain that want samples, behind the chain's evidence stage: two launches
+// for the whole chain.  dev_tab: their PostArgs in device memory (every one with n = N, the bound the chain's calls share)
+int post_launch_chain(const PostArgs* dev_tab, int slots, long N, hipStream_t st)
+{
+    int tiles, per_tile;
+    post_geometry(N, N, tiles, per_tile);
+    hipLaunchKernelGGL(post_sum_chain_kernel, dim3(tiles, slots), dim3(256), 0, st, dev_tab);
+    hipLaunchKernelGGL(post_select_chain_kernel, dim3(tiles, slots), dim3(256), 0, st, dev_tab);
     return hipGetLastError() == hipSuccess ? TRX_OK : TRX_ERR_HIP;
 }
 

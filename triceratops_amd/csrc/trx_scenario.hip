@@ -313,6 +313,16 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
 // and the precision flag (the calls of one target do: triceratops.py:767-1428); flux and sigma may differ (a nearby
 // star's light curve is the target's, renormalised).  Results are those of the calls one by one, bit for bit: the same
 // kernels' bodies on the same rows in the same order.
+// Calls with posterior rows (post_rows > 0) join like any other: every branch that wants samples gets kPostWsBytes of
+// the arena for its tile sums, the chain's final stage leaves the branch's largest log-weight there (ScenFinal.post_x),
+// and behind lnl_lme_chain the two posterior kernels run ONCE for the whole chain (post_launch_chain: the branch as the
+// grid's second dimension, its PostArgs from a table that rides in the upload of the draw-argument table).  The seed
+// and the Philox counter are the call's own (post_seed, the branch WITHIN the call), so a block does not depend on
+// the chain it was drawn in.
+// Scratch: + 49 KB per such branch, + 16 (8 + 16 M) bytes per call whose block the device cannot write directly (at
+// most 1 MB, M = 4096) -- beside the call's 146 N bytes of draw-side buffers (14 columns, masks, prior, lists, chi^2)
+// for which the Python side's stream cap books 360 N (sharding.stream_scratch_bytes): covered from N = 5000 draws on,
+// and below that a whole chain is a few MB.
 constexpr size_t kBranchHead = 64;       // bytes of the zeroed head per branch: [scan counter | finished blocks, flag]
 static_assert(trx::kChainMaxBranchesHost * kBranchHead <= trx::kScratchZeroed, "zeroed head of the chain's arena");
 
@@ -322,16 +332,35 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
     const long N = s0.draw->N;
     if (N < 1 || N > 0x7fffffffL || n < 1 || n > trx::kChainMaxCalls) return TRX_ERR_ARG;
     trx::StreamLock turn(st);
-    int nbr_total = 0;
-    for (int i = 0; i < n; ++i) nbr_total += calls[which[i]].draw->planet ? 1 : 2;
+    int nbr_total = 0, n_post = 0;         // branches; those of them that want posterior rows
+    double* post_dev[trx::kChainMaxCalls];  // where the device writes a call's posterior block: the caller's buffer if it can
+    for (int i = 0; i < n; ++i) {
+        const trx_scenario_args& s = calls[which[i]];
+        const int nbr = s.draw->planet ? 1 : 2, M = s.post_rows;
+        if (M < 0 || M > TRX_POST_MAX_ROWS || (M && !s.post)) return TRX_ERR_ARG;
+        nbr_total += nbr;
+        post_dev[i] = nullptr;
+        if (M) {
+            n_post += nbr;
+            hipPointerAttribute_t attr;
+            if (hipPointerGetAttributes(&attr, s.post) == hipSuccess && attr.devicePointer &&
+                (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice))
+                post_dev[i] = static_cast<double*>(attr.devicePointer);
+            else
+                (void)hipGetLastError();
+        }
+    }
     if (nbr_total > trx::kChainMaxBranchesHost) return TRX_ERR_ARG;
     const size_t branch_bytes = trx::chain_branch_scratch_bytes(N);
 
     Arena A;
     const size_t o_head = A.reserve(trx::kScratchZeroed);
-    const size_t o_tab = A.reserve(sizeof(trx_draw_args) * (size_t)n);
+    // the draw-argument table and, behind it, the PostArgs of the branches that want samples: one upload
+    const size_t post_tab_at = (sizeof(trx_draw_args) * (size_t)n + 255) & ~(size_t)255;
+    const size_t tab_bytes = post_tab_at + sizeof(trx::PostArgs) * (size_t)n_post;
+    const size_t o_tab = A.reserve(tab_bytes);
     const size_t o_cnt = A.reserve(sizeof(int) * 2 * trx::kDrawMaxGroups * (size_t)n);
-    struct CallOff { size_t cols, cols0, mask, mask2, prior, n, res, ws, pv, pi, idx[2], h[2]; };
+    struct CallOff { size_t cols, cols0, mask, mask2, prior, n, res, ws, pv, pi, idx[2], h[2], post; };
     CallOff co[trx::kChainMaxCalls];
     for (int i = 0; i < n; ++i) {
         const trx_scenario_args& s = calls[which[i]];
@@ -350,20 +379,23 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
         co[i].idx[1] = A.reserve(planet ? 0 : sizeof(int) * N);
         co[i].h[0] = A.reserve(sizeof(double) * N);
         co[i].h[1] = A.reserve(planet ? 0 : sizeof(double) * N);
+        co[i].post = A.reserve((s.post_rows && !post_dev[i]) ? sizeof(double) * 2 * TRX_POST_BRANCH(s.post_rows) : 0);
     }
+    const size_t o_post_ws = A.reserve(trx::kPostWsBytes * (size_t)n_post);
     const size_t o_branch = A.reserve(branch_bytes * (size_t)nbr_total);
     TRXS_HIP(trx::stream_scratch(st, 2, A.used, reinterpret_cast<void**>(&A.base)));
 
     // the calls' argument blocks, output pointers set, staged in pinned memory and copied to the device table
     trx_draw_args* stage = nullptr;
     void* stage_ticket = nullptr;
-    TRXS_HIP(trx::pinned_stage_begin(st, sizeof(trx_draw_args) * (size_t)n, reinterpret_cast<void**>(&stage), &stage_ticket));
+    TRXS_HIP(trx::pinned_stage_begin(st, tab_bytes, reinterpret_cast<void**>(&stage), &stage_ticket));
+    trx::PostArgs* post_stage = reinterpret_cast<trx::PostArgs*>(reinterpret_cast<char*>(stage) + post_tab_at);
     trx::ChainFill fills[trx::kChainMaxCalls];
     trx::ChainBranch br[trx::kChainMaxBranchesHost];
     trx::ScenFinal fin[trx::kChainMaxBranchesHost];
     double* res_of[trx::kChainMaxCalls];
     bool copy_back[trx::kChainMaxCalls];
-    int b_at = 0;
+    int b_at = 0, p_at = 0;
     for (int i = 0; i < n; ++i) {
         const trx_scenario_args& s = calls[which[i]];
         trx_draw_args d = *s.draw;
@@ -426,12 +458,27 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
             f.res = res + (size_t)b * f.stride;
             f.flag_out = (b == 0) ? res + 2 * f.stride : nullptr;
             f.state = reinterpret_cast<unsigned*>(head + 8);      // (branch 0: == state0, whose word 1 is the call's flag)
+            if (s.post_rows) {
+                // (enqueue()'s PostArgs of this branch, field by field: the weights are the evidence's own)
+                char* post_ws = A.base + o_post_ws + trx::kPostWsBytes * (size_t)p_at;
+                f.post_x = reinterpret_cast<double*>(post_ws + trx::kPostWsSums + trx::kPostWsCounts);
+                trx::PostArgs p{};
+                p.h = c.h; p.lnprior = d.lnprior; p.n_dev = n_dev + b; p.n = N; p.N = N; p.twin = b;
+                p.c0 = -0.5 * log(trx::kTwoPi) - s.lnsigma;
+                p.M = s.post_rows; p.branch = b; p.seed = s.post_seed;
+                p.xmax = f.post_x;
+                p.tile_q = reinterpret_cast<trx::u128*>(post_ws);
+                p.tile_cnt = reinterpret_cast<long*>(post_ws + trx::kPostWsSums);
+                p.cols = d.cols; p.ncol = ncol;
+                p.block = (post_dev[i] ? post_dev[i] : A.at<double>(co[i].post)) + (size_t)b * TRX_POST_BRANCH(s.post_rows);
+                post_stage[p_at++] = p;
+            }
             c.fin = &f;
         }
     }
     trx_draw_args* dev_tab = A.at<trx_draw_args>(o_tab);
     {
-        const hipError_t e = hipMemcpyAsync(dev_tab, stage, sizeof(trx_draw_args) * (size_t)n, hipMemcpyHostToDevice, st);
+        const hipError_t e = hipMemcpyAsync(dev_tab, stage, tab_bytes, hipMemcpyHostToDevice, st);
         trx::pinned_stage_end(st, stage_ticket);
         if (e != hipSuccess) return trx::fail_hip(e);
     }
@@ -451,14 +498,29 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
         if (rc == trx::kChainNotApplicable) rc = trx::fail_hip(hipErrorInvalidValue);
         return bail(rc);
     }
-    for (int i = 0; i < n; ++i)
+    if (n_post) {
+        const trx::PostArgs* post_tab = reinterpret_cast<const trx::PostArgs*>(A.base + o_tab + post_tab_at);
+        if (trx::post_launch_chain(post_tab, n_post, N, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
+    }
+    for (int i = 0; i < n; ++i) {
+        const trx_scenario_args& s = calls[which[i]];
+        if (s.post_rows && !post_dev[i])
+            TRXS_HIP(hipMemcpyAsync(s.post, A.at<double>(co[i].post),
+                                    sizeof(double) * (size_t)(s.draw->planet ? 1 : 2) * TRX_POST_BRANCH(s.post_rows),
+                                    hipMemcpyDefault, st));
         if (copy_back[i])
-            TRXS_HIP(hipMemcpyAsync(out[which[i]], res_of[i], sizeof(double) * (2 * record_stride(calls[which[i]].flags) + 1),
+            TRXS_HIP(hipMemcpyAsync(out[which[i]], res_of[i], sizeof(double) * (2 * record_stride(s.flags) + 1),
                                     hipMemcpyDeviceToHost, st));
+    }
     return TRX_OK;
 }
 
 bool chain_enabled() { return trx::knob_star_chain() != 0; }
+
+#ifdef TRX_TESTING
+// trx_debug_chain_counts (include/trx_debug.h): what trx_star_enqueue has put into launch chains so far
+std::atomic<long> g_chains{0}, g_calls_in_chains{0}, g_posterior_calls_in_chains{0};
+#endif
 
 // may call j join a chain that starts with call i?  (same stream is the caller's business)
 bool chain_compatible(const trx_scenario_args& a, const trx_scenario_args& b)
@@ -493,11 +555,10 @@ extern "C" int trx_star_enqueue(const trx_scenario_args* calls, int n_calls, dou
         hipStream_t st = static_cast<hipStream_t>(streams[i]);
         int which[trx::kChainMaxCalls];
         int n = 0, nbr = 0;
-        if (chain_enabled() && calls[i].table_rows <= 1 && calls[i].post_rows <= 0 &&
+        if (chain_enabled() && calls[i].table_rows <= 1 &&
             trx::lnl_chain_applicable(calls[i].flags, calls[i].n_time, calls[i].draw->N, calls[i].nsupersample)) {
             for (int j = i; j < n_calls && n < trx::kChainMaxCalls; ++j) {
-                if (streams[j] != streams[i] || calls[j].table_rows > 1 || calls[j].post_rows > 0 ||
-                    !chain_compatible(calls[i], calls[j])) break;
+                if (streams[j] != streams[i] || calls[j].table_rows > 1 || !chain_compatible(calls[i], calls[j])) break;
                 const int add = calls[j].draw->planet ? 1 : 2;
                 if (nbr + add > trx::kChainMaxBranchesHost) break;
                 if ((double)(n + 1) * (double)calls[i].draw->N > draw_budget && n > 0) break;
@@ -507,6 +568,11 @@ extern "C" int trx_star_enqueue(const trx_scenario_args* calls, int n_calls, dou
         }
         if (n >= 2) {
             if (int rc = enqueue_chain(calls, which, n, out, st)) return rc;
+#ifdef TRX_TESTING
+            g_chains += 1;
+            g_calls_in_chains += n;
+            for (int k = 0; k < n; ++k) g_posterior_calls_in_chains += calls[which[k]].post_rows > 0 ? 1 : 0;
+#endif
             i += n;
         } else {
             if (int rc = enqueue(&calls[i], out[i], st)) return rc;
@@ -521,6 +587,19 @@ extern "C" int trx_star_enqueue(const trx_scenario_args* calls, int n_calls, dou
 extern "C" int trx_set_star_chain(int on)
 {
     trx::g_knob_star_chain = on ? 1 : 0;
+    return TRX_OK;
+}
+
+extern "C" int trx_debug_chain_counts(long* chains, long* calls_in_chains, long* posterior_calls_in_chains, int reset)
+{
+    if (chains) *chains = g_chains.load();
+    if (calls_in_chains) *calls_in_chains = g_calls_in_chains.load();
+    if (posterior_calls_in_chains) *posterior_calls_in_chains = g_posterior_calls_in_chains.load();
+    if (reset) {
+        g_chains = 0;
+        g_calls_in_chains = 0;
+        g_posterior_calls_in_chains = 0;
+    }
     return TRX_OK;
 }
 #endif

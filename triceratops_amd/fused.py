@@ -148,6 +148,11 @@ POST_MAX_ROWS = _lib.POST_MAX_ROWS
 POSTERIOR_KEYS = ("M_s", "R_s", "u1", "u2", "P_orb", "inc", "b", "R_p", "ecc", "argp", "M_EB", "R_EB", "fluxratio_EB",
                   "fluxratio_comp", "lnw", "row")
 _POST_SALT = 0x706F7374       # post_seed = _mix(the call's draw seed, this): no generator is advanced
+# calc_posteriors_many(keep="summary"): a tuple of quantile levels q.  The rank that evaluated a unit then reduces every
+# scenario row's samples to len(q) quantiles of the 14 physical columns BEFORE the table is gathered
+# (sharding._run_units: 14 len(q) columns per row instead of 16 M).  None: the rows carry their samples.
+POSTERIOR_SUMMARY = None
+POSTERIOR_PARAMS = POSTERIOR_KEYS[:14]      # the physical columns (POSTERIOR_KEYS less lnw, row)
 
 
 def posterior_to_flat(post, M):
@@ -166,6 +171,22 @@ def posterior_from_flat(flat, M):
     post = {k: flat[i * M:(i + 1) * M].copy() for i, k in enumerate(POSTERIOR_KEYS)}
     post["row"] = post["row"].astype(np.int64)
     return post
+
+
+def posterior_quantiles_to_flat(post, q):
+    """a "posterior" dict (or None) as 14 * len(q) doubles: np.quantile(post[c], q) for c in POSTERIOR_PARAMS, one
+    column after the other; NaN where the row has no samples"""
+    if post is None:
+        return np.full(len(POSTERIOR_PARAMS) * len(q), np.nan)
+    return np.concatenate([np.quantile(post[c], q) for c in POSTERIOR_PARAMS])
+
+
+def posterior_quantiles_from_flat(flat, n_q):
+    """the inverse: dict column -> [n_q] array, or None for a row of NaN"""
+    flat = np.asarray(flat, dtype=np.float64)
+    if n_q == 0 or flat.size != len(POSTERIOR_PARAMS) * n_q or np.isnan(flat[0]):
+        return None
+    return {c: flat[i * n_q:(i + 1) * n_q].copy() for i, c in enumerate(POSTERIOR_PARAMS)}
 
 
 def _fn_scenario():

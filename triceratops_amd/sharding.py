@@ -81,6 +81,9 @@ scratch_budget_bytes = float(os.environ.get("TRX_SCRATCH_GB", "48")) * 1e9
 
 def stream_scratch_bytes(n_draws):
     """estimate of the library's scratch per stream for calls of n_draws draws (see scratch_budget_bytes)"""
+    # (posterior rows in a chain add 49 KB per branch and at most 1 MB per call -- csrc/trx_scenario.hip, enqueue_chain --
+    # to draw-side buffers of 146 bytes per draw for which 360 are booked here: the margin covers them from N = 5000 on,
+    # and the cap below only binds from N ~ 1e6)
     per_call = (0.36e9 + 1.5 * 0.16e9) * n_draws / 1e6
     calls = max(1.0, min(float(chain_calls), 2.5e7 / max(n_draws, 1)))
     return calls * per_call
@@ -201,10 +204,30 @@ def _as_dicts(rec):
     out = tuple({c: rec[i, j] for j, c in enumerate(RECORD_COLS)} for i in range(rec.shape[0]))
     wide = rec.shape[1] - len(RECORD_COLS) - len(MOMENT_COLS)
     if wide > 0:
-        # (a pass with fused.POSTERIOR_ROWS = M: 16 M more columns per scenario row)
         from . import fused as _fused
+        q = _fused.POSTERIOR_SUMMARY
         for i, d in enumerate(out):
-            d["posterior"] = _fused.posterior_from_flat(rec[i, rec.shape[1] - wide:], wide // 16)
+            if q is not None:
+                # (a summary pass: 14 len(q) more columns, the row's quantiles)
+                d["posterior_quantiles"] = _fused.posterior_quantiles_from_flat(rec[i, rec.shape[1] - wide:], len(q))
+            else:
+                # (a pass with fused.POSTERIOR_ROWS = M: 16 M more columns per scenario row)
+                d["posterior"] = _fused.posterior_from_flat(rec[i, rec.shape[1] - wide:], wide // 16)
+    return out
+
+
+def _summarise(rec, post_rows, q):
+    """rows of a unit as its owner has them -- RECORD_COLS, MOMENT_COLS, then 16 M columns of samples -- with the
+    samples of every row reduced to len(q) quantiles of the 14 physical columns (fused.posterior_quantiles_to_flat on
+    the dict fused.posterior_from_flat gives: the dict target.posterior would hold)"""
+    from . import fused as _fused
+    narrow = len(RECORD_COLS) + len(MOMENT_COLS)
+    out = np.full((rec.shape[0], narrow + len(_fused.POSTERIOR_PARAMS) * len(q)), np.nan)
+    have = min(narrow, rec.shape[1])
+    out[:, :have] = rec[:, :have]
+    if rec.shape[1] > narrow:
+        for i in range(rec.shape[0]):
+            out[i, narrow:] = _fused.posterior_quantiles_to_flat(_fused.posterior_from_flat(rec[i, narrow:], post_rows), q)
     return out
 
 
@@ -326,9 +349,18 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
     from . import fused as _fused
     # with posterior rows (fused.POSTERIOR_ROWS = M > 0) a scenario row carries its samples as 16 M more columns
     # (fused.POSTERIOR_KEYS order, NaN where the row has none): they ride in the ONE all_gather below
+    # -- or, with fused.POSTERIOR_SUMMARY = q (calc_posteriors_many(keep="summary")), 14 len(q) columns: the unit's owner
+    # reduces the samples to quantiles as its records come in (put below), before the gather
     post_rows = int(_fused.POSTERIOR_ROWS)
+    summary_q = _fused.POSTERIOR_SUMMARY if post_rows else None
     narrow = len(RECORD_COLS) + len(MOMENT_COLS)
-    table = np.full((total, narrow + 16 * post_rows), np.nan)
+    wide = 16 * post_rows if summary_q is None else len(_fused.POSTERIOR_PARAMS) * len(summary_q)
+    table = np.full((total, narrow + wide), np.nan)
+
+    def put(k, rec):
+        if summary_q is not None:
+            rec = _summarise(rec, post_rows, summary_q)
+        table[offs[k]:offs[k] + rows[k], :rec.shape[1]] = rec
     ncol = len(RECORD_COLS)
     mine_k = [k for k in live if owner[k] == rank]
 
@@ -361,11 +393,12 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
                 table[offs[k]:offs[k] + rows[k], ncol:narrow] = mom
             if post_rows:
                 for i, d in enumerate(res if isinstance(res, tuple) else (res,)):
-                    table[offs[k] + i, narrow:] = _fused.posterior_to_flat(d.get("posterior"), post_rows)
+                    table[offs[k] + i, narrow:] = (_fused.posterior_to_flat(d.get("posterior"), post_rows) if summary_q is None
+                                                   else _fused.posterior_quantiles_to_flat(d.get("posterior"), summary_q))
 
     def resolve():
         for k, rec in _fused.records_to_rows(pending).items():
-            table[offs[k]:offs[k] + rows[k], :rec.shape[1]] = rec
+            put(k, rec)
 
     on_device = _fused.threadable() or _fused.staged_native()
     if on_device:
@@ -450,7 +483,7 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
                 if upto > at:
                     got = _fused.records_to_rows(pending[at:upto])
                     for k, rec in got.items():
-                        table[offs[k]:offs[k] + rows[k], :rec.shape[1]] = rec
+                        put(k, rec)
                     at = upto
                     if job_done is not None:
                         for k in got:
@@ -466,7 +499,7 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
             timing["wait_s"] = t_wait
             if at < len(pending):
                 for k, rec in _fused.records_to_rows(pending[at:]).items():
-                    table[offs[k]:offs[k] + rows[k], :rec.shape[1]] = rec
+                    put(k, rec)
         finally:
             if not drained:
                 # a call failed after others were enqueued: their kernels and record copies still use the

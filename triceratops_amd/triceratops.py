@@ -231,9 +231,17 @@ class target:
         """Quantiles of every scenario's posterior samples (calc_posteriors): a DataFrame with one row per scenario
         that has samples -- ID, scenario, prob, then <param>_q<100 q> for every physical column.  The samples are
         equally weighted, so these are plain np.quantile values."""
+        self._finish_pending()
         post = self.__dict__.get("posterior")
-        if post is None:
+        stored = self.__dict__.get("posterior_quantiles")
+        if post is None and stored is None:
             raise ValueError("no posterior samples: run calc_posteriors first")
+        if post is None:
+            # (calc_posteriors_many(keep="summary"): the quantiles were taken where the samples were; the samples are gone)
+            if tuple(float(x) for x in q) != tuple(self._posterior_q):
+                raise ValueError("this target holds the quantiles %r only (calc_posteriors_many(keep='summary')): "
+                                 "ask for those, or keep the samples" % (tuple(self._posterior_q),))
+            post = stored
         cols = self._probs_columns
         out = []
         for j, p in enumerate(post):
@@ -241,7 +249,7 @@ class target:
                 continue
             row = {"ID": cols["ID"][j], "scenario": cols["scenario"][j], "prob": cols["prob"][j]}
             for c in _POSTERIOR_PARAMS:
-                for qq, v in zip(q, np.quantile(p[c], q)):
+                for qq, v in zip(q, p[c] if post is stored else np.quantile(p[c], q)):
                     row["%s_q%g" % (c, 100 * qq)] = v
             out.append(row)
         return DataFrame(out)
@@ -250,7 +258,11 @@ class target:
         """n draws from the model-averaged posterior: a scenario in proportion to its `prob`, then one of its
         (equally weighted) samples.  DataFrame of n rows: `scenario`, `ID`, and the physical columns.  Scenarios
         without samples contribute nothing (their probability is zero or was dropped).  Host side, numpy only."""
+        self._finish_pending()            # (a table left to its first reader: calc_posteriors_many on several ranks)
         post = self.__dict__.get("posterior")
+        if post is None and self.__dict__.get("posterior_quantiles") is not None:
+            raise ValueError("this target holds quantiles only (calc_posteriors_many(keep='summary')): the samples are "
+                             "gone -- run calc_posteriors_many(keep='samples') to draw from them")
         if post is None:
             raise ValueError("no posterior samples: run calc_posteriors first")
         rng = np.random.default_rng() if rng is None else rng
@@ -285,7 +297,8 @@ class target:
             raise ValueError("n_runs must be >= 1")
         from . import fused
         if fused.POSTERIOR_ROWS:
-            raise NotImplementedError("posterior rows are not available in calc_probs_runs: use calc_posteriors")
+            raise NotImplementedError("posterior rows are not available in calc_probs_runs (repeated runs with posteriors "
+                                      "are not built): use calc_posteriors, or calc_posteriors_many for a batch")
         kw = dict(calc_probs_kwargs)
         verbose = kw.pop("verbose", 0)
         prepared = [self._prepare(time, flux_0, flux_err_0, P_orb, job=r, **kw) for r in range(n_runs)]
@@ -347,12 +360,13 @@ class target:
         weight = float(N) * max(1, time.size)
         return [u[:6] + (weight, int(N), (job, u[6])) for u in units], n_scen
 
-    def _finish(self, units, results, n_scen, warn=True):
+    def _finish(self, units, results, n_scen, warn=True, summary_q=None):
         """Scenario table, normalised probabilities, FPP and NFPP from the per-unit results
         (triceratops.py:1430-1485).  Plain arrays here; the `.probs` DataFrame of the reference is put
         together when it is first read (a batch of 64 targets spent as long building 64 DataFrames nobody
         had asked for yet as waiting for the GPU).  warn = False: the caller has already raised the
-        reference's RuntimeWarnings for these evidences (_defer_finish)."""
+        reference's RuntimeWarnings for these evidences (_defer_finish).  summary_q: the rows carry len(summary_q)
+        quantiles of every posterior column instead of the samples (calc_posteriors_many(keep="summary"))."""
         self.__dict__["_pending_finish"] = None
         targets = np.zeros(n_scen, dtype=np.dtype("i8"))
         star_num = np.zeros(n_scen, dtype=np.dtype("i8"))
@@ -363,6 +377,7 @@ class target:
         ncol = len(sharding.RECORD_COLS)
         lnM2 = np.full(n_scen, np.nan)               # the evidences' moments (sharding.MOMENT_COLS), NaN = unknown
         posterior = [None] * n_scen                  # calc_posteriors: the samples of every scenario row
+        quantiles = [None] * n_scen                  # ... or, in summary mode, their quantiles
         lnWmax = np.full(n_scen, np.nan)
         n_draws = np.full(n_scen, np.nan)            # N of each row's lnZ_* call (units of target._prepare)
         for u, res in zip(units, results):
@@ -383,10 +398,14 @@ class target:
                 if res.shape[1] >= ncol + 2:
                     lnM2[j0:j0 + nb], lnWmax[j0:j0 + nb] = res[:, ncol], res[:, ncol + 1]
                 if res.shape[1] > ncol + 2:
-                    # (16 M more columns: the row's posterior samples, fused.POSTERIOR_KEYS order)
                     from . import fused
                     for i in range(nb):
-                        posterior[j0 + i] = fused.posterior_from_flat(res[i, ncol + 2:], (res.shape[1] - ncol - 2) // 16)
+                        if summary_q is not None:
+                            # (14 len(q) more columns: the quantiles of the row's posterior samples)
+                            quantiles[j0 + i] = fused.posterior_quantiles_from_flat(res[i, ncol + 2:], len(summary_q))
+                        else:
+                            # (16 M more columns: the row's posterior samples, fused.POSTERIOR_KEYS order)
+                            posterior[j0 + i] = fused.posterior_from_flat(res[i, ncol + 2:], (res.shape[1] - ncol - 2) // 16)
                 continue
             for off, name in enumerate(names):
                 j = j0 + off
@@ -399,6 +418,8 @@ class target:
                     best[c][j] = r[c]
                 lnZ[j] = r["lnZ"]
                 posterior[j] = r.get("posterior") if isinstance(r, dict) else None
+                if summary_q is not None and isinstance(r, dict):
+                    quantiles[j] = r.get("posterior_quantiles")
         if rec_tab is not None:
             for i, c in enumerate(sharding.RECORD_COLS[:-1]):
                 best[c] = best[c] + rec_tab[:, i]         # (rows of dict-valued or dropped units stay as filled above)
@@ -415,7 +436,9 @@ class target:
             "prob": relative_probs}
         self._probs = None
         self.lnZ = lnZ
-        self.posterior = posterior
+        self.posterior = posterior if summary_q is None else None
+        self.posterior_quantiles = quantiles if summary_q is not None else None
+        self._posterior_q = None if summary_q is None else tuple(float(x) for x in summary_q)
         self.star_num = star_num
         self.u1 = best["u1"]
         self.u2 = best["u2"]
@@ -470,9 +493,9 @@ class target:
     # what _finish sets: a target whose table is still to be filled (calc_probs_many on several ranks) has none of them
     _RESULTS = ("lnZ", "star_num", "u1", "u2", "fluxratio_EB", "fluxratio_comp", "FPP", "NFPP", "FPP_degenerate",
                 "_probs_columns", "_probs", "ess", "lnZ_err", "w_max_frac", "FPP_err", "NFPP_err", "_mc_inputs", "_mc",
-                "posterior")
+                "posterior", "posterior_quantiles", "_posterior_q")
 
-    def _defer_finish(self, units, results, n_scen):
+    def _defer_finish(self, units, results, n_scen, summary_q=None):
         """The table of this target is filled when one of its results is first read (calc_probs_many on several
         ranks: the targets another rank evaluated).  What is kept is DATA only -- per unit (first row, names, star
         number, ID) and a copy of its own records -- not the units' closures over light curves and star tables nor
@@ -486,7 +509,7 @@ class target:
         # sharding.unit_draws)
         slim = [tuple(u[:4]) + (None,) + tuple(u[5:]) for u in units]
         kept = [None if r is None else (np.array(r, copy=True) if isinstance(r, np.ndarray) else r) for r in results]
-        d["_pending_finish"] = (slim, kept, n_scen)
+        d["_pending_finish"] = (slim, kept, n_scen, summary_q)
         lnz = np.full(n_scen, 0.0)
         for u, r in zip(slim, kept):
             if r is None:
@@ -503,7 +526,7 @@ class target:
         pend = d.get("_pending_finish")
         if pend is not None:
             d["_pending_finish"] = None
-            self._finish(*pend, warn=False)
+            self._finish(*pend[:3], warn=False, summary_q=pend[3] if len(pend) > 3 else None)
 
     def __getattr__(self, name):
         # (only reached when normal lookup fails)
@@ -590,10 +613,55 @@ def calc_probs_many(jobs, verbose: int = 0):
     all_gather as one calc_probs; every target then gets its own table, FPP and NFPP.  On one GPU
     without per-unit seeding this is the jobs' calc_probs calls one after the other on one random
     stream."""
-    import time as _time
     from . import fused
     if fused.POSTERIOR_ROWS:
-        raise NotImplementedError("posterior rows are not available in calc_probs_many: use target.calc_posteriors")
+        raise NotImplementedError("posterior rows are not available in calc_probs_many: use calc_posteriors_many "
+                                  "(or target.calc_posteriors)")
+    return _probs_many(jobs, verbose)
+
+
+def calc_posteriors_many(jobs, n_samples: int = 1000, keep: str = "samples", q=(0.16, 0.5, 0.84), verbose: int = 0):
+    """calc_probs_many with posterior samples: the same pass over the same `jobs` -- from the same seed every table,
+    `.lnZ`, `.FPP`, `.NFPP` and error attribute is bit for bit calc_probs_many's -- in which every lnZ_* call also draws
+    n_samples of its draws in proportion to their weight in the evidence, inside the launch chains and under the same
+    sharding.  Every target ends as target.calc_posteriors leaves it.
+
+    keep="samples": `.posterior` holds the samples of every scenario row (posterior_summary, posterior_samples).  On
+    several ranks the samples ride in the pass's one all_gather: 16 n_samples doubles per scenario row.
+    keep="summary": the rank that evaluated a row reduces its samples to the quantiles `q` of the 14 physical columns
+    (np.quantile, as posterior_summary takes them) before the gather, which then carries 14 len(q) doubles per row.
+    The targets hold `.posterior_quantiles` -- per scenario row a dict column -> [len(q)] array, or None -- and
+    `.posterior = None`; posterior_summary(q) returns the same DataFrame as from the samples, for this q only."""
+    from . import fused
+    n_samples = int(n_samples)
+    if not 1 <= n_samples <= fused.POST_MAX_ROWS:
+        raise ValueError("n_samples must lie in [1, %d]" % fused.POST_MAX_ROWS)
+    if keep not in ("samples", "summary"):
+        raise ValueError("keep must be 'samples' or 'summary', not %r" % (keep,))
+    summary_q = None
+    if keep == "summary":
+        summary_q = tuple(float(x) for x in q)
+        if not summary_q or not all(0.0 <= x <= 1.0 for x in summary_q):
+            raise ValueError("q must be a non-empty sequence of quantile levels in [0, 1]")
+    saved = (fused.POSTERIOR_ROWS, fused.POSTERIOR_SUMMARY)
+    fused.POSTERIOR_ROWS, fused.POSTERIOR_SUMMARY = n_samples, summary_q
+    try:
+        out = _probs_many(jobs, verbose, summary_q)
+    finally:
+        fused.POSTERIOR_ROWS, fused.POSTERIOR_SUMMARY = saved
+    for tg in out:
+        if tg.__dict__.get("_pending_finish") is not None:
+            continue                     # (another rank's target: its table is filled when it is first read)
+        have = tg.posterior if summary_q is None else tg.posterior_quantiles
+        if all(p is None for p in have) and np.isfinite(tg.lnZ).any():
+            raise NotImplementedError("calc_posteriors_many needs the device paths (set_sampling('device') or "
+                                      "'numpy-device'): this sampling mode returns no posterior rows")
+    return out
+
+
+def _probs_many(jobs, verbose, summary_q=None):
+    """the pass of calc_probs_many / calc_posteriors_many (summary_q: the rows carry quantiles, not samples)"""
+    import time as _time
     t0 = _time.perf_counter()
     prepared = []
     for job, (tg, kw) in enumerate(jobs):
@@ -609,7 +677,7 @@ def calc_probs_many(jobs, verbose: int = 0):
     def job_done(job, res):
         t_a = _time.perf_counter()
         tg, units, n_scen = prepared[job]
-        tg._finish(units, res, n_scen)
+        tg._finish(units, res, n_scen, summary_q=summary_q)
         finished.add(job)
         t_fin[0] += _time.perf_counter() - t_a
 
@@ -623,9 +691,9 @@ def calc_probs_many(jobs, verbose: int = 0):
     for job, (tg, units, n_scen) in enumerate(prepared):
         if job not in finished:
             if many_ranks and job not in sharding.last_own_jobs:
-                tg._defer_finish(units, results[at:at + len(units)], n_scen)
+                tg._defer_finish(units, results[at:at + len(units)], n_scen, summary_q)
             else:
-                tg._finish(units, results[at:at + len(units)], n_scen)
+                tg._finish(units, results[at:at + len(units)], n_scen, summary_q=summary_q)
         at += len(units)
     # every rank lists the units of all targets (cheap: no argument is built before a unit's owner calls it)
     # and fills every target's table from the gathered records; both are a few ms for 64 targets
