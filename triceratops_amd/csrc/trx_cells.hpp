@@ -215,7 +215,8 @@ __device__ __forceinline__ double k_rule(double k, bool scalar_rule)
 //     the data tie EXACTLY (the reference's argsort orders such ties in the best-fit table);
 //   * LONG: the row constants ride in scalar registers, time stamps and fluxes are read from global
 //     memory, and the lanes sum (f-m)^2/sigma^2 directly (a perfect fit gives exactly 0); a row
-//     with a flat model takes the launch's flat-model value, so those rows tie exactly as well.
+//     with a flat model takes the launch's flat-model value, so those rows tie exactly as well.  On a uniform grid
+//     (the stencil instantiation) pass 1 walks only the trips that can hold an in-window cell: window_trips.
 // Waves per workgroup of the batched variant (rows of short light curves, several per wave).  Every wave works
 // through its own batches; what the waves of a workgroup share is read-only LDS -- the staged light curve, the
 // node tables -- so four of them hold one copy instead of four and five waves per SIMD fit the CU's 160 KB
@@ -275,6 +276,7 @@ constexpr int kCellsMaxRows = 22;
 #define TRX_BATCH_WAVES_PER_EU 5
 #endif
 constexpr int kCellsWindowLong = TRX_CELLS_WINDOW, kCellsWindowBatch = TRX_CELLS_WINDOW_BATCH;
+static_assert(kCellsWindowLong % 64 == 0 && kCellsWindowLong <= 64 * 64, "window_trips: a lane per trip, windows that begin on a trip");
 __host__ __device__ constexpr int cells_window(bool long_rows) { return long_rows ? kCellsWindowLong : kCellsWindowBatch; }
 constexpr int kCellsPairs = TRX_CELLS_PAIRS;       // (cell, node) pairs per pass (pair table in LDS)
 
@@ -396,6 +398,11 @@ constexpr int kHdrFlat = 0, kHdrStRadius = 1, kHdrStW = 2, kHdrHmin = kHdrStW + 
 // above it is a lower bound of the row's chi^2 before a single cell is looked at.  Most prior draws of a planet
 // scenario are too small for a detected signal: this settles them.
 constexpr int kHdrGrid = kHdrProbe + 1, kHdrG = kHdrGrid + 64, kHdrDoubles = kHdrG + 64;
+// Behind the fixed slots, launches that may take the stencil instantiation only: chi^2 of the flat model over every 64
+// consecutive time stamps, [(n_time + 63) / 64] -- what a window trip without a single in-window cell adds to its row
+// (cells_body, window_trips).
+constexpr int kHdrTrip = kHdrDoubles;
+__host__ __device__ inline size_t trip_sum_doubles(int n_time) { return n_time > 0 ? ((size_t)n_time + 63) / 64 : 0; }
 __host__ __device__ inline double depth_grid(int i) { return pow(10.0, -5.0 + 5.0 * (double)i / 63.0); }
 // Bounded evaluation, several launches (see cells_body, PRUNE, and launch_cells): the first kPilotRows rows are
 // evaluated to the end -- they give the launch's running bounds their first values, so that the bound bites from the
@@ -427,10 +434,11 @@ static_assert(kHdrStW + 2 * kStM + 1 <= kHdrDoubles, "launch header");
 // depend on the row count, which may only be known on the device): one 64-bit counter, then one int per row.
 __host__ __device__ inline size_t scan_list_doubles(long n_upper) { return 2 + (size_t)(n_upper + 1) / 2; }
 // A likelihood launch's scratch: [scan counter, scan list | (bounded evaluation of batches: survivor counter, survivor list,
-// probe counter, probe list) | row blocks | launch header], for a.n rows at most (a.split set).
-__host__ __device__ inline size_t launch_scratch_doubles(long n_upper, bool split)
+// probe counter, probe list) | row blocks | launch header | trip sums], for a.n rows at most (a.split set).
+// (n_time: of a launch that may take the stencil instantiation, for the trip sums behind the header; 0 = none)
+__host__ __device__ inline size_t launch_scratch_doubles(long n_upper, bool split, int n_time = 0)
 {
-    return scan_list_doubles(n_upper) * (split ? 3 : 1) + (size_t)n_upper * kRowDoubles + kHdrDoubles;
+    return scan_list_doubles(n_upper) * (split ? 3 : 1) + (size_t)n_upper * kRowDoubles + kHdrDoubles + trip_sum_doubles(n_time);
 }
 __host__ __device__ inline void set_scratch(RowsArgs& a, double* scratch)
 {
@@ -558,6 +566,21 @@ __device__ __forceinline__ void launch_header(const RowsArgs& a, const long n)
                                                      // same operation everywhere, so that flat rows tie exactly)
         }
         acc = wave_sum(acc);
+        if (a.use_stencil) {
+            // the same terms per 64 consecutive stamps (kHdrTrip), lanes = trips: a lane's 64 loads are independent
+            // of each other, so the serial loop is a few rounds of memory latency, not 64
+            const int ntrip = (int)trip_sum_doubles(a.n_time);
+            for (int b = lane; b < ntrip; b += 64) {
+                const int j1 = (64 * b + 64 < a.n_time) ? 64 * b + 64 : a.n_time;
+                double s = 0.0;
+#pragma unroll 8
+                for (int j = 64 * b; j < j1; ++j) {
+                    const double d = a.flux[j] - 1.0;
+                    s = fma(d * d, a.rs2, s);
+                }
+                hdr[kHdrTrip + b] = s;
+            }
+        }
         if (a.prune) {
             // the depth screen's table (bounded evaluation only): lane i takes depth i of the grid; the light curve goes
             // through LDS 512 points at a time (a lane reading flux[j] from memory in a serial loop waited ~200 cycles
@@ -928,6 +951,41 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Uniform time grids (the stencil instantiation, one row per wave): which 64-cell trips of the window pass over the
+// cells [win0, win1) can hold an in-window cell at all.  Of a 2000-point row of BASELINE config 1 about 760 cells lie in
+// a transit window -- 13 trips of 32 --, and the others paid a time load, the phase, its reduction and the window test
+// per cell, and a flux load and an fma for chi^2, to learn nothing.  On a uniform grid the stamps of trip L are t[0] +
+// j dt, j in [ja, jb], so the mean anomalies of its exposure centres lie in [pa, pb] = nmot (t[0] + (ja - 1, jb + 1) dt -
+// t0): one cell more on either side, delta = nmot dt, which is asked to be 8 times what the arithmetic can be off by
+// (`err`: the stamps' 4 ulp off the grid -- launch_header --, the rounding of the phase and of reduce_2pi, the window
+// test's own slack of 1e-15 |phase|).  A window that does not reach +-pi holds a cell only through ONE epoch n, as 2 pi n
+// + [wlo, whi]; the first epoch whose window ends at or behind pa is n = ceil((pa - whi) / 2 pi), and the trip can hold
+// an in-window cell only if that window begins at or before pb (no later epoch can: its window begins later still).
+// Lane L answers for trip L; the ballot is the set of trips the exact per-cell test still has to look at: a superset,
+// so the in-window list is the same cells in the same order.  Every trip is kept -- the full scan -- when the window
+// wraps round +-pi (wide windows, the hull of two passages of a very eccentric orbit), when a cell is too small a step
+// for the margin, and when anything is NaN (every comparison below is false).
+__device__ __forceinline__ unsigned long long window_trips(const double* __restrict__ tl, int n_time, int win0, int win1, int lane,
+                                                           double nmot, double t0, double wlo, double whi)
+{
+    const int ntrip = (win1 - win0 + 63) >> 6;
+    const unsigned long long all = ntrip >= 64 ? ~0ull : ((1ull << ntrip) - 1ull);
+    const double tg0 = tl[0], tg1 = tl[n_time - 1];
+    const double dt = (tg1 - tg0) / (double)(n_time - 1);             // (launch_header's)
+    const double delta = nmot * dt;
+    const double pmax = fmax(fabs(nmot * (tg0 - t0)), fabs(nmot * (tg1 - t0))) + delta;
+    const double err = 1e-12 * (pmax + kTwoPi + nmot * (fabs(tg0) + fabs(tg1) + fabs(t0)));
+    const bool ok = n_time > 1 && dt > 0.0 && nmot > 0.0 && pmax < 1e8 && delta >= 8.0 * err &&
+                    wlo > -kPi + 1e-6 && whi < kPi - 1e-6;
+    if (!ok) return all;
+    const int ja = win0 + 64 * lane;
+    const int jb = (ja + 63 < win1 - 1) ? ja + 63 : win1 - 1;
+    const double pa = nmot * (fma((double)(ja - 1), dt, tg0) - t0);
+    const double pb = nmot * (fma((double)(jb + 1), dt, tg0) - t0);
+    const double ep = ceil((pa - whi) * 0.15915494309189533577);
+    return __ballot(lane < ntrip && fma(ep, kTwoPi, wlo) <= pb);
+}
+
 // Rows per wave of the passes of the bounded evaluation over LISTED rows (batched variant: the probe pass, part 2, and
 // the survivors' pass, part 3).  ONE rule for cells_entry -- which workgroups have batches at all -- and cells_body --
 // which rows they are: two copies of it that drift apart leave batches that no workgroup evaluates (round 4's "rows
@@ -1276,9 +1334,22 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
             // cells, phase 1 the other cells of the rows still alive)
             TRX_TICK(t_p1);
             int nw = 0;
+            // (uniform grid: the trips that can hold an in-window cell, window_trips; a trip that cannot adds the flat
+            // model's chi^2 of its 64 stamps -- one number, from the launch header -- and is not walked)
+            unsigned long long trips = ~0ull;
+            if (ST && st_radius > 0.0) {
+                const RowC& c = (LONG && !TRX_LONG_ROWS_IN_LDS) ? cu : rows[0];
+                trips = window_trips(tl, n_time, win0, win1, lane, c.nmot, c.t0, rows[0].wlo, rows[0].whi);
+                if (MODE == MODE_LNL && lane < ((win1 - win0 + 63) >> 6) && !mask_bit(trips, lane))
+                    lacc += a.rowc[n * kRowDoubles + kHdrTrip + (win0 >> 6) + lane];
+            }
             for (int c0 = win0; c0 < win1; c0 += 64) {
                 const int cell = c0 + lane;
                 const bool valid = cell < win1;
+                if (ST && !((trips >> ((c0 - win0) >> 6)) & 1ull)) {
+                    if (MODE == MODE_GRID && valid) a.out[(size_t)base * n_time + cell] = a.debug_nodes ? 0.0 : hmout[0];
+                    continue;
+                }
                 int rr = 0, j = valid ? cell : 0;
                 if (!LONG) {
                     rr = valid ? (int)(((float)cell + 0.5f) * inv_nt) : (nb - 1);

@@ -484,7 +484,7 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
     // per wave.  While the stream is being captured into a hipGraph the scratch is a buffer of its own that the
     // GRAPH owns (trx::capture_scratch: the stream's buffer must not be grown, nor baked into a graph).
     void* scratch = nullptr;
-    const size_t scratch_bytes = launch_scratch_doubles(a.n, split) * sizeof(double);
+    const size_t scratch_bytes = launch_scratch_doubles(a.n, split, a.use_stencil ? a.n_time : 0) * sizeof(double);
 #ifdef TRX_CAPTURE_GRAPH_MEM
     // (A/B builds only, profiles/r06/graph_stress.py: rounds 2-5 took a pair of graph memory nodes here)
     if (capturing) TRX_HIP(hipMallocAsync(&scratch, scratch_bytes, st));
