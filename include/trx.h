@@ -322,7 +322,22 @@ typedef struct {
      * where sep_in is given the kernel takes sep_in[i] instead of interpolating.  Both NULL: the kernel's own search. */
     const double* sep_in;
     double* dm_out;
+    /* Importance map of the kernel's own uniforms, NULL = none: [TRX_WARP_DIMS][TRX_WARP_BINS + 1]
+     * doubles (device), row d = the edges of slot d (0 P, 1 q_companion, 2 R_p, 3 inc, 4 q, 5 ecc, 6 argp; slot 7, the
+     * field-star index, is never mapped), e[0] = 0, e[TRX_WARP_BINS] = 1, strictly increasing.  A uniform y the kernel
+     * generated itself for slot d becomes  b = min((int)(y 64), 63), t = y 64 - b, u = e[b] + t (e[b+1] - e[b])  (kept
+     * below 1), and the draw's lnprior gains ln J = sum over the slots the scenario consumes of log(64 (e[b+1] - e[b])),
+     * added AFTER the prior's clamp: the evidence E_y[L prior J] is that of the unmapped draws for any valid grid.  The
+     * fp32 pre-test, the mask pass and the fill pass see the same u; `dump` reports u.  A staged input is never mapped;
+     * warp with use_philox == 0 is TRX_ERR_ARG.  With the identity grid e[b] = b / 64: u == y and ln J == 0 exactly.
+     * A scenario without a prior (TRX_PRIOR_NONE) gets a prior column that holds ln J: trx_scenario_enqueue and
+     * trx_star_enqueue force want_prior on for a call with a map.  The mapped kernels are template instantiations of
+     * their own; a call without a map runs the code it ran before.  In trx_star_enqueue a call with a map and a call
+     * without one do not share a launch chain: the chain is SPLIT there (calls with maps chain among themselves). */
+    const double* warp;
 } trx_draw_args;
+#define TRX_WARP_DIMS 7
+#define TRX_WARP_BINS 64
 
 int trx_draw_scenario(const trx_draw_args* args, void* stream);
 size_t trx_draw_args_size(void);   /* sizeof(trx_draw_args): lets a foreign binding check its layout */
@@ -373,6 +388,19 @@ typedef struct {
      * or device memory.  K <= TRX_TABLE_MAX_ROWS. */
     int table_rows;
     double* table;
+    /* Histogram of the evidence's weight over the bins of the draws' uniforms (the input of an adaptive importance map,
+     * trx_draw_args.warp), NULL = none; pinned host or device memory, as `post`.  Per branch b, TRX_WARP_BRANCH 64-bit
+     * words at warp_hist + b * TRX_WARP_BRANCH:
+     *   [0] X, the branch's largest log-weight, as a double's bits   [1] the number of rows with x_i - X > -80   [2..7] 0
+     *   [8 + d * TRX_WARP_BINS + k]  the sum of floor(w_i 2^32) over the branch's masked draws whose PRE-MAP uniform y of
+     *                                slot d (recomputed from seed, draw index and slot) falls into bin k = min((int)(y 64), 63);
+     *                                w_i = exp(x_i - X) where x_i - X > -80, else 0 -- the weights of `post`
+     * Only the slots the scenario consumes from the kernel's own generator are filled (the others stay 0); needs
+     * use_philox (TRX_ERR_ARG otherwise).  Integer sums: exact, independent of order, the block repeats bit for bit.  A
+     * branch whose lnZ is +-inf or NaN gets TRX_WARP_BRANCH zeros.  The bounded evaluation stays on (an abandoned draw
+     * lies more than 90 below X: weight 0 either way); the record is that of the call without warp_hist, bit for bit.
+     * In trx_star_enqueue such a call joins a launch chain like any other (one more launch per chain). */
+    unsigned long long* warp_hist;
     /* Posterior samples: post_rows = M > 0 draws M of the branch's masked draws in proportion to their weight in the
      * evidence, w_i = exp(x_i - X) with x_i = -ln(sigma) - 0.5 ln(2 pi) - chi2half_i (+ lnprior_i), X = max x_i, and
      * w_i = 0 where x_i - X <= -80 (the evidence's own cut; NaN and -inf: 0) -- by systematic resampling: S = sum w_i,
@@ -398,6 +426,7 @@ typedef struct {
     double* post;
     unsigned long long post_seed;
 } trx_scenario_args;
+#define TRX_WARP_BRANCH (8 + TRX_WARP_DIMS * TRX_WARP_BINS)
 #define TRX_TABLE_MAX_ROWS 127
 #define TRX_TABLE_BRANCH(K) (15 * ((K) + 1))
 #define TRX_POST_MAX_ROWS 4096

@@ -484,6 +484,8 @@ def lnz_moments_from_halfchi2(h_d, lnprior_d, n_total, lnsigma):
 
 
 POST_MAX_ROWS = 4096       # TRX_POST_MAX_ROWS (include/trx.h)
+WARP_DIMS, WARP_BINS = 7, 64                  # TRX_WARP_DIMS, TRX_WARP_BINS: the importance map of trx_draw_args.warp
+WARP_BRANCH = 8 + WARP_DIMS * WARP_BINS       # TRX_WARP_BRANCH: 64-bit words of one branch's weight histogram
 
 
 def posterior_from_halfchi2(h_d, lnprior_d, lnsigma, rows, seed):

@@ -89,3 +89,97 @@ def _mc_errors(lnZ, lnM2, N, status):
     in_c[_NFPP_FIRST:] = True
     out["NFPP_err"] = ratio_err(in_c)
     return out
+
+
+# ---- adaptive importance map of the draw kernel's uniforms (trx_draw_args.warp) ----------------
+WARP_DIMS, WARP_BINS = _lib.WARP_DIMS, _lib.WARP_BINS
+
+
+def warp_identity():
+    """the identity grid: [WARP_DIMS][WARP_BINS + 1] edges b / 64 (the map returns its input, ln J = 0, exactly)"""
+    return np.tile(np.arange(WARP_BINS + 1) / WARP_BINS, (WARP_DIMS, 1))
+
+
+def warp_apply(edges, y):
+    """The kernel's map in numpy: edges [WARP_BINS + 1] of one slot, y uniforms in [0, 1) ->
+    u = e[b] + (y 64 - b) (e[b + 1] - e[b]) with b = min(int(y 64), 63), kept below 1."""
+    e = np.asarray(edges, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    s = y * WARP_BINS
+    b = np.minimum(s.astype(np.int64), WARP_BINS - 1)
+    u = e[b] + (s - b) * (e[b + 1] - e[b])
+    return np.minimum(u, np.nextafter(1.0, 0.0))
+
+
+def warp_lnj(edges, y):
+    """ln of the map's Jacobian at y: log(64 (e[b + 1] - e[b]))"""
+    e = np.asarray(edges, dtype=np.float64)
+    b = np.minimum((np.asarray(y, dtype=np.float64) * WARP_BINS).astype(np.int64), WARP_BINS - 1)
+    return np.log(WARP_BINS * (e[b + 1] - e[b]))
+
+
+def warp_hist_bins(hist):
+    """Branch blocks of trx_scenario_args.warp_hist -- [branches][TRX_WARP_BRANCH] 64-bit words (word 0 = X as a
+    double's bits), or the same as doubles with X as a value (the row columns of sharding.run_units) -- combined into
+    one [WARP_DIMS][WARP_BINS] array of weight: branch b counts with exp(X_b - max X); a branch without rows: not at
+    all."""
+    h = np.atleast_2d(np.asarray(hist))
+    if h.dtype.kind in "ui":
+        X = np.ascontiguousarray(h[:, 0]).astype(np.uint64).view(np.float64)
+        h = h.astype(np.float64)
+    else:
+        h = h.astype(np.float64)
+        X = h[:, 0]
+    live = (h[:, 1] > 0) & np.isfinite(X)
+    out = np.zeros((WARP_DIMS, WARP_BINS))
+    if not live.any():
+        return out
+    top = X[live].max()
+    for b in np.nonzero(live)[0]:
+        out += np.exp(X[b] - top) * h[b, 8:8 + WARP_DIMS * WARP_BINS].reshape(WARP_DIMS, WARP_BINS)
+    return out
+
+
+def warp_refine(edges, hist, alpha=0.5, floor=0.1):
+    """One refinement of an importance grid (the VEGAS rule, Lepage 1978 / 2021, per dimension).
+
+    edges [WARP_DIMS][WARP_BINS + 1]: the grid the histogram was taken under; hist: what warp_hist_bins takes, or the
+    [WARP_DIMS][WARP_BINS] array it returns.  Bin k of row d holds the evidence's weight of the draws whose uniform fell
+    into the k-th bin of the grid -- the weights carry the grid's Jacobian, so this is the posterior's mass between
+    edges k and k + 1.  Per dimension: normalise, smooth (d- + 6 d + d+) / 8, damp ((1 - d) / ln(1 / d)) ** alpha,
+    resplit into WARP_BINS bins of equal damped weight, then mix with the identity -- F(u) = (1 - floor) F_grid(u) +
+    floor u, new edges F^-1(b / 64) -- so that the proposal's density 1 / (64 width) is at least `floor` everywhere (a
+    bounded weight: no region of the prior is starved).  A dimension whose histogram is all zero (the scenario does
+    not consume it, or the pass found no weight) keeps its row -- the identity unless an earlier pass moved it; an
+    unused dimension would otherwise add pure noise through ln J.  A flat histogram keeps the row as well."""
+    edges = np.array(edges, dtype=np.float64)
+    d_all = np.asarray(hist, dtype=np.float64) if np.shape(hist) == (WARP_DIMS, WARP_BINS) else warp_hist_bins(hist)
+    if not 0.0 <= floor < 1.0:
+        raise ValueError("floor must lie in [0, 1)")
+    levels = np.arange(WARP_BINS + 1) / WARP_BINS
+    out = edges.copy()
+    for dim in range(WARP_DIMS):
+        d = d_all[dim]
+        total = d.sum()
+        if not (total > 0 and np.isfinite(total)):
+            continue
+        d = d / total
+        grid = edges[dim]
+        if np.ptp(d) > 0:
+            sm = np.empty_like(d)
+            sm[1:-1] = (d[:-2] + 6.0 * d[1:-1] + d[2:]) / 8.0
+            sm[0], sm[-1] = (7.0 * d[0] + d[1]) / 8.0, (d[-2] + 7.0 * d[-1]) / 8.0
+            sm = sm / sm.sum()
+            with np.errstate(divide="ignore", invalid="ignore"):
+                damp = np.where((sm > 0) & (sm < 1), ((1.0 - sm) / -np.log(sm)) ** alpha, np.where(sm >= 1, 1.0, 0.0))
+            damp = np.maximum(damp, 1e-30 * damp.max())           # (a strictly increasing cumulative sum)
+            cum = np.concatenate([[0.0], np.cumsum(damp)])
+            cum /= cum[-1]
+            grid = np.interp(levels, cum, edges[dim])
+            grid[0], grid[-1] = 0.0, 1.0
+        # F at the grid's knots: b / 64 + floor (u - b / 64); piecewise linear between them, inverted at b / 64
+        F = levels + floor * (grid - levels)
+        new = np.interp(levels, F, grid)
+        new[0], new[-1] = 0.0, 1.0
+        out[dim] = new
+    return out

@@ -281,15 +281,23 @@ __device__ __forceinline__ bool transits(double Ptra, double inc, bool parallel)
 // than once: (R_p | q, inc), (ecc, argp), (q_comp | field index, P).
 // (the struct holds the seed, not the argument block: a reference to the kernel's by-value arguments would
 // force all 1.2 KB of them into scratch memory)
+// WARP (trx_draw_args.warp, include/trx.h): a uniform of slots 0 .. 6 that the kernel generated itself goes through the
+// slot's piecewise-linear map -- `we` = the [TRX_WARP_DIMS][TRX_WARP_BINS + 1] edges, staged in LDS -- and the log of the
+// map's Jacobian collects in lnj (read by draw_one only; every slot is asked for once per draw there).  With the
+// identity edges b / 64 every step is exact: t = y 64 - b and e[b] + t / 64 have y's bits, log(64 / 64) = 0.
+// WARP = false is the code of the rounds before: `we` and `lnj` are never touched.
+constexpr int kWarpRow = TRX_WARP_BINS + 1;
+template <bool WARP>
 struct Uniforms {
     const unsigned long long seed;
     const long i;
+    const double* const we;
+    double lnj = 0.0;
     double u00, u01, u10, u11, u20, u21;
     bool d0 = false, d1 = false, d2 = false;
-    __device__ __forceinline__ Uniforms(unsigned long long seed_, long i_) : seed(seed_), i(i_) {}
-    __device__ __forceinline__ double operator()(const double* staged, unsigned slot)
+    __device__ __forceinline__ Uniforms(unsigned long long seed_, long i_, const double* we_ = nullptr) : seed(seed_), i(i_), we(we_) {}
+    __device__ __forceinline__ double raw(unsigned slot)
     {
-        if (staged) return staged[i];
         if (slot == 2u || slot == 4u || slot == 3u) {
             if (!d0) { philox_uniform2(seed, i, 16u, 0u, u00, u01); d0 = true; }
             return slot == 3u ? u01 : u00;
@@ -301,7 +309,38 @@ struct Uniforms {
         if (!d2) { philox_uniform2(seed, i, 18u, 0u, u20, u21); d2 = true; }
         return slot == 0u ? u21 : u20;
     }
+    __device__ __forceinline__ double operator()(const double* staged, unsigned slot)
+    {
+        if (staged) return staged[i];
+        const double y = raw(slot);
+        if constexpr (WARP) {
+            if (slot < (unsigned)TRX_WARP_DIMS) {
+                const double* e = we + slot * kWarpRow;
+                const double s = y * (double)TRX_WARP_BINS;
+                int b = (int)s;
+                b = b < TRX_WARP_BINS - 1 ? b : TRX_WARP_BINS - 1;
+                const double lo = e[b], width = e[b + 1] - lo;
+                lnj += log((double)TRX_WARP_BINS * width);
+                const double u = lo + (s - (double)b) * width;
+                return u < 0.99999999999999989 ? u : 0.99999999999999989;      // the largest double below 1
+            }
+        }
+        return y;
+    }
 };
+
+// the edges of a call's map in LDS (3.6 KB, WARP instantiations only); the barrier of stage_tables() covers the stores
+template <bool WARP>
+__device__ __forceinline__ const double* stage_warp(const trx_draw_args& a)
+{
+    if constexpr (WARP) {
+        __shared__ double we[TRX_WARP_DIMS * kWarpRow];
+        for (int i = threadIdx.x; i < TRX_WARP_DIMS * kWarpRow; i += blockDim.x) we[i] = a.warp[i];
+        return we;
+    } else {
+        return nullptr;
+    }
+}
 
 // ---- a cheap necessary condition for the geometry mask -------------------------------------------
 // Both masks of a scenario need cos(inc) <= P_tra and P_tra <= 1 (transits(): inc >= acos(P_tra), which no draw
@@ -355,9 +394,10 @@ __device__ __forceinline__ float stellar_radius_f(const Tables& T, float M, floa
     return (R < 0.1f) ? 0.1f : R;
 }
 
-__device__ __forceinline__ bool may_transit(const trx_draw_args& a, const Tables& T, const long i)
+template <bool WARP>
+__device__ __forceinline__ bool may_transit(const trx_draw_args& a, const Tables& T, const double* we, const long i)
 {
-    Uniforms rnd(a.seed, i);
+    Uniforms<WARP> rnd(a.seed, i, we);
     bool unsure = false;          // an input sits on a branch point of the fp64 chain: left to the fp64 mask
     // a [R_sun] = kSma (M [M_sun] P [d]^2)^(1/3)
     const float kSma = 4.2082785f, kRe = (float)(kRearth / kRsun);
@@ -452,14 +492,14 @@ __device__ __forceinline__ bool may_transit(const trx_draw_args& a, const Tables
 //            PHASE 2 where the caller says (col_at, col_stride, prior_at): compact_fill_kernel stores the masked draws
 //            DENSELY, in list order -- the likelihood kernels then read coalesced runs instead of one 64-byte line per
 //            column and row (the masked draws are one in ten: read in place they cost 700 MB of traffic per target)
-template <int PHASE>
-__device__ __forceinline__ void draw_one(const trx_draw_args& a, const Tables& T, const long i, const bool parallel,
+template <int PHASE, bool WARP>
+__device__ __forceinline__ void draw_one(const trx_draw_args& a, const Tables& T, const double* we, const long i, const bool parallel,
                                          bool& hit, bool& hit_twin, double* col_at = nullptr, long col_stride = 0,
                                          double* prior_at = nullptr)
 {
     const long N = (PHASE == 2) ? col_stride : a.N;
     hit = hit_twin = false;
-    Uniforms rnd(a.seed, i);
+    Uniforms<WARP> rnd(a.seed, i, we);
     double dP = 0.0, dQc = 0.0, dRp = 0.0, dQ = 0.0, dEcc = 0.0, dIdx = 0.0, dBeta = 0.0;
     double P = a.P_lo;
     if (a.uP || a.range_P) { dP = rnd(a.uP, 0u); P = a.P_lo + (a.P_hi - a.P_lo) * dP; }
@@ -635,6 +675,8 @@ __device__ __forceinline__ void draw_one(const trx_draw_args& a, const Tables& T
         lnprior = (lnprior > 0.0) ? 0.0 : lnprior;     // clamp_max: NaN stays NaN
         if (dm > 0.0) lnprior = -INFINITY;
     }
+    // the importance map's Jacobian, behind the clamp: it belongs to the proposal, not to the prior
+    if constexpr (WARP && PHASE != 1) lnprior += rnd.lnj;
     if (PHASE == 0 && a.dm_out) a.dm_out[i] = (dm_set || a.prior == TRX_PRIOR_FIELD) ? dm : NAN;
     if (PHASE == 0 && a.lnprior) a.lnprior[i] = lnprior;
     if (PHASE == 2 && prior_at) *prior_at = lnprior;
@@ -665,11 +707,12 @@ __device__ __forceinline__ void stage_tables(const trx_draw_args& a, Tables& T)
 // that passed follow in compact_fill_kernel.  A draw's numbers depend on its index only, so the
 // mapping of draws to threads changes no result.  (Three kernels, not one with branches: with two inlined
 // copies of the draw in one kernel the compiler moved the 1.2 KB argument block into scratch memory.)
-template <int KIND>
+template <int KIND, bool WARP>
 __device__ __forceinline__ void draw_body(const trx_draw_args& a, int* __restrict__ blk_cnt, long per)
 {
     __shared__ Tables T;
     __shared__ int wave_cnt[2][4];
+    const double* we = stage_warp<WARP>(a);
     stage_tables(a, T);
     const long N = a.N;
     const bool parallel = a.parallel != 0;
@@ -677,7 +720,7 @@ __device__ __forceinline__ void draw_body(const trx_draw_args& a, int* __restric
     if (KIND == 0) {
         for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long)gridDim.x * blockDim.x) {
             bool h0, h1;
-            draw_one<0>(a, T, i, parallel, h0, h1);
+            draw_one<0, WARP>(a, T, we, i, parallel, h0, h1);
         }
         return;
     }
@@ -685,7 +728,7 @@ __device__ __forceinline__ void draw_body(const trx_draw_args& a, int* __restric
     if (KIND == 1) {
         for (long i = (long)blockIdx.x * per + threadIdx.x; i < i_end; i += blockDim.x) {
             bool h0, h1;
-            draw_one<1>(a, T, i, parallel, h0, h1);
+            draw_one<1, WARP>(a, T, we, i, parallel, h0, h1);
             hits += h0 ? 1 : 0;
             hits_twin += h1 ? 1 : 0;
         }
@@ -701,13 +744,13 @@ __device__ __forceinline__ void draw_body(const trx_draw_args& a, int* __restric
             for (long i = c0 + threadIdx.x; i < c1; i += blockDim.x) {
                 a.mask[i] = 0;
                 if (!a.planet) a.mask_twin[i] = 0;
-                if (may_transit(a, T, i)) cand[atomicAdd(&ncand, 1)] = (int)(i - c0);
+                if (may_transit<WARP>(a, T, we, i)) cand[atomicAdd(&ncand, 1)] = (int)(i - c0);
             }
             __syncthreads();
             const int nc = ncand;
             for (int j = threadIdx.x; j < nc; j += blockDim.x) {
                 bool h0, h1;
-                draw_one<1>(a, T, c0 + cand[j], parallel, h0, h1);
+                draw_one<1, WARP>(a, T, we, c0 + cand[j], parallel, h0, h1);
                 hits += h0 ? 1 : 0;
                 hits_twin += h1 ? 1 : 0;
             }
@@ -727,19 +770,19 @@ __device__ __forceinline__ void draw_body(const trx_draw_args& a, int* __restric
     }
 }
 
-template <int KIND>
+template <int KIND, bool WARP>
 __global__ __launch_bounds__(256) void draw_kernel(trx_draw_args a, int* __restrict__ blk_cnt, long per)
 {
-    draw_body<KIND>(a, blk_cnt, per);
+    draw_body<KIND, WARP>(a, blk_cnt, per);
 }
 
 // One launch chain for several lnZ_* calls (trx_star_enqueue): the call is the grid's second dimension and its
 // argument block -- 1.2 KB, too large for several to ride in one kernel's argument buffer -- is read from a table in
 // DEVICE memory (uniform addresses: scalar loads, and none of the block is held in registers across the draw).
-template <int KIND>
+template <int KIND, bool WARP>
 __global__ __launch_bounds__(256) void draw_kernel_star(const trx_draw_args* __restrict__ tab, int* __restrict__ blk_cnt_all, long per)
 {
-    draw_body<KIND>(tab[blockIdx.y], blk_cnt_all + (long)blockIdx.y * 2 * trx::kDrawMaxGroups, per);
+    draw_body<KIND, WARP>(tab[blockIdx.y], blk_cnt_all + (long)blockIdx.y * 2 * trx::kDrawMaxGroups, per);
 }
 
 // Ordered compaction of the geometry mask(s) AND the columns / prior of the draws that passed, in one kernel
@@ -769,7 +812,7 @@ __device__ __forceinline__ void fill_wave_sync()
 // Where the masked draws' columns go (dense layout): row r of branch 0 at position r of the [ncol][N] block, row r of the
 // twin branch at position N - 1 - r (a draw passes at most one of the two masks, so the two runs never meet); the
 // prior likewise.  Draw 0 -- the stand-in for the best draw of a branch no draw passed -- goes to `cols0` [ncol].
-template <int W>
+template <int W, bool WARP>
 __device__ __forceinline__ void compact_fill_body(const trx_draw_args& a, long per, int groups, int gper,
                                                   const int* __restrict__ blk_cnt, int* __restrict__ idx0,
                                                   int* __restrict__ idx1, long* __restrict__ n_out, double* __restrict__ cols0,
@@ -799,6 +842,7 @@ __device__ __forceinline__ void compact_fill_body(const trx_draw_args& a, long p
     if (g1 == groups && g0 < groups && lane == 0) n_out[br] = at + mine;
     const bool first = chunk == 0 && br == 0;               // this wave also fills draw 0
     if (W == 1 && mine == 0 && !first) return;
+    const double* we = stage_warp<WARP>(a);
     stage_tables(a, T);                                      // (every thread of the workgroup: it ends with the barrier)
     if (mine == 0 && !first) return;
     const bool parallel = a.parallel != 0;
@@ -845,7 +889,7 @@ __device__ __forceinline__ void compact_fill_body(const trx_draw_args& a, long p
             const long at_col = br ? (N - 1 - (long)pos) : (long)pos;
             double* col_at = (pos < 0) ? cols0 + (-1 - pos) : a.cols + at_col;
             double* prior_at = (pos < 0 || !a.lnprior) ? nullptr : a.lnprior + at_col;
-            draw_one<2>(a, T, (long)hits[lane], parallel, h0, h1, col_at, (pos < 0) ? (long)n_pad : N, prior_at);
+            draw_one<2, WARP>(a, T, we, (long)hits[lane], parallel, h0, h1, col_at, (pos < 0) ? (long)n_pad : N, prior_at);
         }
         fill_wave_sync();
         int carry = 0, carry_pos = 0;
@@ -857,12 +901,13 @@ __device__ __forceinline__ void compact_fill_body(const trx_draw_args& a, long p
     }
 }
 
+template <bool WARP>
 __global__ __launch_bounds__(64) void compact_fill_kernel(trx_draw_args a, long per, int groups, int gper,
                                                           const int* __restrict__ blk_cnt, int* __restrict__ idx0,
                                                           int* __restrict__ idx1, long* __restrict__ n_out, double* __restrict__ cols0,
                                                           int n_pad)
 {
-    compact_fill_body<1>(a, per, groups, gper, blk_cnt, idx0, idx1, n_out, cols0, n_pad);
+    compact_fill_body<1, WARP>(a, per, groups, gper, blk_cnt, idx0, idx1, n_out, cols0, n_pad);
 }
 
 // chain: grid = (draw workgroups / kFillWaves, 2 branches, calls); a planet call has one branch and one draw workgroup per wave
@@ -870,6 +915,7 @@ struct FillTab {
     trx::ChainFill f[trx::kChainMaxCalls];
 };
 constexpr int kFillWaves = TRX_FILL_WAVES;
+template <bool WARP>
 __global__ __launch_bounds__(64 * kFillWaves) void compact_fill_kernel_star(const trx_draw_args* __restrict__ tab, FillTab ft, long per,
                                                                            int groups, const int* __restrict__ blk_cnt_all)
 {
@@ -878,7 +924,7 @@ __global__ __launch_bounds__(64 * kFillWaves) void compact_fill_kernel_star(cons
     if (a.planet && blockIdx.y) return;
     if ((int)blockIdx.x * kFillWaves * gper >= groups) return;
     const trx::ChainFill& f = ft.f[blockIdx.z];
-    compact_fill_body<kFillWaves>(a, per, groups, gper, blk_cnt_all + (long)blockIdx.z * 2 * trx::kDrawMaxGroups, f.idx0, f.idx1, f.n_dev,
+    compact_fill_body<kFillWaves, WARP>(a, per, groups, gper, blk_cnt_all + (long)blockIdx.z * 2 * trx::kDrawMaxGroups, f.idx0, f.idx1, f.n_dev,
                                   f.cols0);
 }
 
@@ -899,6 +945,7 @@ int check_draw_args(const trx_draw_args& a)
         if (a.range_P && !a.uP) return TRX_ERR_ARG;
     }
     if ((a.comp == TRX_COMP_FIELD || a.host == TRX_HOST_FIELD) && (!a.f_fr || (!a.idx && a.n_field_draw < 1))) return TRX_ERR_ARG;
+    if (a.warp && !a.use_philox) return TRX_ERR_ARG;        // a staged uniform is never mapped
     if (a.n_cc < 0 || a.n_cc > TRX_DRAW_MAX_CC || a.n_lut < 0 || a.n_lut > TRX_DRAW_MAX_LUT) return TRX_ERR_ARG;
     return TRX_OK;
 }
@@ -912,8 +959,10 @@ extern "C" int trx_draw_scenario(const trx_draw_args* args, void* stream)
     if (int rc = check_draw_args(a)) return rc;
     long blocks = (a.N + 255) / 256;
     if (blocks > 256L * 16) blocks = 256L * 16;
-    hipLaunchKernelGGL(draw_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a,
-                       (int*)nullptr, 0L);
+    if (a.warp) hipLaunchKernelGGL((draw_kernel<0, true>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a,
+                                   (int*)nullptr, 0L);
+    else        hipLaunchKernelGGL((draw_kernel<0, false>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a,
+                                   (int*)nullptr, 0L);
     return hipGetLastError() == hipSuccess ? TRX_OK : TRX_ERR_HIP;
 }
 
@@ -926,8 +975,13 @@ int trx::draw_counted(const trx_draw_args& a, int* blk_cnt, long* per_out, int* 
     long per = (a.N + kDrawMaxGroups - 1) / kDrawMaxGroups;
     per = ((per + 255) / 256) * 256;
     const int groups = (int)((a.N + per - 1) / per);
-    if (a.pretest) hipLaunchKernelGGL(draw_kernel<2>, dim3((unsigned)groups), dim3(256), 0, st, a, blk_cnt, per);
-    else           hipLaunchKernelGGL(draw_kernel<1>, dim3((unsigned)groups), dim3(256), 0, st, a, blk_cnt, per);
+    if (a.warp) {
+        if (a.pretest) hipLaunchKernelGGL((draw_kernel<2, true>), dim3((unsigned)groups), dim3(256), 0, st, a, blk_cnt, per);
+        else           hipLaunchKernelGGL((draw_kernel<1, true>), dim3((unsigned)groups), dim3(256), 0, st, a, blk_cnt, per);
+    } else {
+        if (a.pretest) hipLaunchKernelGGL((draw_kernel<2, false>), dim3((unsigned)groups), dim3(256), 0, st, a, blk_cnt, per);
+        else           hipLaunchKernelGGL((draw_kernel<1, false>), dim3((unsigned)groups), dim3(256), 0, st, a, blk_cnt, per);
+    }
     *per_out = per;
     *groups_out = groups;
     return hipGetLastError() == hipSuccess ? TRX_OK : TRX_ERR_HIP;
@@ -944,8 +998,10 @@ int trx::compact_fill(const trx_draw_args& a, long per, int groups, const int* b
     // (binary scenarios: two branches scan the same draws, half as many masked draws each -- two draw workgroups per wave)
     const int gper = a.planet ? 1 : 2;
     const int chunks = (groups + gper - 1) / gper;
-    hipLaunchKernelGGL(compact_fill_kernel, dim3((unsigned)chunks, a.planet ? 1u : 2u), dim3(64), 0, st, a, per, groups, gper,
-                       blk_cnt, idx0, idx1, n_dev, cols0, n_pad);
+    if (a.warp) hipLaunchKernelGGL(compact_fill_kernel<true>, dim3((unsigned)chunks, a.planet ? 1u : 2u), dim3(64), 0, st, a, per, groups,
+                                   gper, blk_cnt, idx0, idx1, n_dev, cols0, n_pad);
+    else        hipLaunchKernelGGL(compact_fill_kernel<false>, dim3((unsigned)chunks, a.planet ? 1u : 2u), dim3(64), 0, st, a, per, groups,
+                                   gper, blk_cnt, idx0, idx1, n_dev, cols0, n_pad);
     return hipGetLastError() == hipSuccess ? TRX_OK : TRX_ERR_HIP;
 }
 
@@ -958,9 +1014,10 @@ int trx::draw_chain(const trx_draw_args* host_args, const trx_draw_args* dev_tab
     const long N = host_args[0].N;
     if (N < 1) return TRX_ERR_ARG;
     bool pretest = true;
+    const bool warp = host_args[0].warp != nullptr;        // all calls of a chain or none (trx_star_enqueue splits there)
     FillTab ft{};
     for (int i = 0; i < n_calls; ++i) {
-        if (host_args[i].N != N) return TRX_ERR_ARG;
+        if (host_args[i].N != N || (host_args[i].warp != nullptr) != warp) return TRX_ERR_ARG;
         if (int rc = check_draw_args(host_args[i])) return rc;
         if (!fills[i].idx0 || !fills[i].n_dev || !fills[i].cols0 || (!host_args[i].planet && !fills[i].idx1)) return TRX_ERR_ARG;
         pretest = pretest && host_args[i].pretest;
@@ -969,10 +1026,16 @@ int trx::draw_chain(const trx_draw_args* host_args, const trx_draw_args* dev_tab
     long per = (N + kDrawMaxGroups - 1) / kDrawMaxGroups;
     per = ((per + 255) / 256) * 256;
     const int groups = (int)((N + per - 1) / per);
-    if (pretest) hipLaunchKernelGGL(draw_kernel_star<2>, dim3((unsigned)groups, (unsigned)n_calls), dim3(256), 0, st, dev_tab, blk_cnt, per);
-    else         hipLaunchKernelGGL(draw_kernel_star<1>, dim3((unsigned)groups, (unsigned)n_calls), dim3(256), 0, st, dev_tab, blk_cnt, per);
-    hipLaunchKernelGGL(compact_fill_kernel_star, dim3((unsigned)((groups + kFillWaves - 1) / kFillWaves), 2u, (unsigned)n_calls),
-                       dim3(64 * kFillWaves), 0, st, dev_tab, ft, per, groups, (const int*)blk_cnt);
+    const dim3 dgrid((unsigned)groups, (unsigned)n_calls), fgrid((unsigned)((groups + kFillWaves - 1) / kFillWaves), 2u, (unsigned)n_calls);
+    if (warp) {
+        if (pretest) hipLaunchKernelGGL((draw_kernel_star<2, true>), dgrid, dim3(256), 0, st, dev_tab, blk_cnt, per);
+        else         hipLaunchKernelGGL((draw_kernel_star<1, true>), dgrid, dim3(256), 0, st, dev_tab, blk_cnt, per);
+        hipLaunchKernelGGL(compact_fill_kernel_star<true>, fgrid, dim3(64 * kFillWaves), 0, st, dev_tab, ft, per, groups, (const int*)blk_cnt);
+    } else {
+        if (pretest) hipLaunchKernelGGL((draw_kernel_star<2, false>), dgrid, dim3(256), 0, st, dev_tab, blk_cnt, per);
+        else         hipLaunchKernelGGL((draw_kernel_star<1, false>), dgrid, dim3(256), 0, st, dev_tab, blk_cnt, per);
+        hipLaunchKernelGGL(compact_fill_kernel_star<false>, fgrid, dim3(64 * kFillWaves), 0, st, dev_tab, ft, per, groups, (const int*)blk_cnt);
+    }
     *per_out = per;
     *groups_out = groups;
     return hipGetLastError() == hipSuccess ? TRX_OK : TRX_ERR_HIP;

@@ -40,6 +40,7 @@
 #include "trx_internal.hpp"
 #include "trx_knobs.hpp"
 #include "trx_posterior.hpp"
+#include "trx_warp.hpp"
 
 namespace {
 
@@ -170,6 +171,11 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
     // posterior rows (include/trx.h): M draws per branch in proportion to their weight, selected behind the evidence
     const int M = s->post_rows;
     if (M < 0 || M > TRX_POST_MAX_ROWS || (M && !s->post)) return TRX_ERR_ARG;
+    // a weight histogram (include/trx.h): behind the evidence, like the posterior rows; the kernel's own uniforms only
+    const bool H = s->warp_hist != nullptr;
+    if (H && !d.use_philox) return TRX_ERR_ARG;
+    // a call with an importance map: its prior column carries ln J, whatever the scenario's prior
+    const int want_prior = (s->want_prior || d.warp) ? 1 : 0;
     const int n_pad = K ? K : 1;
     const int flags = s->flags | (K ? TRX_FLAG_FULL_EVALUATION : 0);
     const int stride = record_stride(s->flags);
@@ -189,11 +195,12 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
     Arena A;
     const size_t o_state = A.reserve(trx::kScratchZeroed);     // persistent: finished-block counter, the draw kernel's flag
     const size_t o_cols = A.reserve(sizeof(double) * ncol * N), o_mask = A.reserve(N), o_mask2 = A.reserve(planet ? 0 : N),
-                 o_prior = A.reserve(s->want_prior ? sizeof(double) * N : 0),
+                 o_prior = A.reserve(want_prior ? sizeof(double) * N : 0),
                  o_n = A.reserve(2 * sizeof(long)), o_cols0 = A.reserve(sizeof(double) * 16 * n_pad),
                  o_table = A.reserve(K ? sizeof(double) * 2 * TRX_TABLE_BRANCH(K) : 0),
                  o_post_ws = A.reserve(M ? 2 * trx::kPostWsBytes : 0),
                  o_post = A.reserve(M ? sizeof(double) * 2 * TRX_POST_BRANCH(M) : 0),
+                 o_hist = A.reserve(H ? sizeof(unsigned long long) * 2 * TRX_WARP_BRANCH : 0), o_hist_x = A.reserve(H ? 256 : 0),
                  o_res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1)),
                  o_ws = A.reserve(sizeof(double) * 2 * trx::kLmePart * kLmeParts), o_pv = A.reserve(sizeof(double) * 2 * kLmeParts),
                  o_pi = A.reserve(sizeof(long) * 2 * 2 * kLmeParts), o_cnt = A.reserve(sizeof(int) * 2 * trx::kDrawMaxGroups),
@@ -204,7 +211,7 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
     d.cols = A.at<double>(o_cols);
     d.mask = A.at<unsigned char>(o_mask);
     d.mask_twin = planet ? nullptr : A.at<unsigned char>(o_mask2);
-    d.lnprior = s->want_prior ? A.at<double>(o_prior) : nullptr;
+    d.lnprior = want_prior ? A.at<double>(o_prior) : nullptr;
     d.flag = reinterpret_cast<int*>(state + 1);        // zero between calls: the last branch's final stage clears it
     d.dump = nullptr;
     long* n_dev = A.at<long>(o_n);
@@ -241,6 +248,7 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
     }
     if (trx::knob_poison())          // tests: an unwritten row must show (include/trx_debug.h)
         for (int b = 0; b < nbr; ++b) TRXS_HIP(hipMemsetAsync(h[b], 0, sizeof(double) * (size_t)N, st));
+    if (H) TRXS_HIP(hipMemsetAsync(A.at<char>(o_hist), 0, sizeof(unsigned long long) * 2 * TRX_WARP_BRANCH, st));
     for (int b = 0; b < nbr; ++b) {
         const int model = planet ? TRX_MODEL_TP : (b ? TRX_MODEL_EB_TWIN : TRX_MODEL_EB);
         const double* bounds = nullptr;
@@ -264,6 +272,7 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
         fin.state = state;
         char* post_ws = M ? A.at<char>(o_post_ws) + (size_t)b * trx::kPostWsBytes : nullptr;
         if (M) fin.post_x = reinterpret_cast<double*>(post_ws + trx::kPostWsSums + trx::kPostWsCounts);
+        else if (H) fin.post_x = A.at<double>(o_hist_x) + b;
         if (int rc = trx::lme_draws(h[b], d.lnprior, s->lnsigma, N, n_dev + b, idx[b],
                                     A.at<double>(o_ws) + (size_t)b * trx::kLmePart * kLmeParts, A.at<double>(o_pv) + (size_t)b * kLmeParts,
                                     A.at<long>(o_pi) + (size_t)b * 2 * kLmeParts, bounds, fin, st))
@@ -290,7 +299,20 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
             p.block = (post_dev ? post_dev : A.at<double>(o_post)) + (size_t)b * TRX_POST_BRANCH(M);
             if (trx::post_launch(p, false, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
         }
+        if (H) {
+            trx::WarpHistArgs w{};
+            w.h = h[b]; w.lnprior = d.lnprior; w.n_dev = n_dev + b; w.idx = idx[b]; w.N = N; w.twin = b;
+            w.slots = trx::warp_consumed_slots(d);
+            w.c0 = -0.5 * log(trx::kTwoPi) - s->lnsigma;      // (lme_draws' constant)
+            w.seed = d.seed;
+            w.xmax = fin.post_x;
+            w.out = A.at<unsigned long long>(o_hist) + (size_t)b * TRX_WARP_BRANCH;
+            if (trx::warp_hist_launch(w, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
+        }
     }
+    if (H)
+        TRXS_HIP(hipMemcpyAsync(s->warp_hist, A.at<char>(o_hist), sizeof(unsigned long long) * (size_t)nbr * TRX_WARP_BRANCH,
+                                hipMemcpyDefault, st));
     if (M && !post_dev)
         TRXS_HIP(hipMemcpyAsync(s->post, A.at<double>(o_post), sizeof(double) * (size_t)nbr * TRX_POST_BRANCH(M),
                                 hipMemcpyDefault, st));
@@ -332,13 +354,17 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
     const long N = s0.draw->N;
     if (N < 1 || N > 0x7fffffffL || n < 1 || n > trx::kChainMaxCalls) return TRX_ERR_ARG;
     trx::StreamLock turn(st);
-    int nbr_total = 0, n_post = 0;         // branches; those of them that want posterior rows
+    int nbr_total = 0, n_post = 0, n_hist = 0;      // branches; those of them that want posterior rows / a weight histogram
     double* post_dev[trx::kChainMaxCalls];  // where the device writes a call's posterior block: the caller's buffer if it can
     for (int i = 0; i < n; ++i) {
         const trx_scenario_args& s = calls[which[i]];
         const int nbr = s.draw->planet ? 1 : 2, M = s.post_rows;
         if (M < 0 || M > TRX_POST_MAX_ROWS || (M && !s.post)) return TRX_ERR_ARG;
         nbr_total += nbr;
+        if (s.warp_hist) {
+            if (!s.draw->use_philox) return TRX_ERR_ARG;
+            n_hist += nbr;
+        }
         post_dev[i] = nullptr;
         if (M) {
             n_post += nbr;
@@ -357,7 +383,9 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
     const size_t o_head = A.reserve(trx::kScratchZeroed);
     // the draw-argument table and, behind it, the PostArgs of the branches that want samples: one upload
     const size_t post_tab_at = (sizeof(trx_draw_args) * (size_t)n + 255) & ~(size_t)255;
-    const size_t tab_bytes = post_tab_at + sizeof(trx::PostArgs) * (size_t)n_post;
+    // ... and the WarpHistArgs of the branches that want a histogram
+    const size_t hist_tab_at = (post_tab_at + sizeof(trx::PostArgs) * (size_t)n_post + 255) & ~(size_t)255;
+    const size_t tab_bytes = hist_tab_at + sizeof(trx::WarpHistArgs) * (size_t)n_hist;
     const size_t o_tab = A.reserve(tab_bytes);
     const size_t o_cnt = A.reserve(sizeof(int) * 2 * trx::kDrawMaxGroups * (size_t)n);
     struct CallOff { size_t cols, cols0, mask, mask2, prior, n, res, ws, pv, pi, idx[2], h[2], post; };
@@ -369,7 +397,7 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
         co[i].cols0 = A.reserve(sizeof(double) * 16);
         co[i].mask = A.reserve(N);
         co[i].mask2 = A.reserve(planet ? 0 : N);
-        co[i].prior = A.reserve(s.want_prior ? sizeof(double) * N : 0);
+        co[i].prior = A.reserve((s.want_prior || s.draw->warp) ? sizeof(double) * N : 0);
         co[i].n = A.reserve(2 * sizeof(long));
         co[i].res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1));
         co[i].ws = A.reserve(sizeof(double) * 2 * trx::kLmePart * kLmeParts);
@@ -382,6 +410,9 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
         co[i].post = A.reserve((s.post_rows && !post_dev[i]) ? sizeof(double) * 2 * TRX_POST_BRANCH(s.post_rows) : 0);
     }
     const size_t o_post_ws = A.reserve(trx::kPostWsBytes * (size_t)n_post);
+    // histograms: the branches' blocks side by side (one memset), and a place for X of a branch without posterior rows
+    const size_t o_hist = A.reserve(sizeof(unsigned long long) * TRX_WARP_BRANCH * (size_t)n_hist);
+    const size_t o_hist_x = A.reserve(sizeof(double) * (size_t)n_hist);
     const size_t o_branch = A.reserve(branch_bytes * (size_t)nbr_total);
     TRXS_HIP(trx::stream_scratch(st, 2, A.used, reinterpret_cast<void**>(&A.base)));
 
@@ -390,12 +421,14 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
     void* stage_ticket = nullptr;
     TRXS_HIP(trx::pinned_stage_begin(st, tab_bytes, reinterpret_cast<void**>(&stage), &stage_ticket));
     trx::PostArgs* post_stage = reinterpret_cast<trx::PostArgs*>(reinterpret_cast<char*>(stage) + post_tab_at);
+    trx::WarpHistArgs* hist_stage = reinterpret_cast<trx::WarpHistArgs*>(reinterpret_cast<char*>(stage) + hist_tab_at);
+    int hist_first[trx::kChainMaxCalls];       // a call's first histogram slot
     trx::ChainFill fills[trx::kChainMaxCalls];
     trx::ChainBranch br[trx::kChainMaxBranchesHost];
     trx::ScenFinal fin[trx::kChainMaxBranchesHost];
     double* res_of[trx::kChainMaxCalls];
     bool copy_back[trx::kChainMaxCalls];
-    int b_at = 0, p_at = 0;
+    int b_at = 0, p_at = 0, h_at = 0;
     for (int i = 0; i < n; ++i) {
         const trx_scenario_args& s = calls[which[i]];
         trx_draw_args d = *s.draw;
@@ -417,7 +450,8 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
         d.cols = A.at<double>(co[i].cols);
         d.mask = A.at<unsigned char>(co[i].mask);
         d.mask_twin = planet ? nullptr : A.at<unsigned char>(co[i].mask2);
-        d.lnprior = s.want_prior ? A.at<double>(co[i].prior) : nullptr;
+        d.lnprior = (s.want_prior || d.warp) ? A.at<double>(co[i].prior) : nullptr;      // (a map's ln J rides in the prior column)
+        hist_first[i] = h_at;
         d.flag = reinterpret_cast<int*>(state0 + 1);
         d.dump = nullptr;
         stage[i] = d;
@@ -473,6 +507,18 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
                 p.block = (post_dev[i] ? post_dev[i] : A.at<double>(co[i].post)) + (size_t)b * TRX_POST_BRANCH(s.post_rows);
                 post_stage[p_at++] = p;
             }
+            if (s.warp_hist) {
+                // (enqueue()'s WarpHistArgs of this branch, field by field)
+                if (!f.post_x) f.post_x = A.at<double>(o_hist_x) + h_at;
+                trx::WarpHistArgs w{};
+                w.h = c.h; w.lnprior = d.lnprior; w.n_dev = n_dev + b; w.idx = c.src_idx; w.N = N; w.twin = b;
+                w.slots = trx::warp_consumed_slots(d);
+                w.c0 = -0.5 * log(trx::kTwoPi) - s.lnsigma;
+                w.seed = d.seed;
+                w.xmax = f.post_x;
+                w.out = A.at<unsigned long long>(o_hist) + (size_t)h_at * TRX_WARP_BRANCH;
+                hist_stage[h_at++] = w;
+            }
             c.fin = &f;
         }
     }
@@ -502,8 +548,17 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
         const trx::PostArgs* post_tab = reinterpret_cast<const trx::PostArgs*>(A.base + o_tab + post_tab_at);
         if (trx::post_launch_chain(post_tab, n_post, N, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
     }
+    if (n_hist) {
+        TRXS_HIP(hipMemsetAsync(A.base + o_hist, 0, sizeof(unsigned long long) * TRX_WARP_BRANCH * (size_t)n_hist, st));
+        const trx::WarpHistArgs* hist_tab = reinterpret_cast<const trx::WarpHistArgs*>(A.base + o_tab + hist_tab_at);
+        if (trx::warp_hist_launch_chain(hist_tab, n_hist, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
+    }
     for (int i = 0; i < n; ++i) {
         const trx_scenario_args& s = calls[which[i]];
+        if (s.warp_hist)
+            TRXS_HIP(hipMemcpyAsync(s.warp_hist, A.at<unsigned long long>(o_hist) + (size_t)hist_first[i] * TRX_WARP_BRANCH,
+                                    sizeof(unsigned long long) * (size_t)(s.draw->planet ? 1 : 2) * TRX_WARP_BRANCH,
+                                    hipMemcpyDefault, st));
         if (s.post_rows && !post_dev[i])
             TRXS_HIP(hipMemcpyAsync(s.post, A.at<double>(co[i].post),
                                     sizeof(double) * (size_t)(s.draw->planet ? 1 : 2) * TRX_POST_BRANCH(s.post_rows),
@@ -527,7 +582,8 @@ bool chain_compatible(const trx_scenario_args& a, const trx_scenario_args& b)
 {
     return a.draw->N == b.draw->N && a.n_time == b.n_time && a.time == b.time && a.nsupersample == b.nsupersample &&
            a.exptime == b.exptime &&
-           ((a.flags ^ b.flags) & trx::kChainSharedFlags) == 0;
+           ((a.flags ^ b.flags) & trx::kChainSharedFlags) == 0 &&
+           (a.draw->warp != nullptr) == (b.draw->warp != nullptr);     // mapped and unmapped draw kernels: the chain splits
 }
 
 }  // namespace

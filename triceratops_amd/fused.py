@@ -98,7 +98,7 @@ class DrawArgs(ctypes.Structure):
                                       "idx", "cols", "mask", "mask_twin", "lnprior", "flag")]
                 + [("use_philox", ctypes.c_int), ("range_P", ctypes.c_int), ("n_field_draw", ctypes.c_long),
                    ("pretest", ctypes.c_int), ("seed", ctypes.c_ulonglong), ("dump", _vp),
-                   ("sep_in", _vp), ("dm_out", _vp)])
+                   ("sep_in", _vp), ("dm_out", _vp), ("warp", _vp)])
 
 
 class ScenarioArgs(ctypes.Structure):
@@ -108,7 +108,7 @@ class ScenarioArgs(ctypes.Structure):
                 ("sigma", ctypes.c_double), ("lnsigma", ctypes.c_double), ("exptime", ctypes.c_double),
                 ("flags", ctypes.c_int), ("want_prior", ctypes.c_int),
                 ("out", ctypes.POINTER(ctypes.c_double)), ("out_flag", ctypes.POINTER(ctypes.c_int)),
-                ("table_rows", ctypes.c_int), ("table", _vp),
+                ("table_rows", ctypes.c_int), ("table", _vp), ("warp_hist", _vp),
                 ("post_rows", ctypes.c_int), ("post", _vp), ("post_seed", ctypes.c_ulonglong)]
 
 
@@ -189,6 +189,35 @@ def posterior_quantiles_from_flat(flat, n_q):
     return {c: flat[i * n_q:(i + 1) * n_q].copy() for i, c in enumerate(POSTERIOR_PARAMS)}
 
 
+# Adaptive importance sampling (target.calc_probs_refined sets both for the length of a pass):
+# WARP_GRIDS = {unit: [7][65] edges}: the native lnZ_* call of work unit `unit` (sharding.run_units names the unit it is
+# evaluating: set_thread_unit) draws its uniforms through that importance map (trx_draw_args.warp); a unit without an
+# entry draws as ever.  WARP_HIST = True: every native call also returns the histogram of its evidence's weight over the
+# bins of its uniforms (trx_scenario_args.warp_hist) -- WARP_BRANCH more columns per scenario row in run_units' table:
+# X, the number of rows with weight, six zeros, then the [7][64] sums as doubles.  Needs the kernel's own random numbers.
+WARP_GRIDS = None
+WARP_HIST = False
+WARP_BRANCH = _lib.WARP_BRANCH
+
+
+def warp_identity():
+    from ._numerics import warp_identity as ident
+    return ident()
+
+
+def set_thread_unit(unit):
+    """the work unit whose lnZ_* call this thread makes next (sharding.run_units), or None"""
+    _tls.unit = unit
+
+
+def warp_hist_to_flat(words):
+    """a branch's TRX_WARP_BRANCH words (int64 / uint64) as doubles: word 0 is X's bits, the others are counts"""
+    words = np.ascontiguousarray(words).astype(np.uint64)
+    flat = words.astype(np.float64)
+    flat[0] = words[:1].view(np.float64)[0]
+    return flat
+
+
 def _fn_scenario():
     L = _lib.lib()
     if not getattr(L, "trx_bound_scenario", False):          # (per library: tests switch to the testing build and back)
@@ -221,8 +250,9 @@ class Pending:
     """one trx_scenario_enqueue call whose record has not been read yet"""
 
     def __init__(self, scen, out, stream, keep, ncol, n_time, is_host=False, table=None, table_rows=0,
-                 stride=SCENARIO_OUT, post=None, post_rows=0):
+                 stride=SCENARIO_OUT, post=None, post_rows=0, hist=None):
         self.post, self.post_rows = post, post_rows            # pinned [2][8 + 16 M] block of a call with posterior rows
+        self.hist = hist                                       # pinned [2][WARP_BRANCH] words of a call with a weight histogram
         self.scen, self.out, self.stream, self.keep, self.ncol, self.n_time = scen, out, stream, keep, ncol, n_time
         self.is_host = is_host
         self.stride = stride                                   # doubles per branch record (SCENARIO_OUT[_MOMENTS])
@@ -366,6 +396,10 @@ def records_to_rows(pending):
         if p.post_rows:
             flat = [posterior_to_flat(p.posterior(b), p.post_rows) for b in range(out[k].shape[0])]
             out[k] = np.concatenate([out[k], np.stack(flat)], axis=1)
+        if p.hist is not None:
+            # (a pass with WARP_HIST: WARP_BRANCH more columns per branch)
+            words = p.hist.numpy()
+            out[k] = np.concatenate([out[k], np.stack([warp_hist_to_flat(words[b]) for b in range(out[k].shape[0])])], axis=1)
     for _, p in pending:
         p.keep = None
     return out
@@ -423,6 +457,8 @@ def begin_deferred(n_calls):
     _tls.records = torch.empty((max(int(n_calls), 1), RECORD_MOMENTS), dtype=F64, pin_memory=True)
     _tls.next_record = 0
     _tls.batch = []
+    # (a pass with WARP_HIST: the calls' histogram blocks, one pinned allocation like the records)
+    _tls.hists = torch.empty((max(int(n_calls), 1), 2, WARP_BRANCH), dtype=torch.int64, pin_memory=True) if WARP_HIST else None
 
 
 def flush():
@@ -453,6 +489,7 @@ def flush():
 def end_deferred():
     _tls.records = None
     _tls.batch = None
+    _tls.hists = None
 
 
 def _record_slot():
@@ -691,6 +728,9 @@ class _Scenario:
         a = self.a = DrawArgs()
         a.N, a.parallel, a.flat = self.N, int(self.parallel), int(self.flat)
         self.philox = PHILOX and isinstance(dp.RNG, dp.TorchRng)
+        grids = WARP_GRIDS
+        self.warp = None if grids is None else grids.get(getattr(_tls, "unit", None))
+        self.want_hist = bool(WARP_HIST)
         if self.philox:
             a.use_philox = 1
             ts = getattr(_tls, "seed", None)
@@ -888,6 +928,8 @@ class _Scenario:
         # dump / trace hooks, and the replay of exact ties in the seeded numpy modes.
         if NATIVE and DUMP is None and _lib.TRACE is None and TABLE_ROWS <= TABLE_MAX_ROWS:
             return self._run_native(is_host, ncol)
+        if self.want_hist:
+            raise NotImplementedError("a weight histogram needs the library's own chain")
         return self.run_operator_chain(is_host, ncol)
 
     def run_operator_chain(self, is_host, ncol):
@@ -895,6 +937,14 @@ class _Scenario:
         trx_lnz_scenario per branch: the path of the 100-row tables of direct lnZ_* calls, and the cross-check of
         the library's own chain"""
         a, N, dev = self.a, self.N, self.dev
+        if self.warp is not None:
+            # (the dump / cross-check path of a mapped call: ln J rides in the prior column, whatever the scenario's prior)
+            if not self.philox:
+                raise NotImplementedError("an importance map needs set_sampling('device'): a staged uniform is never mapped")
+            grid = _lib.dev(np.ascontiguousarray(self.warp, dtype=np.float64).reshape(-1), dev)
+            self.keep.append(grid)
+            a.warp = grid.data_ptr()
+            self.want_prior = True
         cols = torch.empty((ncol, N), dtype=F64, device=dev)
         mask = torch.empty(N, dtype=torch.uint8, device=dev)
         mask2 = torch.empty(N, dtype=torch.uint8, device=dev) if not a.planet else None
@@ -989,8 +1039,24 @@ class _Scenario:
         if M:
             post = torch.empty((2, _post_branch(M)), dtype=F64).pin_memory()
             sa.post_rows, sa.post, sa.post_seed = M, post.data_ptr(), self.post_seed()
+        hist = None
+        if self.warp is not None or self.want_hist:
+            if not self.philox:
+                raise NotImplementedError("an importance map / weight histogram needs set_sampling('device'): the numpy "
+                                          "modes stage their uniforms, and a staged uniform is never mapped")
+            if self.want_hist and M:
+                raise NotImplementedError("a weight histogram and posterior rows in one pass are not built")
+        if self.warp is not None:
+            grid = _lib.dev(np.ascontiguousarray(self.warp, dtype=np.float64).reshape(-1), dev)
+            self.keep.append(grid)
+            a.warp = grid.data_ptr()
+        if self.want_hist:
+            block = getattr(_tls, "hists", None)
+            hist = (block[_tls.next_record - 1] if deferred and block is not None and _tls.next_record <= block.shape[0]
+                    else torch.empty((2, WARP_BRANCH), dtype=torch.int64).pin_memory())
+            sa.warp_hist = hist.data_ptr()
         pend = Pending(self, out, stream, self.keep + [self.time, self.flux], ncol, sa.n_time, is_host, table, K if K > 1 else 0,
-                       stride, post, M)
+                       stride, post, M, hist)
         self.keep = []
         if deferred and getattr(_tls, "batch", None) is not None:
             _tls.batch.append((sa, out, stream, dev))      # (sa.draw points at self.a: alive in the Pending)

@@ -355,6 +355,9 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
     summary_q = _fused.POSTERIOR_SUMMARY if post_rows else None
     narrow = len(RECORD_COLS) + len(MOMENT_COLS)
     wide = 16 * post_rows if summary_q is None else len(_fused.POSTERIOR_PARAMS) * len(summary_q)
+    if _fused.WARP_HIST:
+        # (a pass of calc_probs_refined: every row carries its weight histogram, fused.WARP_BRANCH more columns)
+        wide += _fused.WARP_BRANCH
     table = np.full((total, narrow + wide), np.nan)
 
     def put(k, rec):
@@ -380,10 +383,12 @@ def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=Fal
                 import torch
                 torch.manual_seed(unit_seed)         # staged draws from torch's generator
         mark = _lib.moments_mark()                   # (the moments this unit's evidences report: fused / ml)
+        _fused.set_thread_unit(k)                    # (calc_probs_refined keeps an importance grid per unit)
         try:
             res = fn()
         finally:
             _fused.set_thread_seed(None)
+            _fused.set_thread_unit(None)
         mom = _lib.moments_since(mark)
         if isinstance(res, _fused.Pending):
             pending.append((k, res))                 # list.append is atomic: worker threads share it

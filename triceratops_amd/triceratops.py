@@ -227,6 +227,83 @@ class target:
                                       "'numpy-device'): this sampling mode returns no posterior rows")
         return
 
+    def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
+                           n_samples: int = 0, alpha: float = 0.5, floor: float = 0.1, **calc_probs_kwargs):
+        """calc_probs by adaptive importance sampling: n_adapt adaptation passes of N_adapt draws
+        each (default: N), then one final pass of N draws that fills the target exactly as calc_probs does -- and, with
+        n_samples > 0, `.posterior` as calc_posteriors does.
+
+        Every continuous random input of a draw is the inverse-CDF transform of one uniform, so in the space of those
+        uniforms the prior is the constant 1 on the unit cube.  Each lnZ_* call (work unit) keeps a per-dimension
+        piecewise-linear map of that cube (a VEGAS grid of 64 bins for each of P, q_companion, R_p, inc, q, ecc and argp;
+        the identity at first); an adaptation pass returns the histogram of its evidence's weight over the bins, and
+        _numerics.warp_refine(alpha, floor) moves the edges so that the next pass draws mostly where the weight is.  The
+        map's Jacobian enters every weight, so any grid gives the same expectation; only the final pass -- whose grids
+        are fixed by independent earlier draws -- enters the result: the estimate is unbiased.  Every pass draws from the
+        generator's running stream, as consecutive calc_probs calls do.  `.refine_history` holds, per pass, the rows'
+        lnZ, ess and w_max_frac.  n_adapt = 0 is calc_probs (calc_posteriors), bit for bit.
+
+        Needs set_sampling("device") -- the numpy modes stage their uniforms, and a staged uniform is never mapped --
+        and one rank."""
+        from . import fused
+        from ._numerics import warp_refine
+        n_adapt, n_samples = int(n_adapt), int(n_samples)
+        if n_adapt < 0:
+            raise ValueError("n_adapt must be >= 0")
+        kw = dict(calc_probs_kwargs)
+
+        def final():
+            if n_samples > 0:
+                self.calc_posteriors(time, flux_0, flux_err_0, P_orb, n_samples=n_samples, **kw)
+            else:
+                self.calc_probs(time, flux_0, flux_err_0, P_orb, **kw)
+
+        def snapshot():
+            return {"lnZ": np.array(self.lnZ), "ess": np.array(self.ess), "w_max_frac": np.array(self.w_max_frac)}
+
+        if n_adapt == 0:
+            final()
+            self.refine_history = [snapshot()]
+            return
+        if not fused.threadable() or not fused.NATIVE:
+            raise NotImplementedError("calc_probs_refined needs set_sampling('device'): the numpy sampling modes stage "
+                                      "their uniforms, and a staged uniform is never mapped")
+        if sharding._dist() is not None:
+            raise NotImplementedError("calc_probs_refined on several ranks is not built: the grids would have to follow "
+                                      "the schedule")
+        kw_adapt = dict(kw)
+        verbose = kw_adapt.pop("verbose", 1)
+        if N_adapt is not None:
+            kw_adapt["N"] = int(N_adapt)
+        narrow = len(sharding.RECORD_COLS) + len(sharding.MOMENT_COLS)
+        grids = {}                       # work unit -> [7][65] edges (kept per (star, call), not per target)
+        history = []
+        saved = (fused.WARP_GRIDS, fused.WARP_HIST, fused.POSTERIOR_ROWS)
+        try:
+            fused.POSTERIOR_ROWS = 0
+            for _ in range(n_adapt):
+                units, n_scen = self._prepare(time, flux_0, flux_err_0, P_orb, **kw_adapt)
+                fused.WARP_GRIDS, fused.WARP_HIST = grids, True
+                rows = sharding.run_units(units, verbose=verbose, as_rows=True)
+                fused.WARP_HIST = False
+                for k, rec in enumerate(rows):
+                    if rec is None:
+                        continue
+                    hist = rec[:, narrow:narrow + fused.WARP_BRANCH]
+                    if rec.shape[1] < narrow + fused.WARP_BRANCH or np.isnan(hist[:, 1]).any():
+                        raise NotImplementedError("calc_probs_refined needs the library's own chain "
+                                                  "(set_sampling('device')): this pass returned no weight histograms")
+                    grids[k] = warp_refine(grids.get(k, fused.warp_identity()), hist, alpha=alpha, floor=floor)
+                self._finish(units, [None if r is None else r[:, :narrow] for r in rows], n_scen, warn=False)
+                history.append(snapshot())
+            fused.WARP_GRIDS = grids
+            final()
+            history.append(snapshot())
+        finally:
+            fused.WARP_GRIDS, fused.WARP_HIST, fused.POSTERIOR_ROWS = saved
+        self.refine_history = history
+        return
+
     def posterior_summary(self, q=(0.16, 0.5, 0.84)):
         """Quantiles of every scenario's posterior samples (calc_posteriors): a DataFrame with one row per scenario
         that has samples -- ID, scenario, prob, then <param>_q<100 q> for every physical column.  The samples are
