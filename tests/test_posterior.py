@@ -131,11 +131,11 @@ def _fake_units(M, n_stars=3, drop=("PEB",)):
         return run
 
     for key, names, j0, snum in _TARGET_CALLS:
-        units.append((j0, names, snum, 111, None if key in drop else thunk(len(names), j0), key))
+        units.append(sharding.Unit(j0, names, snum, 111, None if key in drop else thunk(len(names), j0), key))
     for i in range(1, n_stars):
         j0 = 15 + 3 * (i - 1)
-        units.append((j0, ("NTP",), 1, 200 + i, thunk(1, j0), "NTP"))
-        units.append((j0 + 1, ("NEB", "NEBx2P"), 1, 200 + i, thunk(2, j0 + 1), "NEB"))
+        units.append(sharding.Unit(j0, ("NTP",), 1, 200 + i, thunk(1, j0), "NTP"))
+        units.append(sharding.Unit(j0 + 1, ("NEB", "NEBx2P"), 1, 200 + i, thunk(2, j0 + 1), "NEB"))
     return units
 
 
@@ -225,9 +225,9 @@ def test_without_posterior_rows_the_table_and_the_message_are_unchanged():
     assert all(r.shape[1] == narrow for r in single if r is not None)
     (_, res0, sent0), (_, res1, sent1) = _gloo(0)
     # header row + the larger share of the 17 scenario rows of these units, 17 doubles each
-    shares = [sum(len(u[1]) for u, o in zip([u for u in _fake_units(0) if u[4] is not None],
-                                              sharding.schedule([sharding._COST.get(u[5], 1.0) for u in _fake_units(0)
-                                                                 if u[4] is not None], 2)) if o == r) for r in range(2)]
+    shares = [sum(len(u.names) for u, o in zip([u for u in _fake_units(0) if u.thunk is not None],
+                                                sharding.schedule([sharding.unit_cost(u) for u in _fake_units(0)
+                                                                   if u.thunk is not None], 2)) if o == r) for r in range(2)]
     assert sent0 == sent1 == [(1 + max(shares)) * narrow]
     for a, b, c in zip(res0, res1, single):
         assert _same(a, b) and _same(a, c)

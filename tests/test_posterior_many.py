@@ -74,6 +74,7 @@ def test_summary_mode_gathers_quantiles_not_samples(q):
     samples = _run(M_FAKE)                               # the rows with their 16 M sample columns, one rank
     np.random.seed(4242)
     single = _run_summary(M_FAKE, q)
+    assert sharding.last_layout.width == width and sharding.last_layout.summary_q == q
     assert len(samples) == len(single)
     with_samples = 0
     for a, b in zip(samples, single):
@@ -98,6 +99,33 @@ def test_summary_mode_gathers_quantiles_not_samples(q):
     assert sent0 == sent1 == [(1 + max(shares)) * width]                               # ONE collective of that width
     for a, b, c in zip(res0, res1, single):
         assert _same(a, b) and _same(a, c)
+
+
+def test_row_layout_is_the_column_arithmetic_done_by_hand():
+    """record 15, moments 2, then 16 M sample columns or 14 len(q) quantile columns, then the histogram words"""
+    from triceratops_amd import fused
+    plain = sharding.RowLayout()
+    assert (plain.record, plain.lnZ, plain.moments, plain.width) == (slice(0, 15), 14, slice(15, 17), NARROW)
+    assert plain.extra == plain.hist == slice(NARROW, NARROW) and plain.extra_key is None
+    wide = sharding.RowLayout(post_rows=M_FAKE)
+    assert wide.extra == slice(NARROW, NARROW + 16 * M_FAKE) and wide.width == NARROW + 16 * M_FAKE
+    assert wide.extra_key == "posterior" and wide.summary_q is None
+    short = sharding.RowLayout(post_rows=M_FAKE, summary_q=Q, hist=True)
+    assert short.extra == slice(NARROW, NARROW + 14 * len(Q)) and short.extra_key == "posterior_quantiles"
+    assert short.hist == slice(NARROW + 14 * len(Q), NARROW + 14 * len(Q) + fused.WARP_BRANCH) and short.width == short.hist.stop
+    assert sharding.RowLayout(summary_q=Q).width == NARROW                  # (no samples: nothing to summarise)
+    with pytest.raises(AttributeError):
+        wide.post_rows = 3
+    # the extras round-trip, and NaN in the defining slot is None
+    post = {k: np.arange(M_FAKE) + 10.0 * i for i, k in enumerate(fused.POSTERIOR_KEYS)}
+    row = np.full(wide.width, np.nan)
+    assert wide.decode(row) is None
+    row[wide.extra] = wide.encode(post)
+    back = wide.decode(row)
+    assert back["row"].dtype == np.int64 and all(np.array_equal(back[k], post[k]) for k in post)
+    assert np.isnan(wide.encode(None)).all() and wide.encode(None).size == 16 * M_FAKE
+    pickled = pickle.loads(pickle.dumps(short))
+    assert (pickled.extra, pickled.hist, pickled.summary_q) == (short.extra, short.hist, Q)
 
 
 def test_summary_rows_as_dicts():
@@ -219,15 +247,16 @@ def test_a_deferred_table_with_quantiles_pickles():
     for name in ("posterior", "posterior_quantiles"):
         assert name in target._RESULTS
     now = target.__new__(target)
-    now._finish(units, res, 21, summary_q=Q)
+    layout = sharding.RowLayout(post_rows=M_FAKE, summary_q=Q)
+    now._finish(units, res, 21, layout=layout)
     later = target.__new__(target)
     later.posterior = "stale"
-    later._defer_finish(units, res, 21, summary_q=Q)
+    later._defer_finish(units, res, 21, layout)
     assert later.__dict__.get("_pending_finish") is not None and "posterior" not in later.__dict__
     clone = pickle.loads(pickle.dumps(later))
     assert clone.__dict__.get("_pending_finish") is None
     again = target.__new__(target)
-    again._defer_finish(units, res, 21, summary_q=Q)
+    again._defer_finish(units, res, 21, layout)
     assert again.posterior is None                           # (reading a result fills the table)
     for tg in (clone, again):
         assert tg.posterior is None and len(tg.posterior_quantiles) == 21
@@ -247,15 +276,16 @@ def test_a_deferred_table_with_samples_serves_summary_and_samples_at_first_read(
     np.random.seed(22)
     units = _fake_units(M_FAKE)                          # (the layout; _run evaluates units of its own, laid out alike)
     res = _run(M_FAKE, per_unit=False)
+    layout = sharding.RowLayout(post_rows=M_FAKE)
     now = target.__new__(target)
-    now._finish(units, res, 21)
+    now._finish(units, res, 21, layout=layout)
     want_frame = now.posterior_summary(Q)
     want_draws = now.posterior_samples(40, rng=np.random.default_rng(5))
     assert len(want_frame) > 0 and len(want_draws) == 40
 
     def deferred():
         tg = target.__new__(target)
-        tg._defer_finish(units, res, 21)
+        tg._defer_finish(units, res, 21, layout)
         assert tg.__dict__.get("_pending_finish") is not None and "posterior" not in tg.__dict__
         return tg
     first = deferred()

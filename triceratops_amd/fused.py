@@ -10,6 +10,7 @@ table.  About 15 launches per scenario branch instead of ~360.
 Host work per call: the constants of the broken power laws (priors.py:16-383), the Moe &
 Di Stefano rate constants (priors.py:601-660) and table pointers -- nothing per draw.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -150,43 +151,20 @@ POSTERIOR_KEYS = ("M_s", "R_s", "u1", "u2", "P_orb", "inc", "b", "R_p", "ecc", "
 _POST_SALT = 0x706F7374       # post_seed = _mix(the call's draw seed, this): no generator is advanced
 # calc_posteriors_many(keep="summary"): a tuple of quantile levels q.  The rank that evaluated a unit then reduces every
 # scenario row's samples to len(q) quantiles of the 14 physical columns BEFORE the table is gathered
-# (sharding._run_units: 14 len(q) columns per row instead of 16 M).  None: the rows carry their samples.
+# (sharding.RowLayout.summarise: quantile columns instead of sample columns).  None: the rows carry their samples.
 POSTERIOR_SUMMARY = None
 POSTERIOR_PARAMS = POSTERIOR_KEYS[:14]      # the physical columns (POSTERIOR_KEYS less lnw, row)
 
 
-def posterior_to_flat(post, M):
-    """a "posterior" dict (or None) as 16 * M doubles, POSTERIOR_KEYS order, NaN where absent: the extra columns of
-    sharding.run_units' table"""
-    if post is None:
-        return np.full(16 * M, np.nan)
-    return np.concatenate([np.asarray(post[k], dtype=np.float64) for k in POSTERIOR_KEYS])
-
-
 def posterior_from_flat(flat, M):
-    """the inverse of posterior_to_flat (None for a row of NaN)"""
+    """the sample columns of a row of sharding.run_units' table (sharding.RowLayout: len(POSTERIOR_KEYS) * M doubles,
+    POSTERIOR_KEYS order) as a "posterior" dict; None for a row of NaN ("lnw" is the defining slot)"""
     flat = np.asarray(flat, dtype=np.float64)
-    if flat.size != 16 * M or M == 0 or np.isnan(flat[14 * M]):
+    if flat.size != len(POSTERIOR_KEYS) * M or M == 0 or np.isnan(flat[POSTERIOR_KEYS.index("lnw") * M]):
         return None
     post = {k: flat[i * M:(i + 1) * M].copy() for i, k in enumerate(POSTERIOR_KEYS)}
     post["row"] = post["row"].astype(np.int64)
     return post
-
-
-def posterior_quantiles_to_flat(post, q):
-    """a "posterior" dict (or None) as 14 * len(q) doubles: np.quantile(post[c], q) for c in POSTERIOR_PARAMS, one
-    column after the other; NaN where the row has no samples"""
-    if post is None:
-        return np.full(len(POSTERIOR_PARAMS) * len(q), np.nan)
-    return np.concatenate([np.quantile(post[c], q) for c in POSTERIOR_PARAMS])
-
-
-def posterior_quantiles_from_flat(flat, n_q):
-    """the inverse: dict column -> [n_q] array, or None for a row of NaN"""
-    flat = np.asarray(flat, dtype=np.float64)
-    if n_q == 0 or flat.size != len(POSTERIOR_PARAMS) * n_q or np.isnan(flat[0]):
-        return None
-    return {c: flat[i * n_q:(i + 1) * n_q].copy() for i, c in enumerate(POSTERIOR_PARAMS)}
 
 
 # Adaptive importance sampling (DESIGN.md section 12; target.calc_probs_refined sets both for the length of a pass):
@@ -198,6 +176,18 @@ def posterior_quantiles_from_flat(flat, n_q):
 WARP_GRIDS = None
 WARP_HIST = False
 WARP_BRANCH = _lib.WARP_BRANCH
+
+
+@contextlib.contextmanager
+def switches(**values):
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST = ... for the length of a `with` block: what they were
+    before -- a user's own setting included -- comes back on exit, also on an error"""
+    saved = {name: globals()[name] for name in values}
+    globals().update(values)
+    try:
+        yield
+    finally:
+        globals().update(saved)
 
 
 def warp_identity():
@@ -357,6 +347,7 @@ def records_to_rows(pending):
     synchronised."""
     if not pending:
         return {}
+    from .sharding import RECORD_COLS, RowLayout
     W = SCENARIO_OUT_MOMENTS
     recs = np.stack([_widen(p.out.numpy(), p.stride) for _, p in pending])      # [calls][41]
     if np.any(recs[:, 2 * W] != 0.0):
@@ -375,10 +366,9 @@ def records_to_rows(pending):
                 res = p.scen.run_operator_chain(p.is_host, p.ncol)
             p.stream.synchronize()
             dicts = res if isinstance(res, tuple) else (res,)
-            from .sharding import RECORD_COLS
             mom = p.scen.moments or [(np.nan, np.nan)] * len(dicts)
             redo[k] = np.array([[d[c] if c == "lnZ" else d[c][0] for c in RECORD_COLS] + list(m)
-                                + (list(posterior_to_flat(d.get("posterior"), p.post_rows)) if p.post_rows else [])
+                                + (list(RowLayout(p.post_rows).encode(d.get("posterior"))) if p.post_rows else [])
                                 for d, m in zip(dicts, mom)])
         with _stats_lock:
             _lib.STATS["native_calls"] += len(replay)
@@ -391,10 +381,10 @@ def records_to_rows(pending):
     n_time = np.array([p.n_time for _, p in pending])
     out = {}
     _rows_fill(pending, recs, planet, n_time, out)
-    # (calls with posterior rows: 16 M more columns per branch, sharding.run_units' wide table)
+    # (calls with posterior rows: the extra columns of sharding.RowLayout, then -- WARP_HIST -- its histogram columns)
     for k, p in pending:
         if p.post_rows:
-            flat = [posterior_to_flat(p.posterior(b), p.post_rows) for b in range(out[k].shape[0])]
+            flat = [RowLayout(p.post_rows).encode(p.posterior(b)) for b in range(out[k].shape[0])]
             out[k] = np.concatenate([out[k], np.stack(flat)], axis=1)
         if p.hist is not None:
             # (a pass with WARP_HIST: WARP_BRANCH more columns per branch)

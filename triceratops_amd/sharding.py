@@ -22,10 +22,12 @@ of a calc_probs; every rank's base rides in its chunk's header row and is kept i
 equal = the run can be repeated from the seed).
 """
 import os
+from typing import NamedTuple
 
 import numpy as np
 
 from . import _lib
+from . import fused as _fused
 
 RECORD_COLS = ("M_s", "R_s", "u1", "u2", "P_orb", "inc", "b", "R_p", "ecc", "argp", "M_EB",
                "R_EB", "fluxratio_EB", "fluxratio_comp", "lnZ")
@@ -60,6 +62,7 @@ last_seed_bases = None
 # what the schedule of the last run_units gave every rank: lnZ_* calls, distinct (job, star)s and distinct jobs
 last_share = {"calls": [0], "stars": [0], "jobs": [0]}
 last_own_jobs = set()
+last_layout = None              # the RowLayout of the last run_units pass: what its rows' columns are
 _warned_bases = False
 # Opt-in (advisor, round 5): True makes the first device pass call gc.freeze() once -- every object alive then moves to
 # the collector's permanent generation, so that the full collection which follows a held-off pass looks at the pass's own
@@ -106,7 +109,6 @@ _COST = {"TP": 1.0, "PTP": 1.1, "STP": 1.2, "DTP": 1.1, "BTP": 1.2, "NTP": 1.0,
 
 def _draw_base():
     """one 31-bit seed base from the host generator that governs the current sampling mode"""
-    from . import fused as _fused
     if _fused.threadable():
         import torch
         return int(torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int64).item())
@@ -181,13 +183,85 @@ def schedule(costs, world, groups=None):
     return owner
 
 
-# fields of a work unit (run_units' docstring) read by name elsewhere
-UNIT_DRAWS = 7          # N: the Monte-Carlo draws of the unit's lnZ_* call (units of target._prepare)
+class Unit(NamedTuple):
+    """One (star, lnZ_* call) work unit of run_units.  A plain tuple underneath: units built by hand with the first six
+    fields (the tests') are coerced with Unit(*u), and a unit pickles and unpacks like the tuple it is."""
+    first_row: int          # of the unit's scenario rows in its target's table
+    names: tuple            # the scenarios of those rows: one per branch of the call
+    star_num: int
+    ID: object
+    thunk: object           # () -> result dict(s) or fused.Pending; None: a dropped scenario
+    key: str                # the drop key, and the call's relative cost (_COST)
+    weight: float = 1.0     # scales that cost in the schedule (calc_probs_many: jobs of different sizes)
+    draws: int = None       # N of the lnZ_* call (stream scratch, the error attributes); None: the unit does not say
+    group: tuple = None     # (job, star): the schedule deals whole jobs and whole stars first
 
 
-def unit_draws(u):
-    """N of the unit's lnZ_* call, or None when the unit does not say (units built by hand)"""
-    return u[UNIT_DRAWS] if len(u) > UNIT_DRAWS else None
+def as_units(units):
+    return [u if type(u) is Unit else Unit(*u) for u in units]
+
+
+def unit_cost(u):
+    return _COST.get(u.key, 1.0) * u.weight
+
+
+def _star_of(u):
+    """(job, star) of a unit when the caller gave it (target._units), else its star's ID"""
+    return u.ID if u.group is None else u.group
+
+
+def _job_of(u):
+    return 0 if u.group is None else u.group[0]
+
+
+class RowLayout:
+    """The one place that knows the columns of a row of run_units' table: RECORD_COLS, MOMENT_COLS, the row's posterior
+    (post_rows samples of each of fused.POSTERIOR_KEYS or, with summary_q, len(summary_q) quantiles of each of
+    fused.POSTERIOR_PARAMS), then with hist (calc_probs_refined) its fused.WARP_BRANCH histogram words.  `record`, `moments`,
+    `extra`, `hist`: the column slices (empty where the pass carries none); `lnZ`: a column; `width`: the row's length."""
+
+    def __init__(self, post_rows=0, summary_q=None, hist=False):
+        post_rows, summary_q = int(post_rows), summary_q if post_rows else None
+        n, m = len(RECORD_COLS), len(RECORD_COLS) + len(MOMENT_COLS)
+        e = m + (len(_fused.POSTERIOR_KEYS) * post_rows if summary_q is None else len(_fused.POSTERIOR_PARAMS) * len(summary_q))
+        h = e + (_fused.WARP_BRANCH if hist else 0)
+        key = None if not post_rows else "posterior" if summary_q is None else "posterior_quantiles"
+        self.__dict__.update(post_rows=post_rows, summary_q=summary_q, record=slice(0, n), lnZ=n - 1, moments=slice(n, m),
+                             extra=slice(m, e), hist=slice(e, h), width=h, extra_key=key)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("RowLayout is immutable")
+
+    def encode(self, post):
+        """a "posterior" dict (or None) as the row's extra columns, one key after the other: the samples, or
+        np.quantile(samples, summary_q); NaN where absent"""
+        if post is None:
+            return np.full(self.extra.stop - self.extra.start, np.nan)
+        if self.summary_q is None:
+            return np.concatenate([np.asarray(post[k], dtype=np.float64) for k in _fused.POSTERIOR_KEYS])
+        return np.concatenate([np.quantile(post[c], self.summary_q) for c in _fused.POSTERIOR_PARAMS])
+
+    def decode(self, row):
+        """the inverse, from a whole row: what a result dict holds under extra_key (None for NaN in the defining slot)"""
+        flat = np.asarray(row[self.extra], dtype=np.float64)
+        if self.summary_q is None:
+            return _fused.posterior_from_flat(flat, self.post_rows)
+        n_q = len(self.summary_q)
+        if n_q == 0 or flat.size != self.extra.stop - self.extra.start or np.isnan(flat[0]):
+            return None
+        return {c: flat[i * n_q:(i + 1) * n_q].copy() for i, c in enumerate(_fused.POSTERIOR_PARAMS)}
+
+    def summarise(self, rec):
+        """the owner-side reduction of a summary pass: a unit's rows as its owner has them -- the samples still in place
+        of the quantiles -- with every row's samples reduced to quantiles (of the dict target.posterior would hold)"""
+        samples = RowLayout(self.post_rows)
+        out = np.full((rec.shape[0], self.width), np.nan)
+        have = min(self.moments.stop, rec.shape[1])
+        out[:, :have] = rec[:, :have]
+        if rec.shape[1] >= samples.width:
+            for i in range(rec.shape[0]):
+                out[i, self.extra] = self.encode(samples.decode(rec[i]))
+        return out
 
 
 def _record(res):
@@ -200,63 +274,36 @@ def _record(res):
     return out
 
 
-def _as_dicts(rec):
+def _as_dicts(rec, layout):
     out = tuple({c: rec[i, j] for j, c in enumerate(RECORD_COLS)} for i in range(rec.shape[0]))
-    wide = rec.shape[1] - len(RECORD_COLS) - len(MOMENT_COLS)
-    if wide > 0:
-        from . import fused as _fused
-        q = _fused.POSTERIOR_SUMMARY
+    if layout.extra_key:
         for i, d in enumerate(out):
-            if q is not None:
-                # (a summary pass: 14 len(q) more columns, the row's quantiles)
-                d["posterior_quantiles"] = _fused.posterior_quantiles_from_flat(rec[i, rec.shape[1] - wide:], len(q))
-            else:
-                # (a pass with fused.POSTERIOR_ROWS = M: 16 M more columns per scenario row)
-                d["posterior"] = _fused.posterior_from_flat(rec[i, rec.shape[1] - wide:], wide // 16)
-    return out
-
-
-def _summarise(rec, post_rows, q):
-    """rows of a unit as its owner has them -- RECORD_COLS, MOMENT_COLS, then 16 M columns of samples -- with the
-    samples of every row reduced to len(q) quantiles of the 14 physical columns (fused.posterior_quantiles_to_flat on
-    the dict fused.posterior_from_flat gives: the dict target.posterior would hold)"""
-    from . import fused as _fused
-    narrow = len(RECORD_COLS) + len(MOMENT_COLS)
-    out = np.full((rec.shape[0], narrow + len(_fused.POSTERIOR_PARAMS) * len(q)), np.nan)
-    have = min(narrow, rec.shape[1])
-    out[:, :have] = rec[:, :have]
-    if rec.shape[1] > narrow:
-        for i in range(rec.shape[0]):
-            out[i, narrow:] = _fused.posterior_quantiles_to_flat(_fused.posterior_from_flat(rec[i, narrow:], post_rows), q)
+            d[layout.extra_key] = layout.decode(rec[i])
     return out
 
 
 def run_units(units, verbose=0, as_rows=False, job_done=None):
     """Evaluate the work units of one calc_probs.
 
-    units: list of (first_row, names, star_num, ID, thunk_or_None, key[, weight, draws, (job, star)]); weight scales
-    the scenario cost of `key` in the schedule (units of differently sized jobs, calc_probs_many), (job, star) lets
-    the schedule deal whole TOIs and whole stars.
+    units: list of Unit, or of plain tuples with a Unit's first six fields or more (coerced here, once).
     Returns, per unit, None (dropped scenario) or a tuple of per-scenario dicts
-    {column: best value, 'lnZ': float} -- with as_rows, the (branches, 17) array of RECORD_COLS + MOMENT_COLS instead
+    {column: best value, 'lnZ': float} -- with as_rows, the unit's (branches, width) rows of the pass's table instead
     (what target._finish reads: building a dict per scenario and taking it apart again cost 4 ms of a 64-target step,
-    on every rank).
+    on every rank); their columns are `last_layout`'s, the RowLayout this pass builds from fused's switches at its start.
     job_done(job, results_of_its_units): called as soon as every unit of a job (the first element of a unit's
-    (job, star)) has its records -- while the GPU still works on later jobs -- on one rank with the calls enqueued
+    group) has its records -- while the GPU still works on later jobs -- on one rank with the calls enqueued
     from one host thread; elsewhere never (the caller finishes what is left)."""
+    units = as_units(units)
     dist = _dist()
-    world = dist.get_world_size() if dist else 1
-    rank = dist.get_rank() if dist else 0
-    live = [k for k, u in enumerate(units) if u[4] is not None]
-    owner = {k: 0 for k in live}
-    base = None
+    world, rank = (dist.get_world_size(), dist.get_rank()) if dist else (1, 0)
+    live = [k for k, u in enumerate(units) if u.thunk is not None]
+    owner, base = {k: 0 for k in live}, None
     if dist:
         base = _draw_base()         # ranks seeded alike draw the same one (module docstring)
-        own = schedule([_COST.get(units[k][5], 1.0) * (units[k][6] if len(units[k]) > 6 else 1.0)
-                        for k in live], world,
-                       [units[k][8] for k in live] if all(len(units[k]) > 8 for k in live) else None)
+        groups = [units[k].group for k in live]
+        own = schedule([unit_cost(units[k]) for k in live], world, None if None in groups else groups)
         owner = {k: own[i] for i, k in enumerate(live)}
-    global last_share
+    global last_share, last_own_jobs
     calls, stars, jobs = [0] * world, [set() for _ in range(world)], [set() for _ in range(world)]
     for k in live:                          # (one pass over the units: this runs on every rank for ALL units)
         r = owner[k]
@@ -264,11 +311,9 @@ def run_units(units, verbose=0, as_rows=False, job_done=None):
         stars[r].add(_star_of(units[k]))
         jobs[r].add(_job_of(units[k]))
     last_share = {"calls": calls, "stars": [len(x) for x in stars], "jobs": [len(x) for x in jobs]}
-    global last_own_jobs
     last_own_jobs = jobs[rank]              # (calc_probs_many: the targets whose tables this rank fills at once)
     # calc_probs keeps the best draw of every scenario only: with the device generator the fused
     # path then selects it with one argmin instead of a top-100 sort (fused.TABLE_ROWS)
-    from . import fused as _fused
     if not dist and (per_unit_seed or (threads > 1 and _fused.threadable())):
         # (threads only apply to the device generator: the numpy modes keep consuming the caller's stream)
         base = _draw_base()
@@ -303,6 +348,7 @@ def _pieces(units, mine_k, n_streams):
     """this rank's units as contiguous runs of one target's calls: whole targets when there are at least as many as
     streams, else a target's calls in enough runs to keep the streams busy (a 75-scenario calc_probs: 50 calls in
     five runs of ten)"""
+    units = as_units(units)
     jobs = []
     for k in mine_k:
         j = _job_of(units[k])
@@ -317,7 +363,7 @@ def _pieces(units, mine_k, n_streams):
         if len(jobs) < n_streams:
             want = max(want, min(n_streams // len(jobs), n // 5))
         want = max(1, min(want, n))
-        cost = [_COST.get(units[k][5], 1.0) for k in ks]
+        cost = [_COST.get(units[k].key, 1.0) for k in ks]
         total, acc, at = sum(cost), 0.0, 0
         for p in range(want):
             # contiguous, balanced by cost: piece p ends where the running cost passes (p + 1) / want of the total
@@ -331,277 +377,266 @@ def _pieces(units, mine_k, n_streams):
     return out
 
 
-def _star_of(u):
-    """(job, star) of a unit when the caller gave it (target._prepare), else its star's ID"""
-    return u[8] if len(u) > 8 else u[3]
+class _Pass:
+    """What the execution modes of one run_units pass share: the record table of all live units (after the gather every
+    rank holds all of it), where each unit's rows lie in it, this rank's units and its calls still in flight."""
 
+    def __init__(self, units, live, owner, base, dist, rank, verbose, layout):
+        self.units, self.live, self.owner, self.base = units, live, owner, base
+        self.dist, self.rank, self.verbose, self.layout = dist, rank, verbose, layout
+        self.rows = {k: len(units[k].names) for k in live}
+        self.at, total = {}, 0                        # unit -> its rows of the table
+        for k in live:
+            self.at[k] = slice(total, total + self.rows[k])
+            total += self.rows[k]
+        self.table = np.full((total, layout.width), np.nan)        # (what a path does not give -- moments, samples -- stays NaN)
+        self.mine_k = [k for k in live if owner[k] == rank]
+        self.pending = []                             # (unit, fused.Pending): calls in flight
+        self.n_threads = 1
 
-def _job_of(u):
-    return u[8][0] if len(u) > 8 else 0
+    def result(self, k, as_rows):
+        return self.table[self.at[k]] if as_rows else _as_dicts(self.table[self.at[k]], self.layout)
 
+    def put(self, k, rec):
+        if self.layout.summary_q is not None:
+            rec = self.layout.summarise(rec)         # (by the unit's owner, as its records come in: before the gather)
+        self.table[self.at[k], :rec.shape[1]] = rec
 
-def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=False, job_done=None):
-    rows = {k: len(units[k][1]) for k in live}
-    offs, total = {}, 0
-    for k in live:
-        offs[k] = total
-        total += rows[k]
-    from . import fused as _fused
-    # with posterior rows (fused.POSTERIOR_ROWS = M > 0) a scenario row carries its samples as 16 M more columns
-    # (fused.POSTERIOR_KEYS order, NaN where the row has none): they ride in the ONE all_gather below
-    # -- or, with fused.POSTERIOR_SUMMARY = q (calc_posteriors_many(keep="summary")), 14 len(q) columns: the unit's owner
-    # reduces the samples to quantiles as its records come in (put below), before the gather
-    post_rows = int(_fused.POSTERIOR_ROWS)
-    summary_q = _fused.POSTERIOR_SUMMARY if post_rows else None
-    narrow = len(RECORD_COLS) + len(MOMENT_COLS)
-    wide = 16 * post_rows if summary_q is None else len(_fused.POSTERIOR_PARAMS) * len(summary_q)
-    if _fused.WARP_HIST:
-        # (a pass of calc_probs_refined: every row carries its weight histogram, fused.WARP_BRANCH more columns)
-        wide += _fused.WARP_BRANCH
-    table = np.full((total, narrow + wide), np.nan)
+    def resolve(self, pending):
+        """the rows of calls whose streams have been synchronised -> the table; returns their units"""
+        got = _fused.records_to_rows(pending)
+        for k, rec in got.items():
+            self.put(k, rec)
+        return got
 
-    def put(k, rec):
-        if summary_q is not None:
-            rec = _summarise(rec, post_rows, summary_q)
-        table[offs[k]:offs[k] + rows[k], :rec.shape[1]] = rec
-    ncol = len(RECORD_COLS)
-    mine_k = [k for k in live if owner[k] == rank]
-
-    pending = []                                  # (unit, fused.Pending): calls in flight
-
-    def one(k):
-        j0, names, snum, ID, fn, key = units[k][:6]
-        if verbose == 1:
-            print("Calculating " + ", ".join(names) + " scenario probabilit"
-                  + ("y" if len(names) == 1 else "ies") + " for " + str(ID)
-                  + (" [rank %d]" % rank if dist else "") + ".")
+    def one(self, k):
+        u, base, layout = self.units[k], self.base, self.layout
+        if self.verbose == 1:
+            print("Calculating " + ", ".join(u.names) + " scenario probabilit"
+                  + ("y" if len(u.names) == 1 else "ies") + " for " + str(u.ID)
+                  + (" [rank %d]" % self.rank if self.dist else "") + ".")
         if base is not None:
             unit_seed = (base + 7919 * (k + 1)) % (2 ** 32)
             _fused.set_thread_seed(unit_seed)        # the draw kernel's Philox key (thread-local)
-            if n_threads == 1 and not _fused.threadable():
+            if self.n_threads == 1 and not _fused.threadable():
                 np.random.seed(unit_seed)            # the numpy sampling modes
                 import torch
                 torch.manual_seed(unit_seed)         # staged draws from torch's generator
         mark = _lib.moments_mark()                   # (the moments this unit's evidences report: fused / ml)
         _fused.set_thread_unit(k)                    # (calc_probs_refined keeps an importance grid per unit)
         try:
-            res = fn()
+            res = u.thunk()
         finally:
             _fused.set_thread_seed(None)
             _fused.set_thread_unit(None)
         mom = _lib.moments_since(mark)
         if isinstance(res, _fused.Pending):
-            pending.append((k, res))                 # list.append is atomic: worker threads share it
+            self.pending.append((k, res))            # list.append is atomic: worker threads share it
         else:
-            table[offs[k]:offs[k] + rows[k], :ncol] = _record(res)
-            if len(mom) == rows[k]:
-                table[offs[k]:offs[k] + rows[k], ncol:narrow] = mom
-            if post_rows:
+            blk = self.table[self.at[k]]
+            blk[:, layout.record] = _record(res)
+            if len(mom) == self.rows[k]:
+                blk[:, layout.moments] = mom
+            if layout.post_rows:
                 for i, d in enumerate(res if isinstance(res, tuple) else (res,)):
-                    table[offs[k] + i, narrow:] = (_fused.posterior_to_flat(d.get("posterior"), post_rows) if summary_q is None
-                                                   else _fused.posterior_quantiles_to_flat(d.get("posterior"), summary_q))
+                    blk[i, layout.extra] = layout.encode(d.get("posterior"))
 
-    def resolve():
-        for k, rec in _fused.records_to_rows(pending).items():
-            put(k, rec)
 
+def _run_units(units, live, owner, base, dist, world, rank, verbose, as_rows=False, job_done=None):
+    # (the switches are read HERE, once a pass: whatever rides beside the records rides in the ONE all_gather below)
+    global last_layout
+    last_layout = RowLayout(_fused.POSTERIOR_ROWS, _fused.POSTERIOR_SUMMARY, _fused.WARP_HIST)
+    p = _Pass(units, live, owner, base, dist, rank, verbose, last_layout)
     on_device = _fused.threadable() or _fused.staged_native()
     if on_device:
         import torch
         on_device = torch.cuda.is_available()          # (without a GPU the thunks fail loudly themselves)
     # (numpy's stream is consumed on this thread, call after call, in the reference's order: one host thread)
-    n_threads = min(threads, len(mine_k)) if (base is not None and on_device and _fused.threadable()) else 1
-    if n_threads <= 1 and not (on_device and mine_k):
-        for k in mine_k:
-            one(k)
-    elif n_threads <= 1:
-        # one host thread, a few streams: every call is enqueued, then one wait per stream
-        import torch
-        device = torch.cuda.current_device()
-        n_draws = max([units[k][7] for k in mine_k if len(units[k]) > 7] + [1])
-        cap = max(2, int(scratch_budget_bytes // stream_scratch_bytes(n_draws)))
-        pool = _worker_streams(device, max(1, min(streams, cap, len(mine_k))))
-        torch.cuda.current_stream().synchronize()    # inputs staged on the caller's stream
-        _fused.begin_deferred(len(mine_k))
-        drained = False
-        # The cyclic garbage collector is held off while the calls are enqueued and awaited: a pass builds a few thousand
-        # small objects (argument blocks, closures, Pending records; no reference cycles among them), which now and then
-        # tips the collector into a FULL collection -- 75 ms in a process that has imported torch and pandas, inside a
-        # 140 ms step (every fourth 64-target step: profiles/r05/gc_pause.txt).  Reference counting frees the pass's
-        # objects as before; the collector is switched back on (if it was on) when the pass is over.
-        import gc
-        global _gc_frozen
-        if freeze_gc and not _gc_frozen:
-            # (once: the objects alive now -- torch, pandas, the star tables -- move to the collector's permanent
-            # generation, so the full collection that follows a held-off pass looks at the pass's objects only)
-            gc.collect()
-            gc.freeze()
-            _gc_frozen = True
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            import time
-            t0 = time.perf_counter()
-            # The library turns consecutive calls on ONE stream that share a light curve's time stamps and N into one
-            # launch chain (trx_star_enqueue, include/trx.h): every kernel once for up to 16 calls.  So the calls go
-            # to the streams in PIECES -- contiguous runs of one target's calls, ~chain_calls each -- and a piece to
-            # the stream with the least work queued so far (by the schedule's cost weights); one library call per piece.
-            load = [0.0] * len(pool)
-            done_marks = []                # (event behind a piece, number of pending calls up to and including it)
-            t_build = t_lib = 0.0          # of enqueue_s: Python building the argument blocks / inside trx_star_enqueue
-            for piece in _pieces(units, mine_k, len(pool)):
-                j = min(range(len(pool)), key=lambda i: (load[i], i))
-                load[j] += sum(_COST.get(units[k][5], 1.0) * (units[k][6] if len(units[k]) > 6 else 1.0) for k in piece)
-                t_a = time.perf_counter()
-                with torch.cuda.stream(pool[j]):
-                    for k in piece:
-                        one(k)
-                t_b = time.perf_counter()
-                _fused.flush()
-                t_build += t_b - t_a
-                t_lib += time.perf_counter() - t_b
-                ev = torch.cuda.Event()
-                ev.record(pool[j])
-                done_marks.append((ev, len(pending)))
-            timing["build_s"], timing["library_s"] = t_build, t_lib
-            timing["enqueue_s"] = time.perf_counter() - t0
-            # The records are turned into table rows piece by piece, as the pieces finish, while the GPU works on the
-            # later ones (the host is idle for most of the wait: until round 5 it slept through it and converted all
-            # records afterwards, 3-5 ms of every step and of every rank).  Pieces on one stream finish in order;
-            # across streams the order of enqueueing is a good guess and a wrong one only waits a little longer.
-            at = 0
-            t_wait = 0.0
-            # (a job whose units all have their rows is handed to the caller at once -- its table is filled while
-            # the GPU works on the later jobs instead of after the last kernel)
-            left, members = {}, {}
-            if job_done is not None:
-                for k, u in enumerate(units):
-                    members.setdefault(_job_of(u), []).append(k)
-                for k in mine_k:
-                    left[_job_of(units[k])] = left.get(_job_of(units[k]), 0) + 1
-                for k in set(mine_k) - {k for k, _ in pending}:         # (calls that returned their records at once)
-                    left[_job_of(units[k])] -= 1
-            for ev, upto in done_marks:
-                t_w = time.perf_counter()
-                ev.synchronize()
-                t_wait += time.perf_counter() - t_w
-                if upto > at:
-                    got = _fused.records_to_rows(pending[at:upto])
-                    for k, rec in got.items():
-                        put(k, rec)
-                    at = upto
-                    if job_done is not None:
-                        for k in got:
-                            j = _job_of(units[k])
-                            left[j] -= 1
-                            if left[j] == 0:
-                                job_done(j, [None if units[m][4] is None else
-                                             (table[offs[m]:offs[m] + rows[m]] if as_rows else _as_dicts(table[offs[m]:offs[m] + rows[m]]))
-                                             for m in members[j]])
+    if base is not None and on_device and _fused.threadable():
+        p.n_threads = min(threads, len(p.mine_k))
+    if p.n_threads <= 1 and not (on_device and p.mine_k):
+        for k in p.mine_k:
+            p.one(k)
+    elif p.n_threads <= 1:
+        _run_streams(p, as_rows, job_done)
+    else:
+        _run_threads(p)
+    if dist:
+        _gather(p, world)
+    return [None if u.thunk is None else p.result(k, as_rows) for k, u in enumerate(units)]
+
+
+def _run_streams(p, as_rows, job_done):
+    """one host thread, a few streams: every call is enqueued, then one wait per stream"""
+    import torch
+    units, mine_k, pending = p.units, p.mine_k, p.pending
+    device = torch.cuda.current_device()
+    n_draws = max([units[k].draws for k in mine_k if units[k].draws is not None] + [1])
+    cap = max(2, int(scratch_budget_bytes // stream_scratch_bytes(n_draws)))
+    pool = _worker_streams(device, max(1, min(streams, cap, len(mine_k))))
+    torch.cuda.current_stream().synchronize()    # inputs staged on the caller's stream
+    _fused.begin_deferred(len(mine_k))
+    drained = False
+    # The cyclic garbage collector is held off while the calls are enqueued and awaited (freeze_gc above, DESIGN.md
+    # section 4.5): the pass's few thousand small objects -- no reference cycles among them -- now and then tipped it into
+    # a FULL collection, 75 ms inside a 140 ms step.  Reference counting frees them as before.
+    import gc
+    global _gc_frozen
+    if freeze_gc and not _gc_frozen:
+        gc.collect()                 # (once: what is alive now moves to the collector's permanent generation)
+        gc.freeze()
+        _gc_frozen = True
+    gc_was_on = gc.isenabled()
+    gc.disable()
+    try:
+        import time
+        t0 = time.perf_counter()
+        # The library turns consecutive calls on ONE stream that share a light curve's time stamps and N into one launch
+        # chain (trx_star_enqueue, include/trx.h).  So the calls go to the streams in PIECES (_pieces), each to the stream
+        # with the least work queued so far (by the schedule's cost weights); one library call per piece.
+        load = [0.0] * len(pool)
+        done_marks = []                # (event behind a piece, number of pending calls up to and including it)
+        t_build = t_lib = 0.0          # of enqueue_s: Python building the argument blocks / inside trx_star_enqueue
+        for piece in _pieces(units, mine_k, len(pool)):
+            j = min(range(len(pool)), key=lambda i: (load[i], i))
+            load[j] += sum(unit_cost(units[k]) for k in piece)
+            t_a = time.perf_counter()
+            with torch.cuda.stream(pool[j]):
+                for k in piece:
+                    p.one(k)
+            t_b = time.perf_counter()
+            _fused.flush()
+            t_build += t_b - t_a
+            t_lib += time.perf_counter() - t_b
+            ev = torch.cuda.Event()
+            ev.record(pool[j])
+            done_marks.append((ev, len(pending)))
+        timing["build_s"], timing["library_s"] = t_build, t_lib
+        timing["enqueue_s"] = time.perf_counter() - t0
+        # The records are turned into table rows piece by piece, as the pieces finish, while the GPU works on the later
+        # ones (3-5 ms of every step that the host would else spend after the wait).  Pieces on one stream finish in
+        # order; across streams the order of enqueueing is a good guess and a wrong one only waits a little longer.
+        at = 0
+        t_wait = 0.0
+        # (a job whose units all have their rows is handed to the caller at once: run_units' docstring)
+        left, members = {}, {}
+        if job_done is not None:
+            for k, u in enumerate(units):
+                members.setdefault(_job_of(u), []).append(k)
+            for k in mine_k:
+                left[_job_of(units[k])] = left.get(_job_of(units[k]), 0) + 1
+            for k in set(mine_k) - {k for k, _ in pending}:         # (calls that returned their records at once)
+                left[_job_of(units[k])] -= 1
+        for ev, upto in done_marks:
+            t_w = time.perf_counter()
+            ev.synchronize()
+            t_wait += time.perf_counter() - t_w
+            if upto > at:
+                got = p.resolve(pending[at:upto])
+                at = upto
+                if job_done is not None:
+                    for k in got:
+                        j = _job_of(units[k])
+                        left[j] -= 1
+                        if left[j] == 0:
+                            job_done(j, [None if units[m].thunk is None else p.result(m, as_rows) for m in members[j]])
+        for st in pool:
+            st.synchronize()
+        drained = True
+        timing["wait_s"] = t_wait
+        if at < len(pending):
+            p.resolve(pending[at:])
+    finally:
+        if not drained:
+            # a call failed after others were enqueued: their kernels and record copies still use the
+            # pinned block and the cached tables -- wait for them before anything is released
             for st in pool:
                 st.synchronize()
-            drained = True
-            timing["wait_s"] = t_wait
-            if at < len(pending):
-                for k, rec in _fused.records_to_rows(pending[at:]).items():
-                    put(k, rec)
+        pending.clear()
+        _fused.end_deferred()
+        if gc_was_on:
+            gc.enable()
+
+
+def _run_threads(p):
+    """worker threads, each on its own stream, take this rank's units from one queue, the dearest first"""
+    import queue
+    import threading
+    import torch
+    mine_k, n_threads = p.mine_k, p.n_threads
+    device = torch.cuda.current_device()
+    todo = queue.SimpleQueue()
+    cost = {k: unit_cost(p.units[k]) for k in mine_k}
+    for k in sorted(mine_k, key=lambda k: (-cost[k], k)):
+        todo.put(k)
+    errors = []
+    pool_streams = _worker_streams(device, n_threads)
+
+    def worker(stream):
+        _lib.moments_swap([] if _fused.MOMENTS else None)
+        try:
+            torch.cuda.set_device(device)        # the current device is thread-local
+            _fused.begin_deferred(len(mine_k))
+            with torch.cuda.stream(stream):
+                while True:
+                    try:
+                        k = todo.get_nowait()
+                    except queue.Empty:
+                        break
+                    p.one(k)
+                    _fused.flush()
+        except BaseException as exc:              # re-raised in the caller's thread
+            errors.append(exc)
         finally:
-            if not drained:
-                # a call failed after others were enqueued: their kernels and record copies still use the
-                # pinned block and the cached tables -- wait for them before anything is released
-                for st in pool:
-                    st.synchronize()
-            pending.clear()
+            stream.synchronize()                  # (also after an error: calls enqueued before it are in flight)
             _fused.end_deferred()
-            if gc_was_on:
-                gc.enable()
-    else:
-        import queue
-        import threading
-        import torch
-        device = torch.cuda.current_device()
-        todo = queue.SimpleQueue()
-        cost = {k: _COST.get(units[k][5], 1.0) * (units[k][6] if len(units[k]) > 6 else 1.0) for k in mine_k}
-        for k in sorted(mine_k, key=lambda k: (-cost[k], k)):
-            todo.put(k)
-        errors = []
+            _lib.moments_swap(None)
 
-        pool_streams = _worker_streams(device, n_threads)
+    torch.cuda.current_stream().synchronize()    # inputs staged on the caller's stream
+    pool = [threading.Thread(target=worker, args=(pool_streams[i],)) for i in range(n_threads)]
+    for t in pool:
+        t.start()
+    for t in pool:
+        t.join()
+    if errors:
+        p.pending.clear()
+        raise errors[0]
+    p.resolve(p.pending)
 
-        def worker(stream):
-            _lib.moments_swap([] if _fused.MOMENTS else None)
-            try:
-                torch.cuda.set_device(device)        # the current device is thread-local
-                _fused.begin_deferred(len(mine_k))
-                with torch.cuda.stream(stream):
-                    while True:
-                        try:
-                            k = todo.get_nowait()
-                        except queue.Empty:
-                            break
-                        one(k)
-                        _fused.flush()
-            except BaseException as exc:              # re-raised in the caller's thread
-                errors.append(exc)
-            finally:
-                stream.synchronize()                  # (also after an error: calls enqueued before it are in flight)
-                _fused.end_deferred()
-                _lib.moments_swap(None)
 
-        torch.cuda.current_stream().synchronize()    # inputs staged on the caller's stream
-        pool = [threading.Thread(target=worker, args=(pool_streams[i],)) for i in range(n_threads)]
-        for t in pool:
-            t.start()
-        for t in pool:
-            t.join()
-        if errors:
-            pending.clear()
-            raise errors[0]
-        resolve()
-
-    if dist:
-        # ONE collective: every rank contributes the records of its own units (in unit order, padded to the
-        # largest share) behind one header row that carries its seed base -- 17 doubles per scenario (RECORD_COLS and
-        # MOMENT_COLS), a few KB per rank (SURVEY section 8e), latency-bound: a direct all_gather, no ring, no bucketing
-        import time
-        import torch
-        t_g = time.perf_counter()
-        dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
-        width = table.shape[1]
-        share = [sum(rows[k] for k in live if owner[k] == r) for r in range(world)]
-        chunk = np.full((1 + max(share + [0]), width), np.nan)
-        chunk[0, 0] = float(base)
-        at = 1
-        for k in mine_k:
-            chunk[at:at + rows[k]] = table[offs[k]:offs[k] + rows[k]]
-            at += rows[k]
-        mine = torch.as_tensor(chunk).to(dev).reshape(-1)
-        gathered = torch.empty(world * mine.numel(), dtype=mine.dtype, device=dev)
-        dist.all_gather_into_tensor(gathered, mine)          # the single collective
-        g = gathered.cpu().numpy().reshape((world,) + chunk.shape)
-        global last_seed_bases, _warned_bases
-        last_seed_bases = [int(b) for b in g[:, 0, 0]]
-        if len(set(last_seed_bases)) > 1 and not _warned_bases:
-            # (relaxed in round 4: unseeded ranks just run -- but a user who seeded only some ranks, or only numpy in
-            # "device" mode, should hear that the run cannot be repeated)
-            import warnings
-            warnings.warn("calc_probs on %d ranks: the ranks drew different seed bases %s, so this run is not reproducible "
-                          "and its numbers depend on the partition.  Seed every rank alike (torch.manual_seed in 'device' "
-                          "mode, np.random.seed in the numpy modes) for a repeatable, partition-independent run."
-                          % (world, last_seed_bases[:4]), RuntimeWarning, stacklevel=4)
-            _warned_bases = True
-        at = [1] * world
-        for k in live:
-            r = owner[k]
-            table[offs[k]:offs[k] + rows[k]] = g[r, at[r]:at[r] + rows[k]]
-            at[r] += rows[k]
-        timing["gather_s"] = time.perf_counter() - t_g
-
-    out = []
-    for k, u in enumerate(units):
-        if u[4] is None:
-            out.append(None)
-        else:
-            rec = table[offs[k]:offs[k] + rows[k]]
-            out.append(rec if as_rows else _as_dicts(rec))
-    return out
+def _gather(p, world):
+    """ONE collective: every rank contributes the records of its own units (in unit order, padded to the largest share)
+    behind one header row that carries its seed base -- a table row per scenario (RowLayout; 17 doubles without posterior
+    columns), a few KB per rank, latency-bound: a direct all_gather, no ring, no bucketing"""
+    import time
+    import torch
+    dist, table, rows, live, owner = p.dist, p.table, p.rows, p.live, p.owner
+    t_g = time.perf_counter()
+    dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
+    share = [sum(rows[k] for k in live if owner[k] == r) for r in range(world)]
+    chunk = np.full((1 + max(share + [0]), p.layout.width), np.nan)
+    chunk[0, 0] = float(p.base)
+    at = 1
+    for k in p.mine_k:
+        chunk[at:at + rows[k]] = table[p.at[k]]
+        at += rows[k]
+    mine = torch.as_tensor(chunk).to(dev).reshape(-1)
+    gathered = torch.empty(world * mine.numel(), dtype=mine.dtype, device=dev)
+    dist.all_gather_into_tensor(gathered, mine)          # the single collective
+    g = gathered.cpu().numpy().reshape((world,) + chunk.shape)
+    global last_seed_bases, _warned_bases
+    last_seed_bases = [int(b) for b in g[:, 0, 0]]
+    if len(set(last_seed_bases)) > 1 and not _warned_bases:
+        # (unseeded ranks just run; who seeded only some, or only numpy in "device" mode, should hear of it)
+        import warnings
+        warnings.warn("calc_probs on %d ranks: the ranks drew different seed bases %s, so this run is not reproducible "
+                      "and its numbers depend on the partition.  Seed every rank alike (torch.manual_seed in 'device' "
+                      "mode, np.random.seed in the numpy modes) for a repeatable, partition-independent run."
+                      % (world, last_seed_bases[:4]), RuntimeWarning, stacklevel=5)
+        _warned_bases = True
+    at = [1] * world
+    for k in live:
+        r = owner[k]
+        table[p.at[k]] = g[r, at[r]:at[r] + rows[k]]
+        at[r] += rows[k]
+    timing["gather_s"] = time.perf_counter() - t_g

@@ -121,13 +121,14 @@ class target:
 
     # -----------------------------------------------------------------------------------
     def _units(self, filtered, flux_0, flux_err_0, time, P_orb, contrast_curve_file, filt, N,
-               parallel, drop_scenario, flatpriors, exptime, nsamples, molusc_file):
+               parallel, drop_scenario, flatpriors, exptime, nsamples, molusc_file, job=0):
         """The independent (star, lnZ_* call) work units of one calc_probs, in the reference's
-        order.  Each unit = (first row, scenario names, star_num, ID, thunk or None, drop key).
+        order: sharding.Unit, the thunk None for a dropped scenario.
         Building the list touches nothing but the star table's columns (once each): a unit's arguments --
         the light curve renormalised to its star, the argument tuples -- are put together when its thunk
         is called, i.e. only on the rank that owns it (sharding.run_units)."""
         units = []
+        Unit, weight, draws = sharding.Unit, float(N) * max(1, time.size), int(N)      # (weight: the job's relative size)
         ok = True
         keep, stars, column = filtered
         cache = {}
@@ -182,11 +183,12 @@ class target:
                     break
                 for key, names, j0, snum in _TARGET_CALLS:
                     fn = None if key in drop_scenario else (lambda k=key: target_call(k))
-                    units.append((j0, names, snum, ID, fn, key, 0))
+                    units.append(Unit(j0, names, snum, ID, fn, key, weight, draws, (job, 0)))
             else:
                 j0 = 15 + 3 * (i - 1)
-                units.append((j0, ("NTP",), 1, ID, lambda i=i: nearby_call(i, lnZ_TTP), "NTP", i))
-                units.append((j0 + 1, ("NEB", "NEBx2P"), 1, ID, lambda i=i: nearby_call(i, lnZ_TEB), "NEB", i))
+                units.append(Unit(j0, ("NTP",), 1, ID, lambda i=i: nearby_call(i, lnZ_TTP), "NTP", weight, draws, (job, i)))
+                units.append(Unit(j0 + 1, ("NEB", "NEBx2P"), 1, ID, lambda i=i: nearby_call(i, lnZ_TEB), "NEB", weight,
+                                  draws, (job, i)))
         return units, ok
 
     def calc_probs(self, time, flux_0, flux_err_0: float, P_orb, contrast_curve_file: str = None,
@@ -200,7 +202,7 @@ class target:
         units, book = self._prepare(time, flux_0, flux_err_0, P_orb, contrast_curve_file, filt, N,
                                     parallel, drop_scenario, flatpriors, exptime, nsamples,
                                     molusc_file)
-        self._finish(units, sharding.run_units(units, verbose=verbose, as_rows=True), book)
+        self._finish(units, sharding.run_units(units, verbose=verbose, as_rows=True), book, layout=sharding.last_layout)
         return
 
     def calc_posteriors(self, time, flux_0, flux_err_0: float, P_orb, n_samples: int = 1000, **calc_probs_kwargs):
@@ -216,12 +218,8 @@ class target:
         n_samples = int(n_samples)
         if not 1 <= n_samples <= fused.POST_MAX_ROWS:
             raise ValueError("n_samples must lie in [1, %d]" % fused.POST_MAX_ROWS)
-        saved = fused.POSTERIOR_ROWS
-        fused.POSTERIOR_ROWS = n_samples
-        try:
+        with fused.switches(POSTERIOR_ROWS=n_samples):
             self.calc_probs(time, flux_0, flux_err_0, P_orb, **calc_probs_kwargs)
-        finally:
-            fused.POSTERIOR_ROWS = saved
         if all(p is None for p in self.posterior) and np.isfinite(self.lnZ).any():
             raise NotImplementedError("calc_posteriors needs the device paths (set_sampling('device') or "
                                       "'numpy-device'): this sampling mode returns no posterior rows")
@@ -275,32 +273,25 @@ class target:
         verbose = kw_adapt.pop("verbose", 1)
         if N_adapt is not None:
             kw_adapt["N"] = int(N_adapt)
-        narrow = len(sharding.RECORD_COLS) + len(sharding.MOMENT_COLS)
         grids = {}                       # work unit -> [7][65] edges (kept per (star, call), not per target)
         history = []
-        saved = (fused.WARP_GRIDS, fused.WARP_HIST, fused.POSTERIOR_ROWS)
-        try:
-            fused.POSTERIOR_ROWS = 0
+        with fused.switches(POSTERIOR_ROWS=0, WARP_GRIDS=grids):
             for _ in range(n_adapt):
                 units, n_scen = self._prepare(time, flux_0, flux_err_0, P_orb, **kw_adapt)
-                fused.WARP_GRIDS, fused.WARP_HIST = grids, True
-                rows = sharding.run_units(units, verbose=verbose, as_rows=True)
-                fused.WARP_HIST = False
+                with fused.switches(WARP_HIST=True):
+                    rows = sharding.run_units(units, verbose=verbose, as_rows=True)
                 for k, rec in enumerate(rows):
                     if rec is None:
                         continue
-                    hist = rec[:, narrow:narrow + fused.WARP_BRANCH]
-                    if rec.shape[1] < narrow + fused.WARP_BRANCH or np.isnan(hist[:, 1]).any():
+                    hist = rec[:, sharding.last_layout.hist]
+                    if np.isnan(hist[:, 1]).any():        # (a row shorter than the table stays NaN there)
                         raise NotImplementedError("calc_probs_refined needs the library's own chain "
                                                   "(set_sampling('device')): this pass returned no weight histograms")
                     grids[k] = warp_refine(grids.get(k, fused.warp_identity()), hist, alpha=alpha, floor=floor)
-                self._finish(units, [None if r is None else r[:, :narrow] for r in rows], n_scen, warn=False)
+                self._finish(units, rows, n_scen, warn=False, layout=sharding.last_layout)
                 history.append(snapshot())
-            fused.WARP_GRIDS = grids
             final()
             history.append(snapshot())
-        finally:
-            fused.WARP_GRIDS, fused.WARP_HIST, fused.POSTERIOR_ROWS = saved
         self.refine_history = history
         return
 
@@ -386,7 +377,7 @@ class target:
         lnZ, prob = [], []
         at = 0
         for r, (units, n_scen) in enumerate(prepared):
-            self._finish(units, results[at:at + len(units)], n_scen)
+            self._finish(units, results[at:at + len(units)], n_scen, layout=sharding.last_layout)
             at += len(units)
             for k in keys:
                 out[k][r] = getattr(self, k)
@@ -431,58 +422,47 @@ class target:
                              "or drop DTP, DEB, BTP and BEB")
         units, _ok = self._units(filtered, flux_0, flux_err_0, time, P_orb, contrast_curve_file,
                                  filt, N, parallel, drop_scenario, flatpriors, exptime, nsamples,
-                                 molusc_file)
-        # relative size of this job's units for the multi-GPU schedule, the draws per unit (stream scratch) and the
-        # (job, star) the unit belongs to: the schedule deals whole jobs and whole stars first (sharding.schedule)
-        weight = float(N) * max(1, time.size)
-        return [u[:6] + (weight, int(N), (job, u[6])) for u in units], n_scen
+                                 molusc_file, job)
+        return units, n_scen
 
-    def _finish(self, units, results, n_scen, warn=True, summary_q=None):
+    def _finish(self, units, results, n_scen, warn=True, layout=None):
         """Scenario table, normalised probabilities, FPP and NFPP from the per-unit results
         (triceratops.py:1430-1485).  Plain arrays here; the `.probs` DataFrame of the reference is put
         together when it is first read (a batch of 64 targets spent as long building 64 DataFrames nobody
         had asked for yet as waiting for the GPU).  warn = False: the caller has already raised the
-        reference's RuntimeWarnings for these evidences (_defer_finish).  summary_q: the rows carry len(summary_q)
-        quantiles of every posterior column instead of the samples (calc_posteriors_many(keep="summary"))."""
+        reference's RuntimeWarnings for these evidences (_defer_finish).  layout: the sharding.RowLayout of the pass
+        that made `results` (sharding.last_layout; default: rows without posterior columns)."""
         self.__dict__["_pending_finish"] = None
+        layout = layout or sharding.RowLayout()
+        summary_q = layout.summary_q
         targets = np.zeros(n_scen, dtype=np.dtype("i8"))
         star_num = np.zeros(n_scen, dtype=np.dtype("i8"))
         scenarios = np.zeros(n_scen, dtype=np.dtype('U6'))
         best = {c: np.zeros(n_scen) for c in _COLS}
         lnZ = np.zeros(n_scen)
         rec_tab = None
-        ncol = len(sharding.RECORD_COLS)
         lnM2 = np.full(n_scen, np.nan)               # the evidences' moments (sharding.MOMENT_COLS), NaN = unknown
-        posterior = [None] * n_scen                  # calc_posteriors: the samples of every scenario row
-        quantiles = [None] * n_scen                  # ... or, in summary mode, their quantiles
+        extras = [None] * n_scen                     # calc_posteriors: every row's samples (summary mode: quantiles)
         lnWmax = np.full(n_scen, np.nan)
-        n_draws = np.full(n_scen, np.nan)            # N of each row's lnZ_* call (units of target._prepare)
-        for u, res in zip(units, results):
-            j0, names, snum, ID = u[:4]
-            draws = sharding.unit_draws(u)
-            if draws is not None:
-                n_draws[j0:j0 + len(names)] = draws
+        n_draws = np.full(n_scen, np.nan)            # N of each row's lnZ_* call (units of target._units)
+        for u, res in zip(sharding.as_units(units), results):
+            j0, names, snum, ID = u.first_row, u.names, u.star_num, u.ID
+            if u.draws is not None:
+                n_draws[j0:j0 + len(names)] = u.draws
             if isinstance(res, np.ndarray):
-                # (sharding.run_units(as_rows=True): the unit's (branches, 15) block of sharding.RECORD_COLS, + the
-                # two of sharding.MOMENT_COLS when the run gave them)
+                # (sharding.run_units(as_rows=True): the unit's rows in `layout` -- or, made by hand, a leading part of it)
                 if rec_tab is None:
-                    rec_tab = np.zeros((n_scen, ncol))
+                    rec_tab = np.zeros((n_scen, len(sharding.RECORD_COLS)))
                 nb = len(names)
-                rec_tab[j0:j0 + nb] = res[:, :ncol]
+                rec_tab[j0:j0 + nb] = res[:, layout.record]
                 targets[j0:j0 + nb], star_num[j0:j0 + nb] = ID, snum
                 scenarios[j0:j0 + nb] = names
-                lnZ[j0:j0 + nb] = res[:, ncol - 1]
-                if res.shape[1] >= ncol + 2:
-                    lnM2[j0:j0 + nb], lnWmax[j0:j0 + nb] = res[:, ncol], res[:, ncol + 1]
-                if res.shape[1] > ncol + 2:
-                    from . import fused
+                lnZ[j0:j0 + nb] = res[:, layout.lnZ]
+                if res.shape[1] >= layout.moments.stop:
+                    lnM2[j0:j0 + nb], lnWmax[j0:j0 + nb] = res[:, layout.moments].T
+                if layout.post_rows and res.shape[1] >= layout.extra.stop:
                     for i in range(nb):
-                        if summary_q is not None:
-                            # (14 len(q) more columns: the quantiles of the row's posterior samples)
-                            quantiles[j0 + i] = fused.posterior_quantiles_from_flat(res[i, ncol + 2:], len(summary_q))
-                        else:
-                            # (16 M more columns: the row's posterior samples, fused.POSTERIOR_KEYS order)
-                            posterior[j0 + i] = fused.posterior_from_flat(res[i, ncol + 2:], (res.shape[1] - ncol - 2) // 16)
+                        extras[j0 + i] = layout.decode(res[i])
                 continue
             for off, name in enumerate(names):
                 j = j0 + off
@@ -494,9 +474,7 @@ class target:
                 for c in _COLS:
                     best[c][j] = r[c]
                 lnZ[j] = r["lnZ"]
-                posterior[j] = r.get("posterior") if isinstance(r, dict) else None
-                if summary_q is not None and isinstance(r, dict):
-                    quantiles[j] = r.get("posterior_quantiles")
+                extras[j] = r.get(layout.extra_key or "posterior") if isinstance(r, dict) else None
         if rec_tab is not None:
             for i, c in enumerate(sharding.RECORD_COLS[:-1]):
                 best[c] = best[c] + rec_tab[:, i]         # (rows of dict-valued or dropped units stay as filled above)
@@ -513,8 +491,8 @@ class target:
             "prob": relative_probs}
         self._probs = None
         self.lnZ = lnZ
-        self.posterior = posterior if summary_q is None else None
-        self.posterior_quantiles = quantiles if summary_q is not None else None
+        self.posterior = extras if summary_q is None else None
+        self.posterior_quantiles = extras if summary_q is not None else None
         self._posterior_q = None if summary_q is None else tuple(float(x) for x in summary_q)
         self.star_num = star_num
         self.u1 = best["u1"]
@@ -572,7 +550,7 @@ class target:
                 "_probs_columns", "_probs", "ess", "lnZ_err", "w_max_frac", "FPP_err", "NFPP_err", "_mc_inputs", "_mc",
                 "posterior", "posterior_quantiles", "_posterior_q")
 
-    def _defer_finish(self, units, results, n_scen, summary_q=None):
+    def _defer_finish(self, units, results, n_scen, layout=None):
         """The table of this target is filled when one of its results is first read (calc_probs_many on several
         ranks: the targets another rank evaluated).  What is kept is DATA only -- per unit (first row, names, star
         number, ID) and a copy of its own records -- not the units' closures over light curves and star tables nor
@@ -582,19 +560,20 @@ class target:
         d = self.__dict__
         for name in self._RESULTS:
             d.pop(name, None)                # (results of an earlier calc_probs must not be read as this one's)
-        # (the unit's layout with its thunk dropped: the other fields are plain data, and the error attributes need
-        # sharding.unit_draws)
-        slim = [tuple(u[:4]) + (None,) + tuple(u[5:]) for u in units]
+        # (the units with their thunks dropped: the other fields are plain data, and the error attributes need the draws)
+        slim = [u._replace(thunk=None) for u in sharding.as_units(units)]
         kept = [None if r is None else (np.array(r, copy=True) if isinstance(r, np.ndarray) else r) for r in results]
-        d["_pending_finish"] = (slim, kept, n_scen, summary_q)
+        layout = layout or sharding.RowLayout()
+        d["_pending_finish"] = (slim, kept, n_scen, layout)
         lnz = np.full(n_scen, 0.0)
         for u, r in zip(slim, kept):
+            mine = slice(u.first_row, u.first_row + len(u.names))
             if r is None:
-                lnz[u[0]:u[0] + len(u[1])] = -np.inf
+                lnz[mine] = -np.inf
             elif isinstance(r, np.ndarray):
-                lnz[u[0]:u[0] + len(u[1])] = r[:, len(sharding.RECORD_COLS) - 1]
+                lnz[mine] = r[:, layout.lnZ]
             else:
-                lnz[u[0]:u[0] + len(u[1])] = [x["lnZ"] for x in r]
+                lnz[mine] = [x["lnZ"] for x in r]
         if not np.all(np.isfinite(lnz)):      # (the common case costs one pass over ~20 numbers)
             self._warn_status(_normalize_probabilities(lnz)[1], stacklevel=4)
 
@@ -603,7 +582,7 @@ class target:
         pend = d.get("_pending_finish")
         if pend is not None:
             d["_pending_finish"] = None
-            self._finish(*pend[:3], warn=False, summary_q=pend[3] if len(pend) > 3 else None)
+            self._finish(*pend[:3], warn=False, layout=pend[3])
 
     def __getattr__(self, name):
         # (only reached when normal lookup fails)
@@ -720,12 +699,8 @@ def calc_posteriors_many(jobs, n_samples: int = 1000, keep: str = "samples", q=(
         summary_q = tuple(float(x) for x in q)
         if not summary_q or not all(0.0 <= x <= 1.0 for x in summary_q):
             raise ValueError("q must be a non-empty sequence of quantile levels in [0, 1]")
-    saved = (fused.POSTERIOR_ROWS, fused.POSTERIOR_SUMMARY)
-    fused.POSTERIOR_ROWS, fused.POSTERIOR_SUMMARY = n_samples, summary_q
-    try:
-        out = _probs_many(jobs, verbose, summary_q)
-    finally:
-        fused.POSTERIOR_ROWS, fused.POSTERIOR_SUMMARY = saved
+    with fused.switches(POSTERIOR_ROWS=n_samples, POSTERIOR_SUMMARY=summary_q):
+        out = _probs_many(jobs, verbose)
     for tg in out:
         if tg.__dict__.get("_pending_finish") is not None:
             continue                     # (another rank's target: its table is filled when it is first read)
@@ -736,8 +711,8 @@ def calc_posteriors_many(jobs, n_samples: int = 1000, keep: str = "samples", q=(
     return out
 
 
-def _probs_many(jobs, verbose, summary_q=None):
-    """the pass of calc_probs_many / calc_posteriors_many (summary_q: the rows carry quantiles, not samples)"""
+def _probs_many(jobs, verbose):
+    """the pass of calc_probs_many / calc_posteriors_many"""
     import time as _time
     t0 = _time.perf_counter()
     prepared = []
@@ -754,7 +729,7 @@ def _probs_many(jobs, verbose, summary_q=None):
     def job_done(job, res):
         t_a = _time.perf_counter()
         tg, units, n_scen = prepared[job]
-        tg._finish(units, res, n_scen, summary_q=summary_q)
+        tg._finish(units, res, n_scen, layout=sharding.last_layout)
         finished.add(job)
         t_fin[0] += _time.perf_counter() - t_a
 
@@ -764,13 +739,13 @@ def _probs_many(jobs, verbose, summary_q=None):
     # Several ranks: every rank holds every record after the all_gather, and a rank fills the tables of the targets it
     # evaluated itself at once; the others' are filled when one of their results is first read (target.__getattr__) --
     # filling all 64 tables of a batch on each of eight ranks was a quarter of a rank's host path.
-    many_ranks = sharding._dist() is not None
+    many_ranks, layout = sharding._dist() is not None, sharding.last_layout
     for job, (tg, units, n_scen) in enumerate(prepared):
         if job not in finished:
             if many_ranks and job not in sharding.last_own_jobs:
-                tg._defer_finish(units, results[at:at + len(units)], n_scen, summary_q)
+                tg._defer_finish(units, results[at:at + len(units)], n_scen, layout)
             else:
-                tg._finish(units, results[at:at + len(units)], n_scen, summary_q=summary_q)
+                tg._finish(units, results[at:at + len(units)], n_scen, layout=layout)
         at += len(units)
     # every rank lists the units of all targets (cheap: no argument is built before a unit's owner calls it)
     # and fills every target's table from the gathered records; both are a few ms for 64 targets
