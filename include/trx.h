@@ -145,6 +145,25 @@ int trx_flux_grid(int model, int flags,
 int trx_chi2_grid(const double* flux, const double* model_grid, int n_time, long n, double sigma,
                   double* out_halfchi2, void* stream);
 
+/* Column quantiles of a row-major grid: out[i][c] = np.quantile(v[:, c], q[i]) (numpy's default "linear" method) over
+ * the n_rows values v[r][c] of column c -- the pointwise credible band of the model curves trx_flux_grid wrote, one
+ * curve per row (no reference counterpart: the reference draws the best-fit curve only).
+ *   grid   [n_grid_rows][n_cols] (device)
+ *   rows   [n_rows] (device) or NULL: the grid row each of the n_rows values comes from, every entry in
+ *          [0, n_grid_rows), repeats allowed (an entry outside contributes a NaN); NULL: rows 0 .. n_rows - 1
+ *   scale  [n_rows] (device) or NULL: v[r][c] = 1 - scale[r] * (1 - grid[rows[r]][c]), the inverse of renorm_flux
+ *          (funcs.py:164-177: a model in its host star's normalisation back in the target's); NULL: the grid value
+ *   q      [n_q] HOST, 0 <= q <= 1, 1 <= n_q <= 16 (copied into the launch: free to reuse on return)
+ *   out    [n_q][n_cols] (device)
+ * With h = (n_rows - 1) q, lo = floor(h), hi = min(lo + 1, n_rows - 1), t = h - lo and a <= b the order statistics lo
+ * and hi of the column: a + (b - a) t for t < 0.5, b - (b - a) (1 - t) for t >= 0.5 (numpy's _lerp, every operation
+ * rounded on its own), exactly a where a == b; NaN for every q of a column that holds a NaN.  The result does not
+ * depend on the launch geometry and repeats bit for bit.  1 <= n_rows <= TRX_POST_MAX_ROWS.  NULL grid / q / out,
+ * n_rows or n_q out of range, n_cols < 1, a q outside [0, 1] or NaN: TRX_ERR_ARG, nothing is enqueued. */
+int trx_grid_quantiles(const double* grid, long n_grid_rows, int n_cols,
+                       const long* rows, const double* scale, long n_rows,
+                       const double* q, int n_q, double* out, void* stream);
+
 /* Bytes of device scratch the reductions below need (a small constant: 64 KiB). */
 size_t trx_workspace_bytes(void);
 

@@ -31,7 +31,7 @@ ERR_NTOTAL = 4
 ABI_SYMBOLS = (
     "trx_lnl_batch", "trx_flux_grid", "trx_chi2_grid", "trx_workspace_bytes",
     "trx_log_mean_exp", "trx_lnz_scenario", "trx_lnz_from_halfchi2", "trx_lnz_moments_from_halfchi2",
-    "trx_posterior_from_halfchi2",
+    "trx_posterior_from_halfchi2", "trx_grid_quantiles",
     "trx_lnl_batch_host", "trx_flux_grid_host",
     "trx_log_mean_exp_host", "trx_skipped_rows", "trx_pruned_rows",
     "trx_draw_scenario", "trx_draw_args_size", "trx_scenario_evidence", "trx_scenario_enqueue", "trx_star_enqueue",
@@ -164,6 +164,8 @@ def _load(path, testing):
     L.trx_posterior_from_halfchi2.restype = c_int
     L.trx_posterior_from_halfchi2.argtypes = [_vp, _vp, c_long, c_double, c_int, ctypes.c_ulonglong, _vp, _vp, _vp,
                                               c_size_t, _vp]
+    L.trx_grid_quantiles.restype = c_int
+    L.trx_grid_quantiles.argtypes = [_vp, c_long, c_int, _vp, _vp, c_long, _vp, c_int, _vp, _vp]
     L.trx_lnl_batch_host.restype = c_int
     L.trx_lnl_batch_host.argtypes = [c_int, c_int, _vp, _vp, c_int, c_double, _vp, c_long,
                                      c_double, c_int, _vp]
@@ -386,11 +388,14 @@ def lnl_batch(model, flags, time_d, flux_d, sigma, params_d, exptime, nsamples, 
     return out
 
 
-def flux_grid(model, flags, time_d, params_d, exptime, nsamples, want_secdepth=True):
+def flux_grid(model, flags, time_d, params_d, exptime, nsamples, want_secdepth=True, out=None):
+    """out: an [n][n_time] contiguous fp64 device tensor to write into (e.g. a slice of rows of a larger grid)"""
     require_gpu()
     n = params_d.shape[1]
     assert params_d.shape[0] == N_PARAM[model] and params_d.is_contiguous()
-    out = torch.empty((n, time_d.numel()), dtype=torch.float64, device=params_d.device)
+    if out is None:
+        out = torch.empty((n, time_d.numel()), dtype=torch.float64, device=params_d.device)
+    assert out.shape == (n, time_d.numel()) and out.dtype == torch.float64 and out.is_contiguous()
     sec = torch.zeros(n, dtype=torch.float64, device=params_d.device) if want_secdepth else None
     with torch.cuda.device(params_d.device):
         check(lib().trx_flux_grid(model, flags, time_d.data_ptr(), time_d.numel(),
@@ -484,6 +489,30 @@ def lnz_moments_from_halfchi2(h_d, lnprior_d, n_total, lnsigma):
 
 
 POST_MAX_ROWS = 4096       # TRX_POST_MAX_ROWS (include/trx.h)
+QUANTILES_MAX = 16         # quantile levels of one trx_grid_quantiles call
+
+
+def grid_quantiles(grid_d, q, rows_d=None, scale_d=None):
+    """Column quantiles of a row-major device grid (trx_grid_quantiles): np.quantile(v, q, axis=0) as an [n_q][n_cols]
+    device tensor (no sync), v the rows of grid_d -- or, with rows_d (int64 device tensor, repeats allowed), the rows
+    grid_d[rows_d] -- and, with scale_d (one fp64 per row of v), 1 - scale[:, None] * (1 - v)."""
+    require_gpu()
+    assert grid_d.dim() == 2 and grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    n_grid_rows, n_cols = grid_d.shape
+    n_rows = n_grid_rows
+    if rows_d is not None:
+        assert rows_d.dtype == torch.int64 and rows_d.is_contiguous() and rows_d.device == grid_d.device
+        n_rows = rows_d.numel()
+    if scale_d is not None:
+        assert scale_d.dtype == torch.float64 and scale_d.is_contiguous() and scale_d.numel() == n_rows
+    qa = np.ascontiguousarray(q, dtype=np.float64).ravel()
+    out = torch.empty((qa.size, n_cols), dtype=torch.float64, device=grid_d.device)
+    with torch.cuda.device(grid_d.device):
+        check(lib().trx_grid_quantiles(grid_d.data_ptr(), n_grid_rows, n_cols,
+                                       rows_d.data_ptr() if rows_d is not None else None,
+                                       scale_d.data_ptr() if scale_d is not None else None, n_rows,
+                                       qa.ctypes.data, qa.size, out.data_ptr(), _stream(grid_d)))
+    return out
 WARP_DIMS, WARP_BINS = 7, 64                  # TRX_WARP_DIMS, TRX_WARP_BINS: the importance map of trx_draw_args.warp
 WARP_BRANCH = 8 + WARP_DIMS * WARP_BINS       # TRX_WARP_BRANCH: 64-bit words of one branch's weight histogram
 

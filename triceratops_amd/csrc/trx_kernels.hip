@@ -53,6 +53,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 
 #include "trx_cells.hpp"
 #include "trx_reduce.hpp"
+#include "trx_bands.hpp"
 
 namespace {
 
@@ -987,6 +988,26 @@ int trx_chi2_grid(const double* flux, const double* model_grid, int n_time, long
                        static_cast<hipStream_t>(stream), flux, model_grid, n_time, n, sigma,
                        out_halfchi2, vec_ok);
     TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trx_grid_quantiles(const double* grid, long n_grid_rows, int n_cols, const long* rows, const double* scale,
+                       long n_rows, const double* q, int n_q, double* out, void* stream)
+{
+    if (!grid || !q || !out) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    if (n_rows < 1 || n_rows > TRX_POST_MAX_ROWS)
+        return fail(TRX_ERR_ARG, "n_rows must lie in [1, TRX_POST_MAX_ROWS]%s (got %ld)", "", n_rows);
+    if (n_cols < 1 || n_grid_rows < 1) return fail(TRX_ERR_ARG, "empty grid%s (n_cols=%ld)", "", (long)n_cols);
+    if (!rows && n_rows > n_grid_rows) return fail(TRX_ERR_ARG, "more rows than the grid holds%s (n_rows=%ld)", "", n_rows);
+    if (n_q < 1 || n_q > kBandMaxQ) return fail(TRX_ERR_ARG, "n_q must lie in [1, 16]%s (got %ld)", "", (long)n_q);
+    BandArgs a{};
+    for (int i = 0; i < n_q; ++i) {
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(TRX_ERR_ARG, "quantile levels must lie in [0, 1]%s (entry %ld)", "", (long)i);
+        a.q[i] = q[i];
+    }
+    a.g = grid; a.n_grid_rows = n_grid_rows; a.n_cols = n_cols; a.rows = rows; a.scale = scale; a.n_rows = (int)n_rows;
+    a.n_q = n_q; a.out = out;
+    TRX_HIP(band_launch(a, static_cast<hipStream_t>(stream)));
     return TRX_OK;
 }
 

@@ -48,6 +48,23 @@ _TARGET_CALLS = (
 )
 
 
+def _model_block(is_tp, comp, c):
+    """(model, flags, [n_param][n] host block) of the light curves of n parameter sets of one kind -- is_tp: planets
+    (else binaries), comp: the companion hosts the transit --, c: the per-set arrays under the names of _COLS.  Kepler's
+    third law on M_s (planets) or M_s + M_EB (binaries) at P_orb as given (a twin row holds 2 P_orb), and the
+    reference's scalar-path radius-ratio rule (likelihoods.py:63-66, 122-131)."""
+    M = c["M_s"] + (0.0 if is_tp else c["M_EB"])
+    P = c["P_orb"]
+    a = ((G * M * Msun) / (4 * pi ** 2) * (P * 86400) ** 2) ** (1 / 3)
+    common = (P, c["inc"], a, c["R_s"], c["u1"], c["u2"], c["ecc"], c["argp"], c["fluxratio_comp"])
+    if is_tp:
+        model, cols = _lib.MODEL_TP, (c["R_p"],) + common
+    else:
+        model, cols = _lib.MODEL_EB, (c["R_EB"], c["fluxratio_EB"]) + common
+    flags = _lib.FLAG_SCALAR_K | (_lib.FLAG_COMPANION_IS_HOST if comp else 0)
+    return model, flags, _lib.pack_params(model, cols, len(P))
+
+
 class target:
     def __init__(self, ID: int, sectors=None, search_radius: int = 10, mission: str = "TESS",
                  lightkurve_cache_dir=None, trilegal_fname=None, ra: float = None,
@@ -322,10 +339,8 @@ class target:
             out.append(row)
         return DataFrame(out)
 
-    def posterior_samples(self, n, rng=None):
-        """n draws from the model-averaged posterior: a scenario in proportion to its `prob`, then one of its
-        (equally weighted) samples.  DataFrame of n rows: `scenario`, `ID`, and the physical columns.  Scenarios
-        without samples contribute nothing (their probability is zero or was dropped).  Host side, numpy only."""
+    def _samples(self):
+        """`.posterior` of the last calc_posteriors; raises where there are no samples to draw from"""
         self._finish_pending()            # (a table left to its first reader: calc_posteriors_many on several ranks)
         post = self.__dict__.get("posterior")
         if post is None and self.__dict__.get("posterior_quantiles") is not None:
@@ -333,21 +348,38 @@ class target:
                              "gone -- run calc_posteriors_many(keep='samples') to draw from them")
         if post is None:
             raise ValueError("no posterior samples: run calc_posteriors first")
+        return post
+
+    def _mixture_picks(self, post, n, rng=None):
+        """n (scenario row, sample index) picks from the model-averaged posterior: a scenario in proportion to its
+        `prob`, then one of its (equally weighted) samples -- the picks of posterior_samples and of fit_bands'
+        model average (the same rng gives both the same picks)."""
         rng = np.random.default_rng() if rng is None else rng
-        cols = self._probs_columns
         have = np.array([p is not None for p in post])
-        w = np.where(have, np.nan_to_num(np.asarray(cols["prob"], dtype=np.float64)), 0.0)
+        w = np.where(have, np.nan_to_num(np.asarray(self._probs_columns["prob"], dtype=np.float64)), 0.0)
         if not w.sum() > 0:
             raise ValueError("no scenario with posterior samples carries probability")
         which = rng.choice(len(post), size=int(n), p=w / w.sum())
+        sample = np.zeros(int(n), dtype=np.int64)
+        for j in np.unique(which):
+            sel = which == j
+            sample[sel] = rng.integers(0, len(post[j]["lnw"]), size=int(sel.sum()))
+        return which, sample
+
+    def posterior_samples(self, n, rng=None):
+        """n draws from the model-averaged posterior: a scenario in proportion to its `prob`, then one of its
+        (equally weighted) samples.  DataFrame of n rows: `scenario`, `ID`, and the physical columns.  Scenarios
+        without samples contribute nothing (their probability is zero or was dropped).  Host side, numpy only."""
+        post = self._samples()
+        cols = self._probs_columns
+        which, sample = self._mixture_picks(post, n, rng)
         out = {"scenario": np.asarray(cols["scenario"])[which], "ID": np.asarray(cols["ID"])[which]}
         for c in _POSTERIOR_PARAMS:
             out[c] = np.empty(int(n))
         for j in np.unique(which):
             sel = which == j
-            pick = rng.integers(0, len(post[j]["lnw"]), size=int(sel.sum()))
             for c in _POSTERIOR_PARAMS:
-                out[c][sel] = np.asarray(post[j][c])[pick]
+                out[c][sel] = np.asarray(post[j][c])[sample[sel]]
         return DataFrame(out)
 
     def calc_probs_runs(self, time, flux_0, flux_err_0: float, P_orb, n_runs: int = 20, **calc_probs_kwargs):
@@ -638,18 +670,12 @@ class target:
         t_d = _lib.dev(model_time)
         for (is_tp, comp), rows in groups.items():
             r = np.array(rows)
-            M = df["M_s"].values[r] + (0.0 if is_tp else df["M_EB"].values[r])
-            P = df["P_orb"].values[r]
-            a = ((G * M * Msun) / (4 * pi ** 2) * (P * 86400) ** 2) ** (1 / 3)
-            common = (P, df["inc"].values[r], a, df["R_s"].values[r], u1[r], u2[r],
-                      df["ecc"].values[r], df["w"].values[r], fr_comp[r])
-            if is_tp:
-                model, cols = _lib.MODEL_TP, (df["R_p"].values[r],) + common
-            else:
-                model, cols = _lib.MODEL_EB, (df["R_EB"].values[r], fr_EB[r]) + common
-            flags = _lib.FLAG_SCALAR_K | (_lib.FLAG_COMPANION_IS_HOST if comp else 0)
-            grid, _ = _lib.flux_grid(model, flags, t_d, _lib.dev(_lib.pack_params(model, cols, len(r))),
-                                     exptime, nsamples, want_secdepth=False)
+            model, flags, block = _model_block(is_tp, comp, {
+                "M_s": df["M_s"].values[r], "M_EB": df["M_EB"].values[r], "P_orb": df["P_orb"].values[r],
+                "inc": df["inc"].values[r], "R_s": df["R_s"].values[r], "u1": u1[r], "u2": u2[r],
+                "ecc": df["ecc"].values[r], "argp": df["w"].values[r], "fluxratio_comp": fr_comp[r],
+                "R_p": df["R_p"].values[r], "R_EB": df["R_EB"].values[r], "fluxratio_EB": fr_EB[r]})
+            grid, _ = _lib.flux_grid(model, flags, t_d, _lib.dev(block), exptime, nsamples, want_secdepth=False)
             models[r] = grid.cpu().numpy()
         curves = []
         for k in range(len(df)):
@@ -658,6 +684,83 @@ class target:
             curves.append({"ID": df["ID"].values[k], "scenario": df["scenario"].values[k],
                            "flux": flux, "flux_err": flux_err, "model": models[k]})
         return model_time, curves
+
+    def fit_bands(self, time, flux_0, flux_err_0: float, n_model: int = 100, q=(0.16, 0.5, 0.84),
+                  exptime: float = 0.00139, nsamples: int = 20, model_average: int = 0, rng=None):
+        """Posterior-predictive light-curve bands of every scenario of the last calc_posteriors (or
+        calc_posteriors_many(keep="samples")): the model curve of EVERY posterior sample, reduced on the device to its
+        pointwise quantiles `q`.  The companion of fit_curves, which gives the best draw's curve.
+
+        Returns (model_time, bands): model_time as in fit_curves, and one dict per row of .probs {ID, scenario, flux,
+        flux_err -- as fit_curves returns them --, q, band, n_samples}: band is the [len(q)][n_model] array
+        np.quantile(curves of the row's samples, q, axis=0) in the normalisation of that scenario's host star, or None
+        for a row without samples (n_samples = 0).  The parameter blocks are fit_curves' with every column taken from
+        the samples; all samples of all rows of one kind (TP / EB, companion-is-host or not) go to the GPU as one block.
+
+        model_average = n > 0 appends the band of the mixture of the scenarios in proportion to `prob` (scenario
+        "model average", the target's ID, flux_0 and flux_err_0 as given): the quantiles over the curves of the n
+        (scenario, sample) picks posterior_samples(n, rng) makes from the same rng, each curve taken back to the TARGET's
+        normalisation, 1 - fluxratio_host (1 - curve).  That entry also names its picks: "rows" (the rows of .probs) and
+        "samples" (the index into that row's samples)."""
+        import torch
+        from . import fused
+        post = self._samples()
+        if all(p is None for p in post):
+            raise ValueError("no scenario with posterior samples carries probability")
+        q = tuple(float(x) for x in np.atleast_1d(q))
+        if not 1 <= len(q) <= _lib.QUANTILES_MAX or not all(0.0 <= x <= 1.0 for x in q):
+            raise ValueError("q must hold 1 to %d quantile levels in [0, 1]" % _lib.QUANTILES_MAX)
+        model_average = int(model_average)
+        if not 0 <= model_average <= fused.POST_MAX_ROWS:
+            raise ValueError("model_average must lie in [0, %d]" % fused.POST_MAX_ROWS)
+        time = np.asarray(time, dtype=np.float64)
+        flux_0 = np.asarray(flux_0, dtype=np.float64)
+        live = np.flatnonzero((self.probs["ID"] != 0).values)       # rows calc_probs never reached keep ID 0
+        df = self.probs.iloc[live]
+        star_num = self.star_num[live]
+        model_time = np.linspace(np.min(time), np.max(time), n_model)
+        star_ids = self.stars["ID"].astype(str).values
+        share = [self.stars["fluxratio"].values[np.argwhere(star_ids == str(ID))[0, 0]] for ID in df["ID"].values]
+        # the samples of every row, grouped as fit_curves groups the rows; the groups' grids are consecutive row ranges
+        # of ONE device grid, so that the mixture's gather list addresses them all
+        groups, n_of = {}, np.zeros(len(df), dtype=np.int64)
+        for k, j in enumerate(live):
+            if post[j] is not None:
+                n_of[k] = len(post[j]["lnw"])
+                groups.setdefault((k % 3 == 0, bool(star_num[k] != 1)), []).append(k)
+        first = np.zeros(len(df), dtype=np.int64)        # grid row of a row's sample 0
+        t_d = _lib.dev(model_time)
+        grid = torch.empty((int(n_of.sum()), n_model), dtype=torch.float64, device=t_d.device)
+        at = 0
+        for (is_tp, comp), rows in groups.items():
+            model, flags, block = _model_block(is_tp, comp, {
+                c: np.concatenate([np.asarray(post[live[k]][c], dtype=np.float64) for k in rows]) for c in _COLS})
+            n = block.shape[1]
+            _lib.flux_grid(model, flags, t_d, _lib.dev(block), exptime, nsamples, want_secdepth=False, out=grid[at:at + n])
+            for k in rows:
+                first[k], at = at, at + n_of[k]
+        have = np.flatnonzero(n_of)
+        bands_d = torch.empty((len(have) + (model_average > 0), len(q), n_model), dtype=torch.float64, device=t_d.device)
+        for i, k in enumerate(have):
+            bands_d[i] = _lib.grid_quantiles(grid[first[k]:first[k] + n_of[k]], q)
+        if model_average:
+            which, sample = self._mixture_picks(post, model_average, rng)
+            at_live = {j: k for k, j in enumerate(live)}
+            rows = np.array([first[at_live[j]] for j in which], dtype=np.int64) + sample
+            scale = np.array([share[at_live[j]] for j in which], dtype=np.float64)
+            bands_d[-1] = _lib.grid_quantiles(grid, q, rows_d=torch.as_tensor(rows).to(grid.device), scale_d=_lib.dev(scale))
+        bands_h = bands_d.cpu().numpy()
+        slot = {k: i for i, k in enumerate(have)}
+        bands = []
+        for k in range(len(df)):
+            flux, flux_err = renorm_flux(flux_0, flux_err_0, share[k])
+            bands.append({"ID": df["ID"].values[k], "scenario": df["scenario"].values[k], "flux": flux,
+                          "flux_err": flux_err, "q": q, "band": bands_h[slot[k]] if k in slot else None,
+                          "n_samples": int(n_of[k])})
+        if model_average:
+            bands.append({"ID": self.ID, "scenario": "model average", "flux": flux_0, "flux_err": flux_err_0, "q": q,
+                          "band": bands_h[-1], "n_samples": model_average, "rows": which, "samples": sample})
+        return model_time, bands
 
 
 def calc_probs_many(jobs, verbose: int = 0):
