@@ -145,6 +145,21 @@ int trx_flux_grid(int model, int flags,
 int trx_chi2_grid(const double* flux, const double* model_grid, int n_time, long n, double sigma,
                   double* out_halfchi2, void* stream);
 
+/* trx_chi2_grid with per-point weights, for light curves whose errors differ from point to point and for evidences
+ * summed over several light curves (no reference counterpart):
+ *   out[r] = (accumulate ? out[r] : 0) + 0.5 * sum_t inv_var[t] * (flux[t] - model_grid[r][t])^2
+ * flux, inv_var [n_time], model_grid [n][n_time] row-major, secdepth [n] or NULL, out_halfchi2 [n]: device, 8-byte
+ * aligned.  With secdepth != NULL out[r] = +inf where secdepth[r] >= sec_limit (false for a NaN depth, as numpy's
+ * comparison); +inf stays +inf under accumulation.  HBM-bound: every grid value is read once.
+ * Each row's sum has one fixed order that depends on n_time alone (csrc/trx_reduce.hpp): the result does not depend on
+ * the launch geometry, on the row's position in the grid or on the alignment of any pointer (16-byte aligned rows are
+ * read with 16-byte loads, the others with 8-byte loads -- same values, same arithmetic, same bits) and repeats bit for
+ * bit.  NULL flux / inv_var / model_grid / out_halfchi2, n < 0 or n_time < 1: TRX_ERR_ARG, nothing is enqueued;
+ * n == 0 launches nothing. */
+int trx_chi2_grid_weighted(const double* flux, const double* inv_var, const double* model_grid,
+                           int n_time, long n, const double* secdepth, double sec_limit,
+                           int accumulate, double* out_halfchi2, void* stream);
+
 /* Column quantiles of a row-major grid: out[i][c] = np.quantile(v[:, c], q[i]) (numpy's default "linear" method) over
  * the n_rows values v[r][c] of column c -- the pointwise credible band of the model curves trx_flux_grid wrote, one
  * curve per row (no reference counterpart: the reference draws the best-fit curve only).

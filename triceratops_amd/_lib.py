@@ -29,7 +29,7 @@ ERR_NTOTAL = 4
 
 # every symbol include/trx.h declares (tests check that libtrx.so exports all of them and nothing of trx_debug.h)
 ABI_SYMBOLS = (
-    "trx_lnl_batch", "trx_flux_grid", "trx_chi2_grid", "trx_workspace_bytes",
+    "trx_lnl_batch", "trx_flux_grid", "trx_chi2_grid", "trx_chi2_grid_weighted", "trx_workspace_bytes",
     "trx_log_mean_exp", "trx_lnz_scenario", "trx_lnz_from_halfchi2", "trx_lnz_moments_from_halfchi2",
     "trx_posterior_from_halfchi2", "trx_grid_quantiles",
     "trx_lnl_batch_host", "trx_flux_grid_host",
@@ -150,6 +150,8 @@ def _load(path, testing):
     L.trx_flux_grid.argtypes = [c_int, c_int, _vp, c_int, _vp, c_long, c_double, c_int, _vp, _vp, _vp]
     L.trx_chi2_grid.restype = c_int
     L.trx_chi2_grid.argtypes = [_vp, _vp, c_int, c_long, c_double, _vp, _vp]
+    L.trx_chi2_grid_weighted.restype = c_int
+    L.trx_chi2_grid_weighted.argtypes = [_vp, _vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp]
     L.trx_workspace_bytes.restype = c_size_t
     L.trx_workspace_bytes.argtypes = []
     L.trx_log_mean_exp.restype = c_int
@@ -413,6 +415,28 @@ def chi2_grid(flux_d, grid_d, sigma):
     with torch.cuda.device(grid_d.device):
         check(lib().trx_chi2_grid(flux_d.data_ptr(), grid_d.data_ptr(), nt, n, float(sigma),
                                   out.data_ptr(), _stream(grid_d)))
+    return out
+
+
+def chi2_grid_weighted(flux_d, inv_var_d, grid_d, secdepth_d=None, sec_limit=float("inf"), out=None):
+    """0.5 * sum_t inv_var[t] (flux[t] - grid[r][t])^2 per row of an [n][n_time] device grid (trx_chi2_grid_weighted);
+    +inf where secdepth_d[r] >= sec_limit.  out: an [n] fp64 device tensor to ADD the rows' values to (the next light
+    curve of an evidence over several); None: a fresh tensor.  Rows may start at any 8-byte boundary (a view's offset)."""
+    require_gpu()
+    n, nt = grid_d.shape
+    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    assert flux_d.numel() == nt and inv_var_d.numel() == nt and flux_d.is_contiguous() and inv_var_d.is_contiguous()
+    assert secdepth_d is None or (secdepth_d.numel() == n and secdepth_d.is_contiguous())
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
+    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
+    if n == 0:
+        return out                     # (an empty tensor has no address to pass)
+    with torch.cuda.device(grid_d.device):
+        check(lib().trx_chi2_grid_weighted(flux_d.data_ptr(), inv_var_d.data_ptr(), grid_d.data_ptr(), nt, n,
+                                           secdepth_d.data_ptr() if secdepth_d is not None else None,
+                                           float(sec_limit), int(accumulate), out.data_ptr(), _stream(grid_d)))
     return out
 
 

@@ -7,7 +7,7 @@
 //                    cell, the (cell, node) pairs dealt to all lanes; centre-value stencil on dense uniform grids; the
 //                    passes of the bounded evaluation), pilot_stats_kernel, depth_screen_kernel, and what host and
 //                    device share (RowsArgs, batch_rows, batch_plan, set_scratch)
-//   trx_reduce.hpp   chi2_grid_kernel (row reduction over a materialised grid) and the log-mean-exp kernels, HBM bound
+//   trx_reduce.hpp   chi2_grid_kernel, chi2_grid_weighted_kernel (row reductions over a materialised grid) and the log-mean-exp kernels, HBM bound
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells), the launchers (launch_cells, lnl_lme_chain), the per-stream scratch and the
 // scratch of captured calls, the node tables, the entry points of include/trx.h and -- testing build only -- of
@@ -987,6 +987,30 @@ int trx_chi2_grid(const double* flux, const double* model_grid, int n_time, long
     hipLaunchKernelGGL(chi2_grid_kernel, dim3((unsigned)blocks), dim3(256), 0,
                        static_cast<hipStream_t>(stream), flux, model_grid, n_time, n, sigma,
                        out_halfchi2, vec_ok);
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trx_chi2_grid_weighted(const double* flux, const double* inv_var, const double* model_grid, int n_time, long n,
+                           const double* secdepth, double sec_limit, int accumulate, double* out_halfchi2, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (!flux || !inv_var || !model_grid || !out_halfchi2) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    if (n == 0) return TRX_OK;
+    // as many blocks as stay resident (8 of 256 threads a CU, fewer where the staged vectors fill the LDS), 256 CUs
+    const bool stage = n_time <= kChi2wStageMax;
+    const size_t lds = stage ? 2 * (size_t)((n_time + 1) & ~1) * sizeof(double) : 0;
+    long per_cu = lds ? (long)((160u * 1024u) / lds) : 8;
+    per_cu = per_cu > 8 ? 8 : per_cu;
+    long blocks = (n + 3) / 4;
+    if (blocks > 256L * per_cu) blocks = 256L * per_cu;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (stage)
+        hipLaunchKernelGGL(chi2_grid_weighted_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, st, flux, inv_var,
+                           model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2);
+    else
+        hipLaunchKernelGGL(chi2_grid_weighted_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, flux, inv_var,
+                           model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2);
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

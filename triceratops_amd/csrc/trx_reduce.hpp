@@ -1,4 +1,5 @@
-// The HBM-bound reductions: chi2_grid_kernel (row reduction over a materialised grid) and the log-mean-exp kernels
+// The HBM-bound reductions: chi2_grid_kernel and chi2_grid_weighted_kernel (row reductions over a materialised grid)
+// and the log-mean-exp kernels
 // (lme_partial_kernel / lme_partial_kernel_star with the scenario's final stage, lme_final_kernel).  Included by
 // trx_kernels.hip only.
 #pragma once
@@ -40,6 +41,102 @@ __global__ __launch_bounds__(256) void chi2_grid_kernel(const double* __restrict
         }
         const double tot = wave_sum(acc);
         if (lane == 0) out[r] = 0.5 * tot;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// 0.5 * sum_t inv_var_t (flux_t - model[r][t])^2 per row, written or added to out[r]; +inf where secdepth[r] >= sec_limit
+// (trx_chi2_grid_weighted).  One wavefront per row, two rows in flight per wave; every grid value is read once
+// (non-temporal), flux and inv_var come from LDS (STAGE: staged once per block) or, past kChi2wStageMax stamps, from the
+// caches.
+//
+// The order of summation of a row is fixed by n_time alone: lane l takes the stamp pairs (2 j, 2 j + 1), j = l, l + 64,
+// ... in ascending order -- an odd n_time's last stamp after them, on lane (n_time / 2) % 64 --, every term is
+// fma(w * d, d, acc) with the product rounded on its own, then wave_sum's butterfly.  A row whose address is a multiple
+// of 16 reads each pair with one 16-byte load, any other row (odd n_time: every second one; a grid view offset by one
+// double) with two 8-byte loads: the same values into the same arithmetic, so the same bits.  Neither the launch
+// geometry nor a row's position in the grid enters its result.
+constexpr int kChi2wStageMax = 2048;                // stamps whose flux and inv_var are staged in LDS: 32 KB a block
+
+template <bool STAGE>
+__device__ __forceinline__ double chi2w_row_partial(const double* __restrict__ row, const double* f, const double* w,
+                                                    int n_time, int lane)
+{
+    typedef double dvec2 __attribute__((ext_vector_type(2)));
+    const int nv = n_time >> 1;
+    const bool vec = ((uintptr_t)row & 15) == 0;      // (per row: wave-uniform)
+    double acc = 0.0;
+    for (int j = lane; j < nv; j += 64) {
+        double m0, m1, f0, f1, w0, w1;
+        if (vec) {
+            const dvec2 m = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(row) + j);
+            m0 = m.x; m1 = m.y;
+        } else {
+            m0 = __builtin_nontemporal_load(row + 2 * j);
+            m1 = __builtin_nontemporal_load(row + 2 * j + 1);
+        }
+        if (STAGE) {
+            // (the staged copies are 16-byte aligned whatever the caller's pointers are)
+            const dvec2 fv = reinterpret_cast<const dvec2*>(f)[j], wv = reinterpret_cast<const dvec2*>(w)[j];
+            f0 = fv.x; f1 = fv.y; w0 = wv.x; w1 = wv.y;
+        } else {
+            f0 = f[2 * j]; f1 = f[2 * j + 1]; w0 = w[2 * j]; w1 = w[2 * j + 1];
+        }
+        const double d0 = f0 - m0, d1 = f1 - m1;
+        acc = fma(w0 * d0, d0, acc);
+        acc = fma(w1 * d1, d1, acc);
+    }
+    if ((n_time & 1) && lane == (nv & 63)) {
+        const int t = n_time - 1;
+        const double d = f[t] - __builtin_nontemporal_load(row + t);
+        acc = fma(w[t] * d, d, acc);
+    }
+    return acc;
+}
+
+__device__ __forceinline__ void chi2w_store(double tot, long r, const double* __restrict__ secdepth, double sec_limit,
+                                            int accumulate, double* __restrict__ out)
+{
+    double h = 0.5 * tot;
+    if (secdepth && secdepth[r] >= sec_limit) h = INFINITY;        // (false for a NaN depth, as in numpy)
+    out[r] = accumulate ? out[r] + h : h;                           // (+inf stays +inf: h is never -inf)
+}
+
+template <bool STAGE>
+__global__ __launch_bounds__(256) void chi2_grid_weighted_kernel(const double* __restrict__ flux,
+                                                                 const double* __restrict__ inv_var,
+                                                                 const double* __restrict__ grid, int n_time, long n,
+                                                                 const double* __restrict__ secdepth, double sec_limit,
+                                                                 int accumulate, double* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) double chi2w_lds[];     // STAGE: [2][n_time rounded up to even]
+    const double* f = flux;
+    const double* w = inv_var;
+    if (STAGE) {
+        const int n_pad = (n_time + 1) & ~1;
+        for (int t = threadIdx.x; t < n_time; t += 256) {
+            chi2w_lds[t] = flux[t];
+            chi2w_lds[n_pad + t] = inv_var[t];
+        }
+        __syncthreads();
+        f = chi2w_lds;
+        w = chi2w_lds + n_pad;
+    }
+    const int lane = threadIdx.x & 63;
+    const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long nwaves = (long)gridDim.x * 4;
+    for (long r = wave0; r < n; r += 2 * nwaves) {
+        // two rows per trip, their loads in flight together; each row's arithmetic is its own
+        const long r2 = r + nwaves;
+        const bool two = r2 < n;
+        const double a0 = chi2w_row_partial<STAGE>(grid + (size_t)r * n_time, f, w, n_time, lane);
+        const double a1 = two ? chi2w_row_partial<STAGE>(grid + (size_t)r2 * n_time, f, w, n_time, lane) : 0.0;
+        const double t0 = wave_sum(a0);
+        const double t1 = wave_sum(a1);
+        if (lane == 0) {
+            chi2w_store(t0, r, secdepth, sec_limit, accumulate, out);
+            if (two) chi2w_store(t1, r2, secdepth, sec_limit, accumulate, out);
+        }
     }
 }
 

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, funcs
+from .datasets import Datasets
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
@@ -178,9 +179,16 @@ WARP_HIST = False
 WARP_BRANCH = _lib.WARP_BRANCH
 
 
+# Several light curves with per-point errors: a lnZ_* call whose `time` is a datasets.Datasets
+# object evaluates every masked draw in full on every dataset -- trx_flux_grid writes the model curves of a chunk of rows,
+# trx_chi2_grid_weighted adds their weighted chi^2/2 -- through run_operator_chain: no bounded evaluation, no launch
+# chain.  DATASET_GRID_BYTES bounds the grid of one chunk; the results are the same bits for any value.
+DATASET_GRID_BYTES = 512 << 20
+
+
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -710,7 +718,16 @@ class _Scenario:
 
     def __init__(self, time, flux, sigma, N, parallel, exptime, nsamples, mission, flatpriors):
         self.dev = _lib.compute_device()
-        self.time, self.flux = _on_device(time, self.dev), _on_device(flux, self.dev)
+        self.datasets = None
+        if isinstance(time, Datasets):
+            # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
+            self.datasets = [(_on_device(d.time, self.dev), _on_device(d.flux, self.dev),
+                              _on_device(1.0 / (d.flux_err * d.flux_err), self.dev), d.exptime, d.nsamples)
+                             for d in time.sets]
+            sigma = time.sigma_ref
+            self.time, self.flux = self.datasets[0][0], self.datasets[0][1]
+        else:
+            self.time, self.flux = _on_device(time, self.dev), _on_device(flux, self.dev)
         self.sigma, self.N = float(sigma), int(N)
         self.parallel, self.exptime, self.nsamples = bool(parallel), exptime, nsamples
         self.mission, self.flat = mission, bool(flatpriors)
@@ -916,6 +933,10 @@ class _Scenario:
         # round 6: the table of the K best draws is selected and gathered on the device (trx_scenario_args.table_rows;
         # every masked draw evaluated to the end).  The operator chain below remains as the cross-check, the path of the
         # dump / trace hooks, and the replay of exact ties in the seeded numpy modes.
+        if self.datasets is not None:
+            if self.warp is not None or self.want_hist:
+                raise NotImplementedError("an importance map / weight histogram together with datasets is not built")
+            return self.run_operator_chain(is_host, ncol)
         if NATIVE and DUMP is None and _lib.TRACE is None and TABLE_ROWS <= TABLE_MAX_ROWS:
             return self._run_native(is_host, ncol)
         if self.want_hist:
@@ -968,8 +989,12 @@ class _Scenario:
                 block[2] *= 2.0                                  # 2 P_orb
                 block[4] = cols[11].index_select(0, idx)         # a at 2 P_orb
             lp = None if lnprior is None else lnprior.index_select(0, idx)
-            h, lnz = _lib.lnz_scenario(model, flags, self.time, self.flux, self.sigma, block, self.exptime,
-                                       self.nsamples, lp, N, float(np.log(self.sigma)))
+            if self.datasets is not None:
+                h = self._datasets_halfchi2(model, flags, block)
+                lnz = _lib.lnz_from_halfchi2(h, lp, N, float(np.log(self.sigma)))
+            else:
+                h, lnz = _lib.lnz_scenario(model, flags, self.time, self.flux, self.sigma, block, self.exptime,
+                                           self.nsamples, lp, N, float(np.log(self.sigma)))
             if moments:
                 mom = _lib.lnz_moments_from_halfchi2(h, lp, N, float(np.log(self.sigma))).cpu().numpy()
                 self.moments.append((float(mom[1]), float(mom[2])))
@@ -998,6 +1023,35 @@ class _Scenario:
             if POSTERIOR_ROWS:
                 res[-1]["posterior"] = None if post is None else self._posterior_dict(post.cpu().numpy(), ncol, twin)
         return res[0] if a.planet else (res[0], res[1])
+
+    def _datasets_halfchi2(self, model, flags, block):
+        """sum over the datasets of the weighted chi^2/2 of every row of `block` ([n_param][n], the masked draws of one
+        branch): per chunk of rows and per dataset one trx_flux_grid and one accumulating trx_chi2_grid_weighted.  The EB
+        branch's secondary-eclipse rule (secdepth >= 1.5 sigma_bar -> +inf) rides in the first dataset's reduction: the
+        depth does not depend on the time stamps.  A row's value does not depend on the chunk it falls in."""
+        n = int(block.shape[1])
+        h = torch.zeros(n, dtype=F64, device=self.dev)         # (0 + x = x: every reduction accumulates)
+        if n == 0:
+            return h
+        flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL         # (set_precision; the evaluation is full either way)
+        t_max = max(int(d[0].numel()) for d in self.datasets)
+        rows = max(1, int(DATASET_GRID_BYTES) // (8 * t_max))
+        buf = torch.empty(min(rows, n) * t_max, dtype=F64, device=self.dev)
+        eb = model == MODEL_EB
+        for r0 in range(0, n, rows):
+            r1 = min(r0 + rows, n)
+            blk = block if (r0 == 0 and r1 == n) else block[:, r0:r1].contiguous()
+            for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
+                nt = int(time_d.numel())
+                grid, sec = _lib.flux_grid(model, flags, time_d, blk, exptime, nsamples, want_secdepth=eb and l == 0,
+                                           out=buf[:(r1 - r0) * nt].view(r1 - r0, nt))
+                _lib.chi2_grid_weighted(flux_d, inv_var_d, grid, sec, 1.5 * self.sigma, out=h[r0:r1])
+        with _stats_lock:
+            # (the masked draws once, every (draw, time stamp) cell of every dataset)
+            _lib.STATS["rows"] += n
+            _lib.STATS["cells"] += n * sum(int(d[0].numel()) for d in self.datasets)
+            _lib.STATS["launches"] += len(self.datasets) * -(-n // rows)
+        return h
 
     def _run_native(self, is_host, ncol):
         """the whole call in the library: draws, masks, compaction, likelihood, evidence, best draw --

@@ -66,3 +66,23 @@ def prepare(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int
     keep = ~np.isnan(yb)
     tb, yb = tb[keep], yb[keep]
     return tb, yb, float(np.std(yb[:n_sigma]))
+
+
+def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int = 50,
+                    exptime: float = 0.00139, nsamples: int = 20):
+    """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
+    {"time", "flux", "flux_err", "exptime", "nsamples"} of one dataset; empty bins are dropped.
+
+    flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
+    (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
+    the same count in every bin all errors equal prepare()'s sigma."""
+    t, y = trim(time, flux, half_width)
+    if t.size == 0:
+        raise ValueError("no points within %g d of the transit midpoint" % half_width)
+    tb, yb, count = bin_lightcurve(t, y, time_bin_size=2 * np.max(t) / n_bins)
+    keep = ~np.isnan(yb)
+    tb, yb, count = tb[keep], yb[keep], count[keep]
+    head = yb[:n_sigma]
+    scatter = float(np.sqrt(np.mean(count[:n_sigma] * (head - np.mean(head)) ** 2)))
+    return {"time": tb, "flux": yb, "flux_err": scatter / np.sqrt(count), "exptime": float(exptime),
+            "nsamples": int(nsamples)}

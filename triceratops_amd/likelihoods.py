@@ -8,7 +8,8 @@ Same names, argument meaning and return values as the reference's triceratops/li
 Every function packs its per-sample arguments into one SoA parameter block, runs libtrx on the
 current CUDA device and returns numpy arrays.  lnL_* return +chi^2/2 (a negative log-likelihood
 without the Gaussian constant); +inf marks an EB draw whose secondary eclipse is deeper than
-1.5 sigma.  Differences from the reference, on purpose: the caller's `inc` array is not
+1.5 sigma.  `sigma` may also be an array of len(time), one error per point (no reference counterpart; the rule then
+uses sigma_bar = mean(sigma^-2)^-1/2).  Differences from the reference, on purpose: the caller's `inc` array is not
 converted to radians in place (likelihoods.py:344, 410), and the functions do not go through
 shared mutable model objects, so they are re-entrant.  The module-level names `tm` and `tm_sec`
 (likelihoods.py:24-25) exist for code that imports them, but nothing here calls `set_data` on
@@ -18,6 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
+from .datasets import sigma_bar
 from .constants import G, Msun, Rearth, Rsun, au, pi  # noqa: F401  (reference module exports)
 from .transit_model import QuadraticModel
 
@@ -41,8 +43,29 @@ def _grid(model, time, cols, companion_is_host, exptime, nsamples, scalar):
 
 
 def _halfchi2(model, time, flux, sigma, cols, companion_is_host, exptime, nsamples, scalar):
+    if np.ndim(sigma) > 0:
+        return _halfchi2_per_point(model, time, flux, sigma, cols, companion_is_host, exptime, nsamples, scalar)
     out = _lib.lnl_batch(model, _flags(companion_is_host, scalar), _lib.dev(time), _lib.dev(flux),
                          sigma, _block(model, cols), exptime, nsamples)
+    return out.cpu().numpy()
+
+
+def _halfchi2_per_point(model, time, flux, sigma, cols, companion_is_host, exptime, nsamples, scalar):
+    """sigma as an array of len(time): the materialised grid (trx_flux_grid), then the weighted row reduction
+    (trx_chi2_grid_weighted).  The EB rule compares the secondary depth with 1.5 sigma_bar of the array
+    (datasets.sigma_ref: sigma itself where all entries are equal)."""
+    sigma = np.asarray(sigma, dtype=np.float64)
+    if sigma.shape != np.shape(time):
+        raise ValueError("sigma must be a number or an array of len(time) = %d (got shape %s)"
+                         % (np.size(time), sigma.shape))
+    if not np.all(np.isfinite(sigma) & (sigma > 0)):
+        raise ValueError("every sigma must be finite and > 0")
+    inv_var = 1.0 / (sigma * sigma)
+    eb = model == MODEL_EB
+    grid, sec = _lib.flux_grid(model, _flags(companion_is_host, scalar), _lib.dev(time), _block(model, cols), exptime,
+                               nsamples, want_secdepth=eb)
+    limit = 1.5 * sigma_bar([sigma])
+    out = _lib.chi2_grid_weighted(_lib.dev(flux), _lib.dev(inv_var), grid, sec if eb else None, limit)
     return out.cpu().numpy()
 
 

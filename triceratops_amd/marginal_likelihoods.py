@@ -771,6 +771,10 @@ def _dispatch(fn):
             # one fused HIP kernel per scenario (fused.py)
             from . import fused
             return getattr(fused, fn.__name__)(*args, **kwargs)
+        from .datasets import Datasets
+        if args and isinstance(args[0], Datasets):
+            raise NotImplementedError("several light curves / per-point errors (calc_probs_datasets) need a device "
+                                      "sampling mode: set_sampling('device') or 'numpy-device'")
         return fn(*args, **kwargs)
     return wrapper
 

@@ -27,6 +27,7 @@ from scipy.special import ndtr
 from . import _lib
 from ._numerics import _mc_errors, _normalize_probabilities
 from .constants import G, Msun, pi
+from .datasets import Datasets, validate as _validate_datasets
 from .funcs import renorm_flux
 from .marginal_likelihoods import *  # noqa: F401,F403  (reference re-exports the lnZ_* names)
 from .marginal_likelihoods import (lnZ_BEB, lnZ_BTP, lnZ_DEB, lnZ_DTP, lnZ_PEB, lnZ_PTP, lnZ_SEB,
@@ -165,13 +166,19 @@ class target:
         def star_args(i, cache={}):
             """(time, flux, flux_err, P_orb, M_s, R_s, Teff) of star i, built on first use"""
             if i not in cache:
-                flux, flux_err = renorm_flux(flux_0, flux_err_0, col("fluxratio")[i])
+                if isinstance(time, Datasets):
+                    # (calc_probs_datasets: every dataset renormalised to the star; sigma is their sigma_bar)
+                    ds = time.renorm(col("fluxratio")[i])
+                    t_i, flux, flux_err = ds, None, ds.sigma_ref
+                else:
+                    t_i = time
+                    flux, flux_err = renorm_flux(flux_0, flux_err_0, col("fluxratio")[i])
                 M_s, R_s, Teff = col("mass")[i], col("rad")[i], col("Teff")[i]
                 if i > 0:      # nearby star: unknown properties default to solar values
                     Teff = 5777 if np.isnan(Teff) else Teff
                     M_s = 1.0 if np.isnan(M_s) else M_s
                     R_s = 1.0 if np.isnan(R_s) else R_s
-                cache[i] = (time, flux, flux_err, P_orb, M_s, R_s, Teff)
+                cache[i] = (t_i, flux, flux_err, P_orb, M_s, R_s, Teff)
             return cache[i]
 
         def target_call(key):
@@ -240,6 +247,43 @@ class target:
         if all(p is None for p in self.posterior) and np.isfinite(self.lnZ).any():
             raise NotImplementedError("calc_posteriors needs the device paths (set_sampling('device') or "
                                       "'numpy-device'): this sampling mode returns no posterior rows")
+        return
+
+    def calc_probs_datasets(self, datasets, P_orb, n_samples: int = 0, **calc_probs_kwargs):
+        """calc_probs on several light curves of one candidate, each with its own cadence and with per-point flux
+        errors (no reference counterpart).
+
+        datasets: a list of 1 to 16 dicts {"time", "flux", "flux_err": a number or an array of len(time),
+        "exptime": 0.00139, "nsamples": 20}.  Points with a NaN time or flux are dropped with their error.  The
+        log-weight of a draw is -ln(sigma_bar) - 0.5 ln 2 pi - sum over the datasets of
+        0.5 sum_t (flux_t - model_t)^2 / sigma_t^2 + lnprior, sigma_bar = mean(sigma_t^-2)^-1/2 over all points: one
+        dataset with one error for all points gives calc_probs' evidences.  calc_probs_kwargs: the other arguments of
+        calc_probs, except exptime and nsamples (each dataset has its own).
+
+        Fills the target as calc_probs does -- and `.posterior` as calc_posteriors does when n_samples > 0 --, plus
+        `.sigma_ref`: sigma_bar in the target star's normalisation.  Every masked draw is evaluated in full on every
+        dataset (model curves written to a grid, then reduced): no bounded evaluation, no launch chains -- several
+        times the time of calc_probs.  Needs set_sampling("device") or "numpy-device"."""
+        from . import fused
+        for k in ("exptime", "nsamples"):
+            if k in calc_probs_kwargs:
+                raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
+        ds = Datasets(_validate_datasets(datasets))
+        n_samples = int(n_samples)
+        if not 0 <= n_samples <= fused.POST_MAX_ROWS:
+            raise ValueError("n_samples must lie in [0, %d]" % fused.POST_MAX_ROWS)
+        from .marginal_likelihoods import _sampling
+        if _sampling["mode"] == "numpy":
+            raise NotImplementedError("calc_probs_datasets needs a device sampling mode: set_sampling('device') or "
+                                      "'numpy-device'")
+        kw = dict(calc_probs_kwargs)
+        verbose = kw.pop("verbose", 1)
+        units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
+        with fused.switches(POSTERIOR_ROWS=n_samples):
+            rows = sharding.run_units(units, verbose=verbose, as_rows=True)
+        self._finish(units, rows, n_scen, layout=sharding.last_layout)
+        share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
+        self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
@@ -426,10 +470,11 @@ class target:
                  nsamples=20, molusc_file=None, job=0):
         """Work units of one calc_probs (triceratops.py:673-735: NaN filter, star filter, table
         sizes) and the number of table rows.  job: index of this target in a calc_probs_many batch."""
-        time = np.asarray(time, dtype=np.float64)
-        flux_0 = np.asarray(flux_0, dtype=np.float64)
-        keep = ~np.isnan(time) & ~np.isnan(flux_0)
-        time, flux_0 = time[keep], flux_0[keep]
+        if not isinstance(time, Datasets):      # (calc_probs_datasets has validated and filtered its light curves)
+            time = np.asarray(time, dtype=np.float64)
+            flux_0 = np.asarray(flux_0, dtype=np.float64)
+            keep = ~np.isnan(time) & ~np.isnan(flux_0)
+            time, flux_0 = time[keep], flux_0[keep]
         # (the stars that can host the signal, triceratops.py:712; as a row mask over the table's own columns --
         # a filtered copy of the DataFrame costs more than everything else in here)
         # (the numeric columns in ONE conversion: eleven `stars[c].to_numpy()` are 30 us of pandas per target, the whole
