@@ -15,7 +15,7 @@
  *   - work is enqueued on `stream` (a hipStream_t passed as void*; NULL = the null
  *     stream) and the call returns without synchronising: safe to call concurrently on
  *     different streams / devices.  The entry points that evaluate the light-curve model
- *     (trx_lnl_batch, trx_flux_grid, trx_lnz_scenario, trx_scenario_evidence, trx_star_enqueue) keep scratch per
+ *     (trx_lnl_batch, trx_lnl_batch_weighted, trx_flux_grid, trx_lnz_scenario, trx_scenario_evidence, trx_star_enqueue) keep scratch per
  *     (device, stream) inside the library -- 152 B per row for the per-row constants, the draw
  *     block of trx_scenario_evidence (~0.36 GB per stream at N = 1e6 draws), the arena of a launch chain of
  *     trx_star_enqueue (that much per call of the chain) -- which serves call after call on that stream and only
@@ -159,6 +159,27 @@ int trx_chi2_grid(const double* flux, const double* model_grid, int n_time, long
 int trx_chi2_grid_weighted(const double* flux, const double* inv_var, const double* model_grid,
                            int n_time, long n, const double* secdepth, double sec_limit,
                            int accumulate, double* out_halfchi2, void* stream);
+
+/* trx_lnl_batch with per-point weights: the light-curve model and its weighted chi^2 in one kernel, the (n x n_time)
+ * grid never materialised (no reference counterpart):
+ *   out[r] = (accumulate ? out[r] : 0) + 0.5 * sum_t inv_var[t] * (flux[t] - m_r(t))^2,
+ * m_r the model trx_flux_grid evaluates for the same arguments (the fused kernel's own order of summation: it agrees
+ * with trx_flux_grid + trx_chi2_grid_weighted to rounding, not bit for bit).  time, flux, inv_var [n_time], params
+ * [n_param][n], out_halfchi2 [n]: device, 8-byte aligned.  inv_var entries are finite and >= 0; a zero drops the point.
+ * The secondary-eclipse rule is trx_chi2_grid_weighted's, not trx_lnl_batch's: for TRX_MODEL_EB out[r] = +inf where
+ * secdepth_r >= sec_limit -- the limit as given, the depth trx_flux_grid's out_secdepth holds; false for a NaN depth
+ * (a depth that is NaN at some of the scan's points only is not told from one that is NaN at none).  sec_limit = +inf
+ * switches the rule off (no secondary scan); +inf stays +inf under accumulation, and with `accumulate` a row whose
+ * out[r] is +inf already is not evaluated.  Every row is evaluated in full whatever `flags` says about the bounded
+ * evaluation; TRX_FLAG_FP32_MODEL and the result-neutral flags apply as in trx_lnl_batch.  Stream order, concurrency
+ * and repeatability: as trx_lnl_batch.  No _host twin.
+ * TRX_MODEL_RAW or an unknown model, a NULL pointer, n < 0, n_time < 1 or nsupersample < 1: TRX_ERR_ARG, nothing is
+ * enqueued; n == 0 launches nothing. */
+int trx_lnl_batch_weighted(int model, int flags,
+                           const double* time, const double* flux, const double* inv_var, int n_time,
+                           const double* params, long n, double exptime, int nsupersample,
+                           double sec_limit, int accumulate,
+                           double* out_halfchi2, void* stream);
 
 /* Column quantiles of a row-major grid: out[i][c] = np.quantile(v[:, c], q[i]) (numpy's default "linear" method) over
  * the n_rows values v[r][c] of column c -- the pointwise credible band of the model curves trx_flux_grid wrote, one

@@ -6,10 +6,14 @@
   python profiles/datasets/measure.py kernels    (a) chi2_grid_weighted_kernel and chi2_grid_kernel on the same 3.2 GB
                                                  grid (200 000 rows x 2000 stamps, bench.py's size), timed with events
   python profiles/datasets/measure.py e2e        (b) TOI-465.01, 75 scenarios, N = 1e6: calc_probs against
-                                                 calc_probs_datasets with one and with two datasets
+                                                 calc_probs_datasets with one and with two datasets, each with
+                                                 evaluation="grid" and evaluation="fused", alternating
+  python profiles/datasets/measure.py routes     (c) the two calc_probs_datasets cases alone, both evaluations, three
+                                                 passes each: the run the job traces for the kernel times of a pass
 
 The job runs `kernels` twice: plainly, and under `rocprofv3 --kernel-trace --stats`, whose kernel trace gives the
-per-launch times quoted (the event timings include the launch gaps of five back-to-back calls).
+per-launch times quoted (the event timings include the launch gaps of five back-to-back calls); `routes` runs under
+the tracer only, in a run of its own.  --only e2e,routes: those steps of the job alone, APPENDED to the results file.
 """
 import csv
 import glob
@@ -57,10 +61,9 @@ def kernels():
     print("events  %-40s %.3f ms  %.2f TB/s  (0.81 GB: 1e6 rows x 100 stamps)" % ("chi2_grid_weighted_kernel", dt * 1e3, 0.808 / dt / 1e3), flush=True)
 
 
-def e2e():
+def _toi465():
     import numpy as np
     import pandas as pd
-    import torch
     from helpers import GOLD, gold
     import triceratops_amd as ta
     from triceratops_amd.triceratops import target
@@ -74,20 +77,95 @@ def e2e():
     kw = dict(contrast_curve_file=os.path.join(GOLD, "toi465_cc.csv"), N=1_000_000, parallel=True, verbose=0)
     one = [{"time": t, "flux": f, "flux_err": s}]
     two = [{"time": t[k::2], "flux": f[k::2], "flux_err": s} for k in (0, 1)]
-    runs = (("calc_probs", lambda: tg.calc_probs(t, f, s, P, **kw)),
-            ("calc_probs_datasets, 1 dataset of 100 points", lambda: tg.calc_probs_datasets(one, P, **kw)),
-            ("calc_probs_datasets, 2 datasets of 50 points", lambda: tg.calc_probs_datasets(two, P, **kw)))
+    return tg, (t, f, s, P), kw, (("1 dataset of 100 points", one), ("2 datasets of 50 points", two))
+
+
+def _timed_pass(fn):
+    import torch
+    torch.manual_seed(1)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+E2E_ROUNDS = 7
+
+
+def e2e():
+    """wall clock of whole calls, each ended by a device synchronise: one warm-up of every case (caches, scratch, code
+    objects), then E2E_ROUNDS rounds in which the cases take turns -- grid and fused next to each other --; the median
+    and the smallest of a case's rounds"""
+    import numpy as np
+    import torch
+    tg, (t, f, s, P), kw, cases = _toi465()
+    runs = [("calc_probs", lambda: tg.calc_probs(t, f, s, P, **kw))]
+    for label, ds in cases:
+        for ev in ("grid", "fused"):
+            runs.append(("calc_probs_datasets, %s, %s" % (label, ev),
+                         lambda ds=ds, ev=ev: tg.calc_probs_datasets(ds, P, evaluation=ev, **kw)))
+    times, fpp, peak = {name: [] for name, _ in runs}, {}, {}
     for name, fn in runs:
-        best = None
-        for rep in range(3):                 # (the first run of each warms caches and scratch)
-            torch.manual_seed(1)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            best = dt if rep and (best is None or dt < best) else best
-        print("e2e     %-48s %.3f s  (%d scenarios, FPP %.4g)" % (name, best, tg.lnZ.size, tg.FPP), flush=True)
+        _timed_pass(fn)
+    for rnd in range(E2E_ROUNDS):
+        for name, fn in runs:
+            torch.cuda.reset_peak_memory_stats()
+            times[name].append(_timed_pass(fn))
+            fpp[name], peak[name] = tg.FPP, torch.cuda.max_memory_allocated()
+    for name, _ in runs:
+        v = np.sort(times[name])
+        print("e2e     %-52s median %.4f s  min %.4f s  max %.4f s  (%d rounds, %d scenarios, FPP %.6g, allocator peak %.0f MiB)"
+              % (name, np.median(v), v[0], v[-1], v.size, tg.lnZ.size, fpp[name], peak[name] / 2 ** 20), flush=True)
+    for label, _ in cases:
+        g, h = (np.median(times["calc_probs_datasets, %s, %s" % (label, ev)]) for ev in ("grid", "fused"))
+        print("e2e     %-52s grid / fused = %.2f  (medians; calc_probs = 1: grid %.1f, fused %.1f)"
+              % (label, g / h, g / np.median(times["calc_probs"]), h / np.median(times["calc_probs"])), flush=True)
+
+
+ROUTE_PASSES = 3
+
+
+def routes():
+    """the run the job traces: every calc_probs_datasets case with both evaluations, ROUTE_PASSES passes each"""
+    tg, (t, f, s, P), kw, cases = _toi465()
+    for label, ds in cases:
+        for ev in ("grid", "fused"):
+            for _ in range(ROUTE_PASSES):
+                dt = _timed_pass(lambda: tg.calc_probs_datasets(ds, P, evaluation=ev, **kw))
+            print("routes  %-52s %.4f s under the tracer (last of %d passes)" % ("%s, %s" % (label, ev), dt, ROUTE_PASSES), flush=True)
+
+
+def routes_summary(trace):
+    """kernel time of the `routes` step by kernel, from rocprofv3's kernel trace: the likelihood kernels are told apart
+    by their template arguments (cells_kernel<1, ...> writes the grid, a last argument `true` is the weighted fused
+    variant), everything else is shared by the two evaluations"""
+    def route(name):
+        if "chi2_grid_weighted" in name or "cells_kernel<1" in name or "sec_scan_kernel<64" in name:
+            return "grid"
+        for k in ("cells_kernel<0", "rowc_kernel<", "sec_scan_kernel<8"):
+            if k in name:
+                return "fused" if name.split(">(")[0].rstrip().endswith("true") else "grid"
+        return "both"
+    lines = []
+    for f in glob.glob(os.path.join(trace, "**", "*kernel_trace.csv"), recursive=True):
+        groups = {}
+        for row in csv.DictReader(open(f)):
+            g = groups.setdefault(row["Kernel_Name"], [0, 0])
+            g[0] += 1
+            g[1] += int(row["End_Timestamp"]) - int(row["Start_Timestamp"])
+        passes = 2 * ROUTE_PASSES              # passes of one evaluation: two cases
+        total = {"grid": 0, "fused": 0, "both": 0}
+        for name, (calls, ns) in sorted(groups.items(), key=lambda kv: -kv[1][1]):
+            total[route(name)] += ns
+            short = name.replace("(anonymous namespace)::", "").split("(")[0]
+            if ns > 0.002 * sum(v[1] for v in groups.values()):
+                lines.append("rocprofv3 %-5s %-72s %6d launches  %9.1f us in all  %7.2f us each\n"
+                             % (route(name), short[:72], calls, ns * 1e-3, ns * 1e-3 / calls))
+        lines.append("rocprofv3 kernel time per calc_probs_datasets pass (mean of the two cases): grid-only kernels %.2f ms, "
+                     "fused-only kernels %.2f ms, kernels of both evaluations %.2f ms per pass of either\n"
+                     % (total["grid"] * 1e-6 / passes, total["fused"] * 1e-6 / passes, total["both"] * 1e-6 / (2 * passes)))
+    return "".join(lines)
 
 
 def trace_summary(trace):
@@ -122,16 +200,31 @@ def _step(out, limit, cmd):
     return r.returncode == 0
 
 
-def job(path):
-    me, trace = os.path.abspath(__file__), os.path.join(os.path.dirname(path) or ".", "rocprof_datasets")
-    with open(path, "w") as out:
-        out.write("# profiles/datasets/measure.py on one MI355X; %.2f GB per chi2 launch\n" % GB)
-        ok = _step(out, 240, [sys.executable, me, "kernels"])
-        ok = ok and _step(out, 300, ["rocprofv3", "--kernel-trace", "--stats", "-d", trace, "-o", "chi2", "--output-format",
-                                     "csv", "--", sys.executable, me, "kernels"])
-        if ok:
-            out.write(trace_summary(trace))
-        ok = ok and _step(out, 420, [sys.executable, me, "e2e"])
+def job(path, only=None):
+    me, base = os.path.abspath(__file__), os.path.dirname(path) or "."
+    trace, trace2 = os.path.join(base, "rocprof_datasets"), os.path.join(base, "rocprof_datasets_routes")
+    want = (lambda step: only is None or step in only)
+    with open(path, "a" if only else "w") as out:
+        if only:
+            out.write("# profiles/datasets/measure.py --only %s on one MI355X: evaluation=\"grid\" against \"fused\"; wall clock of "
+                      "whole calls (one warm-up, then %d rounds, the cases taking turns), then the kernel trace of a run of "
+                      "its own (rocprofv3 --kernel-trace --stats)\n" % (",".join(only), E2E_ROUNDS))
+        else:
+            out.write("# profiles/datasets/measure.py on one MI355X; %.2f GB per chi2 launch\n" % GB)
+        ok = True
+        if want("kernels"):
+            ok = _step(out, 240, [sys.executable, me, "kernels"])
+            ok = ok and _step(out, 300, ["rocprofv3", "--kernel-trace", "--stats", "-d", trace, "-o", "chi2", "--output-format",
+                                         "csv", "--", sys.executable, me, "kernels"])
+            if ok:
+                out.write(trace_summary(trace))
+        if want("e2e"):
+            ok = ok and _step(out, 420, [sys.executable, me, "e2e"])
+        if want("routes"):
+            ok = ok and _step(out, 420, ["rocprofv3", "--kernel-trace", "--stats", "-d", trace2, "-o", "routes", "--output-format",
+                                         "csv", "--", sys.executable, me, "routes"])
+            if ok:
+                out.write(routes_summary(trace2))
         out.write("job %s\n" % ("complete" if ok else "ended early"))
     return 0 if ok else 1
 
@@ -141,6 +234,9 @@ if __name__ == "__main__":
         kernels()
     elif sys.argv[1:2] == ["e2e"]:
         e2e()
+    elif sys.argv[1:2] == ["routes"]:
+        routes()
     else:
         dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(os.path.dirname(os.path.abspath(__file__)), "results.txt")
-        sys.exit(job(dest))
+        only = sys.argv[sys.argv.index("--only") + 1].split(",") if "--only" in sys.argv else None
+        sys.exit(job(dest, only))

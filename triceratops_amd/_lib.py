@@ -29,7 +29,8 @@ ERR_NTOTAL = 4
 
 # every symbol include/trx.h declares (tests check that libtrx.so exports all of them and nothing of trx_debug.h)
 ABI_SYMBOLS = (
-    "trx_lnl_batch", "trx_flux_grid", "trx_chi2_grid", "trx_chi2_grid_weighted", "trx_workspace_bytes",
+    "trx_lnl_batch", "trx_lnl_batch_weighted", "trx_flux_grid", "trx_chi2_grid", "trx_chi2_grid_weighted",
+    "trx_workspace_bytes",
     "trx_log_mean_exp", "trx_lnz_scenario", "trx_lnz_from_halfchi2", "trx_lnz_moments_from_halfchi2",
     "trx_posterior_from_halfchi2", "trx_grid_quantiles",
     "trx_lnl_batch_host", "trx_flux_grid_host",
@@ -146,6 +147,9 @@ def _load(path, testing):
     L.trx_lnl_batch.restype = c_int
     L.trx_lnl_batch.argtypes = [c_int, c_int, _vp, _vp, c_int, c_double, _vp, c_long, c_double,
                                 c_int, _vp, _vp]
+    L.trx_lnl_batch_weighted.restype = c_int
+    L.trx_lnl_batch_weighted.argtypes = [c_int, c_int, _vp, _vp, _vp, c_int, _vp, c_long, c_double, c_int, c_double,
+                                         c_int, _vp, _vp]
     L.trx_flux_grid.restype = c_int
     L.trx_flux_grid.argtypes = [c_int, c_int, _vp, c_int, _vp, c_long, c_double, c_int, _vp, _vp, _vp]
     L.trx_chi2_grid.restype = c_int
@@ -387,6 +391,30 @@ def lnl_batch(model, flags, time_d, flux_d, sigma, params_d, exptime, nsamples, 
         check(lib().trx_lnl_batch(model, flags, time_d.data_ptr(), flux_d.data_ptr(),
                                   time_d.numel(), float(sigma), params_d.data_ptr(), n,
                                   float(exptime), int(nsamples), out.data_ptr(), _stream(params_d)))
+    return out
+
+
+def lnl_batch_weighted(model, flags, time_d, flux_d, inv_var_d, params_d, exptime, nsamples, sec_limit=float("inf"),
+                       out=None):
+    """0.5 * sum_t inv_var[t] (flux[t] - model_r(t))^2 per row, model and reduction in one kernel
+    (trx_lnl_batch_weighted: no grid); +inf where model is MODEL_EB and the row's secondary depth >= sec_limit.  out: an
+    [n] fp64 device tensor to ADD the rows' values to (the next light curve of an evidence over several); None: a fresh
+    tensor.  All tensors are fp64 CUDA tensors; params_d is [n_param][n]."""
+    require_gpu()
+    n, nt = params_d.shape[1], time_d.numel()
+    assert params_d.shape[0] == N_PARAM[model] and params_d.is_contiguous()
+    assert flux_d.numel() == nt and inv_var_d.numel() == nt
+    assert time_d.is_contiguous() and flux_d.is_contiguous() and inv_var_d.is_contiguous()
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=params_d.device)
+    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
+    if n == 0:
+        return out                     # (an empty tensor has no address to pass)
+    with torch.cuda.device(params_d.device):
+        check(lib().trx_lnl_batch_weighted(model, flags, time_d.data_ptr(), flux_d.data_ptr(), inv_var_d.data_ptr(),
+                                           nt, params_d.data_ptr(), n, float(exptime), int(nsamples),
+                                           float(sec_limit), int(accumulate), out.data_ptr(), _stream(params_d)))
     return out
 
 

@@ -84,6 +84,12 @@ struct RowsArgs {
     // wave-uniform fp64 values precomputed on the host: fp64 arithmetic has no scalar unit, so
     // computing them in the kernel parks them in long-lived vector registers
     double s2, rs2, dS, rS;      // sigma^2, 1 / sigma^2, S, 1 / S
+    // Per-point weights (trx_lnl_batch_weighted; the WT instantiations only -- no other kernel reads these three): every
+    // chi^2 term takes inv_var[j] of its stamp where the others take rs2; an EB row is excluded where its secondary depth
+    // >= sec_limit (false for a NaN depth), and `accumulate` adds the row's value to what out[] holds.
+    const double* inv_var;
+    double sec_limit;
+    int accumulate;
 };
 
 // One launch chain for several lnZ_* branches (trx_star_enqueue, trx_scenario.hip): the kernels of the likelihood path
@@ -552,6 +558,7 @@ __device__ __forceinline__ void row_constants(const RowsArgs& a, const long n, c
 // The launch's header (flat-model chi^2, stencil verdict, bounds of the bounded evaluation, the scan's counter):
 // a workgroup of its own (the last one of rowc_kernel's grid), since a wave doing it before its rows would be the
 // launch's long pole on a 2000-point light curve.
+template <bool WT = false>
 __device__ __forceinline__ void launch_header(const RowsArgs& a, const long n)
 {
     const int lane = threadIdx.x;
@@ -562,8 +569,9 @@ __device__ __forceinline__ void launch_header(const RowsArgs& a, const long n)
         double acc = 0.0;
         for (int j = lane; j < a.n_time; j += 64) {
             const double d = a.flux[j] - 1.0;
-            acc = fma(d * d, a.rs2, acc);            // (every chi^2 term of the path is (f - m)^2 x (1 / sigma^2): the
-                                                     // same operation everywhere, so that flat rows tie exactly)
+            acc = fma(d * d, WT ? a.inv_var[j] : a.rs2, acc);   // (every chi^2 term of the path is (f - m)^2 x (1 / sigma^2)
+                                                     // -- WT: x inv_var[j] --: the same operation everywhere, so that
+                                                     // flat rows tie exactly)
         }
         acc = wave_sum(acc);
         if (a.use_stencil) {
@@ -576,7 +584,7 @@ __device__ __forceinline__ void launch_header(const RowsArgs& a, const long n)
 #pragma unroll 8
                 for (int j = 64 * b; j < j1; ++j) {
                     const double d = a.flux[j] - 1.0;
-                    s = fma(d * d, a.rs2, s);
+                    s = fma(d * d, WT ? a.inv_var[j] : a.rs2, s);
                 }
                 hdr[kHdrTrip + b] = s;
             }
@@ -694,7 +702,7 @@ __device__ __forceinline__ void launch_header(const RowsArgs& a, const long n)
 // whatever the stream's previous call left there (two such bugs shipped in round 4).
 constexpr unsigned long long kUnwrittenBits = 0x7ff8dead0badc0deull;
 
-template <bool SEC>
+template <bool SEC, bool WT = false>
 __device__ __forceinline__ void rowc_body(const RowsArgs& a)
 {
     __shared__ RowC rows_out[64];
@@ -704,7 +712,7 @@ __device__ __forceinline__ void rowc_body(const RowsArgs& a)
     // the last workgroup writes the launch header, the others stride over the blocks of rows (with the row count
     // on the device the grid is a guess)
     if (blockIdx.x == gridDim.x - 1) {
-        launch_header(a, n);
+        launch_header<WT>(a, n);
         return;
     }
     const bool quick = SEC && a.out_sec == nullptr;
@@ -726,7 +734,9 @@ __device__ __forceinline__ void rowc_body(const RowsArgs& a)
                 const double m = (f + ysec) / (1.0 + ysec);
                 const double depth = 1.0 - (m + fdil) / (1.0 + fdil);
                 // deep enough already (or NaN: np.min would propagate it) -> RowC::excl, :535; else the scan decides
-                if (!(depth < 1.5 * a.sigma)) c.excl = 1.0;
+                // (WT: the rule of trx_chi2_grid_weighted, depth >= limit -- a NaN depth excludes nothing, and the scan,
+                // whose minimum is NaN as well then, says the same)
+                if (WT ? (depth >= a.sec_limit) : !(depth < 1.5 * a.sigma)) c.excl = 1.0;
                 else open = true;
 #else
                 open = true;
@@ -762,10 +772,10 @@ __device__ __forceinline__ void rowc_body(const RowsArgs& a)
     }
 }
 
-template <bool SEC>
+template <bool SEC, bool WT = false>
 __global__ __launch_bounds__(64) void rowc_kernel(RowsArgs a)
 {
-    rowc_body<SEC>(a);
+    rowc_body<SEC, WT>(a);
 }
 
 // chain: branch = blockIdx.y; the branches that need the secondary-eclipse verdict take the SEC body
@@ -784,7 +794,7 @@ __global__ __launch_bounds__(64) void rowc_kernel_star(RowsArgs common, BranchTa
 // E = 64 when every row is scanned (full lanes throughout).  The open rows of a likelihood call are few -- ~3000 of
 // the 1e5 masked draws of a lnZ_*EB call -- and a wave's work is one serial chain (orbit constants, then E x 25 / 64
 // model evaluations of ~1000 fp64 instructions each): E = 8 spreads them over eight times the waves (117 -> 30 us).
-template <int E>
+template <int E, bool WT = false>
 __device__ __forceinline__ void sec_scan_body(const RowsArgs& a)
 {
     __shared__ RowC srows[E];
@@ -824,17 +834,18 @@ __device__ __forceinline__ void sec_scan_body(const RowsArgs& a)
             double m = secnan[lane] ? NAN : secmin[lane];                   // np.min propagates NaN
             m = (m + ysec) / (1.0 + ysec);
             const double secdepth = 1.0 - (m + fdil) / (1.0 + fdil);
-            a.rowc[row * kRowDoubles + (kRowDoubles - 1)] = (secdepth < 1.5 * a.sigma) ? 0.0 : 1.0;  // RowC::excl, :535
+            a.rowc[row * kRowDoubles + (kRowDoubles - 1)] =
+                (WT ? !(secdepth >= a.sec_limit) : (secdepth < 1.5 * a.sigma)) ? 0.0 : 1.0;          // RowC::excl, :535
             if (a.out_sec) a.out_sec[row] = secdepth;
         }
         __syncthreads();
     }
 }
 
-template <int E>
+template <int E, bool WT = false>
 __global__ __launch_bounds__(64) void sec_scan_kernel(RowsArgs a)
 {
-    sec_scan_body<E>(a);
+    sec_scan_body<E, WT>(a);
 }
 
 // (the grid's second dimension runs over the branches that HAVE a secondary-eclipse rule -- six of a target's eighteen:
@@ -1039,12 +1050,18 @@ __device__ __forceinline__ const T* kernel_arguments()
     return (const T*)p;
 }
 
-template <int MODE, bool STEP, bool FP32, bool LONG, bool ST, bool PRUNE, int ARGS = 0>
+// WT (trx_lnl_batch_weighted; MODE_LNL, full evaluation only): one weight per time stamp.  Every chi^2 term takes
+// inv_var[j] of its stamp -- staged in LDS behind time and flux (batches), read from memory like the flux (one row per
+// wave) -- where the other instantiations take the scalar rs2; the launch's flat-model value and its per-trip sums carry
+// the same weights (launch_header<WT>).  With a.accumulate a row's value is added to what out[] holds, and a row that
+// is +inf there already is not evaluated.  A compile-time variant: the other instantiations test nothing.
+template <int MODE, bool STEP, bool FP32, bool LONG, bool ST, bool PRUNE, int ARGS = 0, bool WT = false>
 __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st_radius)
 {
     constexpr int kReload = TRX_ARGS_RELOAD ? ARGS : 0;
     const RowsArgs& a = a_in;
     static_assert(!PRUNE || (MODE == MODE_LNL && !ST), "bounded evaluation: likelihood mode, no stencil");
+    static_assert(!WT || (MODE == MODE_LNL && !PRUNE), "per-point weights: likelihood mode, full evaluation");
     extern __shared__ double lds_all[];
     // (not in the diagnostic instantiations that solve Kepler's equation per pair; not with one row per wave: 2000 irregular
     // stamps -0.5 %, and the stencil instantiation, which never carries, -2.3 % for the registers the code costs)
@@ -1075,6 +1092,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
     // "rest" work
     const double* tl = LONG ? a.time : (lds_all + a.tl_off);          // [n_time]
     const double* fl = LONG ? a.flux : (tl + a.n_time);               // [n_time] (MODE_LNL)
+    const double* wl = LONG ? a.inv_var : (fl + a.n_time);            // [n_time] (WT)
     // the node tables into LDS as (node offset, weight) pairs (one 16-byte read per pair), an entry per lane: a
     // loop on one lane was 420 wave instructions per workgroup -- 3 % of a batch at 100 points
     if (a.use_tiers) {
@@ -1122,6 +1140,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
         for (int j = threadIdx.x; j < n_time; j += 64 * W) {
             tw[j] = a.time[j];
             if (MODE == MODE_LNL) tw[n_time + j] = a.flux[j];
+            if (WT) tw[2 * n_time + j] = a.inv_var[j];
         }
     }
     if (W > 1) __syncthreads();       // the only workgroup barrier: from here on every wave is on its own
@@ -1228,8 +1247,14 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
         // lnL_EB_p returns +inf for a draw whose secondary eclipse is deeper than 1.5 sigma, whatever its
         // light curve looks like (likelihoods.py:535-538): such rows are not evaluated at all
         unsigned long long skipmask = 0;
-        if (MODE == MODE_LNL && a.skip_excl && a.model == TRX_MODEL_EB) {
-            skipmask = __ballot(lane < nb && rows[lane].excl != 0.0);
+        if (MODE == MODE_LNL && a.skip_excl && (a.model == TRX_MODEL_EB || (WT && a.accumulate))) {
+            bool settled = lane < nb && rows[lane].excl != 0.0;
+            if (WT) {
+                // (+inf from an earlier light curve of the sum stays +inf whatever this one adds)
+                settled = settled && a.model == TRX_MODEL_EB;
+                if (a.accumulate && lane < nb) settled = settled || a.out[rowid] == INFINITY;
+            }
+            skipmask = __ballot(settled);
             n_skipped += (unsigned)__popcll(skipmask);
             if (LONG && skipmask) {                  // the wave's only row: done
                 if (lane == 0) a.out[base] = INFINITY;
@@ -1372,7 +1397,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                         a.out[(size_t)base * n_time + cell] = a.debug_nodes ? 0.0 : hmout[rr];
                     if (LONG && MODE == MODE_LNL && !inw && phase_no == 0) {
                         const double d = fl[j] - 1.0;
-                        lacc = fma(d * d, rs2, lacc);                           // :486, :537, :586
+                        lacc = fma(d * d, WT ? wl[j] : rs2, lacc);              // :486, :537, :586
                     }
                     if (PRUNE) {
                         // what the flat model charges the row for its in-window cells, until they are done
@@ -1455,6 +1480,8 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                 const double t = tl[j];
                 double fobs = 0.0;
                 if (LONG && MODE == MODE_LNL) fobs = fl[j];          // in flight during the chunk
+                double wobs = rs2;
+                if (LONG && WT) wobs = wl[j];
                 CellPlan pl;
                 if (carried) {
                     pl.n = (int)(cmeta >> 18); pl.tier = (int)((cmeta >> 8) & 0xffu) - 1;
@@ -1684,7 +1711,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                         if (LONG) {
                             // the row's own lanes sum (f - m)^2 / sigma^2 directly    :486, :537, :586
                             const double d = fobs - m;
-                            lacc = fma(d * d, rs2, lacc);
+                            lacc = fma(d * d, wobs, lacc);
                             nonflat = nonflat || (m != 1.0);
                         } else {
                             // (f - m)^2 - (f - 1)^2, exactly 0 for m = 1: one LDS atomic per cell with a
@@ -1692,7 +1719,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                             // serialises them in a fixed order, so results repeat bit for bit from run
                             // to run; a six-step shuffle reduction per chunk costs ten times the latency
                             const double f = fl[j];
-                            const double contrib = ((1.0 - m) * ((f - m) + (f - 1.0))) * rs2;
+                            const double contrib = ((1.0 - m) * ((f - m) + (f - 1.0))) * (WT ? wl[j] : rs2);
                             if (contrib != 0.0)
                                 __hip_atomic_fetch_add(&hacc[rr], contrib, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                             if (PRUNE && nphase == 2 && phase_no == 0) {      // this cell's share of chi^2 is now exact
@@ -1763,6 +1790,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                 double h = (hmout[0] == 1.0 || n_time == 0) ? 0.5 * (__any(nonflat) ? direct : flat_sum) : NAN;
                 if (a.model == TRX_MODEL_EB && rows[0].excl != 0.0) h = INFINITY;   // :535-538
                 if (lane == 0) {
+                    if (WT && a.accumulate) h = a.out[base] + h;         // (+inf stays +inf: h is never -inf)
                     a.out[base] = h;
                     if (PRUNE && (probing || a.part == 1 || a.part == 3) && h < INFINITY)
                         tighten_bounds(a.rowc + n * kRowDoubles, h, a.prune_c0 - h + lp_row);
@@ -1773,6 +1801,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                     h = (hmout[lane] == 1.0 || n_time == 0) ? 0.5 * (flat_sum + hacc[lane]) : NAN;
                     if (a.model == TRX_MODEL_EB && rows[lane].excl != 0.0) h = INFINITY;  // :535-538
                     if (PRUNE && mask_bit(deadmask, lane)) h = hrem[lane];
+                    if (WT && a.accumulate) h = a.out[rowid] + h;        // (+inf stays +inf: h is never -inf)
                     a.out[rowid] = h;
                 }
                 if (PRUNE && (probing || a.part == 1 || a.part == 3)) {
@@ -1822,7 +1851,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
 // (Batches: five waves per SIMD for the bounded instantiation too -- until round 4's last day it was compiled for four and
 // took 97 VGPRs, one more than five waves allow on 512 registers in granules of 8; for five it takes 95, no scratch:
 // the unprobed full evaluations of its third pass gain 8 %, profiles/r04/ab_waves5.txt.)
-template <int MODE, bool STEP, bool FP32, bool LONG, bool ST, bool PRUNE = false, int ARGS = 0>
+template <int MODE, bool STEP, bool FP32, bool LONG, bool ST, bool PRUNE = false, int ARGS = 0, bool WT = false>
 __device__ __forceinline__ void cells_entry(const RowsArgs& a)
 {
     // the counter of the secondary-eclipse scan's list (rowc_kernel<true> -> sec_scan_kernel, both done by now) goes
@@ -1869,13 +1898,13 @@ __device__ __forceinline__ void cells_entry(const RowsArgs& a)
         if (a.use_stencil == 1 && (st_radius > 0.0) != ST) return;
         if (!ST) st_radius = 0.0;
     }
-    cells_body<MODE, STEP, FP32, LONG, ST, PRUNE, ARGS>(a, st_radius);
+    cells_body<MODE, STEP, FP32, LONG, ST, PRUNE, ARGS, WT>(a, st_radius);
 }
 
-template <int MODE, bool STEP, bool FP32, bool LONG, bool ST, bool PRUNE = false>
+template <int MODE, bool STEP, bool FP32, bool LONG, bool ST, bool PRUNE = false, bool WT = false>
 __global__ __launch_bounds__(64 * cells_waves(LONG), LONG ? TRX_CELLS_WAVES_PER_EU : TRX_BATCH_WAVES_PER_EU) void cells_kernel(RowsArgs a)
 {
-    cells_entry<MODE, STEP, FP32, LONG, ST, PRUNE, 1>(a);
+    cells_entry<MODE, STEP, FP32, LONG, ST, PRUNE, 1, WT>(a);
 }
 
 // chain (bounded evaluation only): branch = blockIdx.y, `part` = the pass (1 pilot, 2 probe pass / the rest, 3 survivors)

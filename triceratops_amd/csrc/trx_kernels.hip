@@ -2,7 +2,7 @@
 //
 // The kernels live in two headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
-//                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE> (the light-curve model and its
+//                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
 //                    cell, the (cell, node) pairs dealt to all lanes; centre-value stencil on dense uniform grids; the
 //                    passes of the bounded evaluation), pilot_stats_kernel, depth_screen_kernel, and what host and
@@ -306,7 +306,7 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
     a.rS = 1.0 / a.dS;
     a.nbatch = 8 * batch_plan(a.n, a.B).P;          // wave positions of the launch (batch_plan)
     a.debug_bug = knob_debug_bug();
-    a.mark_unwritten = (MODE == MODE_LNL) ? 1 : 0;
+    a.mark_unwritten = (MODE == MODE_LNL && !a.inv_var) ? 1 : 0;     // (a weighted launch may ADD to out[]: never marked)
     bool tiers_ok = false;
     if (tier_device(a.S, a.tiers, &a.tier_xw, &tiers_ok)) return fail(TRX_ERR_HIP, "tier table upload failed%s", "", 0);
     a.use_tiers = tiers_ok && knob_tiers() && !(a.flags & TRX_FLAG_ALL_SUBEXPOSURES);
@@ -333,8 +333,11 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
     a.skip_excl = knob_skip_excluded() && !(a.flags & TRX_FLAG_EVALUATE_EXCLUDED);
     a.need_sec = (a.model == TRX_MODEL_EB && MODE == MODE_LNL) ||
                  ((a.model == TRX_MODEL_EB || a.model == TRX_MODEL_EB_TWIN) && a.out_sec != nullptr);
-    // LDS: [node tables | atan constants | the staged light curve (short curves)] shared by the workgroup's waves,
-    // then per wave [rows, accumulators | pair table | in-window list | cell state (| stencil state)]
+    // (per-point weights: the limit is the caller's; +inf or NaN excludes no depth, so nothing is scanned)
+    if (a.inv_var && !(a.sec_limit < INFINITY)) a.need_sec = 0;
+    // LDS: [node tables | atan constants | the staged light curve (short curves): time, flux and -- per-point weights --
+    // inv_var] shared by the workgroup's waves, then per wave [rows, accumulators | pair table | in-window list | cell
+    // state (| stencil state)]
     static_assert((kCellsPairs + kCellsWindowLong) % 4 == 0 && (kCellsPairs + kCellsWindowBatch) % 4 == 0 &&
                   sizeof(CellState) % 8 == 0 && sizeof(StencilState) % 8 == 0, "8-byte alignment of the LDS arrays");
     const size_t tables = (size_t)(2 * kTiers * kTierMaxNodes + kAtanRanges * kAtanCols + kTierHeadDoubles) * sizeof(double);
@@ -344,7 +347,7 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
              + (long_variant ? sizeof(StencilState) : 0);
     };
     a.tl_off = (int)(tables / sizeof(double));
-    size_t shared = tables + (long_rows ? 0 : (size_t)2 * a.n_time * sizeof(double));
+    size_t shared = tables + (long_rows ? 0 : (size_t)(a.inv_var ? 3 : 2) * a.n_time * sizeof(double));
     size_t lds = shared + cells_waves(long_rows) * wave_bytes(long_rows);
     if (lds > 64 * 1024) {             // a long curve forced through the batched variant by a test knob
         long_rows = true;
@@ -460,7 +463,8 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
     return TRX_OK;
 }
 
-template <int MODE>
+// WT: the instantiations with one weight per time stamp (trx_lnl_batch_weighted: a.inv_var, a.sec_limit, a.accumulate)
+template <int MODE, bool WT = false>
 int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
 {
     trx::StreamLock turn(st);            // rowc_kernel and cells_kernel of one call share the stream's scratch
@@ -469,6 +473,7 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
     if (int rc = plan_cells<MODE>(a, long_rows, P)) return rc;
     long_rows = P.long_rows;
     const bool prune = P.prune, split = P.split, fp32 = P.fp32, step = P.step;
+    (void)split; (void)step;               // (unused by the weighted instantiation)
     const size_t lds = P.lds;
     hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
@@ -504,16 +509,31 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
         // (the scan's counter is zero in the stream's scratch: cleared at allocation, then by every cells_kernel
         // that follows a scan; a captured call's own buffer holds anything)
         if (capturing) TRX_HIP(hipMemsetAsync(a.scan_count, 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(rowc_kernel<true>, dim3(P.grid_rowc), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((rowc_kernel<true, WT>), dim3(P.grid_rowc), dim3(64), 0, st, a);
         if (a.out_sec) hipLaunchKernelGGL(sec_scan_kernel<64>, dim3(P.grid_scan), dim3(64), 0, st, a);
-        else           hipLaunchKernelGGL(sec_scan_kernel<8>, dim3(P.grid_scan), dim3(64), 0, st, a);
+        else           hipLaunchKernelGGL((sec_scan_kernel<8, WT>), dim3(P.grid_scan), dim3(64), 0, st, a);
     } else {
-        hipLaunchKernelGGL(rowc_kernel<false>, dim3(P.grid_rowc), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((rowc_kernel<false, WT>), dim3(P.grid_rowc), dim3(64), 0, st, a);
     }
     const unsigned g2 = P.grid_main;
     t_last_rowc = a.rowc;
     t_last_pruned = prune;
-    if (prune) {
+    if constexpr (WT) {
+        // (full evaluation with Kepler stepping, the production path: trx_lnl_batch_weighted refuses anything else)
+        if (long_rows) {
+            if (verdict != 2) {
+                if (fp32) hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, true, true, false, false, true>), dim3(g2), dim3(64), lds, st, a);
+                else      hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, false, true, false, false, true>), dim3(g2), dim3(64), lds, st, a);
+            }
+            if (a.use_stencil && verdict != 1) {
+                if (fp32) hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, true, true, true, false, true>), dim3(g2), dim3(64), lds, st, a);
+                else      hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, false, true, true, false, true>), dim3(g2), dim3(64), lds, st, a);
+            }
+        } else {
+            if (fp32) hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, true, false, false, false, true>), dim3(g2), dim3(64 * kBatchWaves), lds, st, a);
+            else      hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, false, false, false, false, true>), dim3(g2), dim3(64 * kBatchWaves), lds, st, a);
+        }
+    } else if (prune) {
         // pilot rows (evaluated to the end; first values of the running bounds), verdict on probing, the rest
         RowsArgs ap = a;
         ap.part = 1;
@@ -959,6 +979,26 @@ int trx_lnl_batch(int model, int flags, const double* time, const double* flux, 
     a.params = params; a.n = n; a.exptime = exptime; a.S = nsupersample; a.out = out_halfchi2;
     if (knob_bounded_lnl()) { a.prune = 2; a.prune_c0 = 0.0; a.prune_lp = nullptr; }
     return launch_rows<MODE_LNL>(a, static_cast<hipStream_t>(stream));
+}
+
+int trx_lnl_batch_weighted(int model, int flags, const double* time, const double* flux, const double* inv_var,
+                           int n_time, const double* params, long n, double exptime, int nsupersample,
+                           double sec_limit, int accumulate, double* out_halfchi2, void* stream)
+{
+    if (n_params(model) < 0) return fail(TRX_ERR_ARG, "unknown model%s %ld", "", (long)model);
+    if (model == TRX_MODEL_RAW) return fail(TRX_ERR_ARG, "TRX_MODEL_RAW has no likelihood%s", "", 0);
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (nsupersample < 1) return fail(TRX_ERR_ARG, "nsupersample must be >= 1%s (got %ld)", "", (long)nsupersample);
+    if (!time || !flux || !inv_var || !params || !out_halfchi2) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    if (n == 0) return TRX_OK;
+    // (the testing build's switch for a full Kepler solve per sub-exposure has no weighted instantiation)
+    if (!knob_kepler_stepping()) return fail(TRX_ERR_ARG, "trx_lnl_batch_weighted needs Kepler stepping%s", "", 0);
+    RowsArgs a{};
+    a.model = model; a.flags = flags | TRX_FLAG_FULL_EVALUATION; a.time = time; a.flux = flux; a.n_time = n_time; a.sigma = 1.0;
+    a.params = params; a.n = n; a.exptime = exptime; a.S = nsupersample; a.out = out_halfchi2;
+    a.inv_var = inv_var; a.sec_limit = sec_limit; a.accumulate = accumulate ? 1 : 0;
+    const bool batches = n_time < knob_cells_below();
+    return launch_cells<MODE_LNL, true>(a, static_cast<hipStream_t>(stream), !batches);
 }
 
 int trx_flux_grid(int model, int flags, const double* time, int n_time, const double* params,

@@ -183,12 +183,17 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # object evaluates every masked draw in full on every dataset -- trx_flux_grid writes the model curves of a chunk of rows,
 # trx_chi2_grid_weighted adds their weighted chi^2/2 -- through run_operator_chain: no bounded evaluation, no launch
 # chain.  DATASET_GRID_BYTES bounds the grid of one chunk; the results are the same bits for any value.
+# DATASET_EVALUATION = "fused": one trx_lnl_batch_weighted per dataset over all rows of a branch instead -- model and
+# weighted chi^2 in one kernel, no grid, no chunks; the same evidences to rounding (target.calc_probs_datasets sets it
+# for the length of a call).
 DATASET_GRID_BYTES = 512 << 20
+DATASET_EVALUATIONS = ("grid", "fused")
+DATASET_EVALUATION = "grid"
 
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -1028,12 +1033,25 @@ class _Scenario:
         """sum over the datasets of the weighted chi^2/2 of every row of `block` ([n_param][n], the masked draws of one
         branch): per chunk of rows and per dataset one trx_flux_grid and one accumulating trx_chi2_grid_weighted.  The EB
         branch's secondary-eclipse rule (secdepth >= 1.5 sigma_bar -> +inf) rides in the first dataset's reduction: the
-        depth does not depend on the time stamps.  A row's value does not depend on the chunk it falls in."""
+        depth does not depend on the time stamps.  A row's value does not depend on the chunk it falls in.
+        DATASET_EVALUATION = "fused": one trx_lnl_batch_weighted per dataset over the whole block instead -- no grid, no
+        chunks; the rule rides in the first dataset's call as its sec_limit."""
+        if DATASET_EVALUATION not in DATASET_EVALUATIONS:
+            raise ValueError("fused.DATASET_EVALUATION must be one of %s (got %r)" % (DATASET_EVALUATIONS, DATASET_EVALUATION))
         n = int(block.shape[1])
         h = torch.zeros(n, dtype=F64, device=self.dev)         # (0 + x = x: every reduction accumulates)
         if n == 0:
             return h
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL         # (set_precision; the evaluation is full either way)
+        if DATASET_EVALUATION == "fused":
+            for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
+                limit = 1.5 * self.sigma if (model == MODEL_EB and l == 0) else float("inf")
+                _lib.lnl_batch_weighted(model, flags, time_d, flux_d, inv_var_d, block, exptime, nsamples, limit, out=h)
+            with _stats_lock:
+                _lib.STATS["rows"] += n
+                _lib.STATS["cells"] += n * sum(int(d[0].numel()) for d in self.datasets)
+                _lib.STATS["launches"] += len(self.datasets)
+            return h
         t_max = max(int(d[0].numel()) for d in self.datasets)
         rows = max(1, int(DATASET_GRID_BYTES) // (8 * t_max))
         buf = torch.empty(min(rows, n) * t_max, dtype=F64, device=self.dev)

@@ -249,7 +249,7 @@ class target:
                                       "'numpy-device'): this sampling mode returns no posterior rows")
         return
 
-    def calc_probs_datasets(self, datasets, P_orb, n_samples: int = 0, **calc_probs_kwargs):
+    def calc_probs_datasets(self, datasets, P_orb, n_samples: int = 0, evaluation: str = "grid", **calc_probs_kwargs):
         """calc_probs on several light curves of one candidate, each with its own cadence and with per-point flux
         errors (no reference counterpart).
 
@@ -262,9 +262,13 @@ class target:
 
         Fills the target as calc_probs does -- and `.posterior` as calc_posteriors does when n_samples > 0 --, plus
         `.sigma_ref`: sigma_bar in the target star's normalisation.  Every masked draw is evaluated in full on every
-        dataset (model curves written to a grid, then reduced): no bounded evaluation, no launch chains -- several
-        times the time of calc_probs.  Needs set_sampling("device") or "numpy-device"."""
+        dataset: no bounded evaluation, no launch chains -- several times the time of calc_probs.  evaluation="grid"
+        (default): the model curves of a chunk of rows are written to a grid, then reduced; "fused": model and weighted
+        chi^2 in one kernel per dataset (trx_lnl_batch_weighted), no grid -- the same evidences to rounding (1e-12
+        relative in chi^2/2), the same masked draws and best draws.  Needs set_sampling("device") or "numpy-device"."""
         from . import fused
+        if evaluation not in fused.DATASET_EVALUATIONS:
+            raise ValueError("evaluation must be one of %s (got %r)" % (fused.DATASET_EVALUATIONS, evaluation))
         for k in ("exptime", "nsamples"):
             if k in calc_probs_kwargs:
                 raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
@@ -279,7 +283,7 @@ class target:
         kw = dict(calc_probs_kwargs)
         verbose = kw.pop("verbose", 1)
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
-        with fused.switches(POSTERIOR_ROWS=n_samples):
+        with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation):
             rows = sharding.run_units(units, verbose=verbose, as_rows=True)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
