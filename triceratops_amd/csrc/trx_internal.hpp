@@ -1,6 +1,7 @@
 // Internals shared by the translation units of libtrx.so (not part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stddef.h>
 
 #include "../../include/trx.h"
@@ -8,6 +9,12 @@
 namespace trx {
 
 struct ScenFinal;      // trx_device.hpp
+
+// The constant of a draw's log-weight, ln w = c0 - chi^2/2 (+ ln prior): -ln(sqrt(2 pi) sigma), marginal_likelihoods.py:130
+// etc.  The evidence, the bounds of the bounded evaluation, the posterior rows and the weight histogram all start from this
+// one double.  (2 pi: kTwoPi of trx_device.hpp, which trx_draw.hip does not see; trx_kernels.hip asserts the two equal.)
+constexpr double kTwoPiHost = 6.28318530717958647692528676655900577;
+inline double lnl_c0(double lnsigma) { return -0.5 * log(kTwoPiHost) - lnsigma; }
 
 // Per-(device, stream) scratch owned by the library.  Work on one stream is ordered, so a buffer can
 // serve call after call on that stream without any allocator traffic; it only grows (the stream is

@@ -9,9 +9,10 @@
 //                    device share (RowsArgs, batch_rows, batch_plan, set_scratch)
 //   trx_reduce.hpp   chi2_grid_kernel, chi2_grid_weighted_kernel (row reductions over a materialised grid) and the log-mean-exp kernels, HBM bound
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
-// Here: the launch plan (plan_cells), the launchers (launch_cells, lnl_lme_chain), the per-stream scratch and the
-// scratch of captured calls, the node tables, the entry points of include/trx.h and -- testing build only -- of
-// include/trx_debug.h.
+// Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
+// lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
+// per-stream scratch and the scratch of captured calls, the node tables, the entry points of include/trx.h and -- testing
+// build only -- of include/trx_debug.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -34,6 +35,7 @@
 namespace {
 
 using namespace trx;
+static_assert(kTwoPiHost == kTwoPi, "lnl_c0 (trx_internal.hpp)");
 
 thread_local char g_err[256] = "";
 
@@ -253,20 +255,41 @@ thread_local const double* t_last_rowc = nullptr;
 thread_local bool t_last_pruned = false;
 
 
-// the PRUNE instantiations exist for the likelihood mode only
+// THE place that picks a cells_kernel instantiation; these are all there are.  The call site fixes the variant (LONG: one
+// row per wave, a workgroup of one wave; ST: the centre-value stencil; PRUNE: the passes of the bounded evaluation; WT: one
+// weight per time stamp), the launch chooses among
+//   full evaluation, MODE_LNL and MODE_GRID: {no Kepler stepping, stepping fp64, stepping fp32} x {batched, LONG, LONG + ST}
+//   PRUNE, MODE_LNL only:                    stepping {fp64, fp32} x {batched, LONG}
+//   WT, MODE_LNL only:                       stepping {fp64, fp32} x {batched, LONG, LONG + ST}
+template <int MODE, bool LONG, bool ST, bool PRUNE, bool WT>
+void launch_cells_kernel(bool step, bool fp32, unsigned grid, size_t lds, hipStream_t st, const RowsArgs& a)
+{
+    static_assert(MODE == MODE_LNL || !(PRUNE || WT), "PRUNE and WT exist for the likelihood mode only");
+    static_assert(!ST || (LONG && !PRUNE), "the stencil: one row per wave, full evaluation");
+    static_assert(!(PRUNE && WT), "a weighted launch is evaluated in full");
+    const dim3 g(grid), block(LONG ? 64 : 64 * kBatchWaves);
+    if constexpr (!PRUNE && !WT) {         // (a full Kepler solve per sub-exposure: testing build's switch, fp64 only)
+        if (!step) {
+            hipLaunchKernelGGL((cells_kernel<MODE, false, false, LONG, ST, false, false>), g, block, lds, st, a);
+            return;
+        }
+    }
+    if (fp32) hipLaunchKernelGGL((cells_kernel<MODE, true, true, LONG, ST, PRUNE, WT>), g, block, lds, st, a);
+    else      hipLaunchKernelGGL((cells_kernel<MODE, true, false, LONG, ST, PRUNE, WT>), g, block, lds, st, a);
+}
+
+// a pass of the bounded evaluation (launch_cells of MODE_GRID never takes it: plan_cells)
 template <int MODE>
 void launch_pruned(const RowsArgs& a, hipStream_t st, bool long_rows, bool fp32, unsigned grid, size_t lds)
 {
     if constexpr (MODE == MODE_LNL) {
-        if (long_rows) {
-            if (fp32) hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, true, true, false, true>), dim3(grid), dim3(64), lds, st, a);
-            else      hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, false, true, false, true>), dim3(grid), dim3(64), lds, st, a);
-        } else {
-            if (fp32) hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, true, false, false, true>), dim3(grid), dim3(64 * kBatchWaves), lds, st, a);
-            else      hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, false, false, false, true>), dim3(grid), dim3(64 * kBatchWaves), lds, st, a);
-        }
+        if (long_rows) launch_cells_kernel<MODE_LNL, true, false, true, false>(true, fp32, grid, lds, st, a);
+        else           launch_cells_kernel<MODE_LNL, false, false, true, false>(true, fp32, grid, lds, st, a);
     }
 }
+
+// light curves below the packing threshold go through the batched variant: several rows per wave
+bool short_rows(int n_time) { return n_time > 0 && n_time < knob_cells_below(); }
 
 // What launch_cells and the chain launcher decide before anything is enqueued: the rows per wave and the LDS layout, the
 // node tables, whether the bounded evaluation applies, the grids.
@@ -463,6 +486,24 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
     return TRX_OK;
 }
 
+// Pass `part` of the bounded evaluation as launch_cells and lnl_lme_chain launch it: the arguments, the LDS size and the
+// flux model's precision.  They are the launch's own except in the probe pass (part 2) of a split launch: its rows end
+// abandoned or on the survivors' list, so it takes the fp32 flux model (kProbeFp32) and, where plan_cells found room for
+// more rows per wave, its own LDS layout.
+struct ProbePass { RowsArgs a; size_t lds; bool fp32; };
+ProbePass probe_pass(const RowsArgs& a, const CellsPlan& P, int part)
+{
+    ProbePass p{a, P.lds, P.fp32};
+    if (part == 2 && P.split) {
+        p.fp32 = P.fp32 || kProbeFp32;
+        if (P.probe_B > a.B) {
+            p.a.B = P.probe_B; p.a.probe_rows = P.probe_B; p.a.wave_doubles = P.probe_wave_doubles;
+            p.lds = P.probe_lds;
+        }
+    }
+    return p;
+}
+
 // WT: the instantiations with one weight per time stamp (trx_lnl_batch_weighted: a.inv_var, a.sec_limit, a.accumulate)
 template <int MODE, bool WT = false>
 int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
@@ -472,8 +513,7 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
     CellsPlan P;
     if (int rc = plan_cells<MODE>(a, long_rows, P)) return rc;
     long_rows = P.long_rows;
-    const bool prune = P.prune, split = P.split, fp32 = P.fp32, step = P.step;
-    (void)split; (void)step;               // (unused by the weighted instantiation)
+    const bool prune = P.prune && !WT, split = P.split, fp32 = P.fp32, step = P.step;      // (a weighted launch: always in full)
     const size_t lds = P.lds;
     hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
@@ -518,22 +558,7 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
     const unsigned g2 = P.grid_main;
     t_last_rowc = a.rowc;
     t_last_pruned = prune;
-    if constexpr (WT) {
-        // (full evaluation with Kepler stepping, the production path: trx_lnl_batch_weighted refuses anything else)
-        if (long_rows) {
-            if (verdict != 2) {
-                if (fp32) hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, true, true, false, false, true>), dim3(g2), dim3(64), lds, st, a);
-                else      hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, false, true, false, false, true>), dim3(g2), dim3(64), lds, st, a);
-            }
-            if (a.use_stencil && verdict != 1) {
-                if (fp32) hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, true, true, true, false, true>), dim3(g2), dim3(64), lds, st, a);
-                else      hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, false, true, true, false, true>), dim3(g2), dim3(64), lds, st, a);
-            }
-        } else {
-            if (fp32) hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, true, false, false, false, true>), dim3(g2), dim3(64 * kBatchWaves), lds, st, a);
-            else      hipLaunchKernelGGL((cells_kernel<MODE_LNL, true, false, false, false, false, true>), dim3(g2), dim3(64 * kBatchWaves), lds, st, a);
-        }
-    } else if (prune) {
+    if (prune) {
         // pilot rows (evaluated to the end; first values of the running bounds), verdict on probing, the rest
         RowsArgs ap = a;
         ap.part = 1;
@@ -543,15 +568,8 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
                                a.probe_count);
             if (split) hipLaunchKernelGGL(depth_screen_kernel, dim3(P.grid_screen), dim3(256), 0, st, a);
             ap.part = 2;
-            // (the probe pass of a split launch: its rows end abandoned or on the survivors' list -- fp32 flux model, kProbeFp32)
-            const bool fp32_probe = fp32 || (kProbeFp32 && split);
-            if (split && P.probe_B > a.B) {
-                RowsArgs a2 = ap;
-                a2.B = P.probe_B; a2.probe_rows = P.probe_B; a2.wave_doubles = P.probe_wave_doubles;
-                launch_pruned<MODE>(a2, st, long_rows, fp32_probe, g2, P.probe_lds);
-            } else {
-                launch_pruned<MODE>(ap, st, long_rows, fp32_probe, g2, lds);
-            }
+            const ProbePass probe = probe_pass(ap, P, 2);
+            launch_pruned<MODE>(probe.a, st, long_rows, probe.fp32, g2, probe.lds);
             if (split) {
                 // batches of short light curves: the launch above was the probe pass; the rows it left alive, compacted
                 // across workgroups, are evaluated to the end here
@@ -560,20 +578,11 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
             }
         }
     } else if (long_rows) {
-        if (verdict != 2) {
-            if (!step)      hipLaunchKernelGGL((cells_kernel<MODE, false, false, true, false>), dim3(g2), dim3(64), lds, st, a);
-            else if (fp32)  hipLaunchKernelGGL((cells_kernel<MODE, true, true, true, false>), dim3(g2), dim3(64), lds, st, a);
-            else            hipLaunchKernelGGL((cells_kernel<MODE, true, false, true, false>), dim3(g2), dim3(64), lds, st, a);
-        }
-        if (a.use_stencil && verdict != 1) {
-            if (!step)      hipLaunchKernelGGL((cells_kernel<MODE, false, false, true, true>), dim3(g2), dim3(64), lds, st, a);
-            else if (fp32)  hipLaunchKernelGGL((cells_kernel<MODE, true, true, true, true>), dim3(g2), dim3(64), lds, st, a);
-            else            hipLaunchKernelGGL((cells_kernel<MODE, true, false, true, true>), dim3(g2), dim3(64), lds, st, a);
-        }
+        // (WT: full evaluation with Kepler stepping, the production path -- trx_lnl_batch_weighted refuses anything else)
+        if (verdict != 2) launch_cells_kernel<MODE, true, false, false, WT>(step, fp32, g2, lds, st, a);
+        if (a.use_stencil && verdict != 1) launch_cells_kernel<MODE, true, true, false, WT>(step, fp32, g2, lds, st, a);
     } else {
-        if (!step)      hipLaunchKernelGGL((cells_kernel<MODE, false, false, false, false>), dim3(g2), dim3(64 * kBatchWaves), lds, st, a);
-        else if (fp32)  hipLaunchKernelGGL((cells_kernel<MODE, true, true, false, false>), dim3(g2), dim3(64 * kBatchWaves), lds, st, a);
-        else            hipLaunchKernelGGL((cells_kernel<MODE, true, false, false, false>), dim3(g2), dim3(64 * kBatchWaves), lds, st, a);
+        launch_cells_kernel<MODE, false, false, false, WT>(step, fp32, g2, lds, st, a);
     }
     const hipError_t launched = hipGetLastError();
 #ifdef TRX_CAPTURE_GRAPH_MEM
@@ -584,11 +593,7 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
 }
 
 template <int MODE>
-int launch_rows(const RowsArgs& a0, hipStream_t st)
-{
-    const bool batches = a0.n_time > 0 && a0.n_time < knob_cells_below();
-    return launch_cells<MODE>(a0, st, !batches);
-}
+int launch_rows(const RowsArgs& a0, hipStream_t st) { return launch_cells<MODE>(a0, st, !short_rows(a0.n_time)); }
 
 int launch_lme(const double* logw, const double* h, const double* lnprior, double c0, long n,
                long n_total, double* out, void* workspace, size_t workspace_bytes, hipStream_t st, int moments = 0)
@@ -833,9 +838,8 @@ bool lnl_chain_applicable(int flags, int n_time, long N, int S)
     static const long dummy_n = 0;
     a.n_dev = &dummy_n;              // (never read on the host: "the row count lives on the device")
     a.prune = 1;
-    const bool batches = n_time < knob_cells_below();
     CellsPlan P;
-    if (plan_cells<MODE_LNL>(a, !batches, P) != TRX_OK) return false;
+    if (plan_cells<MODE_LNL>(a, !short_rows(n_time), P) != TRX_OK) return false;
     return P.prune && P.step && P.passes;
 }
 
@@ -856,9 +860,8 @@ int lnl_lme_chain(const ChainBranch* br, int nbr, const double* time, int n_time
     a.n_dev = br[0].n_dev; a.src_idx = br[0].src_idx; a.src_stride = N; a.twin_cols = br[0].twin;
     a.dense = 1;
     a.prune = 1;
-    const bool batches = n_time > 0 && n_time < knob_cells_below();
     CellsPlan P;
-    if (int rc = plan_cells<MODE_LNL>(a, !batches, P)) return rc;
+    if (int rc = plan_cells<MODE_LNL>(a, !short_rows(n_time), P)) return rc;
     if (!P.prune || !P.step || !P.passes) return kChainNotApplicable;
     BranchTab bt{};
     LmeTab lt{};
@@ -873,7 +876,7 @@ int lnl_lme_chain(const ChainBranch* br, int nbr, const double* time, int n_time
         b.model = c.model; b.flags = c.flags; b.twin_cols = c.twin; b.need_sec = (c.model == TRX_MODEL_EB) ? 1 : 0;
         any_sec = any_sec || b.need_sec;
         b.flux = c.flux; b.sigma = c.sigma; b.s2 = c.sigma * c.sigma; b.rs2 = 1.0 / b.s2;
-        b.prune_c0 = -0.5 * log(kTwoPi) - c.lnsigma;
+        b.prune_c0 = lnl_c0(c.lnsigma);
         b.params = c.cols; b.out = c.h; b.n_dev = c.n_dev; b.src_idx = c.src_idx; b.prune_lp = c.lnprior;
         b.scratch = c.scratch; b.scan_count = c.scan_count;
         RowsArgs tmp = a;                       // (where set_scratch puts this branch's row blocks and header)
@@ -900,20 +903,13 @@ int lnl_lme_chain(const ChainBranch* br, int nbr, const double* time, int n_time
     a.wave_floor = floor_env > 0 ? floor_env : (3200 / nbr > 256 ? 3200 / nbr : 256);
     a.wave_floor3 = floor3_env > 0 ? floor3_env : a.wave_floor;
     auto cells = [&](unsigned grid, int part) {
+        const ProbePass p = probe_pass(a, P, part);
         if (P.long_rows) {
-            if (P.fp32) hipLaunchKernelGGL((cells_kernel_star<true, true>), dim3(grid, y), dim3(64), P.lds, st, a, bt, part);
-            else        hipLaunchKernelGGL((cells_kernel_star<false, true>), dim3(grid, y), dim3(64), P.lds, st, a, bt, part);
+            if (p.fp32) hipLaunchKernelGGL((cells_kernel_star<true, true>), dim3(grid, y), dim3(64), p.lds, st, p.a, bt, part);
+            else        hipLaunchKernelGGL((cells_kernel_star<false, true>), dim3(grid, y), dim3(64), p.lds, st, p.a, bt, part);
         } else {
-            // (the probe pass of a split launch: more rows per wave, its own LDS layout -- plan_cells)
-            RowsArgs ax = a;
-            size_t lds = P.lds;
-            if (part == 2 && P.split && P.probe_B > a.B) {
-                ax.B = P.probe_B; ax.probe_rows = P.probe_B; ax.wave_doubles = P.probe_wave_doubles;
-                lds = P.probe_lds;
-            }
-            if (P.fp32 || (kProbeFp32 && part == 2 && P.split))
-                        hipLaunchKernelGGL((cells_kernel_star<true, false>), dim3(grid, y), dim3(64 * kBatchWaves), lds, st, ax, bt, part);
-            else        hipLaunchKernelGGL((cells_kernel_star<false, false>), dim3(grid, y), dim3(64 * kBatchWaves), lds, st, ax, bt, part);
+            if (p.fp32) hipLaunchKernelGGL((cells_kernel_star<true, false>), dim3(grid, y), dim3(64 * kBatchWaves), p.lds, st, p.a, bt, part);
+            else        hipLaunchKernelGGL((cells_kernel_star<false, false>), dim3(grid, y), dim3(64 * kBatchWaves), p.lds, st, p.a, bt, part);
         }
     };
     cells(P.grid_pilot, 1);
@@ -942,7 +938,7 @@ int lnl_draws(int model, int flags, const double* time, const double* flux, int 
     a.dense = 1;              // compact_fill_kernel stored the masked draws' columns and priors densely, in list order
     // the caller keeps only lnZ and the best draw of these rows: bounded evaluation (cells_body, PRUNE)
     a.prune = 1;
-    a.prune_c0 = -0.5 * log(kTwoPi) - lnsigma;
+    a.prune_c0 = lnl_c0(lnsigma);
     a.prune_lp = lnprior;
     const int rc = launch_rows<MODE_LNL>(a, st);
     if (rc == TRX_OK && t_last_pruned) *bounds_base = t_last_rowc;
@@ -955,7 +951,7 @@ int lme_draws(const double* halfchi2, const double* lnprior, double lnsigma, lon
 {
     if (!halfchi2 || !n_dev || !src_idx || !ws || !amin_pv || !amin_pi || ((uintptr_t)halfchi2 % 16) != 0)
         return fail(TRX_ERR_ARG, "lme_draws: bad argument%s", "", 0);
-    const double c0 = -0.5 * log(kTwoPi) - lnsigma;   // marginal_likelihoods.py:130 etc.
+    const double c0 = lnl_c0(lnsigma);   // marginal_likelihoods.py:130 etc.
     hipLaunchKernelGGL(lme_partial_kernel<true>, dim3(lme_blocks(n_upper)), dim3(256), 0, st, (const double*)nullptr,
                        halfchi2, lnprior, c0, n_upper, 1, ws, n_dev, src_idx, amin_pv, amin_pi, bounds_base, fin);
     TRX_HIP(hipGetLastError());
@@ -997,8 +993,7 @@ int trx_lnl_batch_weighted(int model, int flags, const double* time, const doubl
     a.model = model; a.flags = flags | TRX_FLAG_FULL_EVALUATION; a.time = time; a.flux = flux; a.n_time = n_time; a.sigma = 1.0;
     a.params = params; a.n = n; a.exptime = exptime; a.S = nsupersample; a.out = out_halfchi2;
     a.inv_var = inv_var; a.sec_limit = sec_limit; a.accumulate = accumulate ? 1 : 0;
-    const bool batches = n_time < knob_cells_below();
-    return launch_cells<MODE_LNL, true>(a, static_cast<hipStream_t>(stream), !batches);
+    return launch_cells<MODE_LNL, true>(a, static_cast<hipStream_t>(stream), !short_rows(n_time));
 }
 
 int trx_flux_grid(int model, int flags, const double* time, int n_time, const double* params,
@@ -1093,7 +1088,7 @@ int trx_lnz_from_halfchi2(const double* halfchi2, const double* lnprior, long n,
 {
     if (!out_lnz || n < 0 || (n > 0 && !halfchi2)) return fail(TRX_ERR_ARG, "bad argument%s", "", 0);
     if (n_total < n || n_total < 1) return fail(TRX_ERR_NTOTAL, "n_total must be >= n%s (n=%ld)", "", n);
-    const double c0 = -0.5 * log(kTwoPi) - lnsigma;   // marginal_likelihoods.py:130 etc.
+    const double c0 = lnl_c0(lnsigma);   // marginal_likelihoods.py:130 etc.
     return launch_lme(nullptr, halfchi2, lnprior, c0, n, n_total, out_lnz, workspace,
                       workspace_bytes, static_cast<hipStream_t>(stream));
 }
@@ -1104,7 +1099,7 @@ int trx_lnz_moments_from_halfchi2(const double* halfchi2, const double* lnprior,
 {
     if (!out || n < 0 || (n > 0 && !halfchi2)) return fail(TRX_ERR_ARG, "bad argument%s", "", 0);
     if (n_total < n || n_total < 1) return fail(TRX_ERR_NTOTAL, "n_total must be >= n%s (n=%ld)", "", n);
-    const double c0 = -0.5 * log(kTwoPi) - lnsigma;   // (the partition and the fold of trx_lnz_from_halfchi2)
+    const double c0 = lnl_c0(lnsigma);   // (the partition and the fold of trx_lnz_from_halfchi2)
     return launch_lme(nullptr, halfchi2, lnprior, c0, n, n_total, out, workspace, workspace_bytes,
                       static_cast<hipStream_t>(stream), 1);
 }

@@ -158,66 +158,237 @@ __global__ __launch_bounds__(256) void table_kernel(TableArgs t)
 // doubles per branch record: TRX_SCENARIO_OUT, or TRX_SCENARIO_OUT_MOMENTS with TRX_FLAG_WEIGHT_MOMENTS
 int record_stride(int flags) { return (flags & TRX_FLAG_WEIGHT_MOMENTS) ? TRX_SCENARIO_OUT_MOMENTS : TRX_SCENARIO_OUT; }
 
+// ---------------------------------------------------------------------------------------------------------------
+// ONE description of an lnZ_* call for both ways of enqueueing it -- enqueue(): the call alone; enqueue_chain(): up to 16
+// calls in one launch chain -- so that a chained call IS a single call: its argument check (check_call), its buffers
+// (CallLayout::reserve), a branch's ScenFinal / PostArgs / WarpHistArgs (branch_final / branch_post / branch_hist) and
+// the copies back to the caller (copy_back) are written here, once.  What differs between the two is BranchPlace.
+
+// The device's view of a caller's buffer, or null when the device cannot write there: the result then goes through the
+// arena and a copy.  Pinned host memory (hipHostMalloc / torch pin_memory) is mapped into the device's address space.
+enum class Dest { kPinnedHost, kHostOrDevice };
+double* device_view(const void* p, Dest rule)
+{
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) == hipSuccess && attr.devicePointer &&
+        (attr.type == hipMemoryTypeHost || (rule == Dest::kHostOrDevice && attr.type == hipMemoryTypeDevice)))
+        return static_cast<double*>(attr.devicePointer);
+    (void)hipGetLastError();
+    return nullptr;
+}
+
+// a table of the K best draws (include/trx.h): every masked draw evaluated to the end, K stand-in draws
+int table_rows(const trx_scenario_args& s) { return s.table_rows > 1 ? s.table_rows : 0; }
+
+int check_call(const trx_scenario_args& s)
+{
+    const long N = s.draw->N;
+    if (N < 1 || N > 0x7fffffffL) return TRX_ERR_ARG;
+    const int K = table_rows(s);
+    if (K > TRX_TABLE_MAX_ROWS || (K && !s.table)) return TRX_ERR_ARG;
+    // posterior rows (include/trx.h): M draws per branch in proportion to their weight, selected behind the evidence
+    const int M = s.post_rows;
+    if (M < 0 || M > TRX_POST_MAX_ROWS || (M && !s.post)) return TRX_ERR_ARG;
+    // a weight histogram (include/trx.h): behind the evidence, like the posterior rows; the kernel's own uniforms only
+    if (s.warp_hist && !s.draw->use_philox) return TRX_ERR_ARG;
+    return TRX_OK;
+}
+
+struct Call;
+// a call's buffers in an arena (offsets): 146 N bytes of draw-side buffers, the reductions' workspaces, and staging for
+// the record, the posterior block and the table where the device cannot write the caller's
+struct CallLayout {
+    size_t cols, cols0, mask, mask2, prior, n, res, ws, pv, pi, idx[2], h[2], post, table;
+    void reserve(Arena& A, const Call& c);
+};
+
+struct Call {
+    const trx_scenario_args* s;
+    double* out;                              // the caller's record
+    long N;
+    int planet, ncol, nbr, K, M, H, n_pad, want_prior, stride;
+    double *rec_dev, *post_dev, *table_dev;   // the device's view of the caller's record / posterior block / table, or null
+    CallLayout at;
+    const Arena* A;                           // where `at` counts from (once the arena has its memory)
+
+    Call(const trx_scenario_args& s_, double* out_) : s(&s_), out(out_), N(s_.draw->N), A(nullptr)
+    {
+        planet = s_.draw->planet != 0; ncol = planet ? 11 : 14; nbr = planet ? 1 : 2;
+        K = table_rows(s_); M = s_.post_rows; H = s_.warp_hist != nullptr; n_pad = K ? K : 1;
+        // a call with an importance map: its prior column carries ln J, whatever the scenario's prior
+        want_prior = (s_.want_prior || s_.draw->warp) ? 1 : 0;
+        stride = record_stride(s_.flags);         // (per call: a chain may mix calls with and without moments)
+        rec_dev = device_view(out_, Dest::kPinnedHost);
+        post_dev = M ? device_view(s_.post, Dest::kHostOrDevice) : nullptr;
+        table_dev = K ? device_view(s_.table, Dest::kHostOrDevice) : nullptr;
+    }
+    Call() = default;
+
+    double* cols() const { return A->at<double>(at.cols); }
+    double* cols0() const { return A->at<double>(at.cols0); }
+    double* lnprior() const { return want_prior ? A->at<double>(at.prior) : nullptr; }
+    long* n_dev(int b) const { return A->at<long>(at.n) + b; }
+    int* idx(int b) const { return (b && planet) ? nullptr : A->at<int>(at.idx[b]); }
+    double* h(int b) const { return (b && planet) ? nullptr : A->at<double>(at.h[b]); }
+    double* ws(int b) const { return A->at<double>(at.ws) + (size_t)b * trx::kLmePart * kLmeParts; }
+    double* pv(int b) const { return A->at<double>(at.pv) + (size_t)b * kLmeParts; }
+    long* pi(int b) const { return A->at<long>(at.pi) + (size_t)b * 2 * kLmeParts; }
+    // where the device writes the record / a branch's posterior block / a branch's table: the caller's buffer if it can
+    double* res() const { return rec_dev ? rec_dev : A->at<double>(at.res); }
+    double* post(int b) const { return (post_dev ? post_dev : A->at<double>(at.post)) + (size_t)b * TRX_POST_BRANCH(M); }
+    double* table(int b) const { return (table_dev ? table_dev : A->at<double>(at.table)) + (size_t)b * TRX_TABLE_BRANCH(K); }
+    int model(int b) const { return planet ? TRX_MODEL_TP : (b ? TRX_MODEL_EB_TWIN : TRX_MODEL_EB); }
+
+    // the caller's draw arguments with the outputs pointed at this call's buffers; state: the first branch's state word
+    // (its word 1 is the draw kernel's flag -- zero between calls: the last branch's final stage clears it)
+    trx_draw_args draw_args(unsigned* state) const
+    {
+        trx_draw_args d = *s->draw;
+        d.cols = cols(); d.lnprior = lnprior(); d.dump = nullptr;
+        d.mask = A->at<unsigned char>(at.mask);
+        d.mask_twin = planet ? nullptr : A->at<unsigned char>(at.mask2);
+        d.flag = reinterpret_cast<int*>(state + 1);
+        return d;
+    }
+};
+
+void CallLayout::reserve(Arena& A, const Call& c)
+{
+    const size_t N = (size_t)c.N, twin = c.planet ? 0 : N;
+    cols = A.reserve(sizeof(double) * c.ncol * N);
+    cols0 = A.reserve(sizeof(double) * 16 * c.n_pad);
+    mask = A.reserve(N);
+    mask2 = A.reserve(twin);
+    prior = A.reserve(c.want_prior ? sizeof(double) * N : 0);
+    n = A.reserve(2 * sizeof(long));
+    res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1));
+    ws = A.reserve(sizeof(double) * 2 * trx::kLmePart * kLmeParts);
+    pv = A.reserve(sizeof(double) * 2 * kLmeParts);
+    pi = A.reserve(sizeof(long) * 2 * 2 * kLmeParts);
+    idx[0] = A.reserve(sizeof(int) * N);
+    idx[1] = A.reserve(sizeof(int) * twin);
+    h[0] = A.reserve(sizeof(double) * N);              // (256-byte steps: lme_draws / lnl_lme_chain ask for 16)
+    h[1] = A.reserve(sizeof(double) * twin);
+    post = A.reserve((c.M && !c.post_dev) ? sizeof(double) * 2 * TRX_POST_BRANCH(c.M) : 0);
+    table = A.reserve((c.K && !c.table_dev) ? sizeof(double) * 2 * TRX_TABLE_BRANCH(c.K) : 0);
+}
+
+// What the branches of an arena share out among themselves, in branch order: kPostWsBytes of tile sums for each branch
+// with posterior rows, and for each branch with a weight histogram its block -- side by side: one memset -- and a place
+// for X, the largest log-weight, which a branch with posterior rows keeps in its tile workspace instead
+struct SharedLayout {
+    size_t post_ws, hist, hist_x;
+    static size_t hist_bytes(int n_hist) { return sizeof(unsigned long long) * TRX_WARP_BRANCH * (size_t)n_hist; }
+    void reserve(Arena& A, int n_post, int n_hist)
+    {
+        post_ws = A.reserve(trx::kPostWsBytes * (size_t)n_post);
+        hist = A.reserve(hist_bytes(n_hist));
+        hist_x = A.reserve(sizeof(double) * (size_t)n_hist);
+    }
+};
+
+// What differs between a branch of a single call and a branch in a chain
+struct BranchPlace {
+    unsigned* state;              // the branch's state word: the arena's zeroed head / the branch's kBranchHead slot
+    int cols0_stride;             // of the stand-in columns: n_pad / 1
+    char* post_ws;                // the branch's posterior workspace (SharedLayout), or null: no posterior rows
+    double* hist_x;               // the branch's place for X without posterior rows, or null: no histogram
+    unsigned long long* hist;     // the branch's histogram block, or null
+    // the final stage leaves the branch's largest log-weight here, the posterior and histogram kernels read it
+    double* post_x() const
+    {
+        return post_ws ? reinterpret_cast<double*>(post_ws + trx::kPostWsSums + trx::kPostWsCounts) : hist_x;
+    }
+};
+
+BranchPlace branch_place(const Call& c, const Arena& A, const SharedLayout& sh, unsigned* state, int cols0_stride, int p_at,
+                         int h_at)
+{
+    BranchPlace at{state, cols0_stride, nullptr, nullptr, nullptr};
+    if (c.M) at.post_ws = A.at<char>(sh.post_ws) + trx::kPostWsBytes * (size_t)p_at;
+    if (c.H) {
+        at.hist_x = A.at<double>(sh.hist_x) + h_at;
+        at.hist = A.at<unsigned long long>(sh.hist) + (size_t)h_at * TRX_WARP_BRANCH;
+    }
+    return at;
+}
+
+trx::ScenFinal branch_final(const Call& c, int b, const BranchPlace& at)
+{
+    trx::ScenFinal f{};
+    f.idx = c.idx(b); f.cols = c.cols(); f.cols0 = c.cols0(); f.cols0_stride = at.cols0_stride; f.dense = 1;
+    f.N = c.N; f.n_total = c.N; f.ncol = c.ncol; f.branch = b; f.last_branch = (b == c.nbr - 1) ? 1 : 0;
+    f.stride = c.stride;
+    f.res = c.res() + (size_t)b * c.stride;
+    f.flag_out = (b == 0) ? c.res() + 2 * c.stride : nullptr;
+    f.state = at.state;
+    f.post_x = at.post_x();
+    return f;
+}
+
+// the weights are the evidence's own (its largest log-weight is in the scratch: post_x); rows the bounded evaluation
+// abandoned report a bound more than 90 below it and fall to the cut at -80.  The seed and the Philox counter are the
+// call's own (post_seed, the branch WITHIN the call), so a block does not depend on the chain it was drawn in.
+trx::PostArgs branch_post(const Call& c, int b, const BranchPlace& at)
+{
+    trx::PostArgs p{};
+    p.h = c.h(b); p.lnprior = c.lnprior(); p.n_dev = c.n_dev(b); p.n = c.N; p.N = c.N; p.twin = b;
+    p.c0 = trx::lnl_c0(c.s->lnsigma);
+    p.M = c.M; p.branch = b; p.seed = c.s->post_seed;
+    p.xmax = at.post_x();
+    p.tile_q = reinterpret_cast<trx::u128*>(at.post_ws);
+    p.tile_cnt = reinterpret_cast<long*>(at.post_ws + trx::kPostWsSums);
+    p.cols = c.cols(); p.ncol = c.ncol;
+    p.block = c.post(b);
+    return p;
+}
+
+trx::WarpHistArgs branch_hist(const Call& c, int b, const BranchPlace& at)
+{
+    trx::WarpHistArgs w{};
+    w.h = c.h(b); w.lnprior = c.lnprior(); w.n_dev = c.n_dev(b); w.idx = c.idx(b); w.N = c.N; w.twin = b;
+    w.slots = trx::warp_consumed_slots(*c.s->draw);
+    w.c0 = trx::lnl_c0(c.s->lnsigma);
+    w.seed = c.s->draw->seed;
+    w.xmax = at.post_x();
+    w.out = at.hist;
+    return w;
+}
+
+// behind the call's kernels: what the device could not write into the caller's memory; hist: the call's first block
+int copy_back(const Call& c, const unsigned long long* hist, hipStream_t st)
+{
+    const trx_scenario_args& s = *c.s;
+    if (c.H)
+        TRXS_HIP(hipMemcpyAsync(s.warp_hist, hist, sizeof(unsigned long long) * (size_t)c.nbr * TRX_WARP_BRANCH, hipMemcpyDefault, st));
+    if (c.M && !c.post_dev)
+        TRXS_HIP(hipMemcpyAsync(s.post, c.post(0), sizeof(double) * (size_t)c.nbr * TRX_POST_BRANCH(c.M), hipMemcpyDefault, st));
+    if (c.K && !c.table_dev)
+        TRXS_HIP(hipMemcpyAsync(s.table, c.table(0), sizeof(double) * (size_t)c.nbr * TRX_TABLE_BRANCH(c.K), hipMemcpyDefault, st));
+    if (!c.rec_dev)
+        TRXS_HIP(hipMemcpyAsync(c.out, c.res(), sizeof(double) * (2 * c.stride + 1), hipMemcpyDeviceToHost, st));
+    return TRX_OK;
+}
+
 int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
 {
-    trx_draw_args d = *s->draw;
-    const long N = d.N;
-    if (N < 1 || N > 0x7fffffffL) return TRX_ERR_ARG;
-    const int planet = d.planet != 0;
-    const int ncol = planet ? 11 : 14, nbr = planet ? 1 : 2;
-    // a table of the K best draws (include/trx.h): every masked draw evaluated to the end, K stand-in draws
-    const int K = s->table_rows > 1 ? s->table_rows : 0;
-    if (K > TRX_TABLE_MAX_ROWS || (K && !s->table)) return TRX_ERR_ARG;
-    // posterior rows (include/trx.h): M draws per branch in proportion to their weight, selected behind the evidence
-    const int M = s->post_rows;
-    if (M < 0 || M > TRX_POST_MAX_ROWS || (M && !s->post)) return TRX_ERR_ARG;
-    // a weight histogram (include/trx.h): behind the evidence, like the posterior rows; the kernel's own uniforms only
-    const bool H = s->warp_hist != nullptr;
-    if (H && !d.use_philox) return TRX_ERR_ARG;
-    // a call with an importance map: its prior column carries ln J, whatever the scenario's prior
-    const int want_prior = (s->want_prior || d.warp) ? 1 : 0;
-    const int n_pad = K ? K : 1;
-    const int flags = s->flags | (K ? TRX_FLAG_FULL_EVALUATION : 0);
-    const int stride = record_stride(s->flags);
+    if (int rc = check_call(*s)) return rc;
     trx::StreamLock turn(st);              // the whole call is enqueued back to back on the stream's scratch
-
-    // Where the record goes: straight into the caller's buffer when the device can write there (pinned host memory:
-    // hipHostMalloc / torch pin_memory are mapped into the device's address space), else through a device copy
-    double* rec_dev = nullptr;
-    {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, out_host) == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer)
-            rec_dev = static_cast<double*>(attr.devicePointer);
-        else
-            (void)hipGetLastError();
-    }
+    Call c(*s, out_host);
+    const long N = c.N;
+    const int flags = s->flags | (c.K ? TRX_FLAG_FULL_EVALUATION : 0);
+    const int n_post = c.M ? c.nbr : 0, n_hist = c.H ? c.nbr : 0;
 
     Arena A;
     const size_t o_state = A.reserve(trx::kScratchZeroed);     // persistent: finished-block counter, the draw kernel's flag
-    const size_t o_cols = A.reserve(sizeof(double) * ncol * N), o_mask = A.reserve(N), o_mask2 = A.reserve(planet ? 0 : N),
-                 o_prior = A.reserve(want_prior ? sizeof(double) * N : 0),
-                 o_n = A.reserve(2 * sizeof(long)), o_cols0 = A.reserve(sizeof(double) * 16 * n_pad),
-                 o_table = A.reserve(K ? sizeof(double) * 2 * TRX_TABLE_BRANCH(K) : 0),
-                 o_post_ws = A.reserve(M ? 2 * trx::kPostWsBytes : 0),
-                 o_post = A.reserve(M ? sizeof(double) * 2 * TRX_POST_BRANCH(M) : 0),
-                 o_hist = A.reserve(H ? sizeof(unsigned long long) * 2 * TRX_WARP_BRANCH : 0), o_hist_x = A.reserve(H ? 256 : 0),
-                 o_res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1)),
-                 o_ws = A.reserve(sizeof(double) * 2 * trx::kLmePart * kLmeParts), o_pv = A.reserve(sizeof(double) * 2 * kLmeParts),
-                 o_pi = A.reserve(sizeof(long) * 2 * 2 * kLmeParts), o_cnt = A.reserve(sizeof(int) * 2 * trx::kDrawMaxGroups),
-                 o_idx0 = A.reserve(sizeof(int) * N), o_idx1 = A.reserve(planet ? 0 : sizeof(int) * N),
-                 o_h0 = A.reserve(sizeof(double) * N), o_h1 = A.reserve(planet ? 0 : sizeof(double) * N);
+    const size_t o_cnt = A.reserve(sizeof(int) * 2 * trx::kDrawMaxGroups);
+    c.at.reserve(A, c);
+    SharedLayout sh;
+    sh.reserve(A, n_post, n_hist);
     TRXS_HIP(trx::stream_scratch(st, 1, A.used, reinterpret_cast<void**>(&A.base)));
+    c.A = &A;
     unsigned* state = A.at<unsigned>(o_state);
-    d.cols = A.at<double>(o_cols);
-    d.mask = A.at<unsigned char>(o_mask);
-    d.mask_twin = planet ? nullptr : A.at<unsigned char>(o_mask2);
-    d.lnprior = want_prior ? A.at<double>(o_prior) : nullptr;
-    d.flag = reinterpret_cast<int*>(state + 1);        // zero between calls: the last branch's final stage clears it
-    d.dump = nullptr;
-    long* n_dev = A.at<long>(o_n);
-    double* res = rec_dev ? rec_dev : A.at<double>(o_res);
-    int* idx[2] = {A.at<int>(o_idx0), planet ? nullptr : A.at<int>(o_idx1)};
-    double* h[2] = {A.at<double>(o_h0), planet ? nullptr : A.at<double>(o_h1)};
+    const trx_draw_args d = c.draw_args(state);
     long per = 0;
     int groups = 0;
     if (int rc = trx::draw_counted(d, A.at<int>(o_cnt), &per, &groups, st)) return rc;
@@ -226,102 +397,32 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
         (void)hipMemsetAsync(state, 0, trx::kScratchZeroed, st);
         return rc;
     };
-    if (int rc = trx::compact_fill(d, per, groups, A.at<int>(o_cnt), idx[0], idx[1], n_dev, A.at<double>(o_cols0), st, n_pad))
+    if (int rc = trx::compact_fill(d, per, groups, A.at<int>(o_cnt), c.idx(0), c.idx(1), c.n_dev(0), c.cols0(), st, c.n_pad))
         return bail(rc);
-    double* table_dev = nullptr;           // where the device writes the table: the caller's buffer if it can
-    if (K) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, s->table) == hipSuccess && attr.devicePointer &&
-            (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice))
-            table_dev = static_cast<double*>(attr.devicePointer);
-        else
-            (void)hipGetLastError();
-    }
-    double* post_dev = nullptr;            // ... and the posterior block
-    if (M) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, s->post) == hipSuccess && attr.devicePointer &&
-            (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice))
-            post_dev = static_cast<double*>(attr.devicePointer);
-        else
-            (void)hipGetLastError();
-    }
     if (trx::knob_poison())          // tests: an unwritten row must show (include/trx_debug.h)
-        for (int b = 0; b < nbr; ++b) TRXS_HIP(hipMemsetAsync(h[b], 0, sizeof(double) * (size_t)N, st));
-    if (H) TRXS_HIP(hipMemsetAsync(A.at<char>(o_hist), 0, sizeof(unsigned long long) * 2 * TRX_WARP_BRANCH, st));
-    for (int b = 0; b < nbr; ++b) {
-        const int model = planet ? TRX_MODEL_TP : (b ? TRX_MODEL_EB_TWIN : TRX_MODEL_EB);
+        for (int b = 0; b < c.nbr; ++b) TRXS_HIP(hipMemsetAsync(c.h(b), 0, sizeof(double) * (size_t)N, st));
+    if (n_hist) TRXS_HIP(hipMemsetAsync(A.at<char>(sh.hist), 0, SharedLayout::hist_bytes(n_hist), st));
+    for (int b = 0; b < c.nbr; ++b) {
+        const BranchPlace at = branch_place(c, A, sh, state, c.n_pad, b, b);
         const double* bounds = nullptr;
-        if (int rc = trx::lnl_draws(model, flags, s->time, s->flux, s->n_time, s->sigma, d.cols, N, n_dev + b, idx[b], N,
-                                    b, s->exptime, s->nsupersample, h[b], d.lnprior, s->lnsigma, &bounds, st))
+        if (int rc = trx::lnl_draws(c.model(b), flags, s->time, s->flux, s->n_time, s->sigma, d.cols, N, c.n_dev(b), c.idx(b), N,
+                                    b, s->exptime, s->nsupersample, c.h(b), d.lnprior, s->lnsigma, &bounds, st))
             return bail(rc);
-        trx::ScenFinal fin{};
-        fin.idx = idx[b];
-        fin.cols = d.cols;
-        fin.cols0 = A.at<double>(o_cols0);
-        fin.cols0_stride = n_pad;
-        fin.dense = 1;
-        fin.N = N;
-        fin.n_total = N;
-        fin.ncol = ncol;
-        fin.branch = b;
-        fin.last_branch = (b == nbr - 1) ? 1 : 0;
-        fin.stride = stride;
-        fin.res = res + (size_t)b * stride;
-        fin.flag_out = (b == 0) ? res + 2 * stride : nullptr;
-        fin.state = state;
-        char* post_ws = M ? A.at<char>(o_post_ws) + (size_t)b * trx::kPostWsBytes : nullptr;
-        if (M) fin.post_x = reinterpret_cast<double*>(post_ws + trx::kPostWsSums + trx::kPostWsCounts);
-        else if (H) fin.post_x = A.at<double>(o_hist_x) + b;
-        if (int rc = trx::lme_draws(h[b], d.lnprior, s->lnsigma, N, n_dev + b, idx[b],
-                                    A.at<double>(o_ws) + (size_t)b * trx::kLmePart * kLmeParts, A.at<double>(o_pv) + (size_t)b * kLmeParts,
-                                    A.at<long>(o_pi) + (size_t)b * 2 * kLmeParts, bounds, fin, st))
+        if (int rc = trx::lme_draws(c.h(b), d.lnprior, s->lnsigma, N, c.n_dev(b), c.idx(b), c.ws(b), c.pv(b), c.pi(b), bounds,
+                                    branch_final(c, b, at), st))
             return bail(rc);
-        if (K) {
+        if (c.K) {
             TableArgs t{};
-            t.h = h[b]; t.n_dev = n_dev + b; t.cols = d.cols; t.cols_pad = A.at<double>(o_cols0); t.N = N;
-            t.ncol = ncol; t.branch = b; t.K = K;
-            t.table = (table_dev ? table_dev : A.at<double>(o_table)) + (size_t)b * TRX_TABLE_BRANCH(K);
+            t.h = c.h(b); t.n_dev = c.n_dev(b); t.cols = d.cols; t.cols_pad = c.cols0(); t.N = N;
+            t.ncol = c.ncol; t.branch = b; t.K = c.K;
+            t.table = c.table(b);
             hipLaunchKernelGGL(table_kernel, dim3(1), dim3(256), 0, st, t);
             if (hipGetLastError() != hipSuccess) return bail(TRX_ERR_HIP);
         }
-        if (M) {
-            // the weights are the evidence's own (its largest log-weight is in the scratch: fin.post_x); rows the
-            // bounded evaluation abandoned report a bound more than 90 below it and fall to the cut at -80
-            trx::PostArgs p{};
-            p.h = h[b]; p.lnprior = d.lnprior; p.n_dev = n_dev + b; p.n = N; p.N = N; p.twin = b;
-            p.c0 = -0.5 * log(trx::kTwoPi) - s->lnsigma;      // (lme_draws' constant)
-            p.M = M; p.branch = b; p.seed = s->post_seed;
-            p.xmax = fin.post_x;
-            p.tile_q = reinterpret_cast<trx::u128*>(post_ws);
-            p.tile_cnt = reinterpret_cast<long*>(post_ws + trx::kPostWsSums);
-            p.cols = d.cols; p.ncol = ncol;
-            p.block = (post_dev ? post_dev : A.at<double>(o_post)) + (size_t)b * TRX_POST_BRANCH(M);
-            if (trx::post_launch(p, false, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
-        }
-        if (H) {
-            trx::WarpHistArgs w{};
-            w.h = h[b]; w.lnprior = d.lnprior; w.n_dev = n_dev + b; w.idx = idx[b]; w.N = N; w.twin = b;
-            w.slots = trx::warp_consumed_slots(d);
-            w.c0 = -0.5 * log(trx::kTwoPi) - s->lnsigma;      // (lme_draws' constant)
-            w.seed = d.seed;
-            w.xmax = fin.post_x;
-            w.out = A.at<unsigned long long>(o_hist) + (size_t)b * TRX_WARP_BRANCH;
-            if (trx::warp_hist_launch(w, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
-        }
+        if (c.M && trx::post_launch(branch_post(c, b, at), false, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
+        if (c.H && trx::warp_hist_launch(branch_hist(c, b, at), st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
     }
-    if (H)
-        TRXS_HIP(hipMemcpyAsync(s->warp_hist, A.at<char>(o_hist), sizeof(unsigned long long) * (size_t)nbr * TRX_WARP_BRANCH,
-                                hipMemcpyDefault, st));
-    if (M && !post_dev)
-        TRXS_HIP(hipMemcpyAsync(s->post, A.at<double>(o_post), sizeof(double) * (size_t)nbr * TRX_POST_BRANCH(M),
-                                hipMemcpyDefault, st));
-    if (K && !table_dev)
-        TRXS_HIP(hipMemcpyAsync(s->table, A.at<double>(o_table), sizeof(double) * (size_t)nbr * TRX_TABLE_BRANCH(K),
-                                hipMemcpyDefault, st));
-    if (!rec_dev)
-        TRXS_HIP(hipMemcpyAsync(out_host, res, sizeof(double) * (2 * stride + 1), hipMemcpyDeviceToHost, st));
-    return TRX_OK;
+    return copy_back(c, A.at<unsigned long long>(sh.hist), st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -334,47 +435,34 @@ int enqueue(const trx_scenario_args* s, double* out_host, hipStream_t st)
 // 113 of the step's 155 ms enqueueing them.  The calls of a chain must share N, the time stamps, the exposure settings
 // and the precision flag (the calls of one target do: triceratops.py:767-1428); flux and sigma may differ (a nearby
 // star's light curve is the target's, renormalised).  Results are those of the calls one by one, bit for bit: the same
-// kernels' bodies on the same rows in the same order.
-// Calls with posterior rows (post_rows > 0) join like any other: every branch that wants samples gets kPostWsBytes of
-// the arena for its tile sums, the chain's final stage leaves the branch's largest log-weight there (ScenFinal.post_x),
-// and behind lnl_lme_chain the two posterior kernels run ONCE for the whole chain (post_launch_chain: the branch as the
-// grid's second dimension, its PostArgs from a table that rides in the upload of the draw-argument table).  The seed
-// and the Philox counter are the call's own (post_seed, the branch WITHIN the call), so a block does not depend on
-// the chain it was drawn in.
-// Scratch: + 49 KB per such branch, + 16 (8 + 16 M) bytes per call whose block the device cannot write directly (at
-// most 1 MB, M = 4096) -- beside the call's 146 N bytes of draw-side buffers (14 columns, masks, prior, lists, chi^2)
-// for which the Python side's stream cap books 360 N (sharding.stream_scratch_bytes): covered from N = 5000 draws on,
-// and below that a whole chain is a few MB.
+// kernels' bodies on the same rows in the same order, each call described by the same Call as in enqueue().
+// Calls with posterior rows (post_rows > 0) join like any other: behind lnl_lme_chain the two posterior kernels run ONCE
+// for the whole chain (post_launch_chain: the branch as the grid's second dimension, its PostArgs from a table that rides
+// in the upload of the draw-argument table); the weight histograms likewise (warp_hist_launch_chain).
+// Scratch: + 49 KB per branch with posterior rows, + 16 (8 + 16 M) bytes per call whose block the device cannot write
+// directly (at most 1 MB, M = 4096) -- beside the call's 146 N bytes of draw-side buffers (14 columns, masks, prior, lists,
+// chi^2) for which the Python side's stream cap books 360 N (sharding.stream_scratch_bytes): covered from N = 5000 draws
+// on, and below that a whole chain is a few MB.
 constexpr size_t kBranchHead = 64;       // bytes of the zeroed head per branch: [scan counter | finished blocks, flag]
 static_assert(trx::kChainMaxBranchesHost * kBranchHead <= trx::kScratchZeroed, "zeroed head of the chain's arena");
 
 int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, double* const* out, hipStream_t st)
 {
+    if (n < 1 || n > trx::kChainMaxCalls) return TRX_ERR_ARG;
     const trx_scenario_args& s0 = calls[which[0]];
     const long N = s0.draw->N;
-    if (N < 1 || N > 0x7fffffffL || n < 1 || n > trx::kChainMaxCalls) return TRX_ERR_ARG;
     trx::StreamLock turn(st);
+    Call call[trx::kChainMaxCalls];
     int nbr_total = 0, n_post = 0, n_hist = 0;      // branches; those of them that want posterior rows / a weight histogram
-    double* post_dev[trx::kChainMaxCalls];  // where the device writes a call's posterior block: the caller's buffer if it can
     for (int i = 0; i < n; ++i) {
         const trx_scenario_args& s = calls[which[i]];
-        const int nbr = s.draw->planet ? 1 : 2, M = s.post_rows;
-        if (M < 0 || M > TRX_POST_MAX_ROWS || (M && !s.post)) return TRX_ERR_ARG;
-        nbr_total += nbr;
-        if (s.warp_hist) {
-            if (!s.draw->use_philox) return TRX_ERR_ARG;
-            n_hist += nbr;
-        }
-        post_dev[i] = nullptr;
-        if (M) {
-            n_post += nbr;
-            hipPointerAttribute_t attr;
-            if (hipPointerGetAttributes(&attr, s.post) == hipSuccess && attr.devicePointer &&
-                (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice))
-                post_dev[i] = static_cast<double*>(attr.devicePointer);
-            else
-                (void)hipGetLastError();
-        }
+        if (int rc = check_call(s)) return rc;
+        if (s.draw->N != N || s.n_time != s0.n_time || s.time != s0.time || s.nsupersample != s0.nsupersample ||
+            s.exptime != s0.exptime || table_rows(s)) return TRX_ERR_ARG;        // (a table call goes alone: trx_star_enqueue)
+        const Call& c = call[i] = Call(s, out[which[i]]);
+        nbr_total += c.nbr;
+        n_post += c.M ? c.nbr : 0;
+        n_hist += c.H ? c.nbr : 0;
     }
     if (nbr_total > trx::kChainMaxBranchesHost) return TRX_ERR_ARG;
     const size_t branch_bytes = trx::chain_branch_scratch_bytes(N);
@@ -388,31 +476,9 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
     const size_t tab_bytes = hist_tab_at + sizeof(trx::WarpHistArgs) * (size_t)n_hist;
     const size_t o_tab = A.reserve(tab_bytes);
     const size_t o_cnt = A.reserve(sizeof(int) * 2 * trx::kDrawMaxGroups * (size_t)n);
-    struct CallOff { size_t cols, cols0, mask, mask2, prior, n, res, ws, pv, pi, idx[2], h[2], post; };
-    CallOff co[trx::kChainMaxCalls];
-    for (int i = 0; i < n; ++i) {
-        const trx_scenario_args& s = calls[which[i]];
-        const int planet = s.draw->planet != 0, ncol = planet ? 11 : 14;
-        co[i].cols = A.reserve(sizeof(double) * ncol * N);
-        co[i].cols0 = A.reserve(sizeof(double) * 16);
-        co[i].mask = A.reserve(N);
-        co[i].mask2 = A.reserve(planet ? 0 : N);
-        co[i].prior = A.reserve((s.want_prior || s.draw->warp) ? sizeof(double) * N : 0);
-        co[i].n = A.reserve(2 * sizeof(long));
-        co[i].res = A.reserve(sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1));
-        co[i].ws = A.reserve(sizeof(double) * 2 * trx::kLmePart * kLmeParts);
-        co[i].pv = A.reserve(sizeof(double) * 2 * kLmeParts);
-        co[i].pi = A.reserve(sizeof(long) * 2 * 2 * kLmeParts);
-        co[i].idx[0] = A.reserve(sizeof(int) * N);
-        co[i].idx[1] = A.reserve(planet ? 0 : sizeof(int) * N);
-        co[i].h[0] = A.reserve(sizeof(double) * N);
-        co[i].h[1] = A.reserve(planet ? 0 : sizeof(double) * N);
-        co[i].post = A.reserve((s.post_rows && !post_dev[i]) ? sizeof(double) * 2 * TRX_POST_BRANCH(s.post_rows) : 0);
-    }
-    const size_t o_post_ws = A.reserve(trx::kPostWsBytes * (size_t)n_post);
-    // histograms: the branches' blocks side by side (one memset), and a place for X of a branch without posterior rows
-    const size_t o_hist = A.reserve(sizeof(unsigned long long) * TRX_WARP_BRANCH * (size_t)n_hist);
-    const size_t o_hist_x = A.reserve(sizeof(double) * (size_t)n_hist);
+    for (int i = 0; i < n; ++i) call[i].at.reserve(A, call[i]);
+    SharedLayout sh;
+    sh.reserve(A, n_post, n_hist);
     const size_t o_branch = A.reserve(branch_bytes * (size_t)nbr_total);
     TRXS_HIP(trx::stream_scratch(st, 2, A.used, reinterpret_cast<void**>(&A.base)));
 
@@ -426,100 +492,29 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
     trx::ChainFill fills[trx::kChainMaxCalls];
     trx::ChainBranch br[trx::kChainMaxBranchesHost];
     trx::ScenFinal fin[trx::kChainMaxBranchesHost];
-    double* res_of[trx::kChainMaxCalls];
-    bool copy_back[trx::kChainMaxCalls];
     int b_at = 0, p_at = 0, h_at = 0;
     for (int i = 0; i < n; ++i) {
-        const trx_scenario_args& s = calls[which[i]];
-        trx_draw_args d = *s.draw;
-        const int planet = d.planet != 0, ncol = planet ? 11 : 14, nbr = planet ? 1 : 2;
-        if (d.N != N || s.n_time != s0.n_time || s.time != s0.time || s.nsupersample != s0.nsupersample ||
-            s.exptime != s0.exptime) return TRX_ERR_ARG;
-        double* rec_dev = nullptr;
-        {
-            hipPointerAttribute_t attr;
-            if (hipPointerGetAttributes(&attr, out[which[i]]) == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer)
-                rec_dev = static_cast<double*>(attr.devicePointer);
-            else
-                (void)hipGetLastError();
-        }
-        copy_back[i] = rec_dev == nullptr;
-        double* res = rec_dev ? rec_dev : A.at<double>(co[i].res);
-        res_of[i] = res;
-        unsigned* state0 = reinterpret_cast<unsigned*>(A.base + o_head + (size_t)b_at * kBranchHead + 8);
-        d.cols = A.at<double>(co[i].cols);
-        d.mask = A.at<unsigned char>(co[i].mask);
-        d.mask_twin = planet ? nullptr : A.at<unsigned char>(co[i].mask2);
-        d.lnprior = (s.want_prior || d.warp) ? A.at<double>(co[i].prior) : nullptr;      // (a map's ln J rides in the prior column)
+        Call& c = call[i];
+        const trx_scenario_args& s = *c.s;
+        c.A = &A;
+        // (the call's first branch: word 1 of its state is the call's flag)
+        stage[i] = c.draw_args(reinterpret_cast<unsigned*>(A.base + o_head + (size_t)b_at * kBranchHead + 8));
         hist_first[i] = h_at;
-        d.flag = reinterpret_cast<int*>(state0 + 1);
-        d.dump = nullptr;
-        stage[i] = d;
-        long* n_dev = A.at<long>(co[i].n);
-        fills[i] = trx::ChainFill{A.at<int>(co[i].idx[0]), planet ? nullptr : A.at<int>(co[i].idx[1]), n_dev, A.at<double>(co[i].cols0)};
-        for (int b = 0; b < nbr; ++b, ++b_at) {
+        fills[i] = trx::ChainFill{c.idx(0), c.idx(1), c.n_dev(0), c.cols0()};
+        for (int b = 0; b < c.nbr; ++b, ++b_at) {
             char* head = A.base + o_head + (size_t)b_at * kBranchHead;
-            trx::ChainBranch& c = br[b_at];
-            c.model = planet ? TRX_MODEL_TP : (b ? TRX_MODEL_EB_TWIN : TRX_MODEL_EB);
-            c.flags = s.flags;
-            c.twin = b;
-            c.flux = s.flux;
-            c.sigma = s.sigma;
-            c.lnsigma = s.lnsigma;
-            c.cols = d.cols;
-            c.n_dev = n_dev + b;
-            c.src_idx = A.at<int>(co[i].idx[b]);
-            c.h = A.at<double>(co[i].h[b]);
-            c.lnprior = d.lnprior;
-            c.scratch = reinterpret_cast<double*>(A.base + o_branch + branch_bytes * (size_t)b_at);
-            c.scan_count = reinterpret_cast<unsigned long long*>(head);
-            c.ws = A.at<double>(co[i].ws) + (size_t)b * trx::kLmePart * kLmeParts;
-            c.amin_pv = A.at<double>(co[i].pv) + (size_t)b * kLmeParts;
-            c.amin_pi = A.at<long>(co[i].pi) + (size_t)b * 2 * kLmeParts;
-            trx::ScenFinal& f = fin[b_at];
-            f = trx::ScenFinal{};
-            f.idx = c.src_idx;
-            f.cols = d.cols;
-            f.cols0 = A.at<double>(co[i].cols0);
-            f.cols0_stride = 1;
-            f.dense = 1;
-            f.N = N;
-            f.n_total = N;
-            f.ncol = ncol;
-            f.branch = b;
-            f.last_branch = (b == nbr - 1) ? 1 : 0;
-            f.stride = record_stride(s.flags);           // (per call: a chain may mix calls with and without moments)
-            f.res = res + (size_t)b * f.stride;
-            f.flag_out = (b == 0) ? res + 2 * f.stride : nullptr;
-            f.state = reinterpret_cast<unsigned*>(head + 8);      // (branch 0: == state0, whose word 1 is the call's flag)
-            if (s.post_rows) {
-                // (enqueue()'s PostArgs of this branch, field by field: the weights are the evidence's own)
-                char* post_ws = A.base + o_post_ws + trx::kPostWsBytes * (size_t)p_at;
-                f.post_x = reinterpret_cast<double*>(post_ws + trx::kPostWsSums + trx::kPostWsCounts);
-                trx::PostArgs p{};
-                p.h = c.h; p.lnprior = d.lnprior; p.n_dev = n_dev + b; p.n = N; p.N = N; p.twin = b;
-                p.c0 = -0.5 * log(trx::kTwoPi) - s.lnsigma;
-                p.M = s.post_rows; p.branch = b; p.seed = s.post_seed;
-                p.xmax = f.post_x;
-                p.tile_q = reinterpret_cast<trx::u128*>(post_ws);
-                p.tile_cnt = reinterpret_cast<long*>(post_ws + trx::kPostWsSums);
-                p.cols = d.cols; p.ncol = ncol;
-                p.block = (post_dev[i] ? post_dev[i] : A.at<double>(co[i].post)) + (size_t)b * TRX_POST_BRANCH(s.post_rows);
-                post_stage[p_at++] = p;
-            }
-            if (s.warp_hist) {
-                // (enqueue()'s WarpHistArgs of this branch, field by field)
-                if (!f.post_x) f.post_x = A.at<double>(o_hist_x) + h_at;
-                trx::WarpHistArgs w{};
-                w.h = c.h; w.lnprior = d.lnprior; w.n_dev = n_dev + b; w.idx = c.src_idx; w.N = N; w.twin = b;
-                w.slots = trx::warp_consumed_slots(d);
-                w.c0 = -0.5 * log(trx::kTwoPi) - s.lnsigma;
-                w.seed = d.seed;
-                w.xmax = f.post_x;
-                w.out = A.at<unsigned long long>(o_hist) + (size_t)h_at * TRX_WARP_BRANCH;
-                hist_stage[h_at++] = w;
-            }
-            c.fin = &f;
+            const BranchPlace at = branch_place(c, A, sh, reinterpret_cast<unsigned*>(head + 8), 1, p_at, h_at);
+            trx::ChainBranch& cb = br[b_at];
+            cb.model = c.model(b); cb.flags = s.flags; cb.twin = b;
+            cb.flux = s.flux; cb.sigma = s.sigma; cb.lnsigma = s.lnsigma;
+            cb.cols = c.cols(); cb.n_dev = c.n_dev(b); cb.src_idx = c.idx(b); cb.h = c.h(b); cb.lnprior = c.lnprior();
+            cb.scratch = reinterpret_cast<double*>(A.base + o_branch + branch_bytes * (size_t)b_at);
+            cb.scan_count = reinterpret_cast<unsigned long long*>(head);
+            cb.ws = c.ws(b); cb.amin_pv = c.pv(b); cb.amin_pi = c.pi(b);
+            fin[b_at] = branch_final(c, b, at);
+            cb.fin = &fin[b_at];
+            if (c.M) post_stage[p_at++] = branch_post(c, b, at);
+            if (c.H) hist_stage[h_at++] = branch_hist(c, b, at);
         }
     }
     trx_draw_args* dev_tab = A.at<trx_draw_args>(o_tab);
@@ -549,24 +544,12 @@ int enqueue_chain(const trx_scenario_args* calls, const int* which, int n, doubl
         if (trx::post_launch_chain(post_tab, n_post, N, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
     }
     if (n_hist) {
-        TRXS_HIP(hipMemsetAsync(A.base + o_hist, 0, sizeof(unsigned long long) * TRX_WARP_BRANCH * (size_t)n_hist, st));
+        TRXS_HIP(hipMemsetAsync(A.at<char>(sh.hist), 0, SharedLayout::hist_bytes(n_hist), st));
         const trx::WarpHistArgs* hist_tab = reinterpret_cast<const trx::WarpHistArgs*>(A.base + o_tab + hist_tab_at);
         if (trx::warp_hist_launch_chain(hist_tab, n_hist, st) != TRX_OK) return bail(trx::fail_hip(hipErrorLaunchFailure));
     }
-    for (int i = 0; i < n; ++i) {
-        const trx_scenario_args& s = calls[which[i]];
-        if (s.warp_hist)
-            TRXS_HIP(hipMemcpyAsync(s.warp_hist, A.at<unsigned long long>(o_hist) + (size_t)hist_first[i] * TRX_WARP_BRANCH,
-                                    sizeof(unsigned long long) * (size_t)(s.draw->planet ? 1 : 2) * TRX_WARP_BRANCH,
-                                    hipMemcpyDefault, st));
-        if (s.post_rows && !post_dev[i])
-            TRXS_HIP(hipMemcpyAsync(s.post, A.at<double>(co[i].post),
-                                    sizeof(double) * (size_t)(s.draw->planet ? 1 : 2) * TRX_POST_BRANCH(s.post_rows),
-                                    hipMemcpyDefault, st));
-        if (copy_back[i])
-            TRXS_HIP(hipMemcpyAsync(out[which[i]], res_of[i], sizeof(double) * (2 * record_stride(s.flags) + 1),
-                                    hipMemcpyDeviceToHost, st));
-    }
+    for (int i = 0; i < n; ++i)
+        if (int rc = copy_back(call[i], A.at<unsigned long long>(sh.hist) + (size_t)hist_first[i] * TRX_WARP_BRANCH, st)) return rc;
     return TRX_OK;
 }
 
@@ -690,7 +673,7 @@ extern "C" int trx_posterior_from_halfchi2(const double* halfchi2, const double*
     char* ws = static_cast<char*>(workspace);
     trx::PostArgs p{};
     p.h = halfchi2; p.lnprior = lnprior; p.n = n; p.N = n;
-    p.c0 = -0.5 * log(trx::kTwoPi) - lnsigma;
+    p.c0 = trx::lnl_c0(lnsigma);
     p.M = post_rows; p.seed = post_seed;
     p.tile_q = reinterpret_cast<trx::u128*>(ws);
     p.tile_cnt = reinterpret_cast<long*>(ws + trx::kPostWsSums);
