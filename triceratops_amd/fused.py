@@ -147,14 +147,47 @@ MOMENTS = True
 # weight.  The operator chain produces the same key through trx_posterior_from_halfchi2.  Every other key: same bits.
 POSTERIOR_ROWS = 0
 POST_MAX_ROWS = _lib.POST_MAX_ROWS
-POSTERIOR_KEYS = ("M_s", "R_s", "u1", "u2", "P_orb", "inc", "b", "R_p", "ecc", "argp", "M_EB", "R_EB", "fluxratio_EB",
-                  "fluxratio_comp", "lnw", "row")
+# The columns of a branch, once.  *_COLS: as the library writes them (trx_draw_args.cols, include/trx.h) -- the first
+# slots of a branch record, the rows of a table and of a posterior block ("a": the orbit's semi-major axis in cm,
+# "a_twin": at 2 P_orb).  RECORD_COLS: the reference's names (marginal_likelihoods.py:152-171) in the order of a row of
+# sharding.run_units' table; _physical below takes the one to the other.
+PLANET_COLS = ("R_p", "P_orb", "inc", "a", "R_s", "u1", "u2", "ecc", "argp", "fluxratio_comp", "M_s")
+BINARY_COLS = ("R_EB", "fluxratio_EB", "P_orb", "inc", "a", "R_s", "u1", "u2", "ecc", "argp", "fluxratio_comp", "a_twin",
+               "M_EB", "M_s")
+RECORD_COLS = ("M_s", "R_s", "u1", "u2", "P_orb", "inc", "b", "R_p", "ecc", "argp", "M_EB", "R_EB", "fluxratio_EB",
+               "fluxratio_comp", "lnZ")
+POSTERIOR_PARAMS = RECORD_COLS[:14]      # the physical columns
+POSTERIOR_KEYS = POSTERIOR_PARAMS + ("lnw", "row")
 _POST_SALT = 0x706F7374       # post_seed = _mix(the call's draw seed, this): no generator is advanced
 # calc_posteriors_many(keep="summary"): a tuple of quantile levels q.  The rank that evaluated a unit then reduces every
 # scenario row's samples to len(q) quantiles of the 14 physical columns BEFORE the table is gathered
 # (sharding.RowLayout.summarise: quantile columns instead of sample columns).  None: the rows carry their samples.
 POSTERIOR_SUMMARY = None
-POSTERIOR_PARAMS = POSTERIOR_KEYS[:14]      # the physical columns (POSTERIOR_KEYS less lnw, row)
+
+
+def _physical(t, planet, twin):
+    """a branch's columns in the library's order ([11] planet / [14] binary, any trailing shape: [K] draws of a table
+    or posterior block, [calls] of a pass) -> the 14 physical columns in RECORD_COLS order.  The twin branch is the
+    binary at 2 P_orb on the orbit of 2 P_orb."""
+    c = dict(zip(PLANET_COLS if planet else BINARY_COLS, t))
+    P, sm, Rh, ecc, w, inc = c["P_orb"], c["a"], c["R_s"], c["ecc"], c["argp"], c["inc"]
+    if twin:
+        P, sm = 2 * P, c["a_twin"]
+    c["P_orb"] = P
+    c["b"] = sm * (1 - ecc ** 2) / (1 + ecc * np.sin(w * pi / 180)) * np.cos(inc * pi / 180) / (Rh * Rsun)
+    return [c[k] if k in c else np.zeros(np.shape(P)) for k in POSTERIOR_PARAMS]
+
+
+def record_row(d):
+    """a result dict's best draw and lnZ, in RECORD_COLS order"""
+    return [d[c] if c == "lnZ" else d[c][0] for c in RECORD_COLS]
+
+
+def posterior_to_flat(post, M):
+    """a "posterior" dict as the sample columns of a row of sharding.run_units' table, NaN for None"""
+    if post is None:
+        return np.full(len(POSTERIOR_KEYS) * M, np.nan)
+    return np.concatenate([np.asarray(post[k], dtype=np.float64) for k in POSTERIOR_KEYS])
 
 
 def posterior_from_flat(flat, M):
@@ -252,51 +285,48 @@ RECORD_MOMENTS = 2 * SCENARIO_OUT_MOMENTS + 1      # ... of a call with TRX_FLAG
 class Pending:
     """one trx_scenario_enqueue call whose record has not been read yet"""
 
-    def __init__(self, scen, out, stream, keep, ncol, n_time, is_host=False, table=None, table_rows=0,
-                 stride=SCENARIO_OUT, post=None, post_rows=0, hist=None):
-        self.post, self.post_rows = post, post_rows            # pinned [2][8 + 16 M] block of a call with posterior rows
-        self.hist = hist                                       # pinned [2][WARP_BRANCH] words of a call with a weight histogram
-        self.scen, self.out, self.stream, self.keep, self.ncol, self.n_time = scen, out, stream, keep, ncol, n_time
+    def __init__(self, scen, out, stream, keep, ncol, n_time, *, is_host=False, stride=SCENARIO_OUT, table=None,
+                 table_rows=0, post=None, post_rows=0, hist=None):
+        self.scen = scen                  # the _Scenario: its draw arguments, and the operator chain of a replay
+        self.out = out                    # pinned record: two branch records of `stride` doubles + the limb-darkening flag
+        self.stream = stream
+        self.keep = keep                  # tensors the call reads: alive until its record has been read
+        self.ncol = ncol                  # 11 planet / 14 binary
+        self.n_time = n_time
         self.is_host = is_host
-        self.stride = stride                                   # doubles per branch record (SCENARIO_OUT[_MOMENTS])
+        self.stride = stride              # SCENARIO_OUT[_MOMENTS]
         self.table, self.table_rows = table, table_rows        # pinned [2][15][K + 1] block of a call with a table
+        self.post, self.post_rows = post, post_rows            # pinned [2][8 + 16 M] block of a call with posterior rows
+        self.hist = hist                  # pinned [2][WARP_BRANCH] words of a call with a weight histogram
 
     def result(self):
-        """the call's result dict(s); the stream must have been synchronised"""
-        rec = self.out.numpy()
-        W = self.stride
-        if rec[2 * W] != 0.0:
+        """the call's result dict(s); the stream must have been synchronised.  The one-call case of records_to_rows:
+        the same rows, handed out as the dicts of a direct lnZ_* call"""
+        try:
+            (rows,) = _decode([self])
+        except ValueError:
             self.keep = None
-            raise ValueError("can only convert an array of size 1 to a Python scalar")
-        planet, ncol = bool(self.scen.a.planet), self.ncol
-        _check_status(rec[None, :], [planet], W)
-        with _stats_lock:
-            _lib.STATS["native_calls"] += 1
-        if self.replay_for_ties(rec):
-            return self.scen.run_operator_chain(self.is_host, ncol)
+            raise
+        if rows is None:
+            return self.scen.run_operator_chain(self.is_host, self.ncol)
         self.keep = None
-        res = []
-        K = self.table_rows
-        for b in range(1 if planet else 2):
-            row = rec[b * W:(b + 1) * W]
-            if W == SCENARIO_OUT_MOMENTS:
-                _lib.moments_emit(row[SCEN_LNM2], row[SCEN_LNWMAX])
-            n = int(row[ncol + 1])
-            with _stats_lock:
-                _lib.count_launch(n, self.n_time)
+        K, res = self.table_rows, []
+        for b, row in enumerate(rows):
+            lnZ, lnm2, lnwmax = row[len(POSTERIOR_PARAMS):]
+            if self.stride == SCENARIO_OUT_MOMENTS:
+                _lib.moments_emit(lnm2, lnwmax)
             if K > 1:
                 blk = self.table.numpy()[b].reshape(15, K + 1)
-                res.append(self.scen._table(blk[:ncol, :K].copy(), float(row[ncol]), b == 1))
+                res.append(self.scen._table(blk[:self.ncol, :K].copy(), float(lnZ), b == 1))
             else:
-                res.append(self.scen._table(row[:ncol].reshape(ncol, 1).copy(), float(row[ncol]), b == 1))
+                res.append(dict({c: row[j:j + 1] for j, c in enumerate(POSTERIOR_PARAMS)}, lnZ=float(lnZ)))
             if self.post_rows:
                 res[-1]["posterior"] = self.posterior(b)
-        return res[0] if planet else (res[0], res[1])
+        return res[0] if len(res) == 1 else (res[0], res[1])
 
     def posterior(self, b):
         """branch b's "posterior" dict from the library's block (None: no draw carries weight)"""
         return self.scen._posterior(self.post.numpy()[b], self.ncol, b == 1)
-
 
     def replay_for_ties(self, rec):
         """The seeded numpy modes promise the reference's OWN best draw, and the reference takes it from an argsort
@@ -352,104 +382,85 @@ def _widen(rec, stride):
     return out
 
 
+def _decode(calls):
+    """The one reader of the records the library writes (include/trx.h, TRX_SCENARIO_OUT): the Pendings of a pass,
+    their streams synchronised -> per call its (branches, 17) rows -- RECORD_COLS, then lnM2 and lnWmax (NaN where the
+    call did not ask for them) -- or None for a call that the operator chain has to evaluate again
+    (Pending.replay_for_ties).  Raises what a call by call reading raises; books the calls in _lib.STATS."""
+    W = SCENARIO_OUT_MOMENTS
+    recs = np.stack([_widen(p.out.numpy(), p.stride) for p in calls])      # [calls][41]
+    if np.any(recs[:, 2 * W] != 0.0):
+        # (a draw needs a limb-darkening cell the grid lacks: the reference fails there, with this text)
+        raise ValueError("can only convert an array of size 1 to a Python scalar")
+    planet = np.array([bool(p.scen.a.planet) for p in calls])
+    _check_status(recs, planet, W)
+    # (on the record as the library wrote it: replay_for_ties reads it at the call's own stride)
+    live = np.array([not p.replay_for_ties(p.out.numpy()) for p in calls])
+    n_time = np.array([p.n_time for p in calls])
+    rows = [None] * len(calls)
+    n_rows = n_cells = launches = 0
+    for is_planet, ncol in ((True, len(PLANET_COLS)), (False, len(BINARY_COLS))):
+        sel = live & (planet == is_planet)
+        if not sel.any():
+            continue
+        blocks = []
+        for b in range(1 if is_planet else 2):
+            q = recs[sel, b * W:(b + 1) * W]
+            lnz, n = q[:, ncol], q[:, ncol + 1]                            # (n: the draws that passed the mask)
+            blocks.append(np.stack(_physical(q[:, :ncol].T, is_planet, b == 1) + [lnz, q[:, SCEN_LNM2], q[:, SCEN_LNWMAX]],
+                                   axis=1))
+            n_rows += int(n.sum())
+            n_cells += int((n * n_time[sel]).sum())
+            launches += q.shape[0]
+        for i, r in zip(np.flatnonzero(sel), np.stack(blocks, axis=1)):    # [calls][branches][17]
+            rows[i] = r
+    with _stats_lock:
+        _lib.STATS["rows"] += n_rows
+        _lib.STATS["cells"] += n_cells
+        _lib.STATS["launches"] += launches
+        _lib.STATS["native_calls"] += len(calls)
+    return rows
+
+
+def _replay_rows(p):
+    """the rows of a call with a tie at its minimum, from the operator chain on the same staged numbers (seeded numpy
+    modes only: the reference's own order among exactly tied best draws, see Pending.replay_for_ties)"""
+    p.scen.want_moments = p.stride == SCENARIO_OUT_MOMENTS
+    with torch.cuda.stream(p.stream):
+        res = p.scen.run_operator_chain(p.is_host, p.ncol)
+    p.stream.synchronize()
+    dicts = res if isinstance(res, tuple) else (res,)
+    mom = p.scen.moments or [(np.nan, np.nan)] * len(dicts)
+    return np.array([record_row(d) + list(m)
+                     + (list(posterior_to_flat(d.get("posterior"), p.post_rows)) if p.post_rows else [])
+                     for d, m in zip(dicts, mom)])
+
+
 def records_to_rows(pending):
-    """The calls of a pass in one go: [(unit, Pending)] -> {unit: (branches, 17) array in sharding.RECORD_COLS order
+    """The calls of a pass in one go: [(unit, Pending)] -> {unit: (branches, 17) array in RECORD_COLS order
     (M_s R_s u1 u2 P_orb inc b R_p ecc argp M_EB R_EB fluxratio_EB fluxratio_comp lnZ), then sharding.MOMENT_COLS
     (lnM2 lnWmax: NaN where the call did not ask for them)}, what Pending.result() + sharding._record give call by call
-    (768 calls of a 64-target step: 12 ms of dict building; here a few array expressions).  The streams must have been
+    (768 calls of a 64-target step: 12 ms of dict building; here a few array expressions), then the columns of
+    sharding.RowLayout that the call carries: its posterior rows, its weight histogram.  The streams must have been
     synchronised."""
     if not pending:
         return {}
-    from .sharding import RECORD_COLS, RowLayout
-    W = SCENARIO_OUT_MOMENTS
-    recs = np.stack([_widen(p.out.numpy(), p.stride) for _, p in pending])      # [calls][41]
-    if np.any(recs[:, 2 * W] != 0.0):
-        raise ValueError("can only convert an array of size 1 to a Python scalar")
-    planet = np.array([bool(p.scen.a.planet) for _, p in pending])
-    _check_status(recs, planet, W)
-    # (on the record as the library wrote it: replay_for_ties reads it at the call's own stride)
-    replay = [i for i, (_, p) in enumerate(pending) if p.replay_for_ties(p.out.numpy())]
-    if replay:
-        # (seeded numpy modes only: the reference's own order among exactly tied best draws, see Pending.replay_for_ties)
-        redo = {}
-        for i in replay:
-            k, p = pending[i]
-            p.scen.want_moments = p.stride == SCENARIO_OUT_MOMENTS
-            with torch.cuda.stream(p.stream):
-                res = p.scen.run_operator_chain(p.is_host, p.ncol)
-            p.stream.synchronize()
-            dicts = res if isinstance(res, tuple) else (res,)
-            mom = p.scen.moments or [(np.nan, np.nan)] * len(dicts)
-            redo[k] = np.array([[d[c] if c == "lnZ" else d[c][0] for c in RECORD_COLS] + list(m)
-                                + (list(RowLayout(p.post_rows).encode(d.get("posterior"))) if p.post_rows else [])
-                                for d, m in zip(dicts, mom)])
-        with _stats_lock:
-            _lib.STATS["native_calls"] += len(replay)
-        rest = [kp for i, kp in enumerate(pending) if i not in set(replay)]
-        out = records_to_rows(rest)
-        out.update(redo)
-        for _, p in pending:
-            p.keep = None
-        return out
-    n_time = np.array([p.n_time for _, p in pending])
     out = {}
-    _rows_fill(pending, recs, planet, n_time, out)
-    # (calls with posterior rows: the extra columns of sharding.RowLayout, then -- WARP_HIST -- its histogram columns)
-    for k, p in pending:
+    for (k, p), rows in zip(pending, _decode([p for _, p in pending])):
+        if rows is None:
+            out[k] = _replay_rows(p)
+            continue
+        nbr = rows.shape[0]
         if p.post_rows:
-            flat = [RowLayout(p.post_rows).encode(p.posterior(b)) for b in range(out[k].shape[0])]
-            out[k] = np.concatenate([out[k], np.stack(flat)], axis=1)
+            flat = [posterior_to_flat(p.posterior(b), p.post_rows) for b in range(nbr)]
+            rows = np.concatenate([rows, np.stack(flat)], axis=1)
         if p.hist is not None:
             # (a pass with WARP_HIST: WARP_BRANCH more columns per branch)
-            words = p.hist.numpy()
-            out[k] = np.concatenate([out[k], np.stack([warp_hist_to_flat(words[b]) for b in range(out[k].shape[0])])], axis=1)
+            rows = np.concatenate([rows, np.stack([warp_hist_to_flat(w) for w in p.hist.numpy()[:nbr]])], axis=1)
+        out[k] = rows
     for _, p in pending:
         p.keep = None
     return out
-
-
-def _rows_fill(pending, recs, planet, n_time, out):
-    W = SCENARIO_OUT_MOMENTS
-
-    def impact(sm, ecc, w, inc, Rh):
-        return sm * (1 - ecc ** 2) / (1 + ecc * np.sin(w * pi / 180)) * np.cos(inc * pi / 180) / (Rh * Rsun)
-
-    rows_total = cells_total = launches = 0
-    if planet.any():
-        r = recs[planet]
-        rp, P, inc, sm, Rh, u1, u2, ecc, w, frc, Mh, lnz, n = (r[:, j] for j in range(13))
-        lnm2, lnwmax = r[:, SCEN_LNM2], r[:, SCEN_LNWMAX]
-        z = np.zeros(r.shape[0])
-        block = np.stack([Mh, Rh, u1, u2, P, inc, impact(sm, ecc, w, inc, Rh), rp, ecc, w, z, z, z, frc, lnz,
-                          lnm2, lnwmax], axis=1)
-        for row, (k, _) in zip(block, [kp for kp, pl in zip(pending, planet) if pl]):
-            out[k] = row[None, :]
-        rows_total += int(n.sum())
-        cells_total += int((n * n_time[planet]).sum())
-        launches += r.shape[0]
-    if (~planet).any():
-        r = recs[~planet]
-        blocks = []
-        for b in range(2):
-            q = r[:, b * W:(b + 1) * W]
-            rr, fr, P, inc, sm, Rh, u1, u2, ecc, w, frc, sm2, m, Mh, lnz, n = (q[:, j] for j in range(16))
-            lnm2, lnwmax = q[:, SCEN_LNM2], q[:, SCEN_LNWMAX]
-            if b == 1:
-                P, sm = 2 * P, sm2
-            z = np.zeros(q.shape[0])
-            blocks.append(np.stack([Mh, Rh, u1, u2, P, inc, impact(sm, ecc, w, inc, Rh), z, ecc, w, m, rr, fr, frc, lnz,
-                                    lnm2, lnwmax], axis=1))
-            rows_total += int(n.sum())
-            cells_total += int((n * n_time[~planet]).sum())
-            launches += q.shape[0]
-        both = np.stack(blocks, axis=1)                                   # [calls][2][17]
-        for row, (k, _) in zip(both, [kp for kp, pl in zip(pending, planet) if not pl]):
-            out[k] = row
-    with _stats_lock:
-        _lib.STATS["rows"] += rows_total
-        _lib.STATS["cells"] += cells_total
-        _lib.STATS["launches"] += launches
-        _lib.STATS["native_calls"] += len(pending)
 
 
 def begin_deferred(n_calls):
@@ -554,18 +565,23 @@ def _rp_laws():
     return out
 
 
+def _cached(cache, key, limit, build):
+    """cache[key], from build() on a miss.  The caches below hold what the ~10 lnZ_* calls of one star share, so a
+    few entries are live at a time: one that holds more than `limit` is emptied, not trimmed."""
+    v = cache.get(key)
+    if v is None:
+        if len(cache) > limit:
+            cache.clear()
+        v = cache[key] = build()
+    return v
+
+
 _q_law_cache = {}
 
 
 def _q_law(M_s, p_hi, F_twin):
     """tests/torch_pipeline._mass_ratio (priors.py:168-383); constants of a star's calls are built once"""
-    key = (float(M_s), p_hi, F_twin)
-    law = _q_law_cache.get(key)
-    if law is None:
-        if len(_q_law_cache) > 256:
-            _q_law_cache.clear()
-        law = _q_law_cache[key] = _q_law_build(M_s, p_hi, F_twin)
-    return law
+    return _cached(_q_law_cache, (float(M_s), p_hi, F_twin), 256, lambda: _q_law_build(M_s, p_hi, F_twin))
 
 
 def _q_law_build(M_s, p_hi, F_twin):
@@ -622,13 +638,8 @@ _flux0_cache = {}
 def _flux0(M_s, band):
     """flux_relation(M_s) as tests/torch_pipeline._flux_share forms it (the ten calls of a star ask for the
     same two or three values: kept)"""
-    key = (float(M_s), band)
-    v = _flux0_cache.get(key)
-    if v is None:
-        if len(_flux0_cache) > 256:
-            _flux0_cache.clear()
-        v = _flux0_cache[key] = float(10 ** funcs._flux_spl[band](np.array([M_s]))[0])
-    return v
+    return _cached(_flux0_cache, (float(M_s), band), 256,
+                   lambda: float(10 ** funcs._flux_spl[band](np.array([M_s]))[0]))
 
 
 _cc_cache = {}
@@ -708,13 +719,7 @@ def _on_device(a, device):
     if isinstance(a, torch.Tensor):
         return _lib.dev(a, device)
     a = np.ascontiguousarray(a, dtype=np.float64)
-    key = (a.shape, hash(a.tobytes()), device.index)
-    t = _lc_cache.get(key)
-    if t is None:
-        if len(_lc_cache) > 32:
-            _lc_cache.clear()
-        t = _lc_cache[key] = _lib.dev(a, device)
-    return t
+    return _cached(_lc_cache, (a.shape, hash(a.tobytes()), device.index), 32, lambda: _lib.dev(a, device))
 
 
 # ---------------------------------------------------------------------------------------
@@ -783,13 +788,8 @@ class _Scenario:
         a = self.a
         a.M_s, a.R_s, a.Teff = float(M_s), float(R_s), float(Teff)
         if Z is not None:
-            key = (self.mission, float(Z), float(Teff), float(M_s), float(R_s))
-            uu = _ldc_star_cache.get(key)
-            if uu is None:
-                if len(_ldc_star_cache) > 256:
-                    _ldc_star_cache.clear()
-                uu = _ldc_star_cache[key] = ml._ldc(self.mission).star(Z, Teff, ml._logg(M_s, R_s))
-            a.u1, a.u2 = uu
+            a.u1, a.u2 = _cached(_ldc_star_cache, (self.mission, float(Z), float(Teff), float(M_s), float(R_s)), 256,
+                                 lambda: ml._ldc(self.mission).star(Z, Teff, ml._logg(M_s, R_s)))
         a.f0_tess = _flux0(M_s, "TESS")
         a.law_q = _q_law(M_s, -0.5, 0.30)
 
@@ -850,12 +850,9 @@ class _Scenario:
         """TRILEGAL population + the index draw; hi_offset = -1 for the D scenarios (sic)"""
         a = self.a
         # the D and B calls of one star share the population (the last few stars' are kept)
-        key = (trilegal_fname, tuple(float(m) for m in mags), self.mission, self.dev.index)
-        f = _field_cache.get(key)
-        if f is None:
-            if len(_field_cache) >= 8:
-                _field_cache.clear()
-            f = _field_cache[key] = dp._Field({"device": self.dev}, trilegal_fname, *mags, self.mission, False)
+        # (limit 7: the cache never holds more than eight populations)
+        f = _cached(_field_cache, (trilegal_fname, tuple(float(m) for m in mags), self.mission, self.dev.index), 7,
+                    lambda: dp._Field({"device": self.dev}, trilegal_fname, *mags, self.mission, False))
         if need_ldc:
             f.need_ldc()
         self.keep.append(f)
@@ -901,24 +898,44 @@ class _Scenario:
         with numpy's memory -- and the separations go back in (sep_in).  Until round 6 this was a documented deviation
         (|d lnZ| <= 8.5e-8 on TOI-465.01's D and B scenarios, tolerance 1e-6 there); now those rows meet the 1e-8 of
         all the others.  One host synchronisation, in a mode that spends its time drawing 3e8 numpy uniforms anyway."""
+        a = self.a
+        a.sep_in = None
+        o = self._draw(ncol, dm_out=True)
+        x = o["dm_out"].abs().cpu().numpy()
+        self.sep = _lib.dev(np.interp(x, self.cc_host_cons, self.cc_host_seps), self.dev)
+        self.keep.append(self.sep)
+        a.dm_out, a.sep_in = None, self.sep.data_ptr()
+        a.cols = a.mask = a.mask_twin = a.flag = None
+
+    def _draw(self, ncol, lnprior=False, dm_out=False, dump=False):
+        """trx_draw_scenario on the current stream, every draw in full: its outputs as a dict of device tensors under
+        the names of trx_draw_args (None for those not asked for, and for a planet's mask_twin)"""
         a, N, dev = self.a, self.N, self.dev
-        cols = torch.empty((ncol, N), dtype=F64, device=dev)
-        mask = torch.empty(N, dtype=torch.uint8, device=dev)
-        mask2 = torch.empty(N, dtype=torch.uint8, device=dev) if not a.planet else None
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        dm = torch.empty(N, dtype=F64, device=dev)
-        a.cols, a.mask, a.mask_twin, a.lnprior, a.flag = cols.data_ptr(), mask.data_ptr(), _ptr(mask2), None, flag.data_ptr()
-        a.dm_out, a.sep_in = dm.data_ptr(), None
+        o = {"cols": torch.empty((ncol, N), dtype=F64, device=dev),
+             "mask": torch.empty(N, dtype=torch.uint8, device=dev),
+             "mask_twin": torch.empty(N, dtype=torch.uint8, device=dev) if not a.planet else None,
+             "lnprior": torch.empty(N, dtype=F64, device=dev) if lnprior else None,
+             "flag": torch.zeros(1, dtype=torch.int32, device=dev),
+             "dm_out": torch.empty(N, dtype=F64, device=dev) if dm_out else None,
+             "dump": torch.zeros((9, N), dtype=F64, device=dev) if dump else None}
+        for name, t in o.items():
+            setattr(a, name, _ptr(t))
         with torch.cuda.device(dev):
             _lib.wait_uploads(torch.cuda.current_stream(dev))
             rc = _fn()(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream)
         if rc:
             raise _lib.TrxError("trx_draw_scenario failed with status %d" % rc)
-        x = dm.abs().cpu().numpy()
-        self.sep = _lib.dev(np.interp(x, self.cc_host_cons, self.cc_host_seps), dev)
-        self.keep.append(self.sep)
-        a.dm_out, a.sep_in = None, self.sep.data_ptr()
-        a.cols = a.mask = a.mask_twin = a.flag = None
+        return o
+
+    def _upload_warp(self):
+        """the call's importance map (WARP_GRIDS) on the device, alive until the kernel has read it"""
+        grid = _lib.dev(np.ascontiguousarray(self.warp, dtype=np.float64).reshape(-1), self.dev)
+        self.keep.append(grid)
+        self.a.warp = grid.data_ptr()
+
+    def _flags(self, is_host):
+        """the call's TRX_FLAG_* word, less the library-wide _lib.EXTRA_FLAGS"""
+        return (FLAG_COMPANION_IS_HOST if is_host else 0) | (0 if self.parallel else FLAG_SCALAR_K)
 
     # -----------------------------------------------------------------------------------
     def run(self, is_host):
@@ -952,38 +969,24 @@ class _Scenario:
         """trx_draw_scenario (every draw in full) + torch operators for the compaction and the best-draw table +
         trx_lnz_scenario per branch: the path of the 100-row tables of direct lnZ_* calls, and the cross-check of
         the library's own chain"""
-        a, N, dev = self.a, self.N, self.dev
+        a, N = self.a, self.N
         if self.warp is not None:
             # (the dump / cross-check path of a mapped call: ln J rides in the prior column, whatever the scenario's prior)
             if not self.philox:
                 raise NotImplementedError("an importance map needs set_sampling('device'): a staged uniform is never mapped")
-            grid = _lib.dev(np.ascontiguousarray(self.warp, dtype=np.float64).reshape(-1), dev)
-            self.keep.append(grid)
-            a.warp = grid.data_ptr()
+            self._upload_warp()
             self.want_prior = True
-        cols = torch.empty((ncol, N), dtype=F64, device=dev)
-        mask = torch.empty(N, dtype=torch.uint8, device=dev)
-        mask2 = torch.empty(N, dtype=torch.uint8, device=dev) if not a.planet else None
-        lnprior = torch.empty(N, dtype=F64, device=dev) if self.want_prior else None
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        a.cols, a.mask, a.mask_twin, a.lnprior, a.flag = (cols.data_ptr(), mask.data_ptr(), _ptr(mask2),
-                                                          _ptr(lnprior), flag.data_ptr())
+        o = self._draw(ncol, lnprior=self.want_prior, dump=DUMP is not None)
+        cols, mask, mask2, lnprior, flag = o["cols"], o["mask"], o["mask_twin"], o["lnprior"], o["flag"]
         if DUMP is not None:
-            dump = torch.zeros((9, N), dtype=F64, device=dev)
-            a.dump = dump.data_ptr()
-            DUMP.append({"dump": dump, "cols": cols, "mask": mask, "mask_twin": mask2, "lnprior": lnprior})
-        with torch.cuda.device(dev):
-            _lib.wait_uploads(torch.cuda.current_stream(dev))
-            rc = _fn()(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream)
-        if rc:
-            raise _lib.TrxError("trx_draw_scenario failed with status %d" % rc)
+            DUMP.append({k: o[k] for k in ("dump", "cols", "mask", "mask_twin", "lnprior")})
         self.keep = []
         out = []
         # the Monte-Carlo moments of each branch's evidence (calc_probs: _lib.moments_wanted; a replay of a record that
         # carried them: want_moments), from the chi^2/2 values already on the device
         moments = MOMENTS and (_lib.moments_wanted() or self.want_moments)
         self.moments = [] if moments else None
-        flags = (FLAG_COMPANION_IS_HOST if is_host else 0) | (0 if self.parallel else FLAG_SCALAR_K)
+        flags = self._flags(is_host)
         branches = ((MODEL_TP, mask, False),) if a.planet else ((MODEL_EB, mask, False), (MODEL_EB_TWIN, mask2, True))
         for model, m, twin in branches:
             idx = torch.nonzero(m, as_tuple=False).flatten()
@@ -1043,32 +1046,30 @@ class _Scenario:
         if n == 0:
             return h
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL         # (set_precision; the evaluation is full either way)
+        chunks = 1         # (launches per dataset)
         if DATASET_EVALUATION == "fused":
             for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
                 limit = 1.5 * self.sigma if (model == MODEL_EB and l == 0) else float("inf")
                 _lib.lnl_batch_weighted(model, flags, time_d, flux_d, inv_var_d, block, exptime, nsamples, limit, out=h)
-            with _stats_lock:
-                _lib.STATS["rows"] += n
-                _lib.STATS["cells"] += n * sum(int(d[0].numel()) for d in self.datasets)
-                _lib.STATS["launches"] += len(self.datasets)
-            return h
-        t_max = max(int(d[0].numel()) for d in self.datasets)
-        rows = max(1, int(DATASET_GRID_BYTES) // (8 * t_max))
-        buf = torch.empty(min(rows, n) * t_max, dtype=F64, device=self.dev)
-        eb = model == MODEL_EB
-        for r0 in range(0, n, rows):
-            r1 = min(r0 + rows, n)
-            blk = block if (r0 == 0 and r1 == n) else block[:, r0:r1].contiguous()
-            for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
-                nt = int(time_d.numel())
-                grid, sec = _lib.flux_grid(model, flags, time_d, blk, exptime, nsamples, want_secdepth=eb and l == 0,
-                                           out=buf[:(r1 - r0) * nt].view(r1 - r0, nt))
-                _lib.chi2_grid_weighted(flux_d, inv_var_d, grid, sec, 1.5 * self.sigma, out=h[r0:r1])
+        else:
+            t_max = max(int(d[0].numel()) for d in self.datasets)
+            rows = max(1, int(DATASET_GRID_BYTES) // (8 * t_max))
+            chunks = -(-n // rows)
+            buf = torch.empty(min(rows, n) * t_max, dtype=F64, device=self.dev)
+            eb = model == MODEL_EB
+            for r0 in range(0, n, rows):
+                r1 = min(r0 + rows, n)
+                blk = block if (r0 == 0 and r1 == n) else block[:, r0:r1].contiguous()
+                for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
+                    nt = int(time_d.numel())
+                    grid, sec = _lib.flux_grid(model, flags, time_d, blk, exptime, nsamples, want_secdepth=eb and l == 0,
+                                               out=buf[:(r1 - r0) * nt].view(r1 - r0, nt))
+                    _lib.chi2_grid_weighted(flux_d, inv_var_d, grid, sec, 1.5 * self.sigma, out=h[r0:r1])
         with _stats_lock:
             # (the masked draws once, every (draw, time stamp) cell of every dataset)
             _lib.STATS["rows"] += n
             _lib.STATS["cells"] += n * sum(int(d[0].numel()) for d in self.datasets)
-            _lib.STATS["launches"] += len(self.datasets) * -(-n // rows)
+            _lib.STATS["launches"] += len(self.datasets) * chunks
         return h
 
     def _run_native(self, is_host, ncol):
@@ -1081,8 +1082,7 @@ class _Scenario:
         sa.time, sa.flux = self.time.data_ptr(), self.flux.data_ptr()
         sa.n_time, sa.nsupersample = int(self.time.numel()), int(self.nsamples)
         sa.sigma, sa.lnsigma, sa.exptime = float(self.sigma), float(np.log(self.sigma)), float(self.exptime)
-        sa.flags = ((FLAG_COMPANION_IS_HOST if is_host else 0) | (0 if self.parallel else FLAG_SCALAR_K)
-                    | _lib.EXTRA_FLAGS)
+        sa.flags = self._flags(is_host) | _lib.EXTRA_FLAGS
         # (calc_probs / calc_probs_many: records with the moments of the evidence; a direct lnZ_* call keeps today's)
         stride = SCENARIO_OUT
         if MOMENTS and _lib.moments_wanted():
@@ -1109,16 +1109,14 @@ class _Scenario:
             if self.want_hist and M:
                 raise NotImplementedError("a weight histogram and posterior rows in one pass are not built")
         if self.warp is not None:
-            grid = _lib.dev(np.ascontiguousarray(self.warp, dtype=np.float64).reshape(-1), dev)
-            self.keep.append(grid)
-            a.warp = grid.data_ptr()
+            self._upload_warp()
         if self.want_hist:
             block = getattr(_tls, "hists", None)
             hist = (block[_tls.next_record - 1] if deferred and block is not None and _tls.next_record <= block.shape[0]
                     else torch.empty((2, WARP_BRANCH), dtype=torch.int64).pin_memory())
             sa.warp_hist = hist.data_ptr()
-        pend = Pending(self, out, stream, self.keep + [self.time, self.flux], ncol, sa.n_time, is_host, table, K if K > 1 else 0,
-                       stride, post, M, hist)
+        pend = Pending(self, out, stream, self.keep + [self.time, self.flux], ncol, sa.n_time, is_host=is_host, stride=stride,
+                       table=table, table_rows=K if K > 1 else 0, post=post, post_rows=M, hist=hist)
         self.keep = []
         if deferred and getattr(_tls, "batch", None) is not None:
             _tls.batch.append((sa, out, stream, dev))      # (sa.draw points at self.a: alive in the Pending)
@@ -1179,20 +1177,7 @@ class _Scenario:
 
     def _table(self, t, lnZ, twin):
         """the reference's result dict from the gathered columns (marginal_likelihoods.py:152-171)"""
-        z = np.zeros(t.shape[1])
-        if self.a.planet:
-            rp, P, inc, sm, Rh, u1, u2, ecc, w, frc, Mh = t
-            b = sm * (1 - ecc ** 2) / (1 + ecc * np.sin(w * pi / 180)) * np.cos(inc * pi / 180) / (Rh * Rsun)
-            return {"M_s": Mh, "R_s": Rh, "u1": u1, "u2": u2, "P_orb": P, "inc": inc, "b": b, "R_p": rp,
-                    "ecc": ecc, "argp": w, "M_EB": z, "R_EB": z.copy(), "fluxratio_EB": z.copy(),
-                    "fluxratio_comp": frc, "lnZ": lnZ}
-        r, fr, P, inc, sm, Rh, u1, u2, ecc, w, frc, sm2, m, Mh = t
-        if twin:
-            P, sm = 2 * P, sm2
-        b = sm * (1 - ecc ** 2) / (1 + ecc * np.sin(w * pi / 180)) * np.cos(inc * pi / 180) / (Rh * Rsun)
-        return {"M_s": Mh, "R_s": Rh, "u1": u1, "u2": u2, "P_orb": P, "inc": inc, "b": b, "R_p": z,
-                "ecc": ecc, "argp": w, "M_EB": m, "R_EB": r, "fluxratio_EB": fr, "fluxratio_comp": frc,
-                "lnZ": lnZ}
+        return dict(zip(RECORD_COLS, _physical(t, bool(self.a.planet), twin) + [lnZ]))
 
 
 # ---------------------------------------------------------------------------------------

@@ -29,8 +29,7 @@ import numpy as np
 from . import _lib
 from . import fused as _fused
 
-RECORD_COLS = ("M_s", "R_s", "u1", "u2", "P_orb", "inc", "b", "R_p", "ecc", "argp", "M_EB",
-               "R_EB", "fluxratio_EB", "fluxratio_comp", "lnZ")
+RECORD_COLS = _fused.RECORD_COLS      # the best draw's 14 physical columns + lnZ (defined beside the library's own order)
 # run_units' table carries the Monte-Carlo moments of every evidence behind RECORD_COLS (NaN where a path gave none):
 # lnM2 = log of the mean squared weight, lnWmax = log of the largest weight's share (include/trx.h,
 # trx_lnz_moments_from_halfchi2).  They never enter a result dict; target._finish reads them from the rows.
@@ -235,10 +234,10 @@ class RowLayout:
     def encode(self, post):
         """a "posterior" dict (or None) as the row's extra columns, one key after the other: the samples, or
         np.quantile(samples, summary_q); NaN where absent"""
+        if self.summary_q is None:
+            return _fused.posterior_to_flat(post, self.post_rows)
         if post is None:
             return np.full(self.extra.stop - self.extra.start, np.nan)
-        if self.summary_q is None:
-            return np.concatenate([np.asarray(post[k], dtype=np.float64) for k in _fused.POSTERIOR_KEYS])
         return np.concatenate([np.quantile(post[c], self.summary_q) for c in _fused.POSTERIOR_PARAMS])
 
     def decode(self, row):
@@ -267,11 +266,7 @@ class RowLayout:
 def _record(res):
     """(res,) or (res, res_twin) -> (n, 15) array of the best row + lnZ of each dict"""
     dicts = res if isinstance(res, tuple) else (res,)
-    out = np.empty((len(dicts), len(RECORD_COLS)))
-    for i, d in enumerate(dicts):
-        for j, c in enumerate(RECORD_COLS):
-            out[i, j] = d[c] if c == "lnZ" else d[c][0]
-    return out
+    return np.array([_fused.record_row(d) for d in dicts], dtype=np.float64)
 
 
 def _as_dicts(rec, layout):
