@@ -160,6 +160,23 @@ int trx_chi2_grid_weighted(const double* flux, const double* inv_var, const doub
                            int n_time, long n, const double* secdepth, double sec_limit,
                            int accumulate, double* out_halfchi2, void* stream);
 
+/* trx_chi2_grid_weighted with a constant baseline offset of the light curve marginalised in closed form (no reference
+ * counterpart).  With d_t = flux[t] - model_grid[r][t], S2 = sum_t inv_var[t] d_t^2 and
+ * S1 = sum_t inv_var[t] d_t, for an offset c ~ N(0, s^2) added to the model,
+ *   out[r] = (accumulate ? out[r] : 0) + 0.5 * (S2 - S1^2 / (sum_w + prior_prec)),
+ *   offset_out[r] = S1 / (sum_w + prior_prec)                      (the posterior mean of c for row r; may be NULL)
+ * sum_w = sum_t inv_var[t], given by the caller (it does not depend on the row); prior_prec = 1 / s^2: 0 is the flat prior
+ * (the offset profiled out), +inf is no offset -- then out is trx_chi2_grid_weighted's, bit for bit.  The factor
+ * (1 + s^2 sum_w)^(-1/2) of the marginal is NOT included: it is the same for every row.  A difference that rounding
+ * drives below 0 is stored as 0; a NaN stays a NaN.  Buffers, the secondary rule, accumulation, the fixed order of
+ * summation (S2 term for term that of trx_chi2_grid_weighted) and repeatability: as trx_chi2_grid_weighted.
+ * NULL flux / inv_var / model_grid / out_halfchi2, n < 0, n_time < 1, sum_w not finite or <= 0, prior_prec < 0 or NaN:
+ * TRX_ERR_ARG, nothing is enqueued; n == 0 launches nothing. */
+int trx_chi2_grid_offset(const double* flux, const double* inv_var, const double* model_grid,
+                         int n_time, long n, const double* secdepth, double sec_limit,
+                         int accumulate, double* out_halfchi2,
+                         double sum_w, double prior_prec, double* offset_out, void* stream);
+
 /* trx_lnl_batch with per-point weights: the light-curve model and its weighted chi^2 in one kernel, the (n x n_time)
  * grid never materialised (no reference counterpart):
  *   out[r] = (accumulate ? out[r] : 0) + 0.5 * sum_t inv_var[t] * (flux[t] - m_r(t))^2,

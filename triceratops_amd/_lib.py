@@ -30,7 +30,7 @@ ERR_NTOTAL = 4
 # every symbol include/trx.h declares (tests check that libtrx.so exports all of them and nothing of trx_debug.h)
 ABI_SYMBOLS = (
     "trx_lnl_batch", "trx_lnl_batch_weighted", "trx_flux_grid", "trx_chi2_grid", "trx_chi2_grid_weighted",
-    "trx_workspace_bytes",
+    "trx_chi2_grid_offset", "trx_workspace_bytes",
     "trx_log_mean_exp", "trx_lnz_scenario", "trx_lnz_from_halfchi2", "trx_lnz_moments_from_halfchi2",
     "trx_posterior_from_halfchi2", "trx_grid_quantiles",
     "trx_lnl_batch_host", "trx_flux_grid_host",
@@ -156,6 +156,9 @@ def _load(path, testing):
     L.trx_chi2_grid.argtypes = [_vp, _vp, c_int, c_long, c_double, _vp, _vp]
     L.trx_chi2_grid_weighted.restype = c_int
     L.trx_chi2_grid_weighted.argtypes = [_vp, _vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp]
+    L.trx_chi2_grid_offset.restype = c_int
+    L.trx_chi2_grid_offset.argtypes = [_vp, _vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, c_double, c_double, _vp,
+                                       _vp]
     L.trx_workspace_bytes.restype = c_size_t
     L.trx_workspace_bytes.argtypes = []
     L.trx_log_mean_exp.restype = c_int
@@ -465,6 +468,35 @@ def chi2_grid_weighted(flux_d, inv_var_d, grid_d, secdepth_d=None, sec_limit=flo
         check(lib().trx_chi2_grid_weighted(flux_d.data_ptr(), inv_var_d.data_ptr(), grid_d.data_ptr(), nt, n,
                                            secdepth_d.data_ptr() if secdepth_d is not None else None,
                                            float(sec_limit), int(accumulate), out.data_ptr(), _stream(grid_d)))
+    return out
+
+
+def chi2_grid_offset(flux_d, inv_var_d, grid_d, sum_w, prior_prec, secdepth_d=None, sec_limit=float("inf"), out=None,
+                     offset_out=None):
+    """chi2_grid_weighted with a constant offset c ~ N(0, 1 / prior_prec) of the light curve marginalised per row
+    (trx_chi2_grid_offset): 0.5 * (S2 - S1^2 / (sum_w + prior_prec)), S1 and S2 the weighted sums of the residuals and of
+    their squares.  sum_w: sum(inv_var), from the host; prior_prec: 0 = flat prior, +inf = no offset (chi2_grid_weighted's
+    bits).  offset_out: an [n] fp64 device tensor that receives S1 / (sum_w + prior_prec), or None.  The other arguments are
+    chi2_grid_weighted's."""
+    require_gpu()
+    n, nt = grid_d.shape
+    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    assert flux_d.numel() == nt and inv_var_d.numel() == nt and flux_d.is_contiguous() and inv_var_d.is_contiguous()
+    assert secdepth_d is None or (secdepth_d.numel() == n and secdepth_d.is_contiguous())
+    assert offset_out is None or (offset_out.shape == (n,) and offset_out.dtype == torch.float64
+                                  and offset_out.is_contiguous())
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
+    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
+    if n == 0:
+        return out                     # (an empty tensor has no address to pass)
+    with torch.cuda.device(grid_d.device):
+        check(lib().trx_chi2_grid_offset(flux_d.data_ptr(), inv_var_d.data_ptr(), grid_d.data_ptr(), nt, n,
+                                         secdepth_d.data_ptr() if secdepth_d is not None else None,
+                                         float(sec_limit), int(accumulate), out.data_ptr(), float(sum_w),
+                                         float(prior_prec), offset_out.data_ptr() if offset_out is not None else None,
+                                         _stream(grid_d)))
     return out
 
 

@@ -5,6 +5,8 @@ Same call surface as the reference's triceratops/_numerics.py:
   _normalize_probabilities(lnZ)     (_numerics.py:54-76)  -> host arithmetic over the 18-75
                                                              scenario evidences
 """
+import math
+
 import numpy as np
 import torch
 
@@ -93,6 +95,24 @@ def _mc_errors(lnZ, lnM2, N, status):
 
 # ---- adaptive importance map of the draw kernel's uniforms (trx_draw_args.warp) ----------------
 WARP_DIMS, WARP_BINS = _lib.WARP_DIMS, _lib.WARP_BINS
+
+
+def offset_halfchi2(resid, w, offset_sigma):
+    """chi^2/2 of a light curve's residuals with a constant offset c ~ N(0, offset_sigma^2) marginalised (DESIGN.md
+    section 14), float64 on the host: the statement of what trx_chi2_grid_offset computes per row.
+        -ln int exp(-0.5 sum_t w_t (r_t - c)^2) N(c; 0, s^2) dc = h + 0.5 ln(1 + s^2 S0),
+        h = 0.5 (S2 - S1^2 / (S0 + 1 / s^2)),   S0 = sum w, S1 = sum w r, S2 = sum w r^2.
+    Returns h -- the factor (1 + s^2 S0)^(-1/2) depends on the dataset only and is dropped -- never below 0.
+    resid: [..., T]; w: [T]; offset_sigma: > 0, inf for the flat prior (1 / s^2 = 0); None: no offset, 0.5 S2."""
+    resid = np.asarray(resid, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    S2 = np.sum(w * resid * resid, axis=-1)
+    if offset_sigma is None:
+        return 0.5 * S2
+    S0 = math.fsum(w.tolist())
+    S1 = np.sum(w * resid, axis=-1)
+    prec = 0.0 if math.isinf(offset_sigma) else 1.0 / (float(offset_sigma) * float(offset_sigma))
+    return np.maximum(0.5 * (S2 - S1 * S1 / (S0 + prec)), 0.0)
 
 
 def warp_identity():

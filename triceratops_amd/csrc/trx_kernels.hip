@@ -1050,6 +1050,35 @@ int trx_chi2_grid_weighted(const double* flux, const double* inv_var, const doub
     return TRX_OK;
 }
 
+int trx_chi2_grid_offset(const double* flux, const double* inv_var, const double* model_grid, int n_time, long n,
+                         const double* secdepth, double sec_limit, int accumulate, double* out_halfchi2, double sum_w,
+                         double prior_prec, double* offset_out, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (!flux || !inv_var || !model_grid || !out_halfchi2) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    if (!(sum_w > 0.0) || sum_w == INFINITY) return fail(TRX_ERR_ARG, "sum_w must be finite and > 0%s", "", 0);
+    if (!(prior_prec >= 0.0)) return fail(TRX_ERR_ARG, "prior_prec must be >= 0 (+inf allowed)%s", "", 0);
+    if (n == 0) return TRX_OK;
+    // (the launch geometry of trx_chi2_grid_weighted: the same bytes, the same LDS)
+    const bool stage = n_time <= kChi2wStageMax;
+    const size_t lds = stage ? 2 * (size_t)((n_time + 1) & ~1) * sizeof(double) : 0;
+    long per_cu = lds ? (long)((160u * 1024u) / lds) : 8;
+    per_cu = per_cu > 8 ? 8 : per_cu;
+    long blocks = (n + 3) / 4;
+    if (blocks > 256L * per_cu) blocks = 256L * per_cu;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (stage)
+        hipLaunchKernelGGL(chi2_grid_offset_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, st, flux, inv_var,
+                           model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, sum_w, prior_prec,
+                           offset_out);
+    else
+        hipLaunchKernelGGL(chi2_grid_offset_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, flux, inv_var,
+                           model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, sum_w, prior_prec,
+                           offset_out);
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
 int trx_grid_quantiles(const double* grid, long n_grid_rows, int n_cols, const long* rows, const double* scale,
                        long n_rows, const double* q, int n_q, double* out, void* stream)
 {

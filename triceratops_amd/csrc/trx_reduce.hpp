@@ -141,6 +141,102 @@ __global__ __launch_bounds__(256) void chi2_grid_weighted_kernel(const double* _
 }
 
 // ---------------------------------------------------------------------------------------
+// chi2_grid_weighted_kernel with a per-dataset baseline offset c ~ N(0, s^2) marginalised in closed form
+// (trx_chi2_grid_offset): with d_t = flux_t - model[r][t], S2 = sum_t w_t d_t^2, S1 = sum_t w_t d_t,
+//   h[r] = 0.5 * (S2 - S1^2 / (sum_w + prior_prec)),   offset_out[r] = S1 / (sum_w + prior_prec),
+// sum_w = sum_t w_t and prior_prec = 1 / s^2 from the host (0: a flat prior; +inf: no offset, chi2_grid_weighted_kernel's
+// bits).  The same shape -- one wavefront per row, two rows in flight, the same loads, the same staging -- and the same
+// order: S2 is formed term for term as chi2w_row_partial forms it, S1 = fma(w, d, acc1) rides in the same trip over the
+// same stamps, then one wave_sum each.  A difference that rounding drives below 0 is stored as 0; a NaN stays a NaN.
+template <bool STAGE>
+__device__ __forceinline__ void chi2o_row_partial(const double* __restrict__ row, const double* f, const double* w,
+                                                  int n_time, int lane, double& s2, double& s1)
+{
+    typedef double dvec2 __attribute__((ext_vector_type(2)));
+    const int nv = n_time >> 1;
+    const bool vec = ((uintptr_t)row & 15) == 0;      // (per row: wave-uniform)
+    double acc = 0.0, acc1 = 0.0;
+    for (int j = lane; j < nv; j += 64) {
+        double m0, m1, f0, f1, w0, w1;
+        if (vec) {
+            const dvec2 m = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(row) + j);
+            m0 = m.x; m1 = m.y;
+        } else {
+            m0 = __builtin_nontemporal_load(row + 2 * j);
+            m1 = __builtin_nontemporal_load(row + 2 * j + 1);
+        }
+        if (STAGE) {
+            const dvec2 fv = reinterpret_cast<const dvec2*>(f)[j], wv = reinterpret_cast<const dvec2*>(w)[j];
+            f0 = fv.x; f1 = fv.y; w0 = wv.x; w1 = wv.y;
+        } else {
+            f0 = f[2 * j]; f1 = f[2 * j + 1]; w0 = w[2 * j]; w1 = w[2 * j + 1];
+        }
+        const double d0 = f0 - m0, d1 = f1 - m1;
+        acc = fma(w0 * d0, d0, acc);
+        acc1 = fma(w0, d0, acc1);
+        acc = fma(w1 * d1, d1, acc);
+        acc1 = fma(w1, d1, acc1);
+    }
+    if ((n_time & 1) && lane == (nv & 63)) {
+        const int t = n_time - 1;
+        const double d = f[t] - __builtin_nontemporal_load(row + t);
+        acc = fma(w[t] * d, d, acc);
+        acc1 = fma(w[t], d, acc1);
+    }
+    s2 = acc;
+    s1 = acc1;
+}
+
+__device__ __forceinline__ void chi2o_store(double s2, double s1, double den, long r, const double* __restrict__ secdepth,
+                                            double sec_limit, int accumulate, double* __restrict__ out,
+                                            double* __restrict__ offset_out)
+{
+    const double tot = s2 - s1 * s1 / den;
+    chi2w_store(tot < 0.0 ? 0.0 : tot, r, secdepth, sec_limit, accumulate, out);      // (0.5 * tot: the clamp commutes)
+    if (offset_out) offset_out[r] = s1 / den;
+}
+
+template <bool STAGE>
+__global__ __launch_bounds__(256) void chi2_grid_offset_kernel(const double* __restrict__ flux,
+                                                               const double* __restrict__ inv_var,
+                                                               const double* __restrict__ grid, int n_time, long n,
+                                                               const double* __restrict__ secdepth, double sec_limit,
+                                                               int accumulate, double* __restrict__ out, double sum_w,
+                                                               double prior_prec, double* __restrict__ offset_out)
+{
+    extern __shared__ __attribute__((aligned(16))) double chi2o_lds[];     // STAGE: [2][n_time rounded up to even]
+    const double* f = flux;
+    const double* w = inv_var;
+    if (STAGE) {
+        const int n_pad = (n_time + 1) & ~1;
+        for (int t = threadIdx.x; t < n_time; t += 256) {
+            chi2o_lds[t] = flux[t];
+            chi2o_lds[n_pad + t] = inv_var[t];
+        }
+        __syncthreads();
+        f = chi2o_lds;
+        w = chi2o_lds + n_pad;
+    }
+    const int lane = threadIdx.x & 63;
+    const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long nwaves = (long)gridDim.x * 4;
+    const double den = sum_w + prior_prec;
+    for (long r = wave0; r < n; r += 2 * nwaves) {
+        const long r2 = r + nwaves;
+        const bool two = r2 < n;
+        double a0, b0, a1 = 0.0, b1 = 0.0;
+        chi2o_row_partial<STAGE>(grid + (size_t)r * n_time, f, w, n_time, lane, a0, b0);
+        if (two) chi2o_row_partial<STAGE>(grid + (size_t)r2 * n_time, f, w, n_time, lane, a1, b1);
+        const double t0 = wave_sum(a0), u0 = wave_sum(b0);
+        const double t1 = wave_sum(a1), u1 = wave_sum(b1);
+        if (lane == 0) {
+            chi2o_store(t0, u0, den, r, secdepth, sec_limit, accumulate, out, offset_out);
+            if (two) chi2o_store(t1, u1, den, r2, secdepth, sec_limit, accumulate, out, offset_out);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // log-mean-exp.  Partial state per thread: running max m (finite or -inf), s = sum exp(x - m),
 // pinf = saw +inf.  NaN and -inf carry zero weight (_numerics.py:48).
 // (struct Lme, lme_merge: trx_device.hpp)

@@ -1,7 +1,8 @@
 """Several light curves with per-point flux errors: the input of target.calc_probs_datasets.
 
 A dataset is one light curve with its own cadence: `time`, `flux`, `flux_err` (one number or one per point),
-`exptime` and `nsamples`.  This module is host side and numpy only: validation, the reference noise sigma_bar and the
+`exptime` and `nsamples`, and optionally `offset_sigma`: the standard deviation of a Gaussian prior on a constant
+baseline offset of that light curve, marginalised per draw (inf: a flat prior).  This module is host side and numpy only: validation, the reference noise sigma_bar and the
 per-star renormalisation.  A `Datasets` object is what the lnZ_* functions receive in place of `time` (with
 flux = None and sigma = sigma_bar); only the device sampling modes evaluate it (fused._Scenario).
 """
@@ -22,13 +23,26 @@ class Dataset(NamedTuple):
     flux_err: np.ndarray      # [T], finite and > 0
     exptime: float
     nsamples: int
+    offset_sigma: float = None    # prior sigma of a constant baseline offset (inf: flat); None: no offset
+
+
+def _offset_sigma(i, value):
+    """a dataset's "offset_sigma": None, or a float > 0 (inf allowed)"""
+    if value is None:
+        return None
+    if isinstance(value, (bool, str, bytes)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError("dataset %d: offset_sigma must be None, a number > 0 or inf (got %r)" % (i, value))
+    value = float(value)
+    if not value > 0:              # (also NaN)
+        raise ValueError("dataset %d: offset_sigma must be None, a number > 0 or inf (got %r)" % (i, value))
+    return value
 
 
 def validate(datasets):
-    """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples]} -> a list of Dataset.  Points
+    """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma]} -> a list of Dataset.  Points
     with a NaN time or flux are dropped together with their error; a scalar flux_err is broadcast.  ValueError for an
-    empty list, too many datasets, mismatched lengths, an error that is not finite or not positive, or a dataset
-    without points."""
+    empty list, too many datasets, mismatched lengths, an error that is not finite or not positive, a dataset
+    without points, or an offset_sigma that is not None, a number > 0 or inf."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -37,7 +51,7 @@ def validate(datasets):
         raise ValueError("at most %d datasets (got %d)" % (MAX_DATASETS, len(datasets)))
     out = []
     for i, d in enumerate(datasets):
-        unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples"}
+        unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma"}
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -64,7 +78,8 @@ def validate(datasets):
         if nsamples < 1:
             raise ValueError("dataset %d: nsamples must be >= 1" % i)
         out.append(Dataset(np.ascontiguousarray(time), np.ascontiguousarray(flux), np.ascontiguousarray(err),
-                           float(d.get("exptime", DEFAULT_EXPTIME)), nsamples))
+                           float(d.get("exptime", DEFAULT_EXPTIME)), nsamples,
+                           _offset_sigma(i, d.get("offset_sigma"))))
     return out
 
 
@@ -96,14 +111,24 @@ class Datasets:
         return len(self.sets)
 
     @property
+    def has_offsets(self):
+        return any(s.offset_sigma is not None for s in self.sets)
+
+    @property
     def size(self):
         """points of all datasets together"""
         return sum(s.time.size for s in self.sets)
 
     def renorm(self, star_fluxratio):
-        """funcs.renorm_flux on every dataset, elementwise on flux and flux_err; sigma_bar is taken afterwards"""
+        """funcs.renorm_flux on every dataset, elementwise on flux and flux_err; sigma_bar is taken afterwards.  A finite
+        offset_sigma is an error in flux units and is divided by the flux ratio as the errors are: s^2 sum(1 / err^2) --
+        and with it the factor of the marginal that the evidence drops -- is the same for every
+        star."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
-            out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err)))
+            off = s.offset_sigma
+            if off is not None and math.isfinite(off):
+                off = off / star_fluxratio
+            out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err), offset_sigma=off))
         return Datasets(out)

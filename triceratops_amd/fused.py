@@ -12,6 +12,7 @@ Di Stefano rate constants (priors.py:601-660) and table pointers -- nothing per 
 """
 import contextlib
 import ctypes
+import math
 import os
 import threading
 
@@ -219,14 +220,19 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # DATASET_EVALUATION = "fused": one trx_lnl_batch_weighted per dataset over all rows of a branch instead -- model and
 # weighted chi^2 in one kernel, no grid, no chunks; the same evidences to rounding (target.calc_probs_datasets sets it
 # for the length of a call).
+# A dataset with an `offset_sigma` (datasets.py) has its constant baseline offset marginalised per draw: its reduction is
+# trx_chi2_grid_offset in place of trx_chi2_grid_weighted (grid evaluation only).  DATASET_OFFSETS = {}: every such call
+# also leaves {work unit: [per branch, an [L] array]} there -- the posterior-mean offset of the branch's best draw per
+# dataset, in the call's (its star's) normalisation, NaN for a dataset without an offset (target.dataset_offsets).
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
+DATASET_OFFSETS = None
 
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -728,12 +734,18 @@ class _Scenario:
 
     def __init__(self, time, flux, sigma, N, parallel, exptime, nsamples, mission, flatpriors):
         self.dev = _lib.compute_device()
-        self.datasets = None
+        self.datasets = self.offsets = None
         if isinstance(time, Datasets):
             # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
             self.datasets = [(_on_device(d.time, self.dev), _on_device(d.flux, self.dev),
                               _on_device(1.0 / (d.flux_err * d.flux_err), self.dev), d.exptime, d.nsamples)
                              for d in time.sets]
+            # (sum_w, 1 / s^2) of every dataset whose baseline offset is marginalised, else None; sum_w is the correctly
+            # rounded sum of the weights the device holds
+            self.offsets = [None if d.offset_sigma is None else
+                            (math.fsum((1.0 / (d.flux_err * d.flux_err)).tolist()),
+                             0.0 if math.isinf(d.offset_sigma) else 1.0 / (d.offset_sigma * d.offset_sigma))
+                            for d in time.sets]
             sigma = time.sigma_ref
             self.time, self.flux = self.datasets[0][0], self.datasets[0][1]
         else:
@@ -987,6 +999,7 @@ class _Scenario:
         moments = MOMENTS and (_lib.moments_wanted() or self.want_moments)
         self.moments = [] if moments else None
         flags = self._flags(is_host)
+        offsets = []       # (DATASET_OFFSETS: per branch the best draw's offsets, still on the device)
         branches = ((MODEL_TP, mask, False),) if a.planet else ((MODEL_EB, mask, False), (MODEL_EB_TWIN, mask2, True))
         for model, m, twin in branches:
             idx = torch.nonzero(m, as_tuple=False).flatten()
@@ -1008,6 +1021,8 @@ class _Scenario:
                 self.moments.append((float(mom[1]), float(mom[2])))
                 _lib.moments_emit(mom[1], mom[2])
             best = self._best(h, idx, n)
+            if DATASET_OFFSETS is not None and self.datasets is not None and any(o is not None for o in self.offsets):
+                offsets.append(self._best_offsets(model, flags, cols, best, twin, nblk) if n else None)
             post = None
             if POSTERIOR_ROWS:
                 # the same selection on this chain's chi^2/2 values (trx_posterior_from_halfchi2; the twin branch draws
@@ -1030,17 +1045,41 @@ class _Scenario:
             res.append(self._table(tabl[:-2].reshape(ncol, -1), float(tabl[-2]), twin))
             if POSTERIOR_ROWS:
                 res[-1]["posterior"] = None if post is None else self._posterior_dict(post.cpu().numpy(), ncol, twin)
+        if offsets:
+            nan = np.full(len(self.datasets), np.nan)
+            DATASET_OFFSETS[getattr(_tls, "unit", None)] = [nan if o is None else o.cpu().numpy() for o in offsets]
         return res[0] if a.planet else (res[0], res[1])
+
+    def _best_offsets(self, model, flags, cols, best, twin, nblk):
+        """[L] device tensor: per dataset the posterior-mean baseline offset S1 / (S0 + 1 / s^2) of the branch's best
+        draw, NaN for a dataset without an offset.  The one row is evaluated again -- trx_flux_grid on one row, then
+        trx_chi2_grid_offset with offset_out -- so nothing of size n x L is kept."""
+        out = torch.full((len(self.datasets),), float("nan"), dtype=F64, device=self.dev)
+        row = cols[:nblk].index_select(1, best[:1]).contiguous()
+        if twin:
+            row[2] *= 2.0
+            row[4] = cols[11].index_select(0, best[:1])
+        flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL
+        for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
+            if self.offsets[l] is None:
+                continue
+            grid, _ = _lib.flux_grid(model, flags, time_d, row, exptime, nsamples, want_secdepth=False)
+            _lib.chi2_grid_offset(flux_d, inv_var_d, grid, *self.offsets[l], offset_out=out[l:l + 1])
+        return out
 
     def _datasets_halfchi2(self, model, flags, block):
         """sum over the datasets of the weighted chi^2/2 of every row of `block` ([n_param][n], the masked draws of one
-        branch): per chunk of rows and per dataset one trx_flux_grid and one accumulating trx_chi2_grid_weighted.  The EB
+        branch): per chunk of rows and per dataset one trx_flux_grid and one accumulating trx_chi2_grid_weighted -- for a
+        dataset whose baseline offset is marginalised (offset_sigma), trx_chi2_grid_offset in its place.  The EB
         branch's secondary-eclipse rule (secdepth >= 1.5 sigma_bar -> +inf) rides in the first dataset's reduction: the
         depth does not depend on the time stamps.  A row's value does not depend on the chunk it falls in.
         DATASET_EVALUATION = "fused": one trx_lnl_batch_weighted per dataset over the whole block instead -- no grid, no
-        chunks; the rule rides in the first dataset's call as its sec_limit."""
+        chunks; the rule rides in the first dataset's call as its sec_limit.  It has no offset form."""
         if DATASET_EVALUATION not in DATASET_EVALUATIONS:
             raise ValueError("fused.DATASET_EVALUATION must be one of %s (got %r)" % (DATASET_EVALUATIONS, DATASET_EVALUATION))
+        if DATASET_EVALUATION == "fused" and any(o is not None for o in self.offsets):
+            raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: the fused kernel "
+                                      "carries no sum of w * residual; use evaluation='grid'")
         n = int(block.shape[1])
         h = torch.zeros(n, dtype=F64, device=self.dev)         # (0 + x = x: every reduction accumulates)
         if n == 0:
@@ -1064,7 +1103,11 @@ class _Scenario:
                     nt = int(time_d.numel())
                     grid, sec = _lib.flux_grid(model, flags, time_d, blk, exptime, nsamples, want_secdepth=eb and l == 0,
                                                out=buf[:(r1 - r0) * nt].view(r1 - r0, nt))
-                    _lib.chi2_grid_weighted(flux_d, inv_var_d, grid, sec, 1.5 * self.sigma, out=h[r0:r1])
+                    if self.offsets[l] is None:
+                        _lib.chi2_grid_weighted(flux_d, inv_var_d, grid, sec, 1.5 * self.sigma, out=h[r0:r1])
+                    else:
+                        _lib.chi2_grid_offset(flux_d, inv_var_d, grid, *self.offsets[l], sec, 1.5 * self.sigma,
+                                              out=h[r0:r1])
         with _stats_lock:
             # (the masked draws once, every (draw, time stamp) cell of every dataset)
             _lib.STATS["rows"] += n

@@ -69,9 +69,10 @@ def prepare(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int
 
 
 def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int = 50,
-                    exptime: float = 0.00139, nsamples: int = 20):
+                    exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
-    {"time", "flux", "flux_err", "exptime", "nsamples"} of one dataset; empty bins are dropped.
+    {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma"} of one dataset; empty bins are dropped.
+    offset_sigma (None: no offset; a number > 0 or inf) is passed through: the prior of the dataset's baseline offset.
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -85,4 +86,4 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     head = yb[:n_sigma]
     scatter = float(np.sqrt(np.mean(count[:n_sigma] * (head - np.mean(head)) ** 2)))
     return {"time": tb, "flux": yb, "flux_err": scatter / np.sqrt(count), "exptime": float(exptime),
-            "nsamples": int(nsamples)}
+            "nsamples": int(nsamples), "offset_sigma": offset_sigma}

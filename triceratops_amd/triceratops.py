@@ -265,7 +265,19 @@ class target:
         dataset: no bounded evaluation, no launch chains -- several times the time of calc_probs.  evaluation="grid"
         (default): the model curves of a chunk of rows are written to a grid, then reduced; "fused": model and weighted
         chi^2 in one kernel per dataset (trx_lnl_batch_weighted), no grid -- the same evidences to rounding (1e-12
-        relative in chi^2/2), the same masked draws and best draws.  Needs set_sampling("device") or "numpy-device"."""
+        relative in chi^2/2), the same masked draws and best draws.  Needs set_sampling("device") or "numpy-device".
+
+        A dataset may carry "offset_sigma": s > 0 or inf.  Its light curve is then taken to be normalised up to a
+        constant offset c ~ N(0, s^2) (inf: a flat prior), in the units of its flux, and c is marginalised in closed
+        form per draw: with r_t = flux_t - model_t, w_t = sigma_t^-2, S0 = sum w, S1 = sum w r, S2 = sum w r^2 the
+        dataset's term of the log-weight is 0.5 (S2 - S1^2 / (S0 + 1 / s^2)) in place of 0.5 S2.  The factor
+        (1 + s^2 S0)^(-1/2) of the marginal is dropped: it depends on the dataset only -- s scales with the errors when a
+        light curve is renormalised to a star -- so it is common to every scenario of every star, and `.probs`, `.FPP`
+        and `.NFPP` are those of the full marginal (`.lnZ` is short of it by that constant).  Grid evaluation only:
+        evaluation="fused" with such a dataset raises NotImplementedError.  `.dataset_offsets` is then an
+        [n_scenarios][n_datasets] array: the posterior-mean offset S1 / (S0 + 1 / s^2) of each scenario's best draw, in
+        the target's normalisation; NaN for a dataset without offset_sigma and for a scenario without a finite lnZ (on
+        several ranks also for the scenarios another rank evaluated).  None when no dataset has an offset."""
         from . import fused
         if evaluation not in fused.DATASET_EVALUATIONS:
             raise ValueError("evaluation must be one of %s (got %r)" % (fused.DATASET_EVALUATIONS, evaluation))
@@ -283,11 +295,23 @@ class target:
         kw = dict(calc_probs_kwargs)
         verbose = kw.pop("verbose", 1)
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
-        with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation):
+        if ds.has_offsets and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: use evaluation='grid'")
+        best_offsets = {} if ds.has_offsets else None
+        with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, DATASET_OFFSETS=best_offsets):
             rows = sharding.run_units(units, verbose=verbose, as_rows=True)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
+        self.dataset_offsets = None
+        if best_offsets is not None:
+            # (a call's offsets are in its star's normalisation: flux' = (flux - (1 - fr)) / fr, so c = fr c')
+            table = np.full((n_scen, len(ds)), np.nan)
+            for k, u in enumerate(sharding.as_units(units)):
+                for i, c in enumerate(best_offsets.get(k, ())):
+                    table[u.first_row + i] = c * share[u.group[1]]
+            table[~np.isfinite(self.lnZ)] = np.nan
+            self.dataset_offsets = table
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
