@@ -177,6 +177,34 @@ int trx_chi2_grid_offset(const double* flux, const double* inv_var, const double
                          int accumulate, double* out_halfchi2,
                          double sum_w, double prior_prec, double* offset_out, void* stream);
 
+/* trx_chi2_grid_weighted with a linear baseline model of the light curve marginalised in closed form (no reference
+ * counterpart).  The data model is model_grid[r][t] + sum_k c_k B_k[t], k < n_terms <= 4, with
+ * independent priors c_k ~ N(0, s_k^2) (s_k = inf: flat).  With d_t = flux[t] - model_grid[r][t], w = inv_var,
+ * D_k = sum_t w_t B_k[t]^2, A~ = D^(-1/2) (B^T W B + diag(1 / s_k^2)) D^(-1/2) (unit diagonal) and M = A~^(-1), all
+ * formed by the caller (they do not depend on the row),
+ *   S2 = sum_t w_t d_t^2,   b_k = sum_t wbasis[k][t] d_t,   wbasis[k][t] = w_t B_k[t] / sqrt(D_k),
+ *   out[r] = (accumulate ? out[r] : 0) + 0.5 * max(S2 - sum_ij M_ij b_i b_j, 0),
+ *   coef_out[r][i] = sum_j M_ij b_j        (scaled: the posterior mean of c_i for row r is coef_out[r][i] / sqrt(D_i))
+ * The factor det(I + diag(s^2) B^T W B)^(-1/2) of the marginal is NOT included: it is the same for every row.  A
+ * difference that rounding drives below 0 is stored as 0; a NaN stays a NaN.  trx_chi2_grid_offset is the case of one
+ * column of ones (in another order of operations: equal to rounding, not bit for bit).
+ * Order of summation: S2 term for term that of trx_chi2_grid_weighted; every b_k as fma(wbasis[k][t], d_t, acc) over the
+ * same stamps on the same lanes in the same order, then the same butterfly; c_i = sum_j fma(M_ij, b_j, .) for ascending
+ * j, the quadratic form sum_i fma(b_i, c_i, .) for ascending i.  An all-zero minv therefore gives
+ * trx_chi2_grid_weighted's bits (and coefficients 0).  Buffers, the secondary rule, accumulation and repeatability: as
+ * trx_chi2_grid_weighted.  minv is read on the HOST before the call returns and passed to the kernel by value.
+ * NULL flux / inv_var / model_grid / out_halfchi2 / wbasis / minv, n < 0, n_time < 1, n_terms outside 1 .. 4, an entry of
+ * minv that is not finite: TRX_ERR_ARG, nothing is enqueued; n == 0 launches nothing.  No synchronisation inside. */
+int trx_chi2_grid_baseline(const double* flux, const double* inv_var, const double* model_grid,
+                           int n_time, long n, const double* secdepth, double sec_limit,
+                           int accumulate, double* out_halfchi2,
+                           const double* wbasis,   /* device [n_terms][n_time]: g_k[t] */
+                           int n_terms,            /* 1 .. 4 */
+                           const double* minv,     /* HOST, n_terms (n_terms + 1) / 2 doubles, packed upper
+                                                      triangle by rows of M; read before the call returns */
+                           double* coef_out,       /* device [n][n_terms] scaled coefficients, or NULL */
+                           void* stream);
+
 /* trx_lnl_batch with per-point weights: the light-curve model and its weighted chi^2 in one kernel, the (n x n_time)
  * grid never materialised (no reference counterpart):
  *   out[r] = (accumulate ? out[r] : 0) + 0.5 * sum_t inv_var[t] * (flux[t] - m_r(t))^2,

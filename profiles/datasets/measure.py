@@ -10,10 +10,16 @@
                                                  evaluation="grid" and evaluation="fused", alternating
   python profiles/datasets/measure.py routes     (c) the two calc_probs_datasets cases alone, both evaluations, three
                                                  passes each: the run the job traces for the kernel times of a pass
+  python profiles/datasets/measure.py rates      (d) chi2_grid_weighted_kernel, chi2_grid_offset_kernel and
+                                                 chi2_grid_baseline_kernel at K = 1 and 4 on the same 200 000 x 2000 grid
+                                                 and at 1e6 x 100: the run the job traces for the kernels' rates
+  python profiles/datasets/measure.py baseline_e2e   (e) two datasets of 50 points, N = 1e6: calc_probs_datasets with and
+                                                 without polynomial_baseline(t, 1) + a flat offset on the second dataset
 
 The job runs `kernels` twice: plainly, and under `rocprofv3 --kernel-trace --stats`, whose kernel trace gives the
 per-launch times quoted (the event timings include the launch gaps of five back-to-back calls); `routes` runs under
-the tracer only, in a run of its own.  --only e2e,routes: those steps of the job alone, APPENDED to the results file.
+the tracer only, in a run of its own, and so does `rates`.  --only e2e,routes: those steps of the job alone, APPENDED to
+the results file.
 """
 import csv
 import glob
@@ -123,6 +129,85 @@ def e2e():
               % (label, g / h, g / np.median(times["calc_probs"]), h / np.median(times["calc_probs"])), flush=True)
 
 
+def rates():
+    """six launches of every reduction of a dataset's term on both shapes (the first is the warm-up); the job's tracer
+    gives the per-launch times, the events here include the launch gaps"""
+    import numpy as np
+    import torch
+    from triceratops_amd import _lib, synth
+    from triceratops_amd.datasets import linear_system
+    rng = np.random.default_rng(synth.SEED)
+    for n, nt in ((N_GRID, N_TIME), (1_000_000, 100)):
+        f = 1.0 + rng.normal(0.0, synth.SIGMA, nt)
+        w = 1.0 / (rng.uniform(0.5, 2.0, nt) * synth.SIGMA) ** 2
+        f_d, w_d = _lib.dev(f), _lib.dev(w)
+        grid = torch.rand((n, nt), dtype=torch.float64, device="cuda")
+        u = np.linspace(-1.0, 1.0, nt)
+        cases = [("chi2_grid_weighted_kernel", lambda: _lib.chi2_grid_weighted(f_d, w_d, grid)),
+                 ("chi2_grid_offset_kernel", lambda: _lib.chi2_grid_offset(f_d, w_d, grid, float(np.sum(w)), 0.0))]
+        for K in (1, 4):
+            system = linear_system(w, np.stack([u ** p for p in range(K)]), np.inf)
+            g_d, minv = _lib.dev(system.g), system.minv
+            cases.append(("chi2_grid_baseline_kernel K = %d" % K,
+                          lambda g_d=g_d, minv=minv: _lib.chi2_grid_baseline(f_d, w_d, grid, g_d, minv)))
+        gb = (n * nt * 8 + n * 8) / 1e9
+        for name, fn in cases:
+            fn()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(5):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            dt = a.elapsed_time(b) * 1e-3 / 5
+            print("events  %-36s %d x %d  %.3f ms  %.2f TB/s  (%.2f GB)" % (name, n, nt, dt * 1e3, gb / dt / 1e3, gb), flush=True)
+        del grid
+
+
+def rates_summary(trace):
+    """per-launch times of the `rates` step from rocprofv3's kernel trace, by kernel and launch shape, each one's first
+    (warm-up) launch left out"""
+    lines = []
+    for f in glob.glob(os.path.join(trace, "**", "*kernel_trace.csv"), recursive=True):
+        groups = {}
+        for row in csv.DictReader(open(f)):
+            name = row["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
+            if "chi2_grid_" in name:
+                groups.setdefault(name, []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
+        for name, ns in groups.items():
+            # (per kernel: six launches on the large grid, then -- the staged instantiations only fit there -- six on 1e6 x 100)
+            for part, (rows, nt) in zip((ns[i:i + 6] for i in range(0, len(ns), 6)),
+                                        ((N_GRID, N_TIME), (1_000_000, 100)) if len(ns) > 6 else
+                                        (((N_GRID, N_TIME),) if "<false" in name else ((1_000_000, 100),))):
+                avg = sum(part[1:]) / max(len(part) - 1, 1)
+                gb = (rows * nt * 8 + rows * 8) / 1e9
+                lines.append("rocprofv3 %-44s %d x %d  %d launches  %.1f us  %.2f TB/s  (%.2f GB)\n"
+                             % (name[:44], rows, nt, len(part) - 1, avg * 1e-3, gb / (avg * 1e-9) / 1e3, gb))
+    return "".join(lines)
+
+
+def baseline_e2e():
+    """wall clock of calc_probs_datasets on two datasets of 50 points with and without a slope column and a flat offset on
+    the second: one warm-up each, then E2E_ROUNDS rounds in which the two take turns"""
+    import numpy as np
+    from triceratops_amd.lightcurve import polynomial_baseline
+    tg, (t, f, s, P), kw, cases = _toi465()
+    two = cases[1][1]
+    with_b = [two[0], dict(two[1], offset_sigma=float("inf"), baseline=polynomial_baseline(two[1]["time"], 1))]
+    runs = [("2 datasets of 50 points", lambda: tg.calc_probs_datasets(two, P, **kw)),
+            ("2 datasets of 50 points, slope + flat offset on the second", lambda: tg.calc_probs_datasets(with_b, P, **kw))]
+    times = {name: [] for name, _ in runs}
+    for name, fn in runs:
+        _timed_pass(fn)
+    for _ in range(E2E_ROUNDS):
+        for name, fn in runs:
+            times[name].append(_timed_pass(fn))
+    for name, _ in runs:
+        v = np.sort(times[name])
+        print("e2e     %-60s median %.4f s  min %.4f s  max %.4f s  (%d rounds)" % (name, np.median(v), v[0], v[-1], v.size), flush=True)
+
+
 ROUTE_PASSES = 3
 
 
@@ -206,9 +291,9 @@ def job(path, only=None):
     want = (lambda step: only is None or step in only)
     with open(path, "a" if only else "w") as out:
         if only:
-            out.write("# profiles/datasets/measure.py --only %s on one MI355X: evaluation=\"grid\" against \"fused\"; wall clock of "
-                      "whole calls (one warm-up, then %d rounds, the cases taking turns), then the kernel trace of a run of "
-                      "its own (rocprofv3 --kernel-trace --stats)\n" % (",".join(only), E2E_ROUNDS))
+            out.write("# profiles/datasets/measure.py --only %s on one MI355X: wall clock of whole calls (one warm-up, then %d "
+                      "rounds, the cases taking turns); kernel times from the trace of a run of its own (rocprofv3 "
+                      "--kernel-trace --stats)\n" % (",".join(only), E2E_ROUNDS))
         else:
             out.write("# profiles/datasets/measure.py on one MI355X; %.2f GB per chi2 launch\n" % GB)
         ok = True
@@ -225,6 +310,14 @@ def job(path, only=None):
                                          "csv", "--", sys.executable, me, "routes"])
             if ok:
                 out.write(routes_summary(trace2))
+        if want("rates"):
+            trace3 = os.path.join(base, "rocprof_datasets_rates")
+            ok = ok and _step(out, 300, ["rocprofv3", "--kernel-trace", "--stats", "-d", trace3, "-o", "rates", "--output-format",
+                                         "csv", "--", sys.executable, me, "rates"])
+            if ok:
+                out.write(rates_summary(trace3))
+        if want("baseline_e2e"):
+            ok = ok and _step(out, 420, [sys.executable, me, "baseline_e2e"])
         out.write("job %s\n" % ("complete" if ok else "ended early"))
     return 0 if ok else 1
 
@@ -236,6 +329,10 @@ if __name__ == "__main__":
         e2e()
     elif sys.argv[1:2] == ["routes"]:
         routes()
+    elif sys.argv[1:2] == ["rates"]:
+        rates()
+    elif sys.argv[1:2] == ["baseline_e2e"]:
+        baseline_e2e()
     else:
         dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(os.path.dirname(os.path.abspath(__file__)), "results.txt")
         only = sys.argv[sys.argv.index("--only") + 1].split(",") if "--only" in sys.argv else None

@@ -30,7 +30,7 @@ ERR_NTOTAL = 4
 # every symbol include/trx.h declares (tests check that libtrx.so exports all of them and nothing of trx_debug.h)
 ABI_SYMBOLS = (
     "trx_lnl_batch", "trx_lnl_batch_weighted", "trx_flux_grid", "trx_chi2_grid", "trx_chi2_grid_weighted",
-    "trx_chi2_grid_offset", "trx_workspace_bytes",
+    "trx_chi2_grid_offset", "trx_chi2_grid_baseline", "trx_workspace_bytes",
     "trx_log_mean_exp", "trx_lnz_scenario", "trx_lnz_from_halfchi2", "trx_lnz_moments_from_halfchi2",
     "trx_posterior_from_halfchi2", "trx_grid_quantiles",
     "trx_lnl_batch_host", "trx_flux_grid_host",
@@ -159,6 +159,9 @@ def _load(path, testing):
     L.trx_chi2_grid_offset.restype = c_int
     L.trx_chi2_grid_offset.argtypes = [_vp, _vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, c_double, c_double, _vp,
                                        _vp]
+    L.trx_chi2_grid_baseline.restype = c_int
+    L.trx_chi2_grid_baseline.argtypes = [_vp, _vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, c_int, _vp, _vp,
+                                         _vp]
     L.trx_workspace_bytes.restype = c_size_t
     L.trx_workspace_bytes.argtypes = []
     L.trx_log_mean_exp.restype = c_int
@@ -497,6 +500,40 @@ def chi2_grid_offset(flux_d, inv_var_d, grid_d, sum_w, prior_prec, secdepth_d=No
                                          float(sec_limit), int(accumulate), out.data_ptr(), float(sum_w),
                                          float(prior_prec), offset_out.data_ptr() if offset_out is not None else None,
                                          _stream(grid_d)))
+    return out
+
+
+def chi2_grid_baseline(flux_d, inv_var_d, grid_d, wbasis_d, minv, secdepth_d=None, sec_limit=float("inf"), out=None,
+                       coef_out=None):
+    """chi2_grid_weighted with a linear baseline sum_k c_k B_k[t] of the light curve marginalised per row
+    (trx_chi2_grid_baseline): 0.5 * max(S2 - sum_ij M_ij b_i b_j, 0), b_k = sum_t wbasis[k][t] (flux[t] - grid[r][t]).
+    wbasis_d: [K][n_time] fp64 device tensor, the columns w_t B_k[t] / sqrt(D_k); minv: the K (K + 1) / 2 entries of the
+    upper triangle of M by rows, on the host (datasets.baseline_system); K = 1 .. 4.  coef_out: an [n][K] fp64 device
+    tensor that receives the scaled posterior-mean coefficients M b, or None.  The other arguments are
+    chi2_grid_weighted's."""
+    require_gpu()
+    n, nt = grid_d.shape
+    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    assert flux_d.numel() == nt and inv_var_d.numel() == nt and flux_d.is_contiguous() and inv_var_d.is_contiguous()
+    assert secdepth_d is None or (secdepth_d.numel() == n and secdepth_d.is_contiguous())
+    assert wbasis_d.dim() == 2 and wbasis_d.shape[1] == nt and wbasis_d.dtype == torch.float64 and wbasis_d.is_contiguous()
+    k = int(wbasis_d.shape[0])
+    minv = np.ascontiguousarray(minv, dtype=np.float64).reshape(-1)
+    assert minv.size == k * (k + 1) // 2, "minv: the packed upper triangle of a %d x %d matrix" % (k, k)
+    assert coef_out is None or (coef_out.shape == (n, k) and coef_out.dtype == torch.float64
+                                and coef_out.is_contiguous())
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
+    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
+    if n == 0:
+        return out                     # (an empty tensor has no address to pass)
+    with torch.cuda.device(grid_d.device):
+        check(lib().trx_chi2_grid_baseline(flux_d.data_ptr(), inv_var_d.data_ptr(), grid_d.data_ptr(), nt, n,
+                                           secdepth_d.data_ptr() if secdepth_d is not None else None,
+                                           float(sec_limit), int(accumulate), out.data_ptr(), wbasis_d.data_ptr(), k,
+                                           minv.ctypes.data, coef_out.data_ptr() if coef_out is not None else None,
+                                           _stream(grid_d)))
     return out
 
 

@@ -115,6 +115,30 @@ def offset_halfchi2(resid, w, offset_sigma):
     return np.maximum(0.5 * (S2 - S1 * S1 / (S0 + prec)), 0.0)
 
 
+def baseline_halfchi2(resid, w, basis, sigmas=None):
+    """chi^2/2 of a light curve's residuals with a linear baseline sum_k c_k B_k[t], c_k ~ N(0, s_k^2) independent,
+    marginalised, float64 on the host: the statement of what trx_chi2_grid_baseline computes per row.
+        -ln int exp(-0.5 sum_t w_t (r_t - sum_k c_k B_k[t])^2) prod_k N(c_k; 0, s_k^2) dc
+            = h + 0.5 ln det(I + diag(s^2) B^T W B),
+        h = 0.5 (S2 - b^T A^-1 b),   S2 = sum w r^2,   b_k = sum w B_k r,   A = B^T W B + diag(1 / s_k^2),
+    evaluated in the scaled form of datasets.linear_system (D_k = sum w B_k^2, A~ = D^(-1/2) A D^(-1/2), M = A~^-1,
+    b~_k = b_k / sqrt(D_k)): h = 0.5 (S2 - b~^T M b~).  Returns h -- the determinant depends on the dataset only and is
+    dropped -- never below 0.  resid: [..., T]; w: [T]; basis: [K][T] or [T], None: no baseline, 0.5 S2; sigmas: a number
+    or [K], each > 0 or inf (flat: 1 / s^2 = 0), None: all flat.  ValueError for a zero column or a singular system."""
+    from .datasets import linear_system
+    resid = np.asarray(resid, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    S2 = np.sum(w * resid * resid, axis=-1)
+    if basis is None:
+        return 0.5 * S2
+    system = linear_system(w, basis, np.inf if sigmas is None else sigmas)
+    if system.M is None:
+        raise ValueError("the baseline system is singular (smallest eigenvalue %g)" % system.lambda_min)
+    b = resid @ system.g.T
+    q = np.einsum("...i,ij,...j->...", b, system.M, b)
+    return np.maximum(0.5 * (S2 - q), 0.0)
+
+
 def warp_identity():
     """the identity grid: [WARP_DIMS][WARP_BINS + 1] edges b / 64 (the map returns its input, ln J = 0, exactly)"""
     return np.tile(np.arange(WARP_BINS + 1) / WARP_BINS, (WARP_DIMS, 1))

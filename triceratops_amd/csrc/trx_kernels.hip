@@ -1079,6 +1079,33 @@ int trx_chi2_grid_offset(const double* flux, const double* inv_var, const double
     return TRX_OK;
 }
 
+int trx_chi2_grid_baseline(const double* flux, const double* inv_var, const double* model_grid, int n_time, long n,
+                           const double* secdepth, double sec_limit, int accumulate, double* out_halfchi2,
+                           const double* wbasis, int n_terms, const double* minv, double* coef_out, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (!flux || !inv_var || !model_grid || !out_halfchi2 || !wbasis || !minv)
+        return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    if (n_terms < 1 || n_terms > kChi2bMaxTerms)
+        return fail(TRX_ERR_ARG, "n_terms must lie in [1, 4]%s (got %ld)", "", (long)n_terms);
+    Chi2bM M{};
+    for (int i = 0; i < n_terms * (n_terms + 1) / 2; ++i) {
+        if (!(minv[i] - minv[i] == 0.0))                    // (NaN or +-inf)
+            return fail(TRX_ERR_ARG, "minv must be finite%s (entry %ld)", "", (long)i);
+        M.m[i] = minv[i];
+    }
+    if (n == 0) return TRX_OK;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (n_terms) {
+    case 1: chi2b_launch<1>(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, wbasis, M, coef_out, st); break;
+    case 2: chi2b_launch<2>(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, wbasis, M, coef_out, st); break;
+    case 3: chi2b_launch<3>(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, wbasis, M, coef_out, st); break;
+    default: chi2b_launch<4>(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, wbasis, M, coef_out, st); break;
+    }
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
 int trx_grid_quantiles(const double* grid, long n_grid_rows, int n_cols, const long* rows, const double* scale,
                        long n_rows, const double* q, int n_q, double* out, void* stream)
 {

@@ -237,6 +237,188 @@ __global__ __launch_bounds__(256) void chi2_grid_offset_kernel(const double* __r
 }
 
 // ---------------------------------------------------------------------------------------
+// chi2_grid_weighted_kernel with a linear baseline model sum_k c_k B_k[t], c_k ~ N(0, s_k^2), K = 1 .. 4 terms,
+// marginalised in closed form (trx_chi2_grid_baseline): with d_t = flux_t - model[r][t],
+// S2 = sum_t w_t d_t^2 and the scaled sums b_k = sum_t g_k[t] d_t, g_k[t] = w_t B_k[t] / sqrt(D_k) from the host,
+//   h[r] = 0.5 * max(S2 - sum_ij M_ij b_i b_j, 0),   coef_out[r][i] = sum_j M_ij b_j,
+// M the inverse of the unit-diagonal system matrix, packed upper triangle by rows, by value in the kernel arguments (it
+// does not depend on the row).  The same shape as the two kernels above -- one wavefront per row, two rows in flight, the
+// same loads -- and the same order: S2 term for term as chi2w_row_partial forms it, b_k = fma(g_k, d, acc_k) in the same
+// trip over the same stamps, then one wave_sum each.  M = 0 is chi2_grid_weighted_kernel, bit for bit.  flux, inv_var
+// and the K columns are staged in LDS while they fit the 32 KB of kChi2wStageMax: chi2b_stage_max(K) stamps.
+constexpr int kChi2bMaxTerms = 4;
+
+constexpr int chi2b_stage_max(int k) { return ((2 * kChi2wStageMax) / (2 + k)) & ~1; }     // 1364, 1024, 818, 682
+
+struct Chi2bM {
+    double m[kChi2bMaxTerms * (kChi2bMaxTerms + 1) / 2];       // M_ij, i <= j, at chi2b_at<K>(i, j)
+};
+
+template <int K>
+__device__ __forceinline__ constexpr int chi2b_at(int i, int j)
+{
+    return i <= j ? i * K - i * (i - 1) / 2 + (j - i) : j * K - j * (j - 1) / 2 + (i - j);
+}
+
+// (b[]: indexed by unrolled loops over the template argument only, so it lives in registers)
+template <int K>
+struct Chi2bSums {
+    double s2;
+    double b[K];
+};
+
+template <bool STAGE, int K>
+__device__ __forceinline__ void chi2b_row_partial(const double* __restrict__ row, const double* f, const double* w,
+                                                  const double* g, int g_stride, int n_time, int lane, Chi2bSums<K>& s)
+{
+    typedef double dvec2 __attribute__((ext_vector_type(2)));
+    const int nv = n_time >> 1;
+    const bool vec = ((uintptr_t)row & 15) == 0;      // (per row: wave-uniform)
+    double acc = 0.0;
+    double accb[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) accb[k] = 0.0;
+    for (int j = lane; j < nv; j += 64) {
+        double m0, m1, f0, f1, w0, w1;
+        if (vec) {
+            const dvec2 m = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(row) + j);
+            m0 = m.x; m1 = m.y;
+        } else {
+            m0 = __builtin_nontemporal_load(row + 2 * j);
+            m1 = __builtin_nontemporal_load(row + 2 * j + 1);
+        }
+        if (STAGE) {
+            const dvec2 fv = reinterpret_cast<const dvec2*>(f)[j], wv = reinterpret_cast<const dvec2*>(w)[j];
+            f0 = fv.x; f1 = fv.y; w0 = wv.x; w1 = wv.y;
+        } else {
+            f0 = f[2 * j]; f1 = f[2 * j + 1]; w0 = w[2 * j]; w1 = w[2 * j + 1];
+        }
+        const double d0 = f0 - m0, d1 = f1 - m1;
+        acc = fma(w0 * d0, d0, acc);
+        acc = fma(w1 * d1, d1, acc);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            double g0, g1;
+            if (STAGE) {
+                const dvec2 gv = reinterpret_cast<const dvec2*>(g + (size_t)k * g_stride)[j];
+                g0 = gv.x; g1 = gv.y;
+            } else {
+                g0 = g[(size_t)k * g_stride + 2 * j]; g1 = g[(size_t)k * g_stride + 2 * j + 1];
+            }
+            accb[k] = fma(g0, d0, accb[k]);
+            accb[k] = fma(g1, d1, accb[k]);
+        }
+    }
+    if ((n_time & 1) && lane == (nv & 63)) {
+        const int t = n_time - 1;
+        const double d = f[t] - __builtin_nontemporal_load(row + t);
+        acc = fma(w[t] * d, d, acc);
+#pragma unroll
+        for (int k = 0; k < K; ++k) accb[k] = fma(g[(size_t)k * g_stride + t], d, accb[k]);
+    }
+    s.s2 = acc;
+#pragma unroll
+    for (int k = 0; k < K; ++k) s.b[k] = accb[k];
+}
+
+template <int K>
+__device__ __forceinline__ void chi2b_wave_sum(Chi2bSums<K>& s)
+{
+    s.s2 = wave_sum(s.s2);
+#pragma unroll
+    for (int k = 0; k < K; ++k) s.b[k] = wave_sum(s.b[k]);
+}
+
+template <int K>
+__device__ __forceinline__ void chi2b_store(const Chi2bSums<K>& s, const Chi2bM& M, long r,
+                                            const double* __restrict__ secdepth, double sec_limit, int accumulate,
+                                            double* __restrict__ out, double* __restrict__ coef_out)
+{
+    // c_i = sum_j M_ij b_j, then q = sum_i b_i c_i: the quadratic form and the coefficients from the same products
+    double q = 0.0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        double c = 0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) c = fma(M.m[chi2b_at<K>(i, j)], s.b[j], c);
+        q = fma(s.b[i], c, q);
+        if (coef_out) coef_out[r * K + i] = c;
+    }
+    const double tot = s.s2 - q;
+    chi2w_store(tot < 0.0 ? 0.0 : tot, r, secdepth, sec_limit, accumulate, out);      // (a NaN stays a NaN)
+}
+
+template <bool STAGE, int K>
+__global__ __launch_bounds__(256) void chi2_grid_baseline_kernel(const double* __restrict__ flux,
+                                                                 const double* __restrict__ inv_var,
+                                                                 const double* __restrict__ grid, int n_time, long n,
+                                                                 const double* __restrict__ secdepth, double sec_limit,
+                                                                 int accumulate, double* __restrict__ out,
+                                                                 const double* __restrict__ wbasis, Chi2bM M,
+                                                                 double* __restrict__ coef_out)
+{
+    extern __shared__ __attribute__((aligned(16))) double chi2b_lds[];     // STAGE: [2 + K][n_time rounded up to even]
+    const double* f = flux;
+    const double* w = inv_var;
+    const double* g = wbasis;
+    int g_stride = n_time;
+    if (STAGE) {
+        const int n_pad = (n_time + 1) & ~1;
+        for (int t = threadIdx.x; t < n_time; t += 256) {
+            chi2b_lds[t] = flux[t];
+            chi2b_lds[n_pad + t] = inv_var[t];
+#pragma unroll
+            for (int k = 0; k < K; ++k) chi2b_lds[(2 + k) * n_pad + t] = wbasis[(size_t)k * n_time + t];
+        }
+        __syncthreads();
+        f = chi2b_lds;
+        w = chi2b_lds + n_pad;
+        g = chi2b_lds + 2 * n_pad;
+        g_stride = n_pad;
+    }
+    const int lane = threadIdx.x & 63;
+    const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long nwaves = (long)gridDim.x * 4;
+    for (long r = wave0; r < n; r += 2 * nwaves) {
+        const long r2 = r + nwaves;
+        const bool two = r2 < n;
+        Chi2bSums<K> s0, s1;
+        s1.s2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) s1.b[k] = 0.0;
+        chi2b_row_partial<STAGE, K>(grid + (size_t)r * n_time, f, w, g, g_stride, n_time, lane, s0);
+        if (two) chi2b_row_partial<STAGE, K>(grid + (size_t)r2 * n_time, f, w, g, g_stride, n_time, lane, s1);
+        chi2b_wave_sum<K>(s0);
+        chi2b_wave_sum<K>(s1);
+        if (lane == 0) {
+            chi2b_store<K>(s0, M, r, secdepth, sec_limit, accumulate, out, coef_out);
+            if (two) chi2b_store<K>(s1, M, r2, secdepth, sec_limit, accumulate, out, coef_out);
+        }
+    }
+}
+
+// (host) one launch: STAGE by the stamps, the grid by what stays resident
+template <int K>
+static void chi2b_launch(const double* flux, const double* inv_var, const double* model_grid, int n_time, long n,
+                         const double* secdepth, double sec_limit, int accumulate, double* out, const double* wbasis,
+                         const Chi2bM& M, double* coef_out, hipStream_t st)
+{
+    // (the sizing rule of trx_chi2_grid_weighted, with 2 + K staged vectors in place of 2)
+    const bool stage = n_time <= chi2b_stage_max(K);
+    const size_t lds = stage ? (2 + K) * (size_t)((n_time + 1) & ~1) * sizeof(double) : 0;
+    long per_cu = lds ? (long)((160u * 1024u) / lds) : 8;
+    per_cu = per_cu > 8 ? 8 : per_cu;
+    long blocks = (n + 3) / 4;
+    if (blocks > 256L * per_cu) blocks = 256L * per_cu;
+    if (stage)
+        hipLaunchKernelGGL((chi2_grid_baseline_kernel<true, K>), dim3((unsigned)blocks), dim3(256), lds, st, flux,
+                           inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out, wbasis, M, coef_out);
+    else
+        hipLaunchKernelGGL((chi2_grid_baseline_kernel<false, K>), dim3((unsigned)blocks), dim3(256), 0, st, flux,
+                           inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out, wbasis, M, coef_out);
+}
+
+// ---------------------------------------------------------------------------------------
 // log-mean-exp.  Partial state per thread: running max m (finite or -inf), s = sum exp(x - m),
 // pinf = saw +inf.  NaN and -inf carry zero weight (_numerics.py:48).
 // (struct Lme, lme_merge: trx_device.hpp)

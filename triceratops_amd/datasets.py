@@ -2,7 +2,9 @@
 
 A dataset is one light curve with its own cadence: `time`, `flux`, `flux_err` (one number or one per point),
 `exptime` and `nsamples`, and optionally `offset_sigma`: the standard deviation of a Gaussian prior on a constant
-baseline offset of that light curve, marginalised per draw (inf: a flat prior).  This module is host side and numpy only: validation, the reference noise sigma_bar and the
+baseline offset of that light curve, marginalised per draw (inf: a flat prior), and `baseline` / `baseline_sigma`: up to
+MAX_BASELINE_TERMS columns B_k[t] of a linear baseline model sum_k c_k B_k[t] with priors c_k ~ N(0, s_k^2), marginalised
+the same way (baseline_system).  This module is host side and numpy only: validation, the reference noise sigma_bar and the
 per-star renormalisation.  A `Datasets` object is what the lnZ_* functions receive in place of `time` (with
 flux = None and sigma = sigma_bar); only the device sampling modes evaluate it (fused._Scenario).
 """
@@ -14,6 +16,8 @@ import numpy as np
 from .funcs import renorm_flux
 
 MAX_DATASETS = 16
+MAX_BASELINE_TERMS = 4          # terms of a dataset's linear baseline model, the offset_sigma term included
+MIN_BASELINE_EIGENVALUE = 1e-6  # of the scaled system matrix: below it the columns count as collinear
 DEFAULT_EXPTIME, DEFAULT_NSAMPLES = 0.00139, 20
 
 
@@ -24,6 +28,69 @@ class Dataset(NamedTuple):
     exptime: float
     nsamples: int
     offset_sigma: float = None    # prior sigma of a constant baseline offset (inf: flat); None: no offset
+    baseline: np.ndarray = None         # [K_b][T] columns of the linear baseline model, finite; None: none
+    baseline_sigma: np.ndarray = None   # [K_b] prior sigmas of their coefficients (inf: flat); None without baseline
+
+
+class BaselineSystem(NamedTuple):
+    """the linear system of a dataset's marginalised baseline terms (baseline_system)"""
+    terms: tuple              # per term ("offset" | "baseline", index among the dataset's columns or None, prior sigma)
+    D: np.ndarray             # [K] D_k = sum_t w_t B_k[t]^2
+    A: np.ndarray             # [K][K] A~ = D^(-1/2) (B^T W B + diag(1 / s_k^2)) D^(-1/2)
+    M: np.ndarray             # [K][K] A~^(-1), symmetric
+    g: np.ndarray             # [K][T] g_k[t] = w_t B_k[t] / sqrt(D_k)
+    lambda_min: float         # smallest eigenvalue of A~
+
+    @property
+    def minv(self):
+        """M's upper triangle packed by rows: the `minv` of trx_chi2_grid_baseline"""
+        return np.ascontiguousarray(self.M[np.triu_indices(self.M.shape[0])])
+
+
+def linear_system(w, columns, sigmas):
+    """BaselineSystem of the columns B [K][T] with prior sigmas [K] (inf: flat) under the weights w [T]; `terms` is left
+    empty.  D_k by math.fsum; the off-diagonal of A~ in float64, its diagonal 1 + 1 / (s_k^2 D_k).  ValueError for a column
+    whose D_k is 0 (or not finite); a singular A~ gives lambda_min <= 0 and M = None."""
+    w = np.asarray(w, dtype=np.float64)
+    B = np.atleast_2d(np.asarray(columns, dtype=np.float64))
+    s = np.broadcast_to(np.asarray(sigmas, dtype=np.float64), (B.shape[0],))
+    D = np.array([math.fsum((w * b * b).tolist()) for b in B])
+    if not np.all(np.isfinite(D) & (D > 0)):
+        raise ValueError("column %d is zero at every point" % int(np.flatnonzero(~(np.isfinite(D) & (D > 0)))[0]))
+    g = (w * B) / np.sqrt(D)[:, None]
+    A = (g * (1.0 / w)) @ g.T
+    A = 0.5 * (A + A.T)
+    with np.errstate(divide="ignore"):
+        A[np.diag_indices_from(A)] = 1.0 + 1.0 / (s * s * D)          # (1 / inf^2 = 0: the flat prior)
+    lam = float(np.linalg.eigvalsh(A)[0])
+    M = None
+    if lam > 0:
+        try:
+            M = np.linalg.inv(A)
+            M = 0.5 * (M + M.T)
+        except np.linalg.LinAlgError:
+            M = None
+    return BaselineSystem((), D, A, M, np.ascontiguousarray(g), lam)
+
+
+def baseline_system(dataset):
+    """The BaselineSystem of a Dataset's marginalised terms, or None when it has none: the ones column with offset_sigma
+    first when offset_sigma is set, then the `baseline` columns with their baseline_sigma -- the one place that fixes the
+    order of the terms, for the device path (fused._Scenario) and for the numpy statement (_numerics.baseline_halfchi2)."""
+    cols, sig, terms = [], [], []
+    if dataset.offset_sigma is not None:
+        cols.append(np.ones(dataset.time.size))
+        sig.append(dataset.offset_sigma)
+        terms.append(("offset", None, float(dataset.offset_sigma)))
+    if dataset.baseline is not None:
+        for k, (b, s) in enumerate(zip(dataset.baseline, dataset.baseline_sigma)):
+            cols.append(b)
+            sig.append(s)
+            terms.append(("baseline", k, float(s)))
+    if not cols:
+        return None
+    w = 1.0 / (dataset.flux_err * dataset.flux_err)
+    return linear_system(w, np.stack(cols), np.array(sig, dtype=np.float64))._replace(terms=tuple(terms))
 
 
 def _offset_sigma(i, value):
@@ -38,11 +105,66 @@ def _offset_sigma(i, value):
     return value
 
 
+def _baseline(i, value, sigma, n_given, keep):
+    """a dataset's "baseline" and "baseline_sigma" -> ([K_b][T kept] columns, [K_b] sigmas), or (None, None)"""
+    if value is None:
+        if sigma is not None:
+            raise ValueError("dataset %d: baseline_sigma without baseline" % i)
+        return None, None
+    try:
+        B = np.asarray(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("dataset %d: baseline must be an array [K][len(time)] or [len(time)]" % i) from None
+    if B.ndim == 1:
+        B = B[None, :]
+    if B.ndim != 2 or B.shape[0] < 1 or B.shape[1] != n_given:
+        raise ValueError("dataset %d: baseline must be an array [K][len(time)] or [len(time)], len(time) = %d (got shape %s)"
+                         % (i, n_given, np.shape(value)))
+    B = B[:, keep]
+    if not np.all(np.isfinite(B)):
+        raise ValueError("dataset %d: every baseline entry of a kept point must be finite" % i)
+    msg = "dataset %d: baseline_sigma must be a number or %d numbers, each > 0 or inf (got %r)" % (i, B.shape[0], sigma)
+    if sigma is None:
+        s = np.full(B.shape[0], np.inf)
+    else:
+        if isinstance(sigma, (bool, str, bytes)):
+            raise ValueError(msg)
+        try:
+            s = np.asarray(sigma, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(msg) from None
+        if s.ndim == 0:
+            s = np.full(B.shape[0], float(s))
+        if s.shape != (B.shape[0],) or not np.all(s > 0):            # (also NaN)
+            raise ValueError(msg)
+    return np.ascontiguousarray(B), np.ascontiguousarray(s)
+
+
+def _check_baseline(i, dataset):
+    """the limits of a dataset's baseline terms: their number and the conditioning of the scaled system"""
+    n_terms = (dataset.offset_sigma is not None) + (0 if dataset.baseline is None else dataset.baseline.shape[0])
+    if dataset.baseline is None:
+        return
+    if n_terms > MAX_BASELINE_TERMS:
+        raise ValueError("dataset %d: at most %d baseline terms, offset_sigma included (got %d)"
+                         % (i, MAX_BASELINE_TERMS, n_terms))
+    try:
+        system = baseline_system(dataset)
+    except ValueError as e:
+        raise ValueError("dataset %d: baseline term %s" % (i, e)) from None
+    if not system.lambda_min >= MIN_BASELINE_EIGENVALUE:
+        raise ValueError("dataset %d: the baseline terms are collinear (smallest eigenvalue of the scaled system %.3g < %g):"
+                         " drop a column, or a constant column next to offset_sigma, or give finite priors"
+                         % (i, system.lambda_min, MIN_BASELINE_EIGENVALUE))
+
+
 def validate(datasets):
-    """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma]} -> a list of Dataset.  Points
-    with a NaN time or flux are dropped together with their error; a scalar flux_err is broadcast.  ValueError for an
-    empty list, too many datasets, mismatched lengths, an error that is not finite or not positive, a dataset
-    without points, or an offset_sigma that is not None, a number > 0 or inf."""
+    """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
+    baseline_sigma]} -> a list of Dataset.  Points with a NaN time or flux are dropped together with their error and their
+    baseline entries; a scalar flux_err is broadcast.  ValueError for an empty list, too many datasets, mismatched
+    lengths, an error that is not finite or not positive, a dataset without points, an offset_sigma that is not None, a
+    number > 0 or inf, a baseline that is not [K][len(time)] and finite at the kept points, a baseline_sigma that is not
+    > 0 or inf per column (or has no baseline), more than MAX_BASELINE_TERMS terms, or collinear terms."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -51,7 +173,7 @@ def validate(datasets):
         raise ValueError("at most %d datasets (got %d)" % (MAX_DATASETS, len(datasets)))
     out = []
     for i, d in enumerate(datasets):
-        unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma"}
+        unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"}
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -69,6 +191,7 @@ def validate(datasets):
             raise ValueError("dataset %d: flux_err must be a number or an array of len(time) = %d (got shape %s)"
                              % (i, time.size, err.shape))
         keep = ~np.isnan(time) & ~np.isnan(flux)
+        n_given = time.size
         time, flux, err = time[keep], flux[keep], err[keep]
         if time.size == 0:
             raise ValueError("dataset %d has no points left after dropping NaN" % i)
@@ -77,9 +200,11 @@ def validate(datasets):
         nsamples = int(d.get("nsamples", DEFAULT_NSAMPLES))
         if nsamples < 1:
             raise ValueError("dataset %d: nsamples must be >= 1" % i)
+        baseline, baseline_sigma = _baseline(i, d.get("baseline"), d.get("baseline_sigma"), n_given, keep)
         out.append(Dataset(np.ascontiguousarray(time), np.ascontiguousarray(flux), np.ascontiguousarray(err),
                            float(d.get("exptime", DEFAULT_EXPTIME)), nsamples,
-                           _offset_sigma(i, d.get("offset_sigma"))))
+                           _offset_sigma(i, d.get("offset_sigma")), baseline, baseline_sigma))
+        _check_baseline(i, out[-1])
     return out
 
 
@@ -115,6 +240,10 @@ class Datasets:
         return any(s.offset_sigma is not None for s in self.sets)
 
     @property
+    def has_baselines(self):
+        return any(s.baseline is not None for s in self.sets)
+
+    @property
     def size(self):
         """points of all datasets together"""
         return sum(s.time.size for s in self.sets)
@@ -123,12 +252,17 @@ class Datasets:
         """funcs.renorm_flux on every dataset, elementwise on flux and flux_err; sigma_bar is taken afterwards.  A finite
         offset_sigma is an error in flux units and is divided by the flux ratio as the errors are: s^2 sum(1 / err^2) --
         and with it the factor of the marginal that the evidence drops -- is the same for every
-        star."""
+        star.  So is every finite baseline_sigma (flux units per unit of its column); the columns are left alone: the scaled
+        system matrix of baseline_system is then the same for every star."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
             off = s.offset_sigma
             if off is not None and math.isfinite(off):
                 off = off / star_fluxratio
-            out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err), offset_sigma=off))
+            bsig = s.baseline_sigma
+            if bsig is not None:
+                bsig = np.where(np.isfinite(bsig), bsig / star_fluxratio, bsig)
+            out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err), offset_sigma=off,
+                                  baseline_sigma=bsig))
         return Datasets(out)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib, funcs
-from .datasets import Datasets
+from .datasets import Datasets, baseline_system
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
@@ -224,15 +224,20 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # trx_chi2_grid_offset in place of trx_chi2_grid_weighted (grid evaluation only).  DATASET_OFFSETS = {}: every such call
 # also leaves {work unit: [per branch, an [L] array]} there -- the posterior-mean offset of the branch's best draw per
 # dataset, in the call's (its star's) normalisation, NaN for a dataset without an offset (target.dataset_offsets).
+# A dataset with a `baseline` has the coefficients of its baseline columns -- and its offset, if it has offset_sigma, as
+# term 0 of the same system (datasets.baseline_system) -- marginalised per draw by trx_chi2_grid_baseline.
+# DATASET_BASELINES = {}: every such call leaves {work unit: [per branch, a list per dataset: None or the [K_b] posterior-
+# mean coefficients of the branch's best draw]} there, in the call's normalisation (target.dataset_baselines).
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
 DATASET_OFFSETS = None
+DATASET_BASELINES = None
 
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -734,7 +739,7 @@ class _Scenario:
 
     def __init__(self, time, flux, sigma, N, parallel, exptime, nsamples, mission, flatpriors):
         self.dev = _lib.compute_device()
-        self.datasets = self.offsets = None
+        self.datasets = self.offsets = self.baselines = None
         if isinstance(time, Datasets):
             # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
             self.datasets = [(_on_device(d.time, self.dev), _on_device(d.flux, self.dev),
@@ -746,6 +751,15 @@ class _Scenario:
                             (math.fsum((1.0 / (d.flux_err * d.flux_err)).tolist()),
                              0.0 if math.isinf(d.offset_sigma) else 1.0 / (d.offset_sigma * d.offset_sigma))
                             for d in time.sets]
+            # a dataset with baseline columns: (g [K][T] on the device, M's packed upper triangle, sqrt(D), whether term 0
+            # is the offset) of datasets.baseline_system; its offset, if any, is term 0 of that system
+            self.baselines = [None] * len(time.sets)
+            for l, d in enumerate(time.sets):
+                if d.baseline is not None:
+                    system = baseline_system(d)
+                    self.baselines[l] = (_on_device(system.g, self.dev), system.minv, np.sqrt(system.D),
+                                         d.offset_sigma is not None)
+                    self.offsets[l] = None
             sigma = time.sigma_ref
             self.time, self.flux = self.datasets[0][0], self.datasets[0][1]
         else:
@@ -1000,6 +1014,7 @@ class _Scenario:
         self.moments = [] if moments else None
         flags = self._flags(is_host)
         offsets = []       # (DATASET_OFFSETS: per branch the best draw's offsets, still on the device)
+        coefs = []         # (DATASET_BASELINES: per branch and dataset the best draw's scaled coefficients, likewise)
         branches = ((MODEL_TP, mask, False),) if a.planet else ((MODEL_EB, mask, False), (MODEL_EB_TWIN, mask2, True))
         for model, m, twin in branches:
             idx = torch.nonzero(m, as_tuple=False).flatten()
@@ -1021,8 +1036,11 @@ class _Scenario:
                 self.moments.append((float(mom[1]), float(mom[2])))
                 _lib.moments_emit(mom[1], mom[2])
             best = self._best(h, idx, n)
-            if DATASET_OFFSETS is not None and self.datasets is not None and any(o is not None for o in self.offsets):
-                offsets.append(self._best_offsets(model, flags, cols, best, twin, nblk) if n else None)
+            if self.datasets is not None and ((DATASET_OFFSETS is not None and any(o is not None for o in self.offsets))
+                                              or self._any_baseline()):
+                o, c = self._best_offsets(model, flags, cols, best, twin, nblk) if n else (None, None)
+                offsets.append(o)
+                coefs.append(c)
             post = None
             if POSTERIOR_ROWS:
                 # the same selection on this chain's chi^2/2 values (trx_posterior_from_halfchi2; the twin branch draws
@@ -1046,31 +1064,68 @@ class _Scenario:
             if POSTERIOR_ROWS:
                 res[-1]["posterior"] = None if post is None else self._posterior_dict(post.cpu().numpy(), ncol, twin)
         if offsets:
-            nan = np.full(len(self.datasets), np.nan)
-            DATASET_OFFSETS[getattr(_tls, "unit", None)] = [nan if o is None else o.cpu().numpy() for o in offsets]
+            self._leave_best_terms(offsets, coefs)
         return res[0] if a.planet else (res[0], res[1])
 
+    def _any_baseline(self):
+        """whether a dataset's baseline terms are wanted back (DATASET_BASELINES or, for their term 0, DATASET_OFFSETS)"""
+        return ((DATASET_BASELINES is not None or DATASET_OFFSETS is not None) and self.baselines is not None
+                and any(b is not None for b in self.baselines))
+
+    def _leave_best_terms(self, offsets, coefs):
+        """the branches' best-draw offsets and baseline coefficients, from the device to DATASET_OFFSETS / DATASET_BASELINES
+        under this thread's work unit, in the call's normalisation: c_k = c~_k / sqrt(D_k)"""
+        L = len(self.datasets)
+        unit = getattr(_tls, "unit", None)
+        offs, base = [], []
+        for o, c in zip(offsets, coefs):
+            o = np.full(L, np.nan) if o is None else o.cpu().numpy()
+            per = [None] * L
+            for l, b in enumerate(self.baselines):
+                if b is None:
+                    continue
+                _, _, sqrt_d, has_offset = b
+                ck = np.full(sqrt_d.size, np.nan) if c is None else c[l].cpu().numpy().reshape(-1) / sqrt_d
+                if has_offset:
+                    o[l] = ck[0]
+                per[l] = ck[1:] if has_offset else ck
+            offs.append(o)
+            base.append(per)
+        if DATASET_OFFSETS is not None:
+            DATASET_OFFSETS[unit] = offs
+        if DATASET_BASELINES is not None:
+            DATASET_BASELINES[unit] = base
+
     def _best_offsets(self, model, flags, cols, best, twin, nblk):
-        """[L] device tensor: per dataset the posterior-mean baseline offset S1 / (S0 + 1 / s^2) of the branch's best
-        draw, NaN for a dataset without an offset.  The one row is evaluated again -- trx_flux_grid on one row, then
-        trx_chi2_grid_offset with offset_out -- so nothing of size n x L is kept."""
+        """([L] device tensor, list per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
+        S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
+        baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them).  The one row is
+        evaluated again -- trx_flux_grid on one row, then trx_chi2_grid_offset with offset_out or trx_chi2_grid_baseline
+        with coef_out -- so nothing of size n x L is kept."""
         out = torch.full((len(self.datasets),), float("nan"), dtype=F64, device=self.dev)
+        coefs = [None] * len(self.datasets)
         row = cols[:nblk].index_select(1, best[:1]).contiguous()
         if twin:
             row[2] *= 2.0
             row[4] = cols[11].index_select(0, best[:1])
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL
         for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
-            if self.offsets[l] is None:
+            base = None if self.baselines is None else self.baselines[l]
+            if self.offsets[l] is None and base is None:
                 continue
             grid, _ = _lib.flux_grid(model, flags, time_d, row, exptime, nsamples, want_secdepth=False)
-            _lib.chi2_grid_offset(flux_d, inv_var_d, grid, *self.offsets[l], offset_out=out[l:l + 1])
-        return out
+            if base is not None:
+                coefs[l] = torch.empty((1, int(base[0].shape[0])), dtype=F64, device=self.dev)
+                _lib.chi2_grid_baseline(flux_d, inv_var_d, grid, base[0], base[1], coef_out=coefs[l])
+            else:
+                _lib.chi2_grid_offset(flux_d, inv_var_d, grid, *self.offsets[l], offset_out=out[l:l + 1])
+        return out, coefs
 
     def _datasets_halfchi2(self, model, flags, block):
         """sum over the datasets of the weighted chi^2/2 of every row of `block` ([n_param][n], the masked draws of one
         branch): per chunk of rows and per dataset one trx_flux_grid and one accumulating trx_chi2_grid_weighted -- for a
-        dataset whose baseline offset is marginalised (offset_sigma), trx_chi2_grid_offset in its place.  The EB
+        dataset whose baseline offset is marginalised (offset_sigma), trx_chi2_grid_offset in its place, for one with
+        baseline columns trx_chi2_grid_baseline.  The EB
         branch's secondary-eclipse rule (secdepth >= 1.5 sigma_bar -> +inf) rides in the first dataset's reduction: the
         depth does not depend on the time stamps.  A row's value does not depend on the chunk it falls in.
         DATASET_EVALUATION = "fused": one trx_lnl_batch_weighted per dataset over the whole block instead -- no grid, no
@@ -1080,6 +1135,10 @@ class _Scenario:
         if DATASET_EVALUATION == "fused" and any(o is not None for o in self.offsets):
             raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: the fused kernel "
                                       "carries no sum of w * residual; use evaluation='grid'")
+        baselines = self.baselines if self.baselines is not None else [None] * len(self.datasets)
+        if DATASET_EVALUATION == "fused" and any(b is not None for b in baselines):
+            raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: the fused kernel "
+                                      "carries no sums of basis * residual; use evaluation='grid'")
         n = int(block.shape[1])
         h = torch.zeros(n, dtype=F64, device=self.dev)         # (0 + x = x: every reduction accumulates)
         if n == 0:
@@ -1103,7 +1162,10 @@ class _Scenario:
                     nt = int(time_d.numel())
                     grid, sec = _lib.flux_grid(model, flags, time_d, blk, exptime, nsamples, want_secdepth=eb and l == 0,
                                                out=buf[:(r1 - r0) * nt].view(r1 - r0, nt))
-                    if self.offsets[l] is None:
+                    if baselines[l] is not None:
+                        _lib.chi2_grid_baseline(flux_d, inv_var_d, grid, baselines[l][0], baselines[l][1], sec,
+                                                1.5 * self.sigma, out=h[r0:r1])
+                    elif self.offsets[l] is None:
                         _lib.chi2_grid_weighted(flux_d, inv_var_d, grid, sec, 1.5 * self.sigma, out=h[r0:r1])
                     else:
                         _lib.chi2_grid_offset(flux_d, inv_var_d, grid, *self.offsets[l], sec, 1.5 * self.sigma,

@@ -68,11 +68,31 @@ def prepare(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int
     return tb, yb, float(np.std(yb[:n_sigma]))
 
 
+def polynomial_baseline(time, order: int):
+    """[order][T] columns of a polynomial baseline for a dataset's "baseline" key: column p - 1 is u^p, p = 1 ... order,
+    u = (t - mid) / half-span over the finite times, so u spans [-1, 1].  The constant term is not among them: it is the
+    dataset's offset_sigma.  A NaN time gives NaN entries (dropped with the point)."""
+    time = np.asarray(time, dtype=np.float64)
+    order = int(order)
+    if time.ndim != 1 or order < 1:
+        raise ValueError("polynomial_baseline needs a 1-d time array and order >= 1")
+    fin = time[np.isfinite(time)]
+    if fin.size == 0 or np.max(fin) == np.min(fin):
+        raise ValueError("polynomial_baseline needs at least two different finite times")
+    lo, hi = float(np.min(fin)), float(np.max(fin))
+    u = (time - 0.5 * (lo + hi)) / (0.5 * (hi - lo))
+    return np.stack([u ** p for p in range(1, order + 1)])
+
+
 def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int = 50,
-                    exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None):
+                    exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None,
+                    baseline_order: int = 0, baseline_sigma=None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
-    {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma"} of one dataset; empty bins are dropped.
+    {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
+    empty bins are dropped.
     offset_sigma (None: no offset; a number > 0 or inf) is passed through: the prior of the dataset's baseline offset.
+    baseline_order > 0: "baseline" = polynomial_baseline(kept bins' times, baseline_order), with baseline_sigma (a number
+    or one per column; None: flat) passed through; 0: both keys are None.
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -85,5 +105,7 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     tb, yb, count = tb[keep], yb[keep], count[keep]
     head = yb[:n_sigma]
     scatter = float(np.sqrt(np.mean(count[:n_sigma] * (head - np.mean(head)) ** 2)))
+    baseline = polynomial_baseline(tb, baseline_order) if int(baseline_order) > 0 else None
     return {"time": tb, "flux": yb, "flux_err": scatter / np.sqrt(count), "exptime": float(exptime),
-            "nsamples": int(nsamples), "offset_sigma": offset_sigma}
+            "nsamples": int(nsamples), "offset_sigma": offset_sigma, "baseline": baseline,
+            "baseline_sigma": baseline_sigma}

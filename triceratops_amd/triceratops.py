@@ -277,7 +277,24 @@ class target:
         evaluation="fused" with such a dataset raises NotImplementedError.  `.dataset_offsets` is then an
         [n_scenarios][n_datasets] array: the posterior-mean offset S1 / (S0 + 1 / s^2) of each scenario's best draw, in
         the target's normalisation; NaN for a dataset without offset_sigma and for a scenario without a finite lnZ (on
-        several ranks also for the scenarios another rank evaluated).  None when no dataset has an offset."""
+        several ranks also for the scenarios another rank evaluated).  None when no dataset has an offset.
+
+        A dataset may also carry "baseline": K_b columns B_k[t] ([K_b][len(time)], or [len(time)] for one) of a linear
+        baseline model -- a trend with time, airmass, seeing, detector position (lightcurve.polynomial_baseline makes the
+        powers of the scaled time) -- and "baseline_sigma": the prior sigma s_k of each coefficient, a number or [K_b],
+        each > 0 or inf, in flux units per unit of its column (absent: inf, a flat prior).  The data model is
+        model_t + sum_k c_k B_k[t], c_k ~ N(0, s_k^2) independent, and the c_k are marginalised in closed form per draw,
+        together with the constant of offset_sigma if the dataset has one (the column of ones, term 0 of the same system;
+        at most 4 terms in all): the dataset's term of the log-weight is 0.5 (S2 - b^T A^-1 b), b_k = sum w B_k r,
+        A = B^T W B + diag(1 / s_k^2).  The factor det(I + diag(s^2) B^T W B)^(-1/2) of the marginal is dropped for the
+        same reason as the offset's: every finite s_k scales with the errors under renormalisation, so it is common to all
+        scenarios of all stars.  Collinear terms (a constant column next to offset_sigma, more flat terms than points: the
+        smallest eigenvalue of the unit-diagonal scaling of A below 1e-6) are a ValueError.  Grid evaluation only.
+        `.dataset_baselines` is then a list per scenario of a list per dataset: the [K_b] posterior-mean coefficients
+        A^-1 b of the scenario's best draw in the target's normalisation (NaN without a finite lnZ), None for a dataset
+        without "baseline"; the whole attribute is None when no dataset has one.  `.dataset_offsets` reports the offset of
+        a baseline dataset that has offset_sigma as well.  Not built: a multiplicative normalisation, baselines in the
+        fused evaluation, calc_probs_many with datasets."""
         from . import fused
         if evaluation not in fused.DATASET_EVALUATIONS:
             raise ValueError("evaluation must be one of %s (got %r)" % (fused.DATASET_EVALUATIONS, evaluation))
@@ -297,8 +314,12 @@ class target:
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
         if ds.has_offsets and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: use evaluation='grid'")
+        if ds.has_baselines and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: use evaluation='grid'")
         best_offsets = {} if ds.has_offsets else None
-        with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, DATASET_OFFSETS=best_offsets):
+        best_baselines = {} if ds.has_baselines else None
+        with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, DATASET_OFFSETS=best_offsets,
+                            DATASET_BASELINES=best_baselines):
             rows = sharding.run_units(units, verbose=verbose, as_rows=True)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
@@ -312,6 +333,16 @@ class target:
                     table[u.first_row + i] = c * share[u.group[1]]
             table[~np.isfinite(self.lnZ)] = np.nan
             self.dataset_offsets = table
+        self.dataset_baselines = None
+        if best_baselines is not None:
+            # (c_k multiplies a column that is left alone, so it scales as the flux does: c = fr c')
+            sizes = [None if s.baseline is None else s.baseline.shape[0] for s in ds.sets]
+            rows_ = [[None if m is None else np.full(m, np.nan) for m in sizes] for _ in range(n_scen)]
+            for k, u in enumerate(sharding.as_units(units)):
+                for i, per in enumerate(best_baselines.get(k, ())):
+                    if np.isfinite(self.lnZ[u.first_row + i]):
+                        rows_[u.first_row + i] = [None if c is None else c * share[u.group[1]] for c in per]
+            self.dataset_baselines = rows_
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
