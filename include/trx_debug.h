@@ -60,6 +60,16 @@ int trx_set_debug_bug(int on);
 int trx_set_probe_rows(int rows);
 /* 0: trx_star_enqueue enqueues its calls one by one instead of in launch chains (same records, bit for bit) */
 int trx_set_star_chain(int on);
+/* 0: a likelihood launch of one row per wave hands its rows to the waves as they come instead of dearest first
+ * (default 1).  No output depends on it, bit for bit: a row is evaluated by its own wave from its own block. */
+int trx_set_row_order(int on);
+/* The cost order of the last likelihood launch of this thread that built one (it waits for the device): *n_rows its
+ * rows, *segment_capacity the entries a segment's list can hold; counts[64]: the rows filed in segment s = 4 bucket +
+ * shard, bucket 0 the dearest of 16; lists[64 * capacity]: the row numbers of segment s in its first counts[s] entries
+ * from s * capacity on; row_blocks[19 * n_rows]: the rows' constant blocks as the kernels read them (t0 and nmot are
+ * doubles 1 and 2 of a block, the window doubles 10 and 11, the secondary rule's verdict double 18).  Array pointers may be NULL;
+ * called with all of them NULL it tells the sizes.  TRX_ERR_ARG when there has been no such launch. */
+int trx_debug_row_order(long* n_rows, long* segment_capacity, int* counts, int* lists, double* row_blocks);
 /* what trx_star_enqueue has put into launch chains since the library was loaded (or since the last call with
  * reset != 0, which returns the counts and then zeroes them): chains, the calls in them, and those of these calls that
  * had post_rows > 0.  Host counters; they cannot change a result.  Any pointer may be NULL. */

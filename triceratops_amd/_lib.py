@@ -44,6 +44,7 @@ DEBUG_SYMBOLS = (
     "trx_set_stencil", "trx_set_skip_excluded", "trx_set_debug_node_counts", "trx_set_kepler_stepping",
     "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison", "trx_set_debug_bug",
     "trx_set_probe_rows", "trx_set_star_chain", "trx_debug_capture_buffers", "trx_debug_chain_counts",
+    "trx_set_row_order", "trx_debug_row_order",
 )
 
 
@@ -197,12 +198,15 @@ def _load(path, testing):
         for name in ("trx_set_rows_per_wave", "trx_set_kepler_stepping", "trx_set_skip_excluded",
                      "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison",
                      "trx_set_debug_bug", "trx_set_star_chain", "trx_set_probe_rows", "trx_set_stencil",
-                     "trx_set_supersample_tiers", "trx_set_debug_node_counts", "trx_set_cell_packing_below"):
+                     "trx_set_supersample_tiers", "trx_set_debug_node_counts", "trx_set_cell_packing_below",
+                     "trx_set_row_order"):
             fn = getattr(L, name)
             fn.restype = c_int
             fn.argtypes = [c_int]
         L.trx_debug_capture_buffers.restype = c_int
         L.trx_debug_capture_buffers.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long)]
+        L.trx_debug_row_order.restype = c_int
+        L.trx_debug_row_order.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long), _vp, _vp, _vp]
     return L
 
 
@@ -398,6 +402,22 @@ def lnl_batch(model, flags, time_d, flux_d, sigma, params_d, exptime, nsamples, 
                                   time_d.numel(), float(sigma), params_d.data_ptr(), n,
                                   float(exptime), int(nsamples), out.data_ptr(), _stream(params_d)))
     return out
+
+
+def debug_row_order():
+    """Testing library only (trx_debug_row_order): the cost order that the last one-row likelihood launch of this thread
+    built, as (counts [16 buckets][4 shards], lists: 64 arrays of row numbers, row_blocks [n][19])."""
+    L = lib()
+    assert L.trx_testing, "debug_row_order needs use_testing_library()"
+    n, cap = ctypes.c_long(0), ctypes.c_long(0)
+    check(L.trx_debug_row_order(ctypes.byref(n), ctypes.byref(cap), None, None, None))
+    counts = np.zeros(64, dtype=np.int32)
+    lists = np.zeros(64 * cap.value, dtype=np.int32)
+    blocks = np.zeros((n.value, 19), dtype=np.float64)
+    check(L.trx_debug_row_order(ctypes.byref(n), ctypes.byref(cap), counts.ctypes.data, lists.ctypes.data,
+                                blocks.ctypes.data))
+    lists = lists.reshape(64, cap.value)
+    return counts.reshape(16, 4), [lists[s, :max(0, min(int(counts[s]), cap.value))].copy() for s in range(64)], blocks
 
 
 def lnl_batch_weighted(model, flags, time_d, flux_d, inv_var_d, params_d, exptime, nsamples, sec_limit=float("inf"),

@@ -90,6 +90,9 @@ struct RowsArgs {
     const double* inv_var;
     double sec_limit;
     int accumulate;
+    // Cost-ordered rows (one row per wave, full evaluation of a likelihood launch; null: rows as they come): rowc_kernel
+    // files every row under its cost bucket, cells_kernel's position v takes the v-th row of that order (row_order_at)
+    int* order;        // [kOrderSegs counters, kOrderStride ints apart | kOrderSegs lists of order_cap(n) row numbers]
 };
 
 // One launch chain for several lnZ_* branches (trx_star_enqueue, trx_scenario.hip): the kernels of the likelihood path
@@ -166,6 +169,18 @@ __device__ unsigned long long g_phase_cycles[8];
 #else
 #define TRX_TICK(var)
 #define TRX_TOCK(slot, from)
+#endif
+
+// Optional tail timers of the one-row variant (build with -DTRX_TAIL_TIMERS; profiles/r08/tail_once.py): every wave notes
+// the constant-rate wall clock when it starts and when it has finished its row.  g_tail: [0] the earliest start, [1] the
+// latest start -- when the dispatcher ran out of rows --, [2] the latest finish, [3] the sum over waves of finish - start;
+// g_tail_finish: the finish of the wave at each of the first kTailWaves positions, from which the host takes the busy
+// time inside the tail (every wave has started by [1], so a wave that ends at f > [1] is busy for f - [1] of it).  Two
+// clock reads and four atomics per wave; not compiled into the product library.
+#ifdef TRX_TAIL_TIMERS
+constexpr int kTailWaves = 1 << 17;
+__device__ unsigned long long g_tail[4] = {~0ull, 0ull, 0ull, 0ull};
+__device__ unsigned long long g_tail_finish[kTailWaves];
 #endif
 
 // rows whose light curve was not evaluated because lnL_EB_p's secondary-eclipse rule excludes them
@@ -436,6 +451,30 @@ constexpr int kThirdStride = 3;          // the survivors' pass of batches takes
                                          // 64-TOI step 0.1240 -> 0.1211 s, 9371 fuzz configurations clean: profiles/r05/ab_third_stride.txt)
 static_assert(kHdrStW + 2 * kStM + 1 <= kHdrDoubles, "launch header");
 
+// Cost-ordered rows of the one-row variant (RowsArgs::order).  A row's cost is its in-window cells, which
+// rowc_kernel can tell from the row's window and the span of the light curve (row_cost_key); the launch hands the rows
+// out dearest first, so that what is still running when the dispatcher runs dry is the cheapest rows, not a whole-curve
+// row begun in the last microseconds.  kOrderBuckets linear buckets of the key, bucket 0 the dearest; finer buys nothing
+// (the tail is bounded by the cheapest bucket's rows).  Each bucket is kOrderShards lists -- a 64-row block of rowc_kernel
+// files under shard (block & 3), so a counter takes a quarter of the reservations -- of fixed capacity (order_cap: every
+// row of a shard's blocks may land in one bucket), which makes the scatter one pass.  The order is the segments one
+// after the other: kOrderSegs = 64 of them, one per lane of the wave that looks a position up.
+constexpr int kOrderBuckets = 16, kOrderShards = 4, kOrderSegs = kOrderBuckets * kOrderShards;
+constexpr int kOrderStride = 16;          // ints between two counters: a 64-byte line each
+static_assert(kOrderSegs == 64, "row_order_at: one segment per lane");
+__host__ __device__ inline long order_cap(long n) { return 64 * ((((n + 63) / 64) + kOrderShards - 1) / kOrderShards); }
+__host__ __device__ inline size_t order_counter_bytes() { return (size_t)kOrderSegs * kOrderStride * sizeof(int); }
+__host__ __device__ inline size_t order_doubles(long n)
+{
+    return (order_counter_bytes() + (size_t)kOrderSegs * (size_t)order_cap(n) * sizeof(int)) / sizeof(double);
+}
+// bucket of a key in [0, n_time]: linear, the dearest first; key 0 lands in the last one
+__host__ __device__ inline int order_bucket(int key, int n_time)
+{
+    const int b = (int)(((long)key * kOrderBuckets) / ((long)n_time + 1));
+    return kOrderBuckets - 1 - (b < 0 ? 0 : (b > kOrderBuckets - 1 ? kOrderBuckets - 1 : b));
+}
+
 // Undecided-row list of the secondary-eclipse scan, in FRONT of the row blocks in scratch (a place that does not
 // depend on the row count, which may only be known on the device): one 64-bit counter, then one int per row.
 __host__ __device__ inline size_t scan_list_doubles(long n_upper) { return 2 + (size_t)(n_upper + 1) / 2; }
@@ -702,7 +741,61 @@ __device__ __forceinline__ void launch_header(const RowsArgs& a, const long n)
 // whatever the stream's previous call left there (two such bugs shipped in round 4).
 constexpr unsigned long long kUnwrittenBits = 0x7ff8dead0badc0deull;
 
-template <bool SEC, bool WT = false>
+// The cost key of a row (cost-ordered rows, kOrderBuckets): its in-window cells, estimated from the window alone.  The
+// stamps' phases run from pa = nmot (t[0] - t0) to pb = nmot (t[n_time - 1] - t0); the windows are 2 pi j + [wlo, whi];
+// W(x), the length of window below phase x, is piecewise linear, and (W(pb) - W(pa)) / (nmot dt) is the count on a grid
+// of mean spacing dt -- exact to a cell or two on a uniform grid, an estimate on any other, which is all an ORDER needs.
+// 0: a row that will not be evaluated (settled by the EB secondary rule in a launch that skips such rows), an empty
+// window, a window that misses the span, a NaN anywhere.  Every operation is a single IEEE operation in a fixed order
+// (no contraction), so that a host can repeat it bit for bit from the row blocks (tests/test_gpu_row_order.py).
+// (Not inlined: a leaf with its arguments in registers.  Inlined into rowc_kernel it takes this compiler's register
+// allocator down -- a crash, not a diagnostic.)
+__device__ __attribute__((noinline)) int row_cost_key(double wlo, double whi, double nmot, double t0, double tg0, double tg1,
+                                                      int n_time, bool settled)
+{
+#pragma clang fp contract(off)
+    if (settled || n_time < 1) return 0;
+    const double w = whi - wlo;
+    if (!(w >= 0.0) || !(nmot > 0.0) || !(nmot < INFINITY)) return 0;      // (empty window; NaN fails every test)
+    if (n_time < 2 || !(tg1 > tg0) || w >= kTwoPi) return n_time;
+    const double pa = nmot * (tg0 - t0), pb = nmot * (tg1 - t0);
+    if (!(fabs(pa) < 1e15) || !(fabs(pb) < 1e15)) return 0;
+    const double xa = pa - wlo, xb = pb - wlo;
+    const double fa = floor(xa / kTwoPi), fb = floor(xb / kTwoPi);
+    const double ra = fmin(fmax(xa - kTwoPi * fa, 0.0), w), rb = fmin(fmax(xb - kTwoPi * fb, 0.0), w);
+    const double inside = (fb * w + rb) - (fa * w + ra);
+    const double step = (pb - pa) / (double)(n_time - 1);
+    double cells = inside / step;
+    if (!(cells > 0.0)) return 0;
+    cells = fmin(cells, (double)n_time);
+    return (int)(cells + 0.5);
+}
+
+// Files the rows of a 64-row block (lane = row, `bucket` its cost bucket, -1 beyond the block) in the launch's cost
+// order: one reservation per bucket present in the block -- lane b counts the rows of bucket b, and the lanes that have
+// any add to their counters in ONE instruction --, a row's slot being the reservation plus its rank in the bucket.
+__device__ __forceinline__ void order_file_rows(int* order, int bucket, long blk, long base, long n, int lane)
+{
+    int rank = 0, mine = 0;
+#pragma unroll
+    for (int b = 0; b < kOrderBuckets; ++b) {
+        const unsigned long long mb = __ballot(bucket == b);
+        if (bucket == b) rank = lanes_below(mb);
+        if (lane == b) mine = __popcll(mb);
+    }
+    const int shard = (int)(blk & (kOrderShards - 1));
+    int at = 0;
+    if (mine > 0) at = atomicAdd(&order[(lane * kOrderShards + shard) * kOrderStride], mine);      // (lane < kOrderBuckets)
+    at = __shfl(at, bucket < 0 ? 0 : bucket, 64);
+    const long cap = order_cap(n);
+    const long slot = (long)at + rank;
+    // (bounded: counters that were not zero -- there is no such path -- could not push a list past its end)
+    if (bucket >= 0 && at >= 0 && slot < cap)
+        order[kOrderSegs * kOrderStride + (long)(bucket * kOrderShards + shard) * cap + slot] = (int)(base + lane);
+}
+
+// ORDER: the launch files its rows in cost order (RowsArgs::order set); the other instantiations know nothing of it.
+template <bool SEC, bool WT = false, bool ORDER = false>
 __device__ __forceinline__ void rowc_body(const RowsArgs& a)
 {
     __shared__ RowC rows_out[64];
@@ -722,6 +815,7 @@ __device__ __forceinline__ void rowc_body(const RowsArgs& a)
         const long base = blk * 64;
         const int nb = (int)((n - base < 64) ? (n - base) : 64);
         bool open = false;
+        int bucket = -1;
         if (lane < nb) {
             RowC c, sc;
             double ysec, fdil;
@@ -742,6 +836,12 @@ __device__ __forceinline__ void rowc_body(const RowsArgs& a)
                 open = true;
 #endif
             }
+            if (ORDER && a.order) {
+                // cost-ordered rows: the row's bucket, from its window and the span of the light curve
+                const bool settled = a.skip_excl && a.model == TRX_MODEL_EB && c.excl != 0.0;
+                const double tg0 = a.n_time > 0 ? a.time[0] : 0.0, tg1 = a.n_time > 0 ? a.time[a.n_time - 1] : 0.0;
+                bucket = order_bucket(row_cost_key(c.wlo, c.whi, c.nmot, c.t0, tg0, tg1, a.n_time, settled), a.n_time);
+            }
             // through LDS to memory: 64 x 19 doubles leave the block as one contiguous 9.5 KB run (a lane
             // writing its own 152-byte block made every store instruction touch 64 cache lines)
             const double* src = reinterpret_cast<const double*>(&c);
@@ -761,6 +861,7 @@ __device__ __forceinline__ void rowc_body(const RowsArgs& a)
                 if (open && slot <= (unsigned long long)a.n) list[slot] = (int)(base + lane);
             }
         }
+        if (ORDER && a.order) order_file_rows(a.order, bucket, blk, base, n, lane);
         if (a.mark_unwritten && lane < nb) a.out[base + lane] = __longlong_as_double((long long)kUnwrittenBits);
         __syncthreads();
         {
@@ -772,10 +873,10 @@ __device__ __forceinline__ void rowc_body(const RowsArgs& a)
     }
 }
 
-template <bool SEC, bool WT = false>
+template <bool SEC, bool WT = false, bool ORDER = false>
 __global__ __launch_bounds__(64) void rowc_kernel(RowsArgs a)
 {
-    rowc_body<SEC, WT>(a);
+    rowc_body<SEC, WT, ORDER>(a);
 }
 
 // chain: branch = blockIdx.y; the branches that need the secondary-eclipse verdict take the SEC body
@@ -903,6 +1004,31 @@ __device__ __forceinline__ int lane_prefix(int cnt, int& total)
         total += __popcll(m) << b;
     }
     return off;
+}
+
+// Position v of the cost order (RowsArgs::order; wave-uniform v): lane L loads the count of segment L, a wave prefix sum
+// gives the segments' first positions, the ballot of `first <= v` the segment, and the row is that list's entry
+// v - first.  About two dozen wave instructions and two loads per row, against ~2e4 instructions for the row itself;
+// nothing of it lives beyond the call.  -1: no such position (v beyond the rows filed), or an entry that is no row.
+__device__ __forceinline__ long row_order_at(const int* __restrict__ order, long v, long n, int lane)
+{
+    const int cnt = order[lane * kOrderStride];
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    const long first = (long)(incl - cnt);
+    const unsigned long long below = __ballot(cnt >= 0 && first <= v);
+    const int seg = __popcll(below) - 1;
+    const long total = (long)__builtin_amdgcn_readlane(incl, 63);
+    if (seg < 0 || v >= total) return -1;
+    const long at = v - (long)__builtin_amdgcn_readlane((int)first, seg);
+    const long cap = order_cap(n);
+    if (at < 0 || at >= cap) return -1;
+    const long row = (long)__builtin_amdgcn_readfirstlane(order[kOrderSegs * kOrderStride + (long)seg * cap + at]);
+    return (row >= 0 && row < n) ? row : -1;
 }
 
 // LONG = false: a batch of B rows per wave, light curve staged in LDS, row constants read from the
@@ -1063,6 +1189,17 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
     static_assert(!PRUNE || (MODE == MODE_LNL && !ST), "bounded evaluation: likelihood mode, no stencil");
     static_assert(!WT || (MODE == MODE_LNL && !PRUNE), "per-point weights: likelihood mode, full evaluation");
     extern __shared__ double lds_all[];
+    // One row per wave, full evaluation: the rows dearest first (a.order, row_order_at).  Such a launch has a workgroup
+    // per row (launch_cells), so the wave's only position is its blockIdx, and its row is looked up HERE, before
+    // anything else of the kernel is live: the lookup costs the row loop no register.  Consecutive positions go round
+    // the XCDs with blockIdx, which spreads the dear rows evenly over them; a row reads 152 B of block, so which XCD's
+    // L2 holds it does not matter.
+#ifdef TRX_TAIL_TIMERS
+    const unsigned long long tail_start = LONG ? wall_clock64() : 0ull;
+#endif
+    constexpr bool kOrdered = LONG && !PRUNE && !WT && MODE == MODE_LNL;
+    int ordered_row = -2;              // -2: the launch has no order; -1: no row at this wave's position
+    if (kOrdered && a.order) ordered_row = (int)row_order_at(a.order, (long)blockIdx.x, a.n, (int)threadIdx.x);
     // (not in the diagnostic instantiations that solve Kepler's equation per pair; not with one row per wave: 2000 irregular
     // stamps -0.5 %, and the stencil instantiation, which never carries, -2.3 % for the registers the code costs)
     constexpr bool kCarry = TRX_CARRY_CELLS && STEP && !LONG;
@@ -1188,7 +1325,9 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
     const bool probing = PRUNE && pstride > 1 && hdr[kHdrProbe] != 0.0 &&
                          (a.part == 0 || a.part == 2 || third_two);
     if (PRUNE && a.split && a.part == 2 && !probing) return;       // nothing to probe: part 3 takes the rows directly
-    // (one row per wave: nothing to taper -- an XCD's waves take consecutive rows of its eighth)
+    // (one row per wave: nothing to taper -- the rows dearest first, see above, or, without that order -- the passes of the
+    // bounded evaluation, which bring their own lists, the model grid, per-point weights, chains -- an XCD's waves take
+    // consecutive rows of its eighth)
     // (a row count read from the device is wave-uniform, which the compiler cannot know: the plan belongs in scalar
     // registers)
     const BatchPlan bp = LONG ? BatchPlan{} : batch_plan(uniform_long(row1 - row0), __builtin_amdgcn_readfirstlane(B), !PRUNE);
@@ -1206,7 +1345,11 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
         const RowsArgs& a = (kReload == 1) ? *kernel_arguments<RowsArgs>() : ((kReload == 2) ? a_again : a_in);
         long base;
         int nb;
-        if (LONG) {
+        if (kOrdered && ordered_row != -2) {
+            if (v != v0 || ordered_row < 0) continue;
+            base = (long)ordered_row;
+            nb = 1;
+        } else if (LONG) {
             const long batch = (v & 7) * positions + (v >> 3);
             if ((v >> 3) >= positions || batch >= nbatch) continue;
             base = row0 + batch * B;
@@ -1833,6 +1976,16 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
         add_row_stat(0, n_skipped);
         add_row_stat(1, n_pruned);
     }
+#ifdef TRX_TAIL_TIMERS
+    if (LONG && lane == 0) {
+        const unsigned long long tail_end = wall_clock64();
+        atomicMin(&g_tail[0], tail_start);
+        atomicMax(&g_tail[1], tail_start);
+        atomicMax(&g_tail[2], tail_end);
+        atomicAdd(&g_tail[3], tail_end - tail_start);
+        if (blockIdx.y == 0 && blockIdx.x < (unsigned)kTailWaves) g_tail_finish[blockIdx.x] = tail_end;
+    }
+#endif
 #ifdef TRX_PHASE_TIMERS
     TRX_TOCK(7, t_all);
     if (lane == 0)

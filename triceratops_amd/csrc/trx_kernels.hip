@@ -253,6 +253,9 @@ StencilMemo g_stencil_memo;
 // what the last launch_cells of this thread did (trx::lnl_draws hands it to the reduction that follows)
 thread_local const double* t_last_rowc = nullptr;
 thread_local bool t_last_pruned = false;
+// the cost order of this thread's last launch that built one (trx_debug_row_order; the testing build reads it back)
+thread_local const int* t_last_order = nullptr;
+thread_local long t_last_order_rows = 0;
 
 
 // THE place that picks a cells_kernel instantiation; these are all there are.  The call site fixes the variant (LONG: one
@@ -530,7 +533,14 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
     // per wave.  While the stream is being captured into a hipGraph the scratch is a buffer of its own that the
     // GRAPH owns (trx::capture_scratch: the stream's buffer must not be grown, nor baked into a graph).
     void* scratch = nullptr;
-    const size_t scratch_bytes = launch_scratch_doubles(a.n, split, a.use_stencil ? a.n_time : 0) * sizeof(double);
+    const size_t launch_doubles = launch_scratch_doubles(a.n, split, a.use_stencil ? a.n_time : 0);
+    // Cost-ordered rows (RowsArgs::order): a full evaluation of a likelihood launch at one row per wave whose row count
+    // the host knows; the counters and lists sit behind everything else in the call's scratch
+    // (a workgroup per row: the grid's 2^20 bounds the launches that are ordered -- beyond it the waves stride, and the
+    // tail of a launch of so many rounds over the chip is a smaller share of it anyway)
+    const bool ordered = MODE == MODE_LNL && !WT && long_rows && !prune && !a.n_dev && a.n_time > 0 && a.n <= (1L << 20) &&
+                         (long)P.grid_main >= a.n && knob_row_order();
+    const size_t scratch_bytes = (launch_doubles + (ordered ? order_doubles(a.n) : 0)) * sizeof(double);
 #ifdef TRX_CAPTURE_GRAPH_MEM
     // (A/B builds only, profiles/r06/graph_stress.py: rounds 2-5 took a pair of graph memory nodes here)
     if (capturing) TRX_HIP(hipMallocAsync(&scratch, scratch_bytes, st));
@@ -539,6 +549,14 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
 #endif
     else TRX_HIP(trx::stream_scratch(st, 0, scratch_bytes, &scratch));
     set_scratch(a, static_cast<double*>(scratch));
+    if (ordered) {
+        // (the counters' place depends on the row count and the scratch holds whatever the stream's last call left:
+        // cleared here, 4 KB, before rowc_kernel counts)
+        a.order = reinterpret_cast<int*>(static_cast<double*>(scratch) + launch_doubles);
+        TRX_HIP(hipMemsetAsync(a.order, 0, order_counter_bytes(), st));
+        t_last_order = a.order;
+        t_last_order_rows = a.n;
+    }
     // From here on a failure may leave the scan's counter non-zero in the stream's scratch (rowc_kernel<true> counts,
     // the cells_kernel behind it resets): cleared on the way out, or the next call's list would start beyond its end
     auto fail_launch = [&](hipError_t e) {
@@ -549,11 +567,13 @@ int launch_cells(const RowsArgs& a0, hipStream_t st, bool long_rows)
         // (the scan's counter is zero in the stream's scratch: cleared at allocation, then by every cells_kernel
         // that follows a scan; a captured call's own buffer holds anything)
         if (capturing) TRX_HIP(hipMemsetAsync(a.scan_count, 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL((rowc_kernel<true, WT>), dim3(P.grid_rowc), dim3(64), 0, st, a);
+        if (ordered) hipLaunchKernelGGL((rowc_kernel<true, false, true>), dim3(P.grid_rowc), dim3(64), 0, st, a);
+        else         hipLaunchKernelGGL((rowc_kernel<true, WT>), dim3(P.grid_rowc), dim3(64), 0, st, a);
         if (a.out_sec) hipLaunchKernelGGL(sec_scan_kernel<64>, dim3(P.grid_scan), dim3(64), 0, st, a);
         else           hipLaunchKernelGGL((sec_scan_kernel<8, WT>), dim3(P.grid_scan), dim3(64), 0, st, a);
     } else {
-        hipLaunchKernelGGL((rowc_kernel<false, WT>), dim3(P.grid_rowc), dim3(64), 0, st, a);
+        if (ordered) hipLaunchKernelGGL((rowc_kernel<false, false, true>), dim3(P.grid_rowc), dim3(64), 0, st, a);
+        else         hipLaunchKernelGGL((rowc_kernel<false, WT>), dim3(P.grid_rowc), dim3(64), 0, st, a);
     }
     const unsigned g2 = P.grid_main;
     t_last_rowc = a.rowc;
@@ -1387,6 +1407,34 @@ int trx_set_debug_node_counts(int on)
     return TRX_OK;
 }
 
+/* (tests) 0: one row per wave takes its rows as they come, not dearest first */
+int trx_set_row_order(int on)
+{
+    g_knob_row_order = on ? 1 : 0;
+    return TRX_OK;
+}
+
+/* (tests) the cost order the last likelihood launch of this thread built, and the row blocks it was built from */
+int trx_debug_row_order(long* n_rows, long* segment_capacity, int* counts, int* lists, double* row_blocks)
+{
+    if (!t_last_order || !t_last_rowc) return fail(TRX_ERR_ARG, "trx_debug_row_order: no ordered launch yet%s", "", 0);
+    const long n = t_last_order_rows, cap = order_cap(n);
+    if (n_rows) *n_rows = n;
+    if (segment_capacity) *segment_capacity = cap;
+    if (!counts && !lists && !row_blocks) return TRX_OK;
+    TRX_HIP(hipDeviceSynchronize());
+    if (counts) {
+        std::vector<int> raw((size_t)kOrderSegs * kOrderStride);
+        TRX_HIP(hipMemcpy(raw.data(), t_last_order, raw.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int sgm = 0; sgm < kOrderSegs; ++sgm) counts[sgm] = raw[(size_t)sgm * kOrderStride];
+    }
+    if (lists)
+        TRX_HIP(hipMemcpy(lists, t_last_order + kOrderSegs * kOrderStride, (size_t)kOrderSegs * cap * sizeof(int), hipMemcpyDeviceToHost));
+    if (row_blocks)
+        TRX_HIP(hipMemcpy(row_blocks, t_last_rowc, (size_t)n * kRowDoubles * sizeof(double), hipMemcpyDeviceToHost));
+    return TRX_OK;
+}
+
 /* (tests) scratch buffers of captured calls: how many a live graph still owns, how many wait in the pool for reuse */
 int trx_debug_capture_buffers(long* live, long* idle)
 {
@@ -1420,6 +1468,22 @@ int trx_debug_phase_cycles(unsigned long long* out8)
     TRX_HIP(hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_phase_cycles), 8 * sizeof(unsigned long long)));
     unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     TRX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), zero, sizeof(zero)));
+    return TRX_OK;
+}
+#endif
+
+#ifdef TRX_TAIL_TIMERS
+/* debug builds only: read (and clear) the tail timers of the one-row kernels run since the last call -- out4: earliest
+   start, latest start, latest finish, sum of (finish - start), in ticks of the device's wall clock; finish[n]: the
+   finish of the waves at the first n positions (n <= 131072; may be NULL) */
+int trx_debug_tail(unsigned long long* out4, unsigned long long* finish, long n)
+{
+    TRX_HIP(hipDeviceSynchronize());
+    if (n < 0 || n > kTailWaves) return fail(TRX_ERR_ARG, "trx_debug_tail: n out of range%s (n=%ld)", "", n);
+    if (out4) TRX_HIP(hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_tail), 4 * sizeof(unsigned long long)));
+    if (finish && n > 0) TRX_HIP(hipMemcpyFromSymbol(finish, HIP_SYMBOL(g_tail_finish), (size_t)n * sizeof(unsigned long long)));
+    const unsigned long long fresh[4] = {~0ull, 0ull, 0ull, 0ull};
+    TRX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tail), fresh, sizeof(fresh)));
     return TRX_OK;
 }
 #endif
