@@ -1,6 +1,7 @@
 """Shared test helpers: golden loaders and an oracle-backed stand-in for the device calls, so the
 host logic (sampling order, masks, priors, tables) can be checked on a CPU-only box.  The
 stand-in is test infrastructure: the product has no CPU path."""
+import ctypes
 import os
 
 import numpy as np
@@ -92,3 +93,82 @@ def check_extra(res, case, g, lnz_tol):
             assert v.shape == w.shape
             top = n_fin if v.size > 1 else 1
             assert np.allclose(v[:top], w[:top], rtol=1e-12, atol=0), (case, i, k)
+
+
+class ZeroRng:
+    """stands in for device_pipeline.RNG while a scenario's argument block is built for staged(): every array it hands
+    out is replaced there, so it hands out zeros"""
+
+    def uniform(self, n, device):
+        return torch.zeros(n, dtype=torch.float64, device=device)
+
+    def beta(self, n, a, b, device):
+        return torch.zeros(n, dtype=torch.float64, device=device)
+
+    def randint(self, hi, n, device):
+        return torch.zeros(n, dtype=torch.int64, device=device)
+
+    def discard(self, n):
+        pass
+
+
+def scenario(name, *args, **kw):
+    """the _Scenario that fused.lnZ_<name>(*args, **kw) builds -- the project's own host constants in its argument
+    block -- without running it: what staged() takes as run["scen"]"""
+    from triceratops_amd import device_pipeline as dp
+    from triceratops_amd import fused
+    real, saved = fused._Scenario.run, dp.RNG
+    fused._Scenario.run = lambda self, is_host: self
+    dp.RNG = ZeroRng()
+    try:
+        return getattr(fused, "lnZ_" + name)(*args, **kw)
+    finally:
+        fused._Scenario.run, dp.RNG = real, saved
+
+
+def staged(run, fused, qc_in=None):
+    """trx_draw_scenario on the run's argument block with use_philox = 0 and no map: every random input staged from the
+    run's dump ([9][N]: P, q_companion, R_p, inc, q, ecc, argp uniforms, the field-star index, the planets' eccentricity);
+    qc_in: the companions' mass ratios themselves ([N], trx_draw_args.qc_in) in place of their uniforms"""
+    from triceratops_amd import _lib
+    s = run["scen"]
+    a, N, dev = s.a, s.N, s.dev
+    dump = _lib.dev(np.ascontiguousarray(run["dump"]), dev)
+    ncol = 11 if a.planet else 14
+    cols = torch.empty((ncol, N), dtype=torch.float64, device=dev)
+    mask = torch.empty(N, dtype=torch.uint8, device=dev)
+    mask2 = None if a.planet else torch.empty(N, dtype=torch.uint8, device=dev)
+    lnprior = torch.empty(N, dtype=torch.float64, device=dev) if a.prior != fused.PRIOR_NONE else None
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    idx = dump[7].to(torch.int64).contiguous()
+    a.use_philox, a.warp, a.dump = 0, None, None
+    a.uInc, a.uW = dump[3].data_ptr(), dump[6].data_ptr()
+    if a.range_P:
+        a.uP = dump[0].data_ptr()
+    if a.planet:
+        a.uRp, a.ecc_in = dump[2].data_ptr(), dump[8].data_ptr()
+    else:
+        a.uQ, a.uEcc = dump[4].data_ptr(), dump[5].data_ptr()
+    qc = None
+    if a.comp == fused.COMP_BOUND:
+        if qc_in is None:
+            a.uQc, a.qc_in = dump[1].data_ptr(), None
+        else:
+            qc = _lib.dev(np.ascontiguousarray(qc_in, dtype=np.float64), dev)
+            a.uQc, a.qc_in = None, qc.data_ptr()
+    if a.comp == fused.COMP_FIELD or a.host == fused.HOST_FIELD:
+        a.idx = idx.data_ptr()
+    a.cols, a.mask, a.mask_twin, a.flag = cols.data_ptr(), mask.data_ptr(), fused._ptr(mask2), flag.data_ptr()
+    a.lnprior = fused._ptr(lnprior)
+    a.splines = fused._spline_table(dev, s.band).data_ptr()
+    with torch.cuda.device(dev):
+        torch.cuda.synchronize()
+        rc = fused._fn()(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.synchronize()
+    assert rc == 0
+    # the map and staged numbers do not go together
+    a.warp = dump.data_ptr()
+    assert fused._fn()(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream) == 1      # TRX_ERR_ARG
+    a.warp = None
+    return {"cols": cols.cpu().numpy(), "mask": mask.cpu().numpy(), "mask_twin": None if mask2 is None else mask2.cpu().numpy(),
+            "lnprior": None if lnprior is None else lnprior.cpu().numpy()}

@@ -9,6 +9,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from helpers import staged as _staged
 from test_gpu_posterior import SEED, _device_mode
 from test_gpu_posterior_chain import _calls, _slots
 
@@ -194,46 +195,6 @@ def test_the_kernel_maps_as_warp_apply_and_every_phase_sees_it(kind, monkeypatch
     assert rec[ncol + 1] == staged["mask"].sum()
     if staged["mask_twin"] is not None:
         assert rec[W + ncol + 1] == staged["mask_twin"].sum()
-
-
-def _staged(run, fused):
-    """trx_draw_scenario on the run's argument block with use_philox = 0 and no map: every random input staged from the
-    run's dump (the numbers the mapped draw used)"""
-    from triceratops_amd import _lib
-    s = run["scen"]
-    a, N, dev = s.a, s.N, s.dev
-    dump = _lib.dev(np.ascontiguousarray(run["dump"]), dev)
-    ncol = 11 if a.planet else 14
-    cols = torch.empty((ncol, N), dtype=torch.float64, device=dev)
-    mask = torch.empty(N, dtype=torch.uint8, device=dev)
-    mask2 = None if a.planet else torch.empty(N, dtype=torch.uint8, device=dev)
-    lnprior = torch.empty(N, dtype=torch.float64, device=dev) if a.prior != fused.PRIOR_NONE else None
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    idx = dump[7].to(torch.int64).contiguous()
-    a.use_philox, a.warp, a.dump = 0, None, None
-    a.uInc, a.uW = dump[3].data_ptr(), dump[6].data_ptr()
-    if a.planet:
-        a.uRp, a.ecc_in = dump[2].data_ptr(), dump[8].data_ptr()
-    else:
-        a.uQ, a.uEcc = dump[4].data_ptr(), dump[5].data_ptr()
-    if a.comp == fused.COMP_BOUND:
-        a.uQc = dump[1].data_ptr()
-    if a.comp == fused.COMP_FIELD or a.host == fused.HOST_FIELD:
-        a.idx = idx.data_ptr()
-    a.cols, a.mask, a.mask_twin, a.flag = cols.data_ptr(), mask.data_ptr(), fused._ptr(mask2), flag.data_ptr()
-    a.lnprior = fused._ptr(lnprior)
-    a.splines = fused._spline_table(dev, s.band).data_ptr()
-    with torch.cuda.device(dev):
-        torch.cuda.synchronize()
-        rc = fused._fn()(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream)
-        torch.cuda.synchronize()
-    assert rc == 0
-    # the map and staged numbers do not go together
-    a.warp = dump.data_ptr()
-    assert fused._fn()(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream) == 1      # TRX_ERR_ARG
-    a.warp = None
-    return {"cols": cols.cpu().numpy(), "mask": mask.cpu().numpy(), "mask_twin": None if mask2 is None else mask2.cpu().numpy(),
-            "lnprior": None if lnprior is None else lnprior.cpu().numpy()}
 
 
 # ---- 3. the histogram ------------------------------------------------------------------------------------------------

@@ -578,7 +578,11 @@ def _rp_laws():
 
 def _cached(cache, key, limit, build):
     """cache[key], from build() on a miss.  The caches below hold what the ~10 lnZ_* calls of one star share, so a
-    few entries are live at a time: one that holds more than `limit` is emptied, not trimmed."""
+    few entries are live at a time: one that holds more than `limit` is emptied, not trimmed.
+    (Where that happens depends on everything the process has cached before.  Emptying _lc_cache between two calls of one
+    star gives the later call a second device copy of the light curve, and trx_star_enqueue chains calls by the address
+    of their time stamps: that star's chain splits there -- the same results, one launch chain more.  Tests that count
+    chains therefore depend on what ran before them; tests/test_gpu_draw_columns.py hands the caches back as it found them.)"""
     v = cache.get(key)
     if v is None:
         if len(cache) > limit:
