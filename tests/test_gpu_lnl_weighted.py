@@ -298,10 +298,10 @@ def device_mode():
     ta.set_sampling(mode)
 
 
-def _pass(monkeypatch, evaluation):
-    """one calc_probs_datasets pass from the seed: the target's results, per evidence the largest chi^2/2 among the
-    draws within 80 of the best log-weight, the calls of _lib.flux_grid and the peak of the allocator above its level
-    at the start"""
+def _pass(monkeypatch, evaluation, datasets=None):
+    """one calc_probs_datasets pass from the seed (datasets: _two_cadences() unless given): the target's results, per
+    evidence the largest chi^2/2 among the draws within 80 of the best log-weight, the calls of _lib.flux_grid and the
+    peak of the allocator above its level at the start"""
     hmax, grids = [], []
     real_lnz, real_grid = _lib.lnz_from_halfchi2, _lib.flux_grid
 
@@ -324,7 +324,7 @@ def _pass(monkeypatch, evaluation):
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     level = torch.cuda.memory_allocated()
-    tg.calc_probs_datasets(_two_cadences(), LC["P_orb"], n_samples=N_POST, evaluation=evaluation, **KW)
+    tg.calc_probs_datasets(_two_cadences() if datasets is None else datasets, LC["P_orb"], n_samples=N_POST, evaluation=evaluation, **KW)
     torch.cuda.synchronize()
     peak = torch.cuda.max_memory_allocated() - level
     monkeypatch.undo()
