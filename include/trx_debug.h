@@ -70,6 +70,15 @@ int trx_set_row_order(int on);
  * doubles 1 and 2 of a block, the window doubles 10 and 11, the secondary rule's verdict double 18).  Array pointers may be NULL;
  * called with all of them NULL it tells the sizes.  TRX_ERR_ARG when there has been no such launch. */
 int trx_debug_row_order(long* n_rows, long* segment_capacity, int* counts, int* lists, double* row_blocks);
+/* 0: pass 1 of the stencil instantiation of the one-row kernel tests every cell of a walked 64-cell trip instead of
+ * filing the trips that lie wholly inside a transit window as they stand (default 1).  No output depends on it, bit
+ * for bit: the in-window list holds the same cells in the same order. */
+int trx_set_whole_trips(int on);
+/* the 64-cell trips of pass 1 that the stencil instantiation's waves on the current device filed whole and those they
+ * walked cell by cell since the library was loaded (or since the last call with reset != 0, which returns the counts and
+ * then zeroes them); the trips that cannot hold an in-window cell are in neither.  It waits for the device.  Device
+ * counters of the testing library; they cannot change a result.  Either pointer may be NULL. */
+int trx_debug_whole_trips(long* whole, long* walked, int reset);
 /* what trx_star_enqueue has put into launch chains since the library was loaded (or since the last call with
  * reset != 0, which returns the counts and then zeroes them): chains, the calls in them, and those of these calls that
  * had post_rows > 0.  Host counters; they cannot change a result.  Any pointer may be NULL. */

@@ -44,7 +44,7 @@ DEBUG_SYMBOLS = (
     "trx_set_stencil", "trx_set_skip_excluded", "trx_set_debug_node_counts", "trx_set_kepler_stepping",
     "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison", "trx_set_debug_bug",
     "trx_set_probe_rows", "trx_set_star_chain", "trx_debug_capture_buffers", "trx_debug_chain_counts",
-    "trx_set_row_order", "trx_debug_row_order",
+    "trx_set_row_order", "trx_debug_row_order", "trx_set_whole_trips", "trx_debug_whole_trips",
 )
 
 
@@ -199,7 +199,7 @@ def _load(path, testing):
                      "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison",
                      "trx_set_debug_bug", "trx_set_star_chain", "trx_set_probe_rows", "trx_set_stencil",
                      "trx_set_supersample_tiers", "trx_set_debug_node_counts", "trx_set_cell_packing_below",
-                     "trx_set_row_order"):
+                     "trx_set_row_order", "trx_set_whole_trips"):
             fn = getattr(L, name)
             fn.restype = c_int
             fn.argtypes = [c_int]
@@ -207,6 +207,8 @@ def _load(path, testing):
         L.trx_debug_capture_buffers.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long)]
         L.trx_debug_row_order.restype = c_int
         L.trx_debug_row_order.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long), _vp, _vp, _vp]
+        L.trx_debug_whole_trips.restype = c_int
+        L.trx_debug_whole_trips.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long), c_int]
     return L
 
 
@@ -418,6 +420,16 @@ def debug_row_order():
                                 blocks.ctypes.data))
     lists = lists.reshape(64, cap.value)
     return counts.reshape(16, 4), [lists[s, :max(0, min(int(counts[s]), cap.value))].copy() for s in range(64)], blocks
+
+
+def debug_whole_trips(reset=False):
+    """Testing library only (trx_debug_whole_trips): the 64-cell trips of pass 1 that the stencil instantiation filed whole
+    and those it walked cell by cell on the current device since the last reset, as (whole, walked)."""
+    L = lib()
+    assert L.trx_testing, "debug_whole_trips needs use_testing_library()"
+    whole, walked = ctypes.c_long(0), ctypes.c_long(0)
+    check(L.trx_debug_whole_trips(ctypes.byref(whole), ctypes.byref(walked), 1 if reset else 0))
+    return whole.value, walked.value
 
 
 def lnl_batch_weighted(model, flags, time_d, flux_d, inv_var_d, params_d, exptime, nsamples, sec_limit=float("inf"),

@@ -90,6 +90,7 @@ struct RowsArgs {
     const double* inv_var;
     double sec_limit;
     int accumulate;
+    int whole_trips;   // trx_set_whole_trips (read by the testing library's kernels only): see window_trips
     // Cost-ordered rows (one row per wave, full evaluation of a likelihood launch; null: rows as they come): rowc_kernel
     // files every row under its cost bucket, cells_kernel's position v takes the v-th row of that order (row_order_at)
     int* order;        // [kOrderSegs counters, kOrderStride ints apart | kOrderSegs lists of order_cap(n) row numbers]
@@ -195,6 +196,22 @@ __device__ __forceinline__ void add_row_stat(int which, unsigned count)
 {
     if (count) atomicAdd(&g_row_stats[which][(blockIdx.x + 41u * blockIdx.y) & (kStatShards - 1)][0], (unsigned long long)count);
 }
+
+// Testing library only (include/trx_debug.h): the switch of the whole trips of pass 1 (window_trips; the product library
+// always files them) and two counters like the ones above -- the trips of the stencil instantiation's pass 1 that were
+// filed whole and those that were walked cell by cell; a wave adds its totals once, when it leaves.
+#ifdef TRX_TESTING
+__device__ unsigned long long g_trip_stats[2][kStatShards][kStatPad];      // [0] whole, [1] walked
+__device__ __forceinline__ void add_trip_stat(int which, unsigned count)
+{
+    if (count) atomicAdd(&g_trip_stats[which][(blockIdx.x + 41u * blockIdx.y) & (kStatShards - 1)][0], (unsigned long long)count);
+}
+__device__ __forceinline__ bool whole_trips_on(const RowsArgs& a) { return a.whole_trips != 0; }
+#define TRX_TRIP_STAT(var) ++var
+#else
+__device__ __forceinline__ bool whole_trips_on(const RowsArgs&) { return true; }
+#define TRX_TRIP_STAT(var)
+#endif
 
 // radius-ratio rule of the reference (likelihoods.py:122-123 scalar, :406/:418 vector)
 __device__ __forceinline__ double k_rule(double k, bool scalar_rule)
@@ -1102,6 +1119,26 @@ __device__ __forceinline__ void wave_sync()
 // so the in-window list is the same cells in the same order.  Every trip is kept -- the full scan -- when the window
 // wraps round +-pi (wide windows, the hull of two passages of a very eccentric orbit), when a cell is too small a step
 // for the margin, and when anything is NaN (every comparison below is false).
+//
+// `whole` (TRX_WHOLE_TRIPS): the trips ALL of whose cells are in-window cells, which pass 1 files without looking at them
+// -- most of the walked trips: a config-1 row's 760 in-window cells are 13 walked trips, and each of their cells paid the
+// time load, the phase, reduce_2pi, the slack, the compares, the ballot and the list address to learn "yes".  The phases
+// qa, qb of the trip's OWN first and last cell (no cell added on either side), same epoch n: the trip is whole when 2 pi n
+// + wlo + 8 err <= qa and qb <= 2 pi n + whi - 8 err.  Why every cell of it then passes the exact test: (i) the phase of
+// the grid is monotone in the cell index (nmot, dt > 0), so every cell's lies in [qa, qb] but for what the arithmetic is
+// off by, which `err` bounds for the cell's phase as computed by pass 1 and for qa, qb as computed here -- 2 err of the 8;
+// (ii) the cell's phase is therefore within (wlo, whi) of 2 pi n, and |wlo|, |whi| < pi - 1e-6 with the phase below 1e8
+// makes n the multiple reduce_2pi rounds to: its dMc is the phase less 2 pi n, again to within err, inside [wlo, whi];
+// (iii) the per-cell test accepts all of [wlo - slack, whi + slack], slack >= 0.  A subset of the trips the exact test
+// would file completely, lanes in cell order: the same list.  Under every condition that keeps all trips above -- a window
+// that wraps, NaN, too small a step -- no trip is whole; nor is any when the kernel does not come here at all (a stale
+// memo, radius 0).  A window pass has at most 32 trips, so the whole trips ride in the HIGH word of the mask returned (bit
+// 32 + L for trip L) and the trips to look at keep the low word: the stencil instantiation has no scalar register pair to
+// spare for a second mask (its spilled scalars fill their vector registers' lanes; a pair more sent a VGPR to scratch).
+#ifndef TRX_WHOLE_TRIPS
+#define TRX_WHOLE_TRIPS 1
+#endif
+static_assert(!TRX_WHOLE_TRIPS || kCellsWindowLong <= 32 * 64, "window_trips: whole trips in the mask's high word");
 __device__ __forceinline__ unsigned long long window_trips(const double* __restrict__ tl, int n_time, int win0, int win1, int lane,
                                                            double nmot, double t0, double wlo, double whi)
 {
@@ -1120,7 +1157,13 @@ __device__ __forceinline__ unsigned long long window_trips(const double* __restr
     const double pa = nmot * (fma((double)(ja - 1), dt, tg0) - t0);
     const double pb = nmot * (fma((double)(jb + 1), dt, tg0) - t0);
     const double ep = ceil((pa - whi) * 0.15915494309189533577);
-    return __ballot(lane < ntrip && fma(ep, kTwoPi, wlo) <= pb);
+    const unsigned long long look = __ballot(lane < ntrip && fma(ep, kTwoPi, wlo) <= pb);
+    if (!TRX_WHOLE_TRIPS) return look;
+    const double qa = nmot * (fma((double)ja, dt, tg0) - t0);
+    const double qb = nmot * (fma((double)jb, dt, tg0) - t0);
+    const double margin = 8.0 * err;
+    const unsigned long long whole = __ballot(lane < ntrip && fma(ep, kTwoPi, wlo) + margin <= qa && qb <= fma(ep, kTwoPi, whi) - margin);
+    return look | (whole << 32);
 }
 
 // Rows per wave of the passes of the bounded evaluation over LISTED rows (batched variant: the probe pass, part 2, and
@@ -1336,6 +1379,9 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
     // of the rows, whose blocks then stay in that XCD's L2
     const long v0 = (long)(blockIdx.x & 7) + 8 * ((long)(blockIdx.x >> 3) * W + wave);
     unsigned n_skipped = 0, n_pruned = 0;          // this wave's rows for trx_skipped_rows / trx_pruned_rows
+#ifdef TRX_TESTING
+    unsigned n_whole = 0, n_walked = 0;            // ... and its pass-1 trips for trx_debug_whole_trips (ST)
+#endif
     for (long v = v0; v < 8 * positions; v += (long)gridDim.x * W) {
         RowsArgs a_again;
         if (kReload == 2) {
@@ -1504,10 +1550,15 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
             int nw = 0;
             // (uniform grid: the trips that can hold an in-window cell, window_trips; a trip that cannot adds the flat
             // model's chi^2 of its 64 stamps -- one number, from the launch header -- and is not walked)
-            unsigned long long trips = ~0ull;
+            // (... and a trip that holds nothing but in-window cells is filed as it stands: `whole`, window_trips)
+            // (its bit 32 up, which no trip of a pass reaches)
+            static_assert(!ST || LONG, "the stencil instantiation: one row per wave (window_trips: 32 trips a pass)");
+            constexpr bool kWholeTrips = TRX_WHOLE_TRIPS && ST;
+            unsigned long long trips = kWholeTrips ? 0xffffffffull : ~0ull;
             if (ST && st_radius > 0.0) {
                 const RowC& c = (LONG && !TRX_LONG_ROWS_IN_LDS) ? cu : rows[0];
                 trips = window_trips(tl, n_time, win0, win1, lane, c.nmot, c.t0, rows[0].wlo, rows[0].whi);
+                if (kWholeTrips && !whole_trips_on(a)) trips &= 0xffffffffull;
                 if (MODE == MODE_LNL && lane < ((win1 - win0 + 63) >> 6) && !mask_bit(trips, lane))
                     lacc += a.rowc[n * kRowDoubles + kHdrTrip + (win0 >> 6) + lane];
             }
@@ -1518,6 +1569,18 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                     if (MODE == MODE_GRID && valid) a.out[(size_t)base * n_time + cell] = a.debug_nodes ? 0.0 : hmout[0];
                     continue;
                 }
+                if (kWholeTrips && ((trips >> (32 + ((c0 - win0) >> 6))) & 1ull)) {
+                    // every valid lane's cell is an in-window cell: lane order is list order (the census's 0 as below)
+                    // (the lane's number counted afresh -- two instructions -- as the trips below count their places: with
+                    // `lane` itself the compiler keeps a list address per lane for the whole kernel, two VGPRs that this
+                    // instantiation does not have -- 12 B of scratch)
+                    if (MODE == MODE_GRID && a.debug_nodes && valid) a.out[(size_t)base * n_time + cell] = 0.0;
+                    if (valid) winlist[nw + lanes_below(~0ull)] = (unsigned short)(cell - win0);
+                    nw += (win1 - c0 < 64) ? win1 - c0 : 64;
+                    TRX_TRIP_STAT(n_whole);
+                    continue;
+                }
+                TRX_TRIP_STAT(n_walked);
                 int rr = 0, j = valid ? cell : 0;
                 if (!LONG) {
                     rr = valid ? (int)(((float)cell + 0.5f) * inv_nt) : (nb - 1);
@@ -1975,6 +2038,9 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
     if (lane == 0) {
         add_row_stat(0, n_skipped);
         add_row_stat(1, n_pruned);
+#ifdef TRX_TESTING
+        if (ST) { add_trip_stat(0, n_whole); add_trip_stat(1, n_walked); }
+#endif
     }
 #ifdef TRX_TAIL_TIMERS
     if (LONG && lane == 0) {

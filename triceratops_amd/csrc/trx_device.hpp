@@ -40,7 +40,8 @@ __device__ __forceinline__ void census_add(int slot, unsigned long long n = 1ull
 // census slots
 constexpr int kCenBatch = 0, kCenWindowTrip = 1, kCenChunk0 = 2, kCenChunk1 = 3, kCenPass = 4, kCenPairTrip = 5,
               kCenPairLanes = 6, kCenFluxTrip = 7, kCenAgmTrip = 8, kCenKeplerFullPair = 9, kCenKeplerFullPlan = 10,
-              kCenFluxLanes = 11, kCenContactTrip = 12, kCenCrossingTrip = 13, kCenInsideTrip = 14;
+              kCenFluxLanes = 11, kCenContactTrip = 12, kCenCrossingTrip = 13, kCenInsideTrip = 14,
+              kCenAgmLanes = 15, kCenCelCall = 16, kCenCelLanes = 17;      // cel_pair: AGM trips per lane against trips per wave
 
 constexpr double kPi = 3.14159265358979323846264338327950288;
 constexpr double kTwoPi = 6.28318530717958647692528676655900577;
@@ -232,6 +233,8 @@ __device__ __forceinline__ double cel_pair(double kc, double a1, double b1, doub
 {
     double e = kc, em = 1.0, q = kc;
     double p1 = 1.0;
+    TRX_CENSUS_ADD(kCenCelCall, 1);
+    TRX_CENSUS_ADD(kCenCelLanes, (unsigned long long)__popcll(__ballot(1)));
     // one Bulirsch step; true when the kc/em recurrence has converged
     auto step = [&]() -> bool {
         const double r = rcp_fast(p1 * pp);
@@ -259,6 +262,7 @@ __device__ __forceinline__ double cel_pair(double kc, double a1, double b1, doub
 #pragma unroll 1
     for (int it = 0; it < 20; ++it) {
         TRX_CENSUS_ADD(kCenAgmTrip, 1);
+        TRX_CENSUS_ADD(kCenAgmLanes, (unsigned long long)__popcll(__ballot(1)));
         if (step()) break;
         if (step()) break;
     }

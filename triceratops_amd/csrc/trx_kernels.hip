@@ -332,6 +332,7 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
     a.rS = 1.0 / a.dS;
     a.nbatch = 8 * batch_plan(a.n, a.B).P;          // wave positions of the launch (batch_plan)
     a.debug_bug = knob_debug_bug();
+    a.whole_trips = knob_whole_trips();
     a.mark_unwritten = (MODE == MODE_LNL && !a.inv_var) ? 1 : 0;     // (a weighted launch may ADD to out[]: never marked)
     bool tiers_ok = false;
     if (tier_device(a.S, a.tiers, &a.tier_xw, &tiers_ok)) return fail(TRX_ERR_HIP, "tier table upload failed%s", "", 0);
@@ -1411,6 +1412,33 @@ int trx_set_debug_node_counts(int on)
 int trx_set_row_order(int on)
 {
     g_knob_row_order = on ? 1 : 0;
+    return TRX_OK;
+}
+
+/* (tests) 0: pass 1 of the stencil instantiation tests every cell of a walked trip */
+int trx_set_whole_trips(int on)
+{
+    g_knob_whole_trips = on ? 1 : 0;
+    return TRX_OK;
+}
+
+/* (tests) the pass-1 trips filed whole / walked cell by cell on the current device since the last reset */
+int trx_debug_whole_trips(long* whole, long* walked, int reset)
+{
+    static unsigned long long host[2][kStatShards][kStatPad];
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    TRX_HIP(hipDeviceSynchronize());
+    TRX_HIP(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trip_stats), sizeof(host), 0));
+    long sum[2] = {0, 0};
+    for (int w = 0; w < 2; ++w)
+        for (int i = 0; i < kStatShards; ++i) sum[w] += (long)host[w][i][0];
+    if (whole) *whole = sum[0];
+    if (walked) *walked = sum[1];
+    if (reset) {
+        memset(host, 0, sizeof(host));
+        TRX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_trip_stats), host, sizeof(host), 0));
+    }
     return TRX_OK;
 }
 
