@@ -499,7 +499,8 @@ typedef struct {
      * use_philox (TRX_ERR_ARG otherwise).  Integer sums: exact, independent of order, the block repeats bit for bit.  A
      * branch whose lnZ is +-inf or NaN gets TRX_WARP_BRANCH zeros.  The bounded evaluation stays on (an abandoned draw
      * lies more than 90 below X: weight 0 either way); the record is that of the call without warp_hist, bit for bit.
-     * In trx_star_enqueue such a call joins a launch chain like any other (one more launch per chain). */
+     * In trx_star_enqueue such a call joins a launch chain like any other (one more launch per chain).  The same block
+     * from chi^2/2 values a caller computed outside this chain: trxw_hist_from_halfchi2 (include/trx_warp.h). */
     unsigned long long* warp_hist;
     /* Posterior samples: post_rows = M > 0 draws M of the branch's masked draws in proportion to their weight in the
      * evidence, w_i = exp(x_i - X) with x_i = -ln(sigma) - 0.5 ln(2 pi) - chi2half_i (+ lnprior_i), X = max x_i, and

@@ -38,6 +38,8 @@ ABI_SYMBOLS = (
     "trx_draw_scenario", "trx_draw_args_size", "trx_scenario_evidence", "trx_scenario_enqueue", "trx_star_enqueue",
     "trx_scenario_args_size", "trx_release_scratch", "trx_version", "trx_last_error", "trx_device_count",
 )
+# ... include/trx_warp.h (both libraries: the weight histogram on its own, prefix trxw_)
+WARP_SYMBOLS = ("trxw_hist_from_halfchi2",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -177,6 +179,8 @@ def _load(path, testing):
     L.trx_posterior_from_halfchi2.restype = c_int
     L.trx_posterior_from_halfchi2.argtypes = [_vp, _vp, c_long, c_double, c_int, ctypes.c_ulonglong, _vp, _vp, _vp,
                                               c_size_t, _vp]
+    L.trxw_hist_from_halfchi2.restype = c_int
+    L.trxw_hist_from_halfchi2.argtypes = [_vp, _vp, _vp, _vp, c_long, c_double, _vp, _vp, c_size_t, _vp]
     L.trx_grid_quantiles.restype = c_int
     L.trx_grid_quantiles.argtypes = [_vp, c_long, c_int, _vp, _vp, c_long, _vp, c_int, _vp, _vp]
     L.trx_lnl_batch_host.restype = c_int
@@ -686,6 +690,25 @@ def posterior_from_halfchi2(h_d, lnprior_d, lnsigma, rows, seed):
                                                 pos.data_ptr() if rows else None, hdr.data_ptr(),
                                                 ws.data_ptr(), ws.numel() * 8, _stream(h_d)))
     return pos, hdr
+
+
+def warp_hist_from_halfchi2(draw_args, h_d, lnprior_d, idx_d, lnsigma):
+    """The weight histogram of one branch from device chi^2/2 values (trxw_hist_from_halfchi2, include/trx_warp.h): a device
+    int64[WARP_BRANCH] -- word 0 X's bits, word 1 the rows with weight, words 8.. the [WARP_DIMS][WARP_BINS] sums of
+    floor(w 2^32) over the bins of the draws' pre-map uniforms.  draw_args: the ctypes trx_draw_args the draws were made
+    with (host; its seed and consumed slots); idx_d: the rows' draw indices (int64).  No sync."""
+    require_gpu()
+    device = h_d.device
+    assert idx_d.dtype == torch.int64 and idx_d.is_contiguous() and idx_d.numel() == h_d.numel()
+    assert h_d.dtype == torch.float64 and h_d.is_contiguous()
+    out = torch.empty(WARP_BRANCH, dtype=torch.int64, device=device)
+    ws = workspace(device)
+    with torch.cuda.device(device):
+        check(lib().trxw_hist_from_halfchi2(ctypes.addressof(draw_args), h_d.data_ptr() if h_d.numel() else None,
+                                                lnprior_d.data_ptr() if lnprior_d is not None else None,
+                                                idx_d.data_ptr() if idx_d.numel() else None, h_d.numel(), float(lnsigma),
+                                                out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(h_d)))
+    return out
 
 
 # The Monte-Carlo moments (lnM2, lnWmax) of the branches a lnZ_* call evaluates, on their way to sharding.run_units

@@ -36,6 +36,7 @@
 #include <atomic>
 
 #include "../../include/trx.h"
+#include "../../include/trx_warp.h"
 #include "trx_device.hpp"
 #include "trx_internal.hpp"
 #include "trx_knobs.hpp"
@@ -681,6 +682,38 @@ extern "C" int trx_posterior_from_halfchi2(const double* halfchi2, const double*
     p.xmax = reinterpret_cast<double*>(ws + trx::kPostWsSums + trx::kPostWsCounts);
     p.out_pos = out_pos; p.out_hdr = out_hdr;
     if (trx::post_launch(p, true, static_cast<hipStream_t>(stream)) != TRX_OK) return trx::fail_hip(hipErrorLaunchFailure);
+    return TRX_OK;
+}
+
+extern "C" int trxw_hist_from_halfchi2(const trx_draw_args* draw, const double* halfchi2, const double* lnprior,
+                                       const long* idx, long n, double lnsigma, unsigned long long* out,
+                                       void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!draw || !out || n < 0 || n > 0x7fffffffL || (n > 0 && (!halfchi2 || !idx)) || !draw->use_philox) return TRX_ERR_ARG;
+    if (!workspace || workspace_bytes < trx_workspace_bytes() || trx_workspace_bytes() < trx::kPostWsBytes)
+        return TRX_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    // X, the largest log-weight: there is no evidence pass to take it from (as in trx_posterior_from_halfchi2)
+    trx::PostArgs p{};
+    p.h = halfchi2; p.lnprior = lnprior; p.n = n; p.N = n;
+    p.c0 = trx::lnl_c0(lnsigma);
+    p.tile_max = reinterpret_cast<double*>(ws + trx::kPostWsSums);
+    p.xmax = reinterpret_cast<double*>(ws + trx::kPostWsSums + trx::kPostWsCounts);
+    int tiles, per_tile;
+    trx::post_geometry(n, n, tiles, per_tile);
+    hipLaunchKernelGGL(trx::post_max_kernel, dim3(tiles), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(trx::post_x_kernel, dim3(1), dim3(256), 0, st, p);
+    if (hipGetLastError() != hipSuccess) return trx::fail_hip(hipErrorLaunchFailure);
+    TRXS_HIP(hipMemsetAsync(out, 0, sizeof(unsigned long long) * TRX_WARP_BRANCH, st));
+    trx::WarpHistArgs w{};
+    w.h = halfchi2; w.lnprior = lnprior; w.n = n; w.idx64 = idx; w.N = n;
+    w.slots = trx::warp_consumed_slots(*draw);
+    w.c0 = p.c0;
+    w.seed = draw->seed;
+    w.xmax = p.xmax;
+    w.out = out;
+    if (trx::warp_hist_launch(w, st) != TRX_OK) return trx::fail_hip(hipErrorLaunchFailure);
     return TRX_OK;
 }
 

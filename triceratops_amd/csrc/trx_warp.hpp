@@ -14,6 +14,8 @@
 //                           block in device scratch (zeroed on the stream before the launch); the caller's block is a copy
 //   warp_hist_chain_kernel  the same for every branch of a launch chain that wants a histogram: the branch is the grid's
 //                           second dimension and picks its WarpHistArgs from a table in the chain's arena
+// trxw_hist_from_halfchi2 (trx_scenario.hip) is warp_hist_kernel on a caller's chi^2/2 values: the row count by value
+// (n_dev null), the draw indices as 64-bit integers (idx64), X found by post_max_kernel / post_x_kernel (trx_posterior.hpp).
 //
 // The bounded evaluation stays on, as for the posterior rows: a draw it abandoned reports a lower
 // bound of its chi^2/2 that puts it more than 90 below X -- beyond the cut at -80, weight 0 with and without the flag.
@@ -31,8 +33,10 @@ constexpr int kWarpHistBlocks = 256;       // workgroups per branch (256 threads
 struct WarpHistArgs {
     const double* h;          // chi^2/2 of the masked draws, list order
     const double* lnprior;    // null, or per row: position r (twin: N - 1 - r)
-    const long* n_dev;        // the number of rows
+    const long* n_dev;        // the number of rows on the device, or null: n
+    long n;
     const int* idx;           // the rows' draw indices
+    const long* idx64;        // ... or, when not null, the same as 64-bit integers (idx is not read then)
     long N;
     int twin;
     unsigned slots;           // bit d: slot d is consumed from the kernel's own generator
@@ -89,7 +93,7 @@ __device__ __forceinline__ void warp_hist_body(const WarpHistArgs& a, unsigned l
     const int tid = (int)threadIdx.x;
     for (int i = tid; i < TRX_WARP_DIMS * TRX_WARP_BINS; i += blockDim.x) lds[i] = 0ull;
     __syncthreads();
-    const long n = *a.n_dev;
+    const long n = a.n_dev ? *a.n_dev : a.n;
     unsigned long long rows = 0ull;
     for (long r = (long)blockIdx.x * blockDim.x + tid; r < n; r += (long)gridDim.x * blockDim.x) {
         double x = a.c0 - a.h[r];                                   // (lme_partial_body's expression: the same bits)
@@ -99,7 +103,7 @@ __device__ __forceinline__ void warp_hist_body(const WarpHistArgs& a, unsigned l
         rows += 1ull;
         const unsigned long long q = (unsigned long long)(fmin(exp(d), 1.0) * 4294967296.0);
         if (q == 0ull) continue;
-        const long i = (long)a.idx[r];
+        const long i = a.idx64 ? a.idx64[r] : (long)a.idx[r];
         double u0, u1;
         if (a.slots & (1u << 2 | 1u << 4 | 1u << 3)) {
             warp_uniform2(a.seed, i, 16u, u0, u1);

@@ -233,11 +233,17 @@ DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
 DATASET_OFFSETS = None
 DATASET_BASELINES = None
+# An importance map (WARP_GRIDS) applies to a datasets call as to any other: its draws are trx_draw_scenario's.  The weight
+# histogram of the library's own chain (WARP_HIST) does not exist here -- chi^2/2 is computed outside that chain -- so
+# DATASET_WARP_HIST = {}: every datasets call leaves {work unit: [branches][WARP_BRANCH] uint64 words} there, one
+# trxw_hist_from_halfchi2 per branch on the numbers its evidence is formed from (target.calc_probs_datasets_refined
+# opens it for the length of an adaptation pass).  The row layout of sharding.run_units does not change.
+DATASET_WARP_HIST = None
 
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -986,8 +992,10 @@ class _Scenario:
         # every masked draw evaluated to the end).  The operator chain below remains as the cross-check, the path of the
         # dump / trace hooks, and the replay of exact ties in the seeded numpy modes.
         if self.datasets is not None:
-            if self.warp is not None or self.want_hist:
-                raise NotImplementedError("an importance map / weight histogram together with datasets is not built")
+            # (an importance map goes through the operator chain's draw; the histogram of ITS weights is DATASET_WARP_HIST)
+            if self.want_hist:
+                raise NotImplementedError("WARP_HIST together with datasets is not built: the histogram of the library's "
+                                          "own chain; the datasets path leaves its histograms in DATASET_WARP_HIST")
             return self.run_operator_chain(is_host, ncol)
         if NATIVE and DUMP is None and _lib.TRACE is None and TABLE_ROWS <= TABLE_MAX_ROWS:
             return self._run_native(is_host, ncol)
@@ -1019,6 +1027,12 @@ class _Scenario:
         flags = self._flags(is_host)
         offsets = []       # (DATASET_OFFSETS: per branch the best draw's offsets, still on the device)
         coefs = []         # (DATASET_BASELINES: per branch and dataset the best draw's scaled coefficients, likewise)
+        hists = None       # (DATASET_WARP_HIST: per branch the weight histogram of its evidence, likewise)
+        if self.datasets is not None and DATASET_WARP_HIST is not None:
+            if not self.philox:
+                raise NotImplementedError("a weight histogram needs set_sampling('device'): the pre-map uniforms are "
+                                          "recomputed from the kernel's own generator")
+            hists = []
         branches = ((MODEL_TP, mask, False),) if a.planet else ((MODEL_EB, mask, False), (MODEL_EB_TWIN, mask2, True))
         for model, m, twin in branches:
             idx = torch.nonzero(m, as_tuple=False).flatten()
@@ -1032,6 +1046,8 @@ class _Scenario:
             if self.datasets is not None:
                 h = self._datasets_halfchi2(model, flags, block)
                 lnz = _lib.lnz_from_halfchi2(h, lp, N, float(np.log(self.sigma)))
+                if hists is not None:
+                    hists.append(_lib.warp_hist_from_halfchi2(a, h, lp, idx, float(np.log(self.sigma))))
             else:
                 h, lnz = _lib.lnz_scenario(model, flags, self.time, self.flux, self.sigma, block, self.exptime,
                                            self.nsamples, lp, N, float(np.log(self.sigma)))
@@ -1069,6 +1085,8 @@ class _Scenario:
                 res[-1]["posterior"] = None if post is None else self._posterior_dict(post.cpu().numpy(), ncol, twin)
         if offsets:
             self._leave_best_terms(offsets, coefs)
+        if hists is not None:
+            DATASET_WARP_HIST[getattr(_tls, "unit", None)] = torch.stack(hists).cpu().numpy().view(np.uint64)
         return res[0] if a.planet else (res[0], res[1])
 
     def _any_baseline(self):

@@ -249,6 +249,40 @@ class target:
                                       "'numpy-device'): this sampling mode returns no posterior rows")
         return
 
+    @staticmethod
+    def _datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs):
+        """the checked arguments of calc_probs_datasets: (Datasets, n_samples, calc_probs' keywords less verbose, verbose)"""
+        from . import fused
+        if evaluation not in fused.DATASET_EVALUATIONS:
+            raise ValueError("evaluation must be one of %s (got %r)" % (fused.DATASET_EVALUATIONS, evaluation))
+        for k in ("exptime", "nsamples"):
+            if k in calc_probs_kwargs:
+                raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
+        ds = Datasets(_validate_datasets(datasets))
+        n_samples = int(n_samples)
+        if not 0 <= n_samples <= fused.POST_MAX_ROWS:
+            raise ValueError("n_samples must lie in [0, %d]" % fused.POST_MAX_ROWS)
+        from .marginal_likelihoods import _sampling
+        if _sampling["mode"] == "numpy":
+            raise NotImplementedError("calc_probs_datasets needs a device sampling mode: set_sampling('device') or "
+                                      "'numpy-device'")
+        kw = dict(calc_probs_kwargs)
+        verbose = kw.pop("verbose", 1)
+        return ds, n_samples, kw, verbose
+
+    def _datasets_pass(self, ds, P_orb, kw, verbose, evaluation, n_samples=0, **dataset_switches):
+        """one pass of the datasets path over the target's work units: (units, rows, n_scen) for _finish.
+        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_WARP_HIST for the length of the pass."""
+        from . import fused
+        units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
+        if ds.has_offsets and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: use evaluation='grid'")
+        if ds.has_baselines and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: use evaluation='grid'")
+        with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, **dataset_switches):
+            rows = sharding.run_units(units, verbose=verbose, as_rows=True)
+        return units, rows, n_scen
+
     def calc_probs_datasets(self, datasets, P_orb, n_samples: int = 0, evaluation: str = "grid", **calc_probs_kwargs):
         """calc_probs on several light curves of one candidate, each with its own cadence and with per-point flux
         errors (no reference counterpart).
@@ -295,32 +329,11 @@ class target:
         without "baseline"; the whole attribute is None when no dataset has one.  `.dataset_offsets` reports the offset of
         a baseline dataset that has offset_sigma as well.  Not built: a multiplicative normalisation, baselines in the
         fused evaluation, calc_probs_many with datasets."""
-        from . import fused
-        if evaluation not in fused.DATASET_EVALUATIONS:
-            raise ValueError("evaluation must be one of %s (got %r)" % (fused.DATASET_EVALUATIONS, evaluation))
-        for k in ("exptime", "nsamples"):
-            if k in calc_probs_kwargs:
-                raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
-        ds = Datasets(_validate_datasets(datasets))
-        n_samples = int(n_samples)
-        if not 0 <= n_samples <= fused.POST_MAX_ROWS:
-            raise ValueError("n_samples must lie in [0, %d]" % fused.POST_MAX_ROWS)
-        from .marginal_likelihoods import _sampling
-        if _sampling["mode"] == "numpy":
-            raise NotImplementedError("calc_probs_datasets needs a device sampling mode: set_sampling('device') or "
-                                      "'numpy-device'")
-        kw = dict(calc_probs_kwargs)
-        verbose = kw.pop("verbose", 1)
-        units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
-        if ds.has_offsets and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: use evaluation='grid'")
-        if ds.has_baselines and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: use evaluation='grid'")
+        ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
         best_offsets = {} if ds.has_offsets else None
         best_baselines = {} if ds.has_baselines else None
-        with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, DATASET_OFFSETS=best_offsets,
-                            DATASET_BASELINES=best_baselines):
-            rows = sharding.run_units(units, verbose=verbose, as_rows=True)
+        units, rows, n_scen = self._datasets_pass(ds, P_orb, kw, verbose, evaluation, n_samples,
+                                                  DATASET_OFFSETS=best_offsets, DATASET_BASELINES=best_baselines)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
@@ -364,7 +377,6 @@ class target:
         Needs set_sampling("device") -- the numpy modes stage their uniforms, and a staged uniform is never mapped --
         and one rank."""
         from . import fused
-        from ._numerics import warp_refine
         n_adapt, n_samples = int(n_adapt), int(n_samples)
         if n_adapt < 0:
             raise ValueError("n_adapt must be >= 0")
@@ -376,6 +388,36 @@ class target:
             else:
                 self.calc_probs(time, flux_0, flux_err_0, P_orb, **kw)
 
+        kw_adapt = dict(kw)
+        verbose = kw_adapt.pop("verbose", 1)
+        if N_adapt is not None:
+            kw_adapt["N"] = int(N_adapt)
+
+        def adapt_pass():
+            units, n_scen = self._prepare(time, flux_0, flux_err_0, P_orb, **kw_adapt)
+            with fused.switches(WARP_HIST=True):
+                rows = sharding.run_units(units, verbose=verbose, as_rows=True)
+            hists = {}
+            for k, rec in enumerate(rows):
+                if rec is None:
+                    continue
+                hists[k] = rec[:, sharding.last_layout.hist]
+                if np.isnan(hists[k][:, 1]).any():        # (a row shorter than the table stays NaN there)
+                    raise NotImplementedError("calc_probs_refined needs the library's own chain "
+                                              "(set_sampling('device')): this pass returned no weight histograms")
+            return units, rows, n_scen, hists
+
+        self._refined("calc_probs_refined", n_adapt, adapt_pass, final, alpha, floor)
+        return
+
+    def _refined(self, who, n_adapt, adapt_pass, final, alpha, floor):
+        """The loop of calc_probs_refined and calc_probs_datasets_refined.  adapt_pass() runs one adaptation pass under
+        fused.WARP_GRIDS and returns (units, rows, n_scen, {work unit: its branches' weight histograms}); every unit's
+        grid is refined from its histogram (_numerics.warp_refine) and the pass enters `.refine_history`.  final() is
+        the plain call, run under the grids the adaptation left."""
+        from . import fused
+        from ._numerics import warp_refine
+
         def snapshot():
             return {"lnZ": np.array(self.lnZ), "ess": np.array(self.ess), "w_max_frac": np.array(self.w_max_frac)}
 
@@ -384,35 +426,57 @@ class target:
             self.refine_history = [snapshot()]
             return
         if not fused.threadable() or not fused.NATIVE:
-            raise NotImplementedError("calc_probs_refined needs set_sampling('device'): the numpy sampling modes stage "
-                                      "their uniforms, and a staged uniform is never mapped")
+            raise NotImplementedError("%s needs set_sampling('device'): the numpy sampling modes stage "
+                                      "their uniforms, and a staged uniform is never mapped" % who)
         if sharding._dist() is not None:
-            raise NotImplementedError("calc_probs_refined on several ranks is not built: the grids would have to follow "
-                                      "the schedule")
-        kw_adapt = dict(kw)
-        verbose = kw_adapt.pop("verbose", 1)
-        if N_adapt is not None:
-            kw_adapt["N"] = int(N_adapt)
+            raise NotImplementedError("%s on several ranks is not built: the grids would have to follow "
+                                      "the schedule" % who)
         grids = {}                       # work unit -> [7][65] edges (kept per (star, call), not per target)
         history = []
         with fused.switches(POSTERIOR_ROWS=0, WARP_GRIDS=grids):
             for _ in range(n_adapt):
-                units, n_scen = self._prepare(time, flux_0, flux_err_0, P_orb, **kw_adapt)
-                with fused.switches(WARP_HIST=True):
-                    rows = sharding.run_units(units, verbose=verbose, as_rows=True)
-                for k, rec in enumerate(rows):
-                    if rec is None:
-                        continue
-                    hist = rec[:, sharding.last_layout.hist]
-                    if np.isnan(hist[:, 1]).any():        # (a row shorter than the table stays NaN there)
-                        raise NotImplementedError("calc_probs_refined needs the library's own chain "
-                                                  "(set_sampling('device')): this pass returned no weight histograms")
+                units, rows, n_scen, hists = adapt_pass()
+                for k, hist in hists.items():
                     grids[k] = warp_refine(grids.get(k, fused.warp_identity()), hist, alpha=alpha, floor=floor)
                 self._finish(units, rows, n_scen, warn=False, layout=sharding.last_layout)
                 history.append(snapshot())
             final()
             history.append(snapshot())
         self.refine_history = history
+        return
+
+    def calc_probs_datasets_refined(self, datasets, P_orb, n_adapt: int = 2, N_adapt: int = None, n_samples: int = 0,
+                                    evaluation: str = "grid", alpha: float = 0.5, floor: float = 0.1,
+                                    **calc_probs_kwargs):
+        """calc_probs_datasets by adaptive importance sampling: calc_probs_refined's loop on the
+        datasets path (section 14).  n_adapt adaptation passes of N_adapt draws each (default: N) evaluate the datasets
+        under each work unit's importance map, take the histogram of the evidence's weight over the bins of the draws'
+        uniforms from the chi^2/2 values of that pass (trxw_hist_from_halfchi2, fused.DATASET_WARP_HIST) and refine
+        the map; best-draw offsets and baselines are not computed in them.  The final pass is calc_probs_datasets under
+        the maps the adaptation left: it fills `.probs`, `.FPP`, `.lnZ_err`, `.posterior` (n_samples > 0), `.sigma_ref`,
+        `.dataset_offsets` and `.dataset_baselines` as calc_probs_datasets does, and only it enters the result, so the
+        estimate is unbiased.  `.refine_history` holds, per pass, the rows' lnZ, ess and w_max_frac.  n_adapt = 0 is
+        calc_probs_datasets, bit for bit.  Both evaluations ("grid", "fused") feed the histogram the same way.
+
+        Needs set_sampling("device") and one rank."""
+        n_adapt = int(n_adapt)
+        if n_adapt < 0:
+            raise ValueError("n_adapt must be >= 0")
+        ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
+
+        def final():
+            self.calc_probs_datasets(datasets, P_orb, n_samples=n_samples, evaluation=evaluation, **calc_probs_kwargs)
+
+        kw_adapt = dict(kw)
+        if N_adapt is not None:
+            kw_adapt["N"] = int(N_adapt)
+
+        def adapt_pass():
+            hists = {}
+            units, rows, n_scen = self._datasets_pass(ds, P_orb, kw_adapt, verbose, evaluation, DATASET_WARP_HIST=hists)
+            return units, rows, n_scen, hists
+
+        self._refined("calc_probs_datasets_refined", n_adapt, adapt_pass, final, alpha, floor)
         return
 
     def posterior_summary(self, q=(0.16, 0.5, 0.84)):
