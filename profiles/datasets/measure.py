@@ -3,15 +3,16 @@
   python profiles/datasets/measure.py            the whole job: each GPU step a child process under its own time
                                                  limit, the next one only after the last ended well; writes
                                                  profiles/datasets/results.txt (or --out FILE)
-  python profiles/datasets/measure.py kernels    (a) chi2_grid_weighted_kernel and chi2_grid_kernel on the same 3.2 GB
+  python profiles/datasets/measure.py kernels    (a) the weighted reduction and chi2_grid_kernel on the same 3.2 GB
                                                  grid (200 000 rows x 2000 stamps, bench.py's size), timed with events
   python profiles/datasets/measure.py e2e        (b) TOI-465.01, 75 scenarios, N = 1e6: calc_probs against
                                                  calc_probs_datasets with one and with two datasets, each with
                                                  evaluation="grid" and evaluation="fused", alternating
   python profiles/datasets/measure.py routes     (c) the two calc_probs_datasets cases alone, both evaluations, three
                                                  passes each: the run the job traces for the kernel times of a pass
-  python profiles/datasets/measure.py rates      (d) chi2_grid_weighted_kernel, chi2_grid_offset_kernel and
-                                                 chi2_grid_baseline_kernel at K = 1 and 4 on the same 200 000 x 2000 grid
+  python profiles/datasets/measure.py rates      (d) chi2_rows_kernel with Chi2Plain, Chi2Offset and Chi2Baseline<K>
+                                                 at K = 1 and 4 (labelled as in earlier results: chi2_grid_weighted_kernel,
+                                                 _offset_, _baseline_) on the same 200 000 x 2000 grid
                                                  and at 1e6 x 100: the run the job traces for the kernels' rates
   python profiles/datasets/measure.py baseline_e2e   (e) two datasets of 50 points, N = 1e6: calc_probs_datasets with and
                                                  without polynomial_baseline(t, 1) + a flat offset on the second dataset
@@ -173,7 +174,7 @@ def rates_summary(trace):
         groups = {}
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
-            if "chi2_grid_" in name:
+            if "chi2_rows_kernel" in name:
                 groups.setdefault(name, []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
         for name, ns in groups.items():
             # (per kernel: six launches on the large grid, then -- the staged instantiations only fit there -- six on 1e6 x 100)
@@ -226,7 +227,7 @@ def routes_summary(trace):
     by their template arguments (cells_kernel<1, ...> writes the grid, a last argument `true` is the weighted fused
     variant), everything else is shared by the two evaluations"""
     def route(name):
-        if "chi2_grid_weighted" in name or "cells_kernel<1" in name or "sec_scan_kernel<64" in name:
+        if "chi2_rows_kernel" in name or "cells_kernel<1" in name or "sec_scan_kernel<64" in name:
             return "grid"
         for k in ("cells_kernel<0", "rowc_kernel<", "sec_scan_kernel<8"):
             if k in name:
@@ -260,8 +261,9 @@ def trace_summary(trace):
     for f in glob.glob(os.path.join(trace, "**", "*kernel_trace.csv"), recursive=True):
         groups = {}
         for row in csv.DictReader(open(f)):
-            if "chi2_grid" in row["Kernel_Name"]:
-                name = "chi2_grid_weighted_kernel" if "weighted" in row["Kernel_Name"] else "chi2_grid_kernel"
+            if "chi2_grid_kernel" in row["Kernel_Name"] or "chi2_rows_kernel" in row["Kernel_Name"]:
+                # (the weighted reduction keeps its label of earlier results: chi2_rows_kernel<STAGE, Chi2Plain>)
+                name = "chi2_grid_weighted_kernel" if "chi2_rows_kernel" in row["Kernel_Name"] else "chi2_grid_kernel"
                 groups.setdefault((name, row["Grid_Size_X"]), []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
         for (name, grid), ns in groups.items():
             big = len(ns) != 6 or name == "chi2_grid_kernel"      # (12 launches: six that write, then six that accumulate)

@@ -1,4 +1,4 @@
-"""chi2_grid_baseline_kernel<STAGE, K> (trx_chi2_grid_baseline): the weighted row reduction with a
+"""chi2_rows_kernel<STAGE, Chi2Baseline<K>> (trx_chi2_grid_baseline): the weighted row reduction with a
 linear baseline model sum_k c_k B_k[t] of the light curve marginalised in closed form,
     h = 0.5 max(S2 - b~^T M b~, 0),  coef = M b~,  S2 = sum w d^2,  b~_k = sum g_k d,  g_k = w B_k / sqrt(D_k),  M = A~^-1.
 
@@ -11,8 +11,8 @@ The yardstick is the same formula in np.longdouble on the grid the device holds,
   coef_out (scaled coefficients): 1e-12 x sqrt(K S2) / lambda_min + 1e-15 per entry;
   minv = 0: the bits of chi2_grid_weighted (S2 is formed term for term the same way; S2 - 0 = S2).
 Shapes: as many stamps as terms and one more, lanes without stamps, one pair a lane (63, 64, 65), odd lengths (every second
-row off its 16-byte boundary), both sides of each K's LDS staging limit (1364, 1024, 818, 682 stamps); odd row counts with
-two rows in flight.  Columns u^p, p = 0 .. K - 1; the data shifted by 0, 3 and 100 mean sigma times (1 + u); flat priors
+row off its 16-byte boundary), both sides of each K's LDS staging limit (1364, 1024, 818, 682 stamps); odd row counts; and
+(CAPPED) more rows than the capped grid has waves, so that a wave's trip takes two rows, an odd remainder of them.  Columns u^p, p = 0 .. K - 1; the data shifted by 0, 3 and 100 mean sigma times (1 + u); flat priors
 and A~ + I."""
 import ctypes
 import math
@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+from test_gpu_reductions import chi2_rows_blocks
 from triceratops_amd import _lib, synth
 from triceratops_amd.datasets import linear_system
 
@@ -29,6 +30,7 @@ pytestmark = pytest.mark.gpu
 KS = [1, 2, 3, 4]
 STAGE_MAX = {1: 1364, 2: 1024, 3: 818, 4: 682}
 NS = [1, 2, 3, 257]
+CAPPED = [(4, 65, 8195), (1, 1364, 5123)]          # (K, n_time, n): 8 blocks a CU; 5 at K = 1's staged limit
 SIGMA = 1e-3
 INF = float("inf")
 LD = np.longdouble
@@ -122,9 +124,12 @@ def _case(K, n_time, n):
     return _cases[key]
 
 
-@pytest.mark.parametrize("K, n_time", [(K, t) for K in KS for t in _n_times(K)])
-def test_baseline_reduction_matches_longdouble(K, n_time):
-    for n in NS:
+@pytest.mark.parametrize("K, n_time, ns", [pytest.param(K, t, NS, id="%d-%d" % (K, t)) for K in KS for t in _n_times(K)]
+                         + [pytest.param(K, t, [n], id="%d-%d-%d" % (K, t, n)) for K, t, n in CAPPED])
+def test_baseline_reduction_matches_longdouble(K, n_time, ns):
+    for n in ns:
+        if (K, n_time, n) in CAPPED:
+            assert 4 * chi2_rows_blocks(n, n_time, 2 + K, STAGE_MAX[K]) < n
         c = _case(K, n_time, n)
         for k, sh in c["shifts"].items():
             f_d = _lib.dev(sh["flux"])

@@ -1,4 +1,4 @@
-"""chi2_grid_offset_kernel<STAGE> (trx_chi2_grid_offset): the weighted row reduction with a constant
+"""chi2_rows_kernel<STAGE, Chi2Offset> (trx_chi2_grid_offset): the weighted row reduction with a constant
 baseline offset of the light curve marginalised in closed form,
     h = 0.5 (S2 - S1^2 / (S0 + prior_prec)),  offset = S1 / (S0 + prior_prec),  S0 = sum w, S1 = sum w d, S2 = sum w d^2.
 
@@ -8,7 +8,8 @@ The yardstick is the same formula in np.longdouble on the downloaded grid.  Bars
   offset_out: 1e-12 relative + 1e-15;
   prior_prec = +inf: the bits of chi2_grid_weighted (S1^2 / inf = 0; S2 is formed term for term the same way).
 Shapes: lanes without stamps (1, 2), one pair a lane (63, 64, 65 pairs are 31 .. 32), odd lengths (every second row off
-its 16-byte boundary), both sides of the LDS staging limit (2048, 2049); odd row counts with two rows in flight."""
+its 16-byte boundary), both sides of the LDS staging limit (2048, 2049); odd row counts; and (CAPPED) more rows than
+the capped grid has waves, so that a wave's trip takes two rows, an odd remainder of them."""
 import ctypes
 import math
 
@@ -16,12 +17,14 @@ import numpy as np
 import pytest
 import torch
 
+from test_gpu_reductions import chi2_rows_blocks
 from triceratops_amd import _lib, synth
 
 pytestmark = pytest.mark.gpu
 
 N_TIMES = [1, 2, 63, 64, 65, 129, 333, 2048, 2049]
 NS = [1, 2, 3, 257]
+CAPPED = [(65, 8195), (2048, 5123)]          # (n_time, n): 8 blocks a CU; 5 at the staged limit's 32 KB of LDS a block
 SIGMA = 1e-3
 INF = float("inf")
 LD = np.longdouble
@@ -65,9 +68,10 @@ def _bar(S2):
     return 1e-12 * 0.5 * S2.astype(np.float64) + 1e-12
 
 
-@pytest.mark.parametrize("n", NS)
-@pytest.mark.parametrize("n_time", N_TIMES)
+@pytest.mark.parametrize("n_time, n", [(t, n) for n in NS for t in N_TIMES] + CAPPED)
 def test_offset_reduction_matches_longdouble(n_time, n):
+    if (n_time, n) in CAPPED:
+        assert 4 * chi2_rows_blocks(n, n_time) < n
     c = _case(n_time, n)
     for k, (flux, S1, S2) in c["sums"].items():
         f_d = _lib.dev(flux)
@@ -134,17 +138,19 @@ def test_secondary_rule_is_the_weighted_kernels(n_time):
         assert np.array_equal(_lib.chi2_grid_offset(f_d, c["w_d"], g, c["S0"], 0.0, sec_d, INF).cpu().numpy(), free)
 
 
-@pytest.mark.parametrize("n_time", [64, 333, 2049])
-def test_accumulates_onto_finite_inf_and_nan(n_time):
-    c = _case(n_time, 257)
+@pytest.mark.parametrize("n_time, n", [(64, 257), (333, 257), (2049, 257), CAPPED[0]], ids=["64", "333", "2049", "65-8195"])
+def test_accumulates_onto_finite_inf_and_nan(n_time, n):
+    if (n_time, n) in CAPPED:
+        assert 4 * chi2_rows_blocks(n, n_time) < n
+    c = _case(n_time, n)
     f_d = _lib.dev(c["sums"][3.0][0])
     h = _lib.chi2_grid_offset(f_d, c["w_d"], c["g_d"], c["S0"], 0.0).cpu().numpy()
-    out0 = np.random.default_rng(n_time).uniform(0.0, 50.0, 257)
+    out0 = np.random.default_rng(n_time).uniform(0.0, 50.0, n)
     out0[::5] = np.inf
     out0[1::7] = np.nan
     fin = np.isfinite(out0)
     assert fin.sum() > 100 and np.isposinf(out0).sum() > 10 and np.isnan(out0).sum() > 10
-    off = torch.empty(257, dtype=torch.float64, device=f_d.device)
+    off = torch.empty(n, dtype=torch.float64, device=f_d.device)
     acc = _lib.chi2_grid_offset(f_d, c["w_d"], c["g_d"], c["S0"], 0.0, out=_lib.dev(out0).clone(),
                                 offset_out=off).cpu().numpy()
     assert np.array_equal(acc[fin], out0[fin] + h[fin])
@@ -154,7 +160,7 @@ def test_accumulates_onto_finite_inf_and_nan(n_time):
     _lib.chi2_grid_offset(f_d, c["w_d"], c["g_d"], c["S0"], 0.0, offset_out=off2)
     assert torch.equal(off, off2)
     # with a rule of its own: +inf from either side
-    sec = np.linspace(0.0, 1.0, 257)
+    sec = np.linspace(0.0, 1.0, n)
     acc = _lib.chi2_grid_offset(f_d, c["w_d"], c["g_d"], c["S0"], 0.0, _lib.dev(sec), 0.5,
                                 out=_lib.dev(out0).clone()).cpu().numpy()
     assert np.array_equal(np.isposinf(acc), (np.isposinf(out0) | (sec >= 0.5)) & ~np.isnan(out0))

@@ -1,4 +1,4 @@
-"""Several light curves with per-point errors on the GPU: chi2_grid_weighted_kernel, the array
+"""Several light curves with per-point errors on the GPU: chi2_rows_kernel<STAGE, Chi2Plain>, the array
 path of lnL_*_p, and target.calc_probs_datasets against calc_probs (one dataset, one sigma) and against the CPU oracle
 (two cadences, errors that differ from point to point).
 

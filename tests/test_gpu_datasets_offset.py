@@ -46,11 +46,11 @@ class _Spy:
 
         def halfchi2(scen, model, flags, block):
             h = real_h(scen, model, flags, block)
-            kept, scen.offsets = scen.offsets, [None] * len(scen.offsets)
+            kept, scen.datasets = scen.datasets, [d._replace(offset=None) for d in scen.datasets]
             try:
                 spy.plain.append(real_h(scen, model, flags, block).cpu().numpy())
             finally:
-                scen.offsets = kept
+                scen.datasets = kept
             return h
 
         def lnz(h_d, lp_d, n_total, lnsigma):

@@ -1,6 +1,6 @@
 """The HBM-bound reductions of triceratops_amd/csrc/trx_reduce.hpp against extended-precision host references: every
 arm of the log-mean-exp fold (lme_partial_kernel<false> + lme_final_kernel), both of its load paths, the moments that
-ride through it, and the two chi^2 row reductions (chi2_grid_kernel, chi2_grid_weighted_kernel<STAGE>) at the sizes
+ride through it, and the two chi^2 row reductions (chi2_grid_kernel, chi2_rows_kernel<STAGE, Chi2Plain>) at the sizes
 and alignments where their index arithmetic changes.  Everything runs on the production library.
 
 The reference (_reference) is numpy only: m = max, s = sum exp(x - m), s2 = sum exp(2 (x - m)) in np.longdouble
@@ -31,7 +31,7 @@ Tolerance of the chi^2 rows: relative, (ceil(n_time / 128) + 12) * 2^-52.  chi2_
 term twice (d * d, the division), adds a lane's terms in a chain of at most ceil(n_time / 64) + 1 steps and the lanes
 in a butterfly of 6; all terms are >= 0, so the relative error of the sum is at most the number of roundings on the
 longest path times 2^-53: (ceil(n_time / 64) + 11) * 2^-53 with the reference's own rounding, which is below the
-bound.  chi2_grid_weighted_kernel rounds w * d once and every fma once, two per stamp pair of a lane, + 1 for an odd
+bound.  chi2_rows_kernel rounds w * d once and every fma once, two per stamp pair of a lane, + 1 for an odd
 last stamp: the same count.  The float64 difference flux - model is the reference's too (it is the kernel's input to
 the reduction); it is squared and summed in long double.
 
@@ -461,14 +461,29 @@ def test_chi2_grid_even_n_time_with_misaligned_pointers(which, n_time):
         _assert_rows(got, want, n_time, "chi2_grid/offset-%s %dx%d" % (which, n, n_time))
 
 
-@pytest.mark.parametrize("n_time", [2047, 2048, 2049, 2050, 4099])
+def chi2_rows_blocks(n, n_time, vectors=2, stage_max=2048):
+    """the grid of a weighted row reduction by the launcher's rule (trx_kernels.hip, chi2_rows_launch): one wave a row,
+    four a block, as many blocks as stay resident on 256 CUs -- 8 a CU, fewer where the `vectors` staged vectors fill the
+    160 KB of LDS"""
+    lds = vectors * ((n_time + 1) & ~1) * 8 if n_time <= stage_max else 0
+    per_cu = min(8, (160 * 1024) // lds) if lds else 8
+    return min((n + 3) // 4, 256 * per_cu)
+
+
+CHI2W_CAPPED = 8195          # more rows than the capped grid has waves at 65 and 2047 stamps: a trip takes two rows
+
+
+@pytest.mark.parametrize("n_time", [65, 2047, 2048, 2049, 2050, 4099])
 def test_chi2_grid_weighted_on_both_sides_of_the_staging_limit(n_time):
     """n_time <= 2048 stages flux and inv_var in LDS (STAGE), above it they are read through the caches; odd and even on
     either side.  The written value, the value added to `out`, the secondary-depth rule with a NaN depth, and a grid
     view offset by one double -- which must give the aligned grid's bits (trx_reduce.hpp: the order of summation of a
-    row is fixed by n_time alone)."""
+    row is fixed by n_time alone).  65 and 2047 stamps also with more rows than the capped grid has waves: the second
+    row of a trip, an odd remainder of them."""
     bound = _chi2_rel_bound(n_time)
-    for n in (1, 5, 9):
+    for n in {65: (CHI2W_CAPPED,), 2047: (1, 5, 9, CHI2W_CAPPED)}.get(n_time, (1, 5, 9)):
+        if n == CHI2W_CAPPED:
+            assert 4 * chi2_rows_blocks(n, n_time) < n
         rng, flux, grid = _chi2_inputs(n, n_time, 3)
         inv_var = 10.0 ** rng.uniform(4.0, 7.0, n_time)            # three decades
         f_d, w_d, g_d = _lib.dev(flux), _lib.dev(inv_var), _lib.dev(grid)

@@ -488,10 +488,10 @@ def chi2_grid(flux_d, grid_d, sigma):
     return out
 
 
-def chi2_grid_weighted(flux_d, inv_var_d, grid_d, secdepth_d=None, sec_limit=float("inf"), out=None):
-    """0.5 * sum_t inv_var[t] (flux[t] - grid[r][t])^2 per row of an [n][n_time] device grid (trx_chi2_grid_weighted);
-    +inf where secdepth_d[r] >= sec_limit.  out: an [n] fp64 device tensor to ADD the rows' values to (the next light
-    curve of an evidence over several); None: a fresh tensor.  Rows may start at any 8-byte boundary (a view's offset)."""
+def _chi2_rows(entry, flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out, *extra):
+    """What chi2_grid_weighted, chi2_grid_offset and chi2_grid_baseline share: the checks of the grid, the light curve, the
+    secondary depths and `out`, a fresh `out` unless one is given to add to, and the call of libtrx's `entry` -- `extra`:
+    its arguments between out_halfchi2 and the stream."""
     require_gpu()
     n, nt = grid_d.shape
     assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
@@ -504,10 +504,17 @@ def chi2_grid_weighted(flux_d, inv_var_d, grid_d, secdepth_d=None, sec_limit=flo
     if n == 0:
         return out                     # (an empty tensor has no address to pass)
     with torch.cuda.device(grid_d.device):
-        check(lib().trx_chi2_grid_weighted(flux_d.data_ptr(), inv_var_d.data_ptr(), grid_d.data_ptr(), nt, n,
-                                           secdepth_d.data_ptr() if secdepth_d is not None else None,
-                                           float(sec_limit), int(accumulate), out.data_ptr(), _stream(grid_d)))
+        check(getattr(lib(), entry)(flux_d.data_ptr(), inv_var_d.data_ptr(), grid_d.data_ptr(), nt, n,
+                                    secdepth_d.data_ptr() if secdepth_d is not None else None, float(sec_limit),
+                                    int(accumulate), out.data_ptr(), *extra, _stream(grid_d)))
     return out
+
+
+def chi2_grid_weighted(flux_d, inv_var_d, grid_d, secdepth_d=None, sec_limit=float("inf"), out=None):
+    """0.5 * sum_t inv_var[t] (flux[t] - grid[r][t])^2 per row of an [n][n_time] device grid (trx_chi2_grid_weighted);
+    +inf where secdepth_d[r] >= sec_limit.  out: an [n] fp64 device tensor to ADD the rows' values to (the next light
+    curve of an evidence over several); None: a fresh tensor.  Rows may start at any 8-byte boundary (a view's offset)."""
+    return _chi2_rows("trx_chi2_grid_weighted", flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out)
 
 
 def chi2_grid_offset(flux_d, inv_var_d, grid_d, sum_w, prior_prec, secdepth_d=None, sec_limit=float("inf"), out=None,
@@ -517,26 +524,10 @@ def chi2_grid_offset(flux_d, inv_var_d, grid_d, sum_w, prior_prec, secdepth_d=No
     their squares.  sum_w: sum(inv_var), from the host; prior_prec: 0 = flat prior, +inf = no offset (chi2_grid_weighted's
     bits).  offset_out: an [n] fp64 device tensor that receives S1 / (sum_w + prior_prec), or None.  The other arguments are
     chi2_grid_weighted's."""
-    require_gpu()
-    n, nt = grid_d.shape
-    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
-    assert flux_d.numel() == nt and inv_var_d.numel() == nt and flux_d.is_contiguous() and inv_var_d.is_contiguous()
-    assert secdepth_d is None or (secdepth_d.numel() == n and secdepth_d.is_contiguous())
-    assert offset_out is None or (offset_out.shape == (n,) and offset_out.dtype == torch.float64
+    assert offset_out is None or (offset_out.shape == (grid_d.shape[0],) and offset_out.dtype == torch.float64
                                   and offset_out.is_contiguous())
-    accumulate = out is not None
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
-    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
-    if n == 0:
-        return out                     # (an empty tensor has no address to pass)
-    with torch.cuda.device(grid_d.device):
-        check(lib().trx_chi2_grid_offset(flux_d.data_ptr(), inv_var_d.data_ptr(), grid_d.data_ptr(), nt, n,
-                                         secdepth_d.data_ptr() if secdepth_d is not None else None,
-                                         float(sec_limit), int(accumulate), out.data_ptr(), float(sum_w),
-                                         float(prior_prec), offset_out.data_ptr() if offset_out is not None else None,
-                                         _stream(grid_d)))
-    return out
+    return _chi2_rows("trx_chi2_grid_offset", flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out, float(sum_w),
+                      float(prior_prec), offset_out.data_ptr() if offset_out is not None else None)
 
 
 def chi2_grid_baseline(flux_d, inv_var_d, grid_d, wbasis_d, minv, secdepth_d=None, sec_limit=float("inf"), out=None,
@@ -547,30 +538,15 @@ def chi2_grid_baseline(flux_d, inv_var_d, grid_d, wbasis_d, minv, secdepth_d=Non
     upper triangle of M by rows, on the host (datasets.baseline_system); K = 1 .. 4.  coef_out: an [n][K] fp64 device
     tensor that receives the scaled posterior-mean coefficients M b, or None.  The other arguments are
     chi2_grid_weighted's."""
-    require_gpu()
     n, nt = grid_d.shape
-    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
-    assert flux_d.numel() == nt and inv_var_d.numel() == nt and flux_d.is_contiguous() and inv_var_d.is_contiguous()
-    assert secdepth_d is None or (secdepth_d.numel() == n and secdepth_d.is_contiguous())
     assert wbasis_d.dim() == 2 and wbasis_d.shape[1] == nt and wbasis_d.dtype == torch.float64 and wbasis_d.is_contiguous()
     k = int(wbasis_d.shape[0])
     minv = np.ascontiguousarray(minv, dtype=np.float64).reshape(-1)
     assert minv.size == k * (k + 1) // 2, "minv: the packed upper triangle of a %d x %d matrix" % (k, k)
     assert coef_out is None or (coef_out.shape == (n, k) and coef_out.dtype == torch.float64
                                 and coef_out.is_contiguous())
-    accumulate = out is not None
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
-    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
-    if n == 0:
-        return out                     # (an empty tensor has no address to pass)
-    with torch.cuda.device(grid_d.device):
-        check(lib().trx_chi2_grid_baseline(flux_d.data_ptr(), inv_var_d.data_ptr(), grid_d.data_ptr(), nt, n,
-                                           secdepth_d.data_ptr() if secdepth_d is not None else None,
-                                           float(sec_limit), int(accumulate), out.data_ptr(), wbasis_d.data_ptr(), k,
-                                           minv.ctypes.data, coef_out.data_ptr() if coef_out is not None else None,
-                                           _stream(grid_d)))
-    return out
+    return _chi2_rows("trx_chi2_grid_baseline", flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out, wbasis_d.data_ptr(),
+                      k, minv.ctypes.data, coef_out.data_ptr() if coef_out is not None else None)
 
 
 def log_mean_exp(logw_d, n_total):

@@ -7,7 +7,8 @@
 //                    cell, the (cell, node) pairs dealt to all lanes; centre-value stencil on dense uniform grids; the
 //                    passes of the bounded evaluation), pilot_stats_kernel, depth_screen_kernel, and what host and
 //                    device share (RowsArgs, batch_rows, batch_plan, set_scratch)
-//   trx_reduce.hpp   chi2_grid_kernel, chi2_grid_weighted_kernel (row reductions over a materialised grid) and the log-mean-exp kernels, HBM bound
+//   trx_reduce.hpp   chi2_grid_kernel, chi2_rows_kernel<STAGE, Terms> (row reductions over a materialised grid; one launcher
+//                    here, chi2_rows_launch) and the log-mean-exp kernels, HBM bound
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
 // lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
@@ -980,6 +981,27 @@ int lme_draws(const double* halfchi2, const double* lnprior, double lnsigma, lon
 }
 }  // namespace trx
 
+namespace {
+// One launch of chi2_rows_kernel<STAGE, Terms> (trx_chi2_grid_weighted, _offset, _baseline): STAGE while flux, inv_var
+// and the policy's columns fit the LDS budget, and as many blocks as stay resident -- 8 of 256 threads a CU, fewer where
+// the staged vectors fill the 160 KB of LDS -- on 256 CUs.
+template <class Terms>
+void chi2_rows_launch(const double* flux, const double* inv_var, const double* model_grid, int n_time, long n,
+                      const double* secdepth, double sec_limit, int accumulate, double* out, const Terms& terms,
+                      hipStream_t st)
+{
+    const bool stage = n_time <= chi2b_stage_max(Terms::kCols);
+    const size_t lds = stage ? (2 + Terms::kCols) * (size_t)((n_time + 1) & ~1) * sizeof(double) : 0;
+    long per_cu = lds ? (long)((160u * 1024u) / lds) : 8;
+    per_cu = per_cu > 8 ? 8 : per_cu;
+    long blocks = (n + 3) / 4;
+    if (blocks > 256L * per_cu) blocks = 256L * per_cu;
+    const auto kernel = stage ? chi2_rows_kernel<true, Terms> : chi2_rows_kernel<false, Terms>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, st, flux, inv_var, model_grid, n_time, n, secdepth,
+                       sec_limit, accumulate, out, terms);
+}
+}  // namespace
+
 // =========================================================================================
 extern "C" {
 
@@ -1053,20 +1075,8 @@ int trx_chi2_grid_weighted(const double* flux, const double* inv_var, const doub
     if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
     if (!flux || !inv_var || !model_grid || !out_halfchi2) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
     if (n == 0) return TRX_OK;
-    // as many blocks as stay resident (8 of 256 threads a CU, fewer where the staged vectors fill the LDS), 256 CUs
-    const bool stage = n_time <= kChi2wStageMax;
-    const size_t lds = stage ? 2 * (size_t)((n_time + 1) & ~1) * sizeof(double) : 0;
-    long per_cu = lds ? (long)((160u * 1024u) / lds) : 8;
-    per_cu = per_cu > 8 ? 8 : per_cu;
-    long blocks = (n + 3) / 4;
-    if (blocks > 256L * per_cu) blocks = 256L * per_cu;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (stage)
-        hipLaunchKernelGGL(chi2_grid_weighted_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, st, flux, inv_var,
-                           model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2);
-    else
-        hipLaunchKernelGGL(chi2_grid_weighted_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, flux, inv_var,
-                           model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2);
+    chi2_rows_launch(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, Chi2Plain{},
+                     static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }
@@ -1080,22 +1090,8 @@ int trx_chi2_grid_offset(const double* flux, const double* inv_var, const double
     if (!(sum_w > 0.0) || sum_w == INFINITY) return fail(TRX_ERR_ARG, "sum_w must be finite and > 0%s", "", 0);
     if (!(prior_prec >= 0.0)) return fail(TRX_ERR_ARG, "prior_prec must be >= 0 (+inf allowed)%s", "", 0);
     if (n == 0) return TRX_OK;
-    // (the launch geometry of trx_chi2_grid_weighted: the same bytes, the same LDS)
-    const bool stage = n_time <= kChi2wStageMax;
-    const size_t lds = stage ? 2 * (size_t)((n_time + 1) & ~1) * sizeof(double) : 0;
-    long per_cu = lds ? (long)((160u * 1024u) / lds) : 8;
-    per_cu = per_cu > 8 ? 8 : per_cu;
-    long blocks = (n + 3) / 4;
-    if (blocks > 256L * per_cu) blocks = 256L * per_cu;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (stage)
-        hipLaunchKernelGGL(chi2_grid_offset_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, st, flux, inv_var,
-                           model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, sum_w, prior_prec,
-                           offset_out);
-    else
-        hipLaunchKernelGGL(chi2_grid_offset_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, flux, inv_var,
-                           model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, sum_w, prior_prec,
-                           offset_out);
+    chi2_rows_launch(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2,
+                     Chi2Offset{sum_w, prior_prec, offset_out}, static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }
@@ -1116,12 +1112,15 @@ int trx_chi2_grid_baseline(const double* flux, const double* inv_var, const doub
         M.m[i] = minv[i];
     }
     if (n == 0) return TRX_OK;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const auto launch = [&](const auto& terms) {
+        chi2_rows_launch(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, terms,
+                         static_cast<hipStream_t>(stream));
+    };
     switch (n_terms) {
-    case 1: chi2b_launch<1>(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, wbasis, M, coef_out, st); break;
-    case 2: chi2b_launch<2>(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, wbasis, M, coef_out, st); break;
-    case 3: chi2b_launch<3>(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, wbasis, M, coef_out, st); break;
-    default: chi2b_launch<4>(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, wbasis, M, coef_out, st); break;
+    case 1: launch(Chi2Baseline<1>{wbasis, M, coef_out}); break;
+    case 2: launch(Chi2Baseline<2>{wbasis, M, coef_out}); break;
+    case 3: launch(Chi2Baseline<3>{wbasis, M, coef_out}); break;
+    default: launch(Chi2Baseline<4>{wbasis, M, coef_out}); break;
     }
     TRX_HIP(hipGetLastError());
     return TRX_OK;

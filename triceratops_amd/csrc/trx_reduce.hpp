@@ -1,5 +1,5 @@
-// The HBM-bound reductions: chi2_grid_kernel and chi2_grid_weighted_kernel (row reductions over a materialised grid)
-// and the log-mean-exp kernels
+// The HBM-bound reductions: chi2_grid_kernel and chi2_rows_kernel<STAGE, Terms> (row reductions over a materialised
+// grid; Terms = Chi2Plain, Chi2Offset, Chi2Baseline<K>) and the log-mean-exp kernels
 // (lme_partial_kernel / lme_partial_kernel_star with the scenario's final stage, lme_final_kernel).  Included by
 // trx_kernels.hip only.
 #pragma once
@@ -45,27 +45,133 @@ __global__ __launch_bounds__(256) void chi2_grid_kernel(const double* __restrict
 }
 
 // ---------------------------------------------------------------------------------------
-// 0.5 * sum_t inv_var_t (flux_t - model[r][t])^2 per row, written or added to out[r]; +inf where secdepth[r] >= sec_limit
-// (trx_chi2_grid_weighted).  One wavefront per row, two rows in flight per wave; every grid value is read once
-// (non-temporal), flux and inv_var come from LDS (STAGE: staged once per block) or, past kChi2wStageMax stamps, from the
-// caches.
+// The weighted row reductions over a materialised grid (trx_chi2_grid_weighted, trx_chi2_grid_offset,
+// trx_chi2_grid_baseline): chi2_rows_kernel<STAGE, Terms>.  With d_t = flux_t - model[r][t] every
+// form needs S2 = sum_t w_t d_t^2, w = inv_var; the Terms policy says which further sums over the same residuals ride
+// along with it and what the store makes of them:
+//   Chi2Plain         none                              h[r] = 0.5 * S2
+//   Chi2Offset        S1 = sum_t w_t d_t                h[r] = 0.5 * (S2 - S1^2 / (sum_w + prior_prec)),
+//                                                       offset_out[r] = S1 / (sum_w + prior_prec)
+//   Chi2Baseline<K>   b_k = sum_t g_k[t] d_t, K = 1..4  h[r] = 0.5 * max(S2 - sum_ij M_ij b_i b_j, 0),
+//                                                       coef_out[r][i] = sum_j M_ij b_j
+// h[r] is written or added to out[r]; +inf where secdepth[r] >= sec_limit.  Chi2Offset marginalises a per-dataset
+// baseline offset c ~ N(0, s^2): sum_w = sum_t w_t and prior_prec = 1 / s^2 from the host (0: a flat prior; +inf: no
+// offset, Chi2Plain's bits).  Chi2Baseline<K> marginalises a linear baseline model sum_k c_k B_k[t], c_k ~ N(0, s_k^2):
+// g_k[t] = w_t B_k[t] / sqrt(D_k) from the host, M the inverse of the unit-diagonal system matrix, packed upper triangle
+// by rows, by value in the kernel arguments (it does not depend on the row); M = 0 gives Chi2Plain's bits.  A difference
+// that rounding drives below 0 is stored as 0; a NaN stays a NaN.  The offset keeps a form of its own: a column of ones
+// through the baseline's store rounds differently.
+//
+// One wavefront per row, two rows in flight per wave; every grid value is read once (non-temporal); flux, inv_var and
+// the K columns come from LDS (STAGE: staged once per block) while they fit the 32 KB of kChi2wStageMax -- 2048 stamps
+// without columns, chi2b_stage_max(K) with K -- and from the caches past that.
 //
 // The order of summation of a row is fixed by n_time alone: lane l takes the stamp pairs (2 j, 2 j + 1), j = l, l + 64,
-// ... in ascending order -- an odd n_time's last stamp after them, on lane (n_time / 2) % 64 --, every term is
-// fma(w * d, d, acc) with the product rounded on its own, then wave_sum's butterfly.  A row whose address is a multiple
-// of 16 reads each pair with one 16-byte load, any other row (odd n_time: every second one; a grid view offset by one
-// double) with two 8-byte loads: the same values into the same arithmetic, so the same bits.  Neither the launch
-// geometry nor a row's position in the grid enters its result.
+// ... in ascending order -- an odd n_time's last stamp after them, on lane (n_time / 2) % 64 --, every term of S2 is
+// fma(w * d, d, acc) with the product rounded on its own, every term of a further sum fma(column, d, acc_k) in the same
+// trip, then one wave_sum's butterfly per sum.  A row whose address is a multiple of 16 reads each pair with one 16-byte
+// load, any other row (odd n_time: every second one; a grid view offset by one double) with two 8-byte loads: the same
+// values into the same arithmetic, so the same bits.  Neither the launch geometry nor a row's position in the grid
+// enters its result.
 constexpr int kChi2wStageMax = 2048;                // stamps whose flux and inv_var are staged in LDS: 32 KB a block
+constexpr int kChi2bMaxTerms = 4;
 
-template <bool STAGE>
-__device__ __forceinline__ double chi2w_row_partial(const double* __restrict__ row, const double* f, const double* w,
-                                                    int n_time, int lane)
+constexpr int chi2b_stage_max(int k) { return ((2 * kChi2wStageMax) / (2 + k)) & ~1; }     // 1364, 1024, 818, 682
+static_assert(chi2b_stage_max(0) == kChi2wStageMax, "no columns: the two staged vectors alone");
+
+struct Chi2bM {
+    double m[kChi2bMaxTerms * (kChi2bMaxTerms + 1) / 2];       // M_ij, i <= j, at chi2b_at<K>(i, j)
+};
+
+template <int K>
+__device__ __forceinline__ constexpr int chi2b_at(int i, int j)
+{
+    return i <= j ? i * K - i * (i - 1) / 2 + (j - i) : j * K - j * (j - 1) / 2 + (i - j);
+}
+
+// S2 and the N further sums of one row
+// (x[]: indexed by unrolled loops over the template argument only, so it lives in registers)
+template <int N>
+struct Chi2Sums {
+    double s2 = 0.0;
+    double x[N] = {};
+};
+template <>
+struct Chi2Sums<0> {
+    double s2 = 0.0;
+};
+
+__device__ __forceinline__ void chi2w_store(double tot, long r, const double* __restrict__ secdepth, double sec_limit,
+                                            int accumulate, double* __restrict__ out)
+{
+    double h = 0.5 * tot;
+    if (secdepth && secdepth[r] >= sec_limit) h = INFINITY;        // (false for a NaN depth, as in numpy)
+    out[r] = accumulate ? out[r] + h : h;                           // (+inf stays +inf: h is never -inf)
+}
+
+// The policies.  kSums: the further sums; kCols: the columns of their own that they run over, staged behind flux and
+// inv_var (none: the one sum runs over the weights, which the row's trip already holds).
+struct Chi2Plain {
+    static constexpr int kSums = 0, kCols = 0;
+    __device__ const double* columns() const { return nullptr; }
+    __device__ __forceinline__ void store(const Chi2Sums<0>& s, long r, const double* __restrict__ secdepth,
+                                          double sec_limit, int accumulate, double* __restrict__ out) const
+    {
+        chi2w_store(s.s2, r, secdepth, sec_limit, accumulate, out);
+    }
+};
+
+struct Chi2Offset {
+    static constexpr int kSums = 1, kCols = 0;
+    double sum_w, prior_prec;
+    double* offset_out;
+    __device__ const double* columns() const { return nullptr; }
+    __device__ __forceinline__ void store(const Chi2Sums<1>& s, long r, const double* __restrict__ secdepth,
+                                          double sec_limit, int accumulate, double* __restrict__ out) const
+    {
+        const double den = sum_w + prior_prec;          // (the same for every row: one addition a thread)
+        const double s1 = s.x[0];
+        const double tot = s.s2 - s1 * s1 / den;
+        chi2w_store(tot < 0.0 ? 0.0 : tot, r, secdepth, sec_limit, accumulate, out);      // (0.5 * tot: the clamp commutes)
+        if (offset_out) offset_out[r] = s1 / den;
+    }
+};
+
+template <int K>
+struct Chi2Baseline {
+    static constexpr int kSums = K, kCols = K;
+    const double* wbasis;
+    Chi2bM M;
+    double* coef_out;
+    __device__ const double* columns() const { return wbasis; }
+    __device__ __forceinline__ void store(const Chi2Sums<K>& s, long r, const double* __restrict__ secdepth,
+                                          double sec_limit, int accumulate, double* __restrict__ out) const
+    {
+        // c_i = sum_j M_ij b_j, then q = sum_i b_i c_i: the quadratic form and the coefficients from the same products
+        double q = 0.0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            double c = 0.0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) c = fma(M.m[chi2b_at<K>(i, j)], s.x[j], c);
+            q = fma(s.x[i], c, q);
+            if (coef_out) coef_out[r * K + i] = c;
+        }
+        const double tot = s.s2 - q;
+        chi2w_store(tot < 0.0 ? 0.0 : tot, r, secdepth, sec_limit, accumulate, out);      // (a NaN stays a NaN)
+    }
+};
+
+// one lane's share of a row's sums; g: the policy's columns, g_stride apart (unused without)
+template <bool STAGE, class Terms>
+__device__ __forceinline__ Chi2Sums<Terms::kSums> chi2_row_partial(const double* __restrict__ row, const double* f,
+                                                                   const double* w, const double* g, int g_stride,
+                                                                   int n_time, int lane)
 {
     typedef double dvec2 __attribute__((ext_vector_type(2)));
     const int nv = n_time >> 1;
     const bool vec = ((uintptr_t)row & 15) == 0;      // (per row: wave-uniform)
-    double acc = 0.0;
+    Chi2Sums<Terms::kSums> s;
     for (int j = lane; j < nv; j += 64) {
         double m0, m1, f0, f1, w0, w1;
         if (vec) {
@@ -83,44 +189,81 @@ __device__ __forceinline__ double chi2w_row_partial(const double* __restrict__ r
             f0 = f[2 * j]; f1 = f[2 * j + 1]; w0 = w[2 * j]; w1 = w[2 * j + 1];
         }
         const double d0 = f0 - m0, d1 = f1 - m1;
-        acc = fma(w0 * d0, d0, acc);
-        acc = fma(w1 * d1, d1, acc);
+        s.s2 = fma(w0 * d0, d0, s.s2);
+        s.s2 = fma(w1 * d1, d1, s.s2);
+        if constexpr (Terms::kSums > 0) {
+#pragma unroll
+            for (int k = 0; k < Terms::kSums; ++k) {
+                double g0 = w0, g1 = w1;
+                if constexpr (Terms::kCols > 0) {
+                    const double* gk = g + (size_t)k * g_stride;
+                    if (STAGE) {
+                        const dvec2 gv = reinterpret_cast<const dvec2*>(gk)[j];
+                        g0 = gv.x; g1 = gv.y;
+                    } else {
+                        g0 = gk[2 * j]; g1 = gk[2 * j + 1];
+                    }
+                }
+                s.x[k] = fma(g0, d0, s.x[k]);
+                s.x[k] = fma(g1, d1, s.x[k]);
+            }
+        }
     }
     if ((n_time & 1) && lane == (nv & 63)) {
         const int t = n_time - 1;
         const double d = f[t] - __builtin_nontemporal_load(row + t);
-        acc = fma(w[t] * d, d, acc);
+        const double wt = w[t];
+        s.s2 = fma(wt * d, d, s.s2);
+        if constexpr (Terms::kSums > 0) {
+#pragma unroll
+            for (int k = 0; k < Terms::kSums; ++k) {
+                double gt = wt;
+                if constexpr (Terms::kCols > 0) gt = g[(size_t)k * g_stride + t];
+                s.x[k] = fma(gt, d, s.x[k]);
+            }
+        }
     }
-    return acc;
+    return s;
 }
 
-__device__ __forceinline__ void chi2w_store(double tot, long r, const double* __restrict__ secdepth, double sec_limit,
-                                            int accumulate, double* __restrict__ out)
+template <int N>
+__device__ __forceinline__ void chi2_wave_sums(Chi2Sums<N>& s)
 {
-    double h = 0.5 * tot;
-    if (secdepth && secdepth[r] >= sec_limit) h = INFINITY;        // (false for a NaN depth, as in numpy)
-    out[r] = accumulate ? out[r] + h : h;                           // (+inf stays +inf: h is never -inf)
+    s.s2 = wave_sum(s.s2);
+    if constexpr (N > 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s.x[k] = wave_sum(s.x[k]);
+    }
 }
 
-template <bool STAGE>
-__global__ __launch_bounds__(256) void chi2_grid_weighted_kernel(const double* __restrict__ flux,
-                                                                 const double* __restrict__ inv_var,
-                                                                 const double* __restrict__ grid, int n_time, long n,
-                                                                 const double* __restrict__ secdepth, double sec_limit,
-                                                                 int accumulate, double* __restrict__ out)
+template <bool STAGE, class Terms>
+__global__ __launch_bounds__(256) void chi2_rows_kernel(const double* __restrict__ flux,
+                                                        const double* __restrict__ inv_var,
+                                                        const double* __restrict__ grid, int n_time, long n,
+                                                        const double* __restrict__ secdepth, double sec_limit,
+                                                        int accumulate, double* __restrict__ out, const Terms terms)
 {
-    extern __shared__ __attribute__((aligned(16))) double chi2w_lds[];     // STAGE: [2][n_time rounded up to even]
+    // STAGE: [2 + Terms::kCols][n_time rounded up to even]
+    extern __shared__ __attribute__((aligned(16))) double chi2_lds[];
     const double* f = flux;
     const double* w = inv_var;
+    const double* g = terms.columns();
+    int g_stride = n_time;
     if (STAGE) {
         const int n_pad = (n_time + 1) & ~1;
         for (int t = threadIdx.x; t < n_time; t += 256) {
-            chi2w_lds[t] = flux[t];
-            chi2w_lds[n_pad + t] = inv_var[t];
+            chi2_lds[t] = flux[t];
+            chi2_lds[n_pad + t] = inv_var[t];
+            if constexpr (Terms::kCols > 0) {
+#pragma unroll
+                for (int k = 0; k < Terms::kCols; ++k) chi2_lds[(2 + k) * n_pad + t] = g[(size_t)k * n_time + t];
+            }
         }
         __syncthreads();
-        f = chi2w_lds;
-        w = chi2w_lds + n_pad;
+        f = chi2_lds;
+        w = chi2_lds + n_pad;
+        g = chi2_lds + 2 * n_pad;
+        g_stride = n_pad;
     }
     const int lane = threadIdx.x & 63;
     const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -129,293 +272,16 @@ __global__ __launch_bounds__(256) void chi2_grid_weighted_kernel(const double* _
         // two rows per trip, their loads in flight together; each row's arithmetic is its own
         const long r2 = r + nwaves;
         const bool two = r2 < n;
-        const double a0 = chi2w_row_partial<STAGE>(grid + (size_t)r * n_time, f, w, n_time, lane);
-        const double a1 = two ? chi2w_row_partial<STAGE>(grid + (size_t)r2 * n_time, f, w, n_time, lane) : 0.0;
-        const double t0 = wave_sum(a0);
-        const double t1 = wave_sum(a1);
+        Chi2Sums<Terms::kSums> s0 = chi2_row_partial<STAGE, Terms>(grid + (size_t)r * n_time, f, w, g, g_stride, n_time, lane);
+        Chi2Sums<Terms::kSums> s1;
+        if (two) s1 = chi2_row_partial<STAGE, Terms>(grid + (size_t)r2 * n_time, f, w, g, g_stride, n_time, lane);
+        chi2_wave_sums(s0);
+        chi2_wave_sums(s1);
         if (lane == 0) {
-            chi2w_store(t0, r, secdepth, sec_limit, accumulate, out);
-            if (two) chi2w_store(t1, r2, secdepth, sec_limit, accumulate, out);
+            terms.store(s0, r, secdepth, sec_limit, accumulate, out);
+            if (two) terms.store(s1, r2, secdepth, sec_limit, accumulate, out);
         }
     }
-}
-
-// ---------------------------------------------------------------------------------------
-// chi2_grid_weighted_kernel with a per-dataset baseline offset c ~ N(0, s^2) marginalised in closed form
-// (trx_chi2_grid_offset): with d_t = flux_t - model[r][t], S2 = sum_t w_t d_t^2, S1 = sum_t w_t d_t,
-//   h[r] = 0.5 * (S2 - S1^2 / (sum_w + prior_prec)),   offset_out[r] = S1 / (sum_w + prior_prec),
-// sum_w = sum_t w_t and prior_prec = 1 / s^2 from the host (0: a flat prior; +inf: no offset, chi2_grid_weighted_kernel's
-// bits).  The same shape -- one wavefront per row, two rows in flight, the same loads, the same staging -- and the same
-// order: S2 is formed term for term as chi2w_row_partial forms it, S1 = fma(w, d, acc1) rides in the same trip over the
-// same stamps, then one wave_sum each.  A difference that rounding drives below 0 is stored as 0; a NaN stays a NaN.
-template <bool STAGE>
-__device__ __forceinline__ void chi2o_row_partial(const double* __restrict__ row, const double* f, const double* w,
-                                                  int n_time, int lane, double& s2, double& s1)
-{
-    typedef double dvec2 __attribute__((ext_vector_type(2)));
-    const int nv = n_time >> 1;
-    const bool vec = ((uintptr_t)row & 15) == 0;      // (per row: wave-uniform)
-    double acc = 0.0, acc1 = 0.0;
-    for (int j = lane; j < nv; j += 64) {
-        double m0, m1, f0, f1, w0, w1;
-        if (vec) {
-            const dvec2 m = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(row) + j);
-            m0 = m.x; m1 = m.y;
-        } else {
-            m0 = __builtin_nontemporal_load(row + 2 * j);
-            m1 = __builtin_nontemporal_load(row + 2 * j + 1);
-        }
-        if (STAGE) {
-            const dvec2 fv = reinterpret_cast<const dvec2*>(f)[j], wv = reinterpret_cast<const dvec2*>(w)[j];
-            f0 = fv.x; f1 = fv.y; w0 = wv.x; w1 = wv.y;
-        } else {
-            f0 = f[2 * j]; f1 = f[2 * j + 1]; w0 = w[2 * j]; w1 = w[2 * j + 1];
-        }
-        const double d0 = f0 - m0, d1 = f1 - m1;
-        acc = fma(w0 * d0, d0, acc);
-        acc1 = fma(w0, d0, acc1);
-        acc = fma(w1 * d1, d1, acc);
-        acc1 = fma(w1, d1, acc1);
-    }
-    if ((n_time & 1) && lane == (nv & 63)) {
-        const int t = n_time - 1;
-        const double d = f[t] - __builtin_nontemporal_load(row + t);
-        acc = fma(w[t] * d, d, acc);
-        acc1 = fma(w[t], d, acc1);
-    }
-    s2 = acc;
-    s1 = acc1;
-}
-
-__device__ __forceinline__ void chi2o_store(double s2, double s1, double den, long r, const double* __restrict__ secdepth,
-                                            double sec_limit, int accumulate, double* __restrict__ out,
-                                            double* __restrict__ offset_out)
-{
-    const double tot = s2 - s1 * s1 / den;
-    chi2w_store(tot < 0.0 ? 0.0 : tot, r, secdepth, sec_limit, accumulate, out);      // (0.5 * tot: the clamp commutes)
-    if (offset_out) offset_out[r] = s1 / den;
-}
-
-template <bool STAGE>
-__global__ __launch_bounds__(256) void chi2_grid_offset_kernel(const double* __restrict__ flux,
-                                                               const double* __restrict__ inv_var,
-                                                               const double* __restrict__ grid, int n_time, long n,
-                                                               const double* __restrict__ secdepth, double sec_limit,
-                                                               int accumulate, double* __restrict__ out, double sum_w,
-                                                               double prior_prec, double* __restrict__ offset_out)
-{
-    extern __shared__ __attribute__((aligned(16))) double chi2o_lds[];     // STAGE: [2][n_time rounded up to even]
-    const double* f = flux;
-    const double* w = inv_var;
-    if (STAGE) {
-        const int n_pad = (n_time + 1) & ~1;
-        for (int t = threadIdx.x; t < n_time; t += 256) {
-            chi2o_lds[t] = flux[t];
-            chi2o_lds[n_pad + t] = inv_var[t];
-        }
-        __syncthreads();
-        f = chi2o_lds;
-        w = chi2o_lds + n_pad;
-    }
-    const int lane = threadIdx.x & 63;
-    const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long nwaves = (long)gridDim.x * 4;
-    const double den = sum_w + prior_prec;
-    for (long r = wave0; r < n; r += 2 * nwaves) {
-        const long r2 = r + nwaves;
-        const bool two = r2 < n;
-        double a0, b0, a1 = 0.0, b1 = 0.0;
-        chi2o_row_partial<STAGE>(grid + (size_t)r * n_time, f, w, n_time, lane, a0, b0);
-        if (two) chi2o_row_partial<STAGE>(grid + (size_t)r2 * n_time, f, w, n_time, lane, a1, b1);
-        const double t0 = wave_sum(a0), u0 = wave_sum(b0);
-        const double t1 = wave_sum(a1), u1 = wave_sum(b1);
-        if (lane == 0) {
-            chi2o_store(t0, u0, den, r, secdepth, sec_limit, accumulate, out, offset_out);
-            if (two) chi2o_store(t1, u1, den, r2, secdepth, sec_limit, accumulate, out, offset_out);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// chi2_grid_weighted_kernel with a linear baseline model sum_k c_k B_k[t], c_k ~ N(0, s_k^2), K = 1 .. 4 terms,
-// marginalised in closed form (trx_chi2_grid_baseline): with d_t = flux_t - model[r][t],
-// S2 = sum_t w_t d_t^2 and the scaled sums b_k = sum_t g_k[t] d_t, g_k[t] = w_t B_k[t] / sqrt(D_k) from the host,
-//   h[r] = 0.5 * max(S2 - sum_ij M_ij b_i b_j, 0),   coef_out[r][i] = sum_j M_ij b_j,
-// M the inverse of the unit-diagonal system matrix, packed upper triangle by rows, by value in the kernel arguments (it
-// does not depend on the row).  The same shape as the two kernels above -- one wavefront per row, two rows in flight, the
-// same loads -- and the same order: S2 term for term as chi2w_row_partial forms it, b_k = fma(g_k, d, acc_k) in the same
-// trip over the same stamps, then one wave_sum each.  M = 0 is chi2_grid_weighted_kernel, bit for bit.  flux, inv_var
-// and the K columns are staged in LDS while they fit the 32 KB of kChi2wStageMax: chi2b_stage_max(K) stamps.
-constexpr int kChi2bMaxTerms = 4;
-
-constexpr int chi2b_stage_max(int k) { return ((2 * kChi2wStageMax) / (2 + k)) & ~1; }     // 1364, 1024, 818, 682
-
-struct Chi2bM {
-    double m[kChi2bMaxTerms * (kChi2bMaxTerms + 1) / 2];       // M_ij, i <= j, at chi2b_at<K>(i, j)
-};
-
-template <int K>
-__device__ __forceinline__ constexpr int chi2b_at(int i, int j)
-{
-    return i <= j ? i * K - i * (i - 1) / 2 + (j - i) : j * K - j * (j - 1) / 2 + (i - j);
-}
-
-// (b[]: indexed by unrolled loops over the template argument only, so it lives in registers)
-template <int K>
-struct Chi2bSums {
-    double s2;
-    double b[K];
-};
-
-template <bool STAGE, int K>
-__device__ __forceinline__ void chi2b_row_partial(const double* __restrict__ row, const double* f, const double* w,
-                                                  const double* g, int g_stride, int n_time, int lane, Chi2bSums<K>& s)
-{
-    typedef double dvec2 __attribute__((ext_vector_type(2)));
-    const int nv = n_time >> 1;
-    const bool vec = ((uintptr_t)row & 15) == 0;      // (per row: wave-uniform)
-    double acc = 0.0;
-    double accb[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) accb[k] = 0.0;
-    for (int j = lane; j < nv; j += 64) {
-        double m0, m1, f0, f1, w0, w1;
-        if (vec) {
-            const dvec2 m = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(row) + j);
-            m0 = m.x; m1 = m.y;
-        } else {
-            m0 = __builtin_nontemporal_load(row + 2 * j);
-            m1 = __builtin_nontemporal_load(row + 2 * j + 1);
-        }
-        if (STAGE) {
-            const dvec2 fv = reinterpret_cast<const dvec2*>(f)[j], wv = reinterpret_cast<const dvec2*>(w)[j];
-            f0 = fv.x; f1 = fv.y; w0 = wv.x; w1 = wv.y;
-        } else {
-            f0 = f[2 * j]; f1 = f[2 * j + 1]; w0 = w[2 * j]; w1 = w[2 * j + 1];
-        }
-        const double d0 = f0 - m0, d1 = f1 - m1;
-        acc = fma(w0 * d0, d0, acc);
-        acc = fma(w1 * d1, d1, acc);
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double g0, g1;
-            if (STAGE) {
-                const dvec2 gv = reinterpret_cast<const dvec2*>(g + (size_t)k * g_stride)[j];
-                g0 = gv.x; g1 = gv.y;
-            } else {
-                g0 = g[(size_t)k * g_stride + 2 * j]; g1 = g[(size_t)k * g_stride + 2 * j + 1];
-            }
-            accb[k] = fma(g0, d0, accb[k]);
-            accb[k] = fma(g1, d1, accb[k]);
-        }
-    }
-    if ((n_time & 1) && lane == (nv & 63)) {
-        const int t = n_time - 1;
-        const double d = f[t] - __builtin_nontemporal_load(row + t);
-        acc = fma(w[t] * d, d, acc);
-#pragma unroll
-        for (int k = 0; k < K; ++k) accb[k] = fma(g[(size_t)k * g_stride + t], d, accb[k]);
-    }
-    s.s2 = acc;
-#pragma unroll
-    for (int k = 0; k < K; ++k) s.b[k] = accb[k];
-}
-
-template <int K>
-__device__ __forceinline__ void chi2b_wave_sum(Chi2bSums<K>& s)
-{
-    s.s2 = wave_sum(s.s2);
-#pragma unroll
-    for (int k = 0; k < K; ++k) s.b[k] = wave_sum(s.b[k]);
-}
-
-template <int K>
-__device__ __forceinline__ void chi2b_store(const Chi2bSums<K>& s, const Chi2bM& M, long r,
-                                            const double* __restrict__ secdepth, double sec_limit, int accumulate,
-                                            double* __restrict__ out, double* __restrict__ coef_out)
-{
-    // c_i = sum_j M_ij b_j, then q = sum_i b_i c_i: the quadratic form and the coefficients from the same products
-    double q = 0.0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        double c = 0.0;
-#pragma unroll
-        for (int j = 0; j < K; ++j) c = fma(M.m[chi2b_at<K>(i, j)], s.b[j], c);
-        q = fma(s.b[i], c, q);
-        if (coef_out) coef_out[r * K + i] = c;
-    }
-    const double tot = s.s2 - q;
-    chi2w_store(tot < 0.0 ? 0.0 : tot, r, secdepth, sec_limit, accumulate, out);      // (a NaN stays a NaN)
-}
-
-template <bool STAGE, int K>
-__global__ __launch_bounds__(256) void chi2_grid_baseline_kernel(const double* __restrict__ flux,
-                                                                 const double* __restrict__ inv_var,
-                                                                 const double* __restrict__ grid, int n_time, long n,
-                                                                 const double* __restrict__ secdepth, double sec_limit,
-                                                                 int accumulate, double* __restrict__ out,
-                                                                 const double* __restrict__ wbasis, Chi2bM M,
-                                                                 double* __restrict__ coef_out)
-{
-    extern __shared__ __attribute__((aligned(16))) double chi2b_lds[];     // STAGE: [2 + K][n_time rounded up to even]
-    const double* f = flux;
-    const double* w = inv_var;
-    const double* g = wbasis;
-    int g_stride = n_time;
-    if (STAGE) {
-        const int n_pad = (n_time + 1) & ~1;
-        for (int t = threadIdx.x; t < n_time; t += 256) {
-            chi2b_lds[t] = flux[t];
-            chi2b_lds[n_pad + t] = inv_var[t];
-#pragma unroll
-            for (int k = 0; k < K; ++k) chi2b_lds[(2 + k) * n_pad + t] = wbasis[(size_t)k * n_time + t];
-        }
-        __syncthreads();
-        f = chi2b_lds;
-        w = chi2b_lds + n_pad;
-        g = chi2b_lds + 2 * n_pad;
-        g_stride = n_pad;
-    }
-    const int lane = threadIdx.x & 63;
-    const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long nwaves = (long)gridDim.x * 4;
-    for (long r = wave0; r < n; r += 2 * nwaves) {
-        const long r2 = r + nwaves;
-        const bool two = r2 < n;
-        Chi2bSums<K> s0, s1;
-        s1.s2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) s1.b[k] = 0.0;
-        chi2b_row_partial<STAGE, K>(grid + (size_t)r * n_time, f, w, g, g_stride, n_time, lane, s0);
-        if (two) chi2b_row_partial<STAGE, K>(grid + (size_t)r2 * n_time, f, w, g, g_stride, n_time, lane, s1);
-        chi2b_wave_sum<K>(s0);
-        chi2b_wave_sum<K>(s1);
-        if (lane == 0) {
-            chi2b_store<K>(s0, M, r, secdepth, sec_limit, accumulate, out, coef_out);
-            if (two) chi2b_store<K>(s1, M, r2, secdepth, sec_limit, accumulate, out, coef_out);
-        }
-    }
-}
-
-// (host) one launch: STAGE by the stamps, the grid by what stays resident
-template <int K>
-static void chi2b_launch(const double* flux, const double* inv_var, const double* model_grid, int n_time, long n,
-                         const double* secdepth, double sec_limit, int accumulate, double* out, const double* wbasis,
-                         const Chi2bM& M, double* coef_out, hipStream_t st)
-{
-    // (the sizing rule of trx_chi2_grid_weighted, with 2 + K staged vectors in place of 2)
-    const bool stage = n_time <= chi2b_stage_max(K);
-    const size_t lds = stage ? (2 + K) * (size_t)((n_time + 1) & ~1) * sizeof(double) : 0;
-    long per_cu = lds ? (long)((160u * 1024u) / lds) : 8;
-    per_cu = per_cu > 8 ? 8 : per_cu;
-    long blocks = (n + 3) / 4;
-    if (blocks > 256L * per_cu) blocks = 256L * per_cu;
-    if (stage)
-        hipLaunchKernelGGL((chi2_grid_baseline_kernel<true, K>), dim3((unsigned)blocks), dim3(256), lds, st, flux,
-                           inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out, wbasis, M, coef_out);
-    else
-        hipLaunchKernelGGL((chi2_grid_baseline_kernel<false, K>), dim3((unsigned)blocks), dim3(256), 0, st, flux,
-                           inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out, wbasis, M, coef_out);
 }
 
 // ---------------------------------------------------------------------------------------

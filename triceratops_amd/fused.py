@@ -15,6 +15,7 @@ import ctypes
 import math
 import os
 import threading
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -743,35 +744,65 @@ def _on_device(a, device):
     return _cached(_lc_cache, (a.shape, hash(a.tobytes()), device.index), 32, lambda: _lib.dev(a, device))
 
 
+class _Baseline(NamedTuple):
+    """the system of a dataset with baseline columns (datasets.baseline_system)"""
+    g: torch.Tensor              # the scaled columns [K][T], on the device
+    minv: np.ndarray             # M's packed upper triangle
+    sqrt_d: np.ndarray           # sqrt(D): c_k = c~_k / sqrt(D_k)
+    has_offset: bool             # term 0 is the dataset's offset
+
+
+class _Dataset(NamedTuple):
+    """one light curve of a Datasets call on the device, and what its reduction marginalises: nothing, a constant offset,
+    or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then"""
+    time: torch.Tensor
+    flux: torch.Tensor
+    inv_var: torch.Tensor
+    exptime: float
+    nsamples: int
+    offset: Optional[tuple] = None           # (sum_w, 1 / s^2)
+    baseline: Optional[_Baseline] = None
+
+    @classmethod
+    def upload(cls, d, dev):
+        inv_var = 1.0 / (d.flux_err * d.flux_err)
+        rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
+        if d.baseline is not None:
+            system = baseline_system(d)
+            return rec._replace(baseline=_Baseline(_on_device(system.g, dev), system.minv, np.sqrt(system.D),
+                                                    d.offset_sigma is not None))
+        if d.offset_sigma is not None:
+            # (sum_w is the correctly rounded sum of the weights the device holds)
+            return rec._replace(offset=(math.fsum(inv_var.tolist()),
+                                         0.0 if math.isinf(d.offset_sigma) else 1.0 / (d.offset_sigma * d.offset_sigma)))
+        return rec
+
+    def halfchi2(self, grid, secdepth=None, sec_limit=float("inf"), out=None, offset_out=None, coef_out=None):
+        """this dataset's weighted chi^2/2 of every row of a model grid [n][T], written or added to `out`; +inf where
+        secdepth >= sec_limit.  The one place that picks the reduction: trx_chi2_grid_baseline for baseline columns (coef_out:
+        the rows' scaled coefficients), trx_chi2_grid_offset for an offset alone (offset_out: the rows' offsets), else
+        trx_chi2_grid_weighted."""
+        if self.baseline is not None:
+            return _lib.chi2_grid_baseline(self.flux, self.inv_var, grid, self.baseline.g, self.baseline.minv, secdepth,
+                                           sec_limit, out=out, coef_out=coef_out)
+        if self.offset is not None:
+            return _lib.chi2_grid_offset(self.flux, self.inv_var, grid, *self.offset, secdepth, sec_limit, out=out,
+                                         offset_out=offset_out)
+        return _lib.chi2_grid_weighted(self.flux, self.inv_var, grid, secdepth, sec_limit, out=out)
+
+
 # ---------------------------------------------------------------------------------------
 class _Scenario:
     """one lnZ_* call: draws, the fused kernel, the branch evidences and tables"""
 
     def __init__(self, time, flux, sigma, N, parallel, exptime, nsamples, mission, flatpriors):
         self.dev = _lib.compute_device()
-        self.datasets = self.offsets = self.baselines = None
+        self.datasets = None
         if isinstance(time, Datasets):
             # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
-            self.datasets = [(_on_device(d.time, self.dev), _on_device(d.flux, self.dev),
-                              _on_device(1.0 / (d.flux_err * d.flux_err), self.dev), d.exptime, d.nsamples)
-                             for d in time.sets]
-            # (sum_w, 1 / s^2) of every dataset whose baseline offset is marginalised, else None; sum_w is the correctly
-            # rounded sum of the weights the device holds
-            self.offsets = [None if d.offset_sigma is None else
-                            (math.fsum((1.0 / (d.flux_err * d.flux_err)).tolist()),
-                             0.0 if math.isinf(d.offset_sigma) else 1.0 / (d.offset_sigma * d.offset_sigma))
-                            for d in time.sets]
-            # a dataset with baseline columns: (g [K][T] on the device, M's packed upper triangle, sqrt(D), whether term 0
-            # is the offset) of datasets.baseline_system; its offset, if any, is term 0 of that system
-            self.baselines = [None] * len(time.sets)
-            for l, d in enumerate(time.sets):
-                if d.baseline is not None:
-                    system = baseline_system(d)
-                    self.baselines[l] = (_on_device(system.g, self.dev), system.minv, np.sqrt(system.D),
-                                         d.offset_sigma is not None)
-                    self.offsets[l] = None
+            self.datasets = [_Dataset.upload(d, self.dev) for d in time.sets]
             sigma = time.sigma_ref
-            self.time, self.flux = self.datasets[0][0], self.datasets[0][1]
+            self.time, self.flux = self.datasets[0].time, self.datasets[0].flux
         else:
             self.time, self.flux = _on_device(time, self.dev), _on_device(flux, self.dev)
         self.sigma, self.N = float(sigma), int(N)
@@ -1056,7 +1087,7 @@ class _Scenario:
                 self.moments.append((float(mom[1]), float(mom[2])))
                 _lib.moments_emit(mom[1], mom[2])
             best = self._best(h, idx, n)
-            if self.datasets is not None and ((DATASET_OFFSETS is not None and any(o is not None for o in self.offsets))
+            if self.datasets is not None and ((DATASET_OFFSETS is not None and any(d.offset is not None for d in self.datasets))
                                               or self._any_baseline()):
                 o, c = self._best_offsets(model, flags, cols, best, twin, nblk) if n else (None, None)
                 offsets.append(o)
@@ -1091,8 +1122,8 @@ class _Scenario:
 
     def _any_baseline(self):
         """whether a dataset's baseline terms are wanted back (DATASET_BASELINES or, for their term 0, DATASET_OFFSETS)"""
-        return ((DATASET_BASELINES is not None or DATASET_OFFSETS is not None) and self.baselines is not None
-                and any(b is not None for b in self.baselines))
+        return ((DATASET_BASELINES is not None or DATASET_OFFSETS is not None)
+                and any(d.baseline is not None for d in self.datasets))
 
     def _leave_best_terms(self, offsets, coefs):
         """the branches' best-draw offsets and baseline coefficients, from the device to DATASET_OFFSETS / DATASET_BASELINES
@@ -1103,14 +1134,14 @@ class _Scenario:
         for o, c in zip(offsets, coefs):
             o = np.full(L, np.nan) if o is None else o.cpu().numpy()
             per = [None] * L
-            for l, b in enumerate(self.baselines):
+            for l, d in enumerate(self.datasets):
+                b = d.baseline
                 if b is None:
                     continue
-                _, _, sqrt_d, has_offset = b
-                ck = np.full(sqrt_d.size, np.nan) if c is None else c[l].cpu().numpy().reshape(-1) / sqrt_d
-                if has_offset:
+                ck = np.full(b.sqrt_d.size, np.nan) if c is None else c[l].cpu().numpy().reshape(-1) / b.sqrt_d
+                if b.has_offset:
                     o[l] = ck[0]
-                per[l] = ck[1:] if has_offset else ck
+                per[l] = ck[1:] if b.has_offset else ck
             offs.append(o)
             base.append(per)
         if DATASET_OFFSETS is not None:
@@ -1122,8 +1153,8 @@ class _Scenario:
         """([L] device tensor, list per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
         S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
         baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them).  The one row is
-        evaluated again -- trx_flux_grid on one row, then trx_chi2_grid_offset with offset_out or trx_chi2_grid_baseline
-        with coef_out -- so nothing of size n x L is kept."""
+        evaluated again -- trx_flux_grid on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out or
+        coef_out -- so nothing of size n x L is kept."""
         out = torch.full((len(self.datasets),), float("nan"), dtype=F64, device=self.dev)
         coefs = [None] * len(self.datasets)
         row = cols[:nblk].index_select(1, best[:1]).contiguous()
@@ -1131,34 +1162,29 @@ class _Scenario:
             row[2] *= 2.0
             row[4] = cols[11].index_select(0, best[:1])
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL
-        for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
-            base = None if self.baselines is None else self.baselines[l]
-            if self.offsets[l] is None and base is None:
+        for l, d in enumerate(self.datasets):
+            if d.offset is None and d.baseline is None:
                 continue
-            grid, _ = _lib.flux_grid(model, flags, time_d, row, exptime, nsamples, want_secdepth=False)
-            if base is not None:
-                coefs[l] = torch.empty((1, int(base[0].shape[0])), dtype=F64, device=self.dev)
-                _lib.chi2_grid_baseline(flux_d, inv_var_d, grid, base[0], base[1], coef_out=coefs[l])
-            else:
-                _lib.chi2_grid_offset(flux_d, inv_var_d, grid, *self.offsets[l], offset_out=out[l:l + 1])
+            grid, _ = _lib.flux_grid(model, flags, d.time, row, d.exptime, d.nsamples, want_secdepth=False)
+            if d.baseline is not None:
+                coefs[l] = torch.empty((1, int(d.baseline.g.shape[0])), dtype=F64, device=self.dev)
+            d.halfchi2(grid, offset_out=out[l:l + 1], coef_out=coefs[l])
         return out, coefs
 
     def _datasets_halfchi2(self, model, flags, block):
         """sum over the datasets of the weighted chi^2/2 of every row of `block` ([n_param][n], the masked draws of one
-        branch): per chunk of rows and per dataset one trx_flux_grid and one accumulating trx_chi2_grid_weighted -- for a
-        dataset whose baseline offset is marginalised (offset_sigma), trx_chi2_grid_offset in its place, for one with
-        baseline columns trx_chi2_grid_baseline.  The EB
+        branch): per chunk of rows and per dataset one trx_flux_grid and the dataset's accumulating reduction
+        (_Dataset.halfchi2: trx_chi2_grid_weighted, or what marginalises its offset or baseline columns).  The EB
         branch's secondary-eclipse rule (secdepth >= 1.5 sigma_bar -> +inf) rides in the first dataset's reduction: the
         depth does not depend on the time stamps.  A row's value does not depend on the chunk it falls in.
         DATASET_EVALUATION = "fused": one trx_lnl_batch_weighted per dataset over the whole block instead -- no grid, no
         chunks; the rule rides in the first dataset's call as its sec_limit.  It has no offset form."""
         if DATASET_EVALUATION not in DATASET_EVALUATIONS:
             raise ValueError("fused.DATASET_EVALUATION must be one of %s (got %r)" % (DATASET_EVALUATIONS, DATASET_EVALUATION))
-        if DATASET_EVALUATION == "fused" and any(o is not None for o in self.offsets):
+        if DATASET_EVALUATION == "fused" and any(d.offset is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: the fused kernel "
                                       "carries no sum of w * residual; use evaluation='grid'")
-        baselines = self.baselines if self.baselines is not None else [None] * len(self.datasets)
-        if DATASET_EVALUATION == "fused" and any(b is not None for b in baselines):
+        if DATASET_EVALUATION == "fused" and any(d.baseline is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: the fused kernel "
                                       "carries no sums of basis * residual; use evaluation='grid'")
         n = int(block.shape[1])
@@ -1168,11 +1194,11 @@ class _Scenario:
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL         # (set_precision; the evaluation is full either way)
         chunks = 1         # (launches per dataset)
         if DATASET_EVALUATION == "fused":
-            for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
+            for l, d in enumerate(self.datasets):
                 limit = 1.5 * self.sigma if (model == MODEL_EB and l == 0) else float("inf")
-                _lib.lnl_batch_weighted(model, flags, time_d, flux_d, inv_var_d, block, exptime, nsamples, limit, out=h)
+                _lib.lnl_batch_weighted(model, flags, d.time, d.flux, d.inv_var, block, d.exptime, d.nsamples, limit, out=h)
         else:
-            t_max = max(int(d[0].numel()) for d in self.datasets)
+            t_max = max(int(d.time.numel()) for d in self.datasets)
             rows = max(1, int(DATASET_GRID_BYTES) // (8 * t_max))
             chunks = -(-n // rows)
             buf = torch.empty(min(rows, n) * t_max, dtype=F64, device=self.dev)
@@ -1180,22 +1206,15 @@ class _Scenario:
             for r0 in range(0, n, rows):
                 r1 = min(r0 + rows, n)
                 blk = block if (r0 == 0 and r1 == n) else block[:, r0:r1].contiguous()
-                for l, (time_d, flux_d, inv_var_d, exptime, nsamples) in enumerate(self.datasets):
-                    nt = int(time_d.numel())
-                    grid, sec = _lib.flux_grid(model, flags, time_d, blk, exptime, nsamples, want_secdepth=eb and l == 0,
+                for l, d in enumerate(self.datasets):
+                    nt = int(d.time.numel())
+                    grid, sec = _lib.flux_grid(model, flags, d.time, blk, d.exptime, d.nsamples, want_secdepth=eb and l == 0,
                                                out=buf[:(r1 - r0) * nt].view(r1 - r0, nt))
-                    if baselines[l] is not None:
-                        _lib.chi2_grid_baseline(flux_d, inv_var_d, grid, baselines[l][0], baselines[l][1], sec,
-                                                1.5 * self.sigma, out=h[r0:r1])
-                    elif self.offsets[l] is None:
-                        _lib.chi2_grid_weighted(flux_d, inv_var_d, grid, sec, 1.5 * self.sigma, out=h[r0:r1])
-                    else:
-                        _lib.chi2_grid_offset(flux_d, inv_var_d, grid, *self.offsets[l], sec, 1.5 * self.sigma,
-                                              out=h[r0:r1])
+                    d.halfchi2(grid, sec, 1.5 * self.sigma, out=h[r0:r1])
         with _stats_lock:
             # (the masked draws once, every (draw, time stamp) cell of every dataset)
             _lib.STATS["rows"] += n
-            _lib.STATS["cells"] += n * sum(int(d[0].numel()) for d in self.datasets)
+            _lib.STATS["cells"] += n * sum(int(d.time.numel()) for d in self.datasets)
             _lib.STATS["launches"] += len(self.datasets) * chunks
         return h
 
