@@ -16,6 +16,11 @@
                                                  and at 1e6 x 100: the run the job traces for the kernels' rates
   python profiles/datasets/measure.py baseline_e2e   (e) two datasets of 50 points, N = 1e6: calc_probs_datasets with and
                                                  without polynomial_baseline(t, 1) + a flat offset on the second dataset
+  python profiles/datasets/measure.py ou_kernels     (f) chi2_ou_kernel (correlated noise) next to the plain weighted reduction
+                                                 on the same grids, 200 000 x 2000 and 1e6 x 100: the run the job's step
+                                                 `ou_rates` traces
+  python profiles/datasets/measure.py ou_e2e     (g) two datasets of 50 points, N = 1e6: calc_probs_datasets with and without
+                                                 red_sigma / red_timescale on the second dataset (the other half of `ou_rates`)
 
 The job runs `kernels` twice: plainly, and under `rocprofv3 --kernel-trace --stats`, whose kernel trace gives the
 per-launch times quoted (the event timings include the launch gaps of five back-to-back calls); `routes` runs under
@@ -209,6 +214,97 @@ def baseline_e2e():
         print("e2e     %-60s median %.4f s  min %.4f s  max %.4f s  (%d rounds)" % (name, np.median(v), v[0], v[-1], v.size), flush=True)
 
 
+OU_PARAMS = (3.0, 10.0)          # s_r in units of the mean error, tau in cadences
+
+
+def _ou_tables(nt, rng, sigma):
+    """(flux, white weights, (alpha, beta, omega)) of a light curve of nt stamps at unit cadence"""
+    import numpy as np
+    from triceratops_amd.datasets import ou_system, validate
+    err = rng.uniform(0.5, 2.0, nt) * sigma
+    d = validate([{"time": np.arange(nt, dtype=np.float64), "flux": np.ones(nt), "flux_err": err,
+                   "red_sigma": OU_PARAMS[0] * sigma, "red_timescale": OU_PARAMS[1]}])[0]
+    return 1.0 + rng.normal(0.0, sigma, nt), 1.0 / err ** 2, ou_system(d)
+
+
+def ou_kernels():
+    """six launches of the plain weighted reduction and of chi2_ou_kernel on the same grids, both shapes (the first is
+    the warm-up); the job's tracer gives the per-launch times, the events here include the launch gaps"""
+    import numpy as np
+    import torch
+    from triceratops_amd import _lib, synth
+    rng = np.random.default_rng(synth.SEED)
+    for n, nt in ((N_GRID, N_TIME), (1_000_000, 100)):
+        f, w, abw = _ou_tables(nt, rng, synth.SIGMA)
+        f_d, w_d, abw_d = _lib.dev(f), _lib.dev(w), tuple(_lib.dev(v) for v in abw)
+        grid = torch.rand((n, nt), dtype=torch.float64, device="cuda")
+        gb = (n * nt * 8 + n * 8) / 1e9
+        for name, fn in (("chi2_grid_weighted_kernel", lambda: _lib.chi2_grid_weighted(f_d, w_d, grid)),
+                         ("chi2_ou_kernel", lambda: _lib.chi2_grid_ou(f_d, grid, *abw_d))):
+            fn()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(5):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            dt = a.elapsed_time(b) * 1e-3 / 5
+            print("events  %-36s %d x %d  %.3f ms  %.2f TB/s  (%.2f GB)" % (name, n, nt, dt * 1e3, gb / dt / 1e3, gb), flush=True)
+        del grid
+
+
+def ou_summary(trace):
+    """per-launch times of the `ou_kernels` step from rocprofv3's kernel trace, by kernel, each shape's first (warm-up)
+    launch left out, and the ratio of chi2_ou_kernel to the plain reduction on the same grid"""
+    lines, avg = [], {}
+    for f in glob.glob(os.path.join(trace, "**", "*kernel_trace.csv"), recursive=True):
+        groups = {}
+        for row in csv.DictReader(open(f)):
+            name = row["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
+            if "chi2_rows_kernel" in name or "chi2_ou_kernel" in name:
+                groups.setdefault(name, []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
+        for name, ns in groups.items():
+            # (the staged plain reduction runs on both shapes, six launches each, the large grid first; chi2_ou_kernel<false>
+            # on the large grid only, <true> -- one trip -- at 100 stamps only)
+            shapes = ((N_GRID, N_TIME), (1_000_000, 100))
+            if "chi2_ou" in name:
+                shapes = shapes[1:] if "<true" in name else shapes[:1]
+            for part, (rows, nt) in zip((ns[i:i + 6] for i in range(0, len(ns), 6)), shapes):
+                avg[("ou" if "chi2_ou" in name else "plain", nt)] = a = sum(part[1:]) / max(len(part) - 1, 1)
+                gb = (rows * nt * 8 + rows * 8) / 1e9
+                lines.append("rocprofv3 %-44s %d x %d  %d launches  %.1f us  %.2f TB/s  (%.2f GB)\n"
+                             % (name[:44], rows, nt, len(part) - 1, a * 1e-3, gb / (a * 1e-9) / 1e3, gb))
+    for nt in (N_TIME, 100):
+        if ("ou", nt) in avg and ("plain", nt) in avg:
+            lines.append("rocprofv3 chi2_ou_kernel / chi2_rows_kernel<Chi2Plain> at %d stamps: %.2f\n"
+                         % (nt, avg[("ou", nt)] / avg[("plain", nt)]))
+    return "".join(lines)
+
+
+def ou_e2e():
+    """wall clock of calc_probs_datasets on two datasets of 50 points with and without red_sigma / red_timescale on the
+    second: one warm-up each, then E2E_ROUNDS rounds in which the two take turns"""
+    import numpy as np
+    tg, (t, f, s, P), kw, cases = _toi465()
+    two = cases[1][1]
+    cadence = float(np.median(np.diff(two[1]["time"])))
+    with_r = [two[0], dict(two[1], red_sigma=OU_PARAMS[0] * s, red_timescale=OU_PARAMS[1] * cadence)]
+    runs = [("2 datasets of 50 points", lambda: tg.calc_probs_datasets(two, P, **kw)),
+            ("2 datasets of 50 points, red noise on the second", lambda: tg.calc_probs_datasets(with_r, P, **kw))]
+    times, fpp = {name: [] for name, _ in runs}, {}
+    for name, fn in runs:
+        _timed_pass(fn)
+    for _ in range(E2E_ROUNDS):
+        for name, fn in runs:
+            times[name].append(_timed_pass(fn))
+            fpp[name] = tg.FPP
+    for name, _ in runs:
+        v = np.sort(times[name])
+        print("e2e     %-60s median %.4f s  min %.4f s  max %.4f s  (%d rounds, FPP %.6g)"
+              % (name, np.median(v), v[0], v[-1], v.size, fpp[name]), flush=True)
+
+
 ROUTE_PASSES = 3
 
 
@@ -320,6 +416,13 @@ def job(path, only=None):
                 out.write(rates_summary(trace3))
         if want("baseline_e2e"):
             ok = ok and _step(out, 420, [sys.executable, me, "baseline_e2e"])
+        if want("ou_rates"):
+            trace4 = os.path.join(base, "rocprof_datasets_ou")
+            ok = ok and _step(out, 300, ["rocprofv3", "--kernel-trace", "--stats", "-d", trace4, "-o", "ou", "--output-format",
+                                         "csv", "--", sys.executable, me, "ou_kernels"])
+            if ok:
+                out.write(ou_summary(trace4))
+            ok = ok and _step(out, 420, [sys.executable, me, "ou_e2e"])
         out.write("job %s\n" % ("complete" if ok else "ended early"))
     return 0 if ok else 1
 
@@ -335,6 +438,10 @@ if __name__ == "__main__":
         rates()
     elif sys.argv[1:2] == ["baseline_e2e"]:
         baseline_e2e()
+    elif sys.argv[1:2] == ["ou_kernels"]:
+        ou_kernels()
+    elif sys.argv[1:2] == ["ou_e2e"]:
+        ou_e2e()
     else:
         dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(os.path.dirname(os.path.abspath(__file__)), "results.txt")
         only = sys.argv[sys.argv.index("--only") + 1].split(",") if "--only" in sys.argv else None

@@ -40,6 +40,8 @@ ABI_SYMBOLS = (
 )
 # ... include/trx_warp.h (both libraries: the weight histogram on its own, prefix trxw_)
 WARP_SYMBOLS = ("trxw_hist_from_halfchi2",)
+# ... include/trx_noise.h (both libraries: the row reduction under correlated noise, prefix trxn_)
+NOISE_SYMBOLS = ("trxn_chi2_grid_ou",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -181,6 +183,8 @@ def _load(path, testing):
                                               c_size_t, _vp]
     L.trxw_hist_from_halfchi2.restype = c_int
     L.trxw_hist_from_halfchi2.argtypes = [_vp, _vp, _vp, _vp, c_long, c_double, _vp, _vp, c_size_t, _vp]
+    L.trxn_chi2_grid_ou.restype = c_int
+    L.trxn_chi2_grid_ou.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, _vp]
     L.trx_grid_quantiles.restype = c_int
     L.trx_grid_quantiles.argtypes = [_vp, c_long, c_int, _vp, _vp, c_long, _vp, c_int, _vp, _vp]
     L.trx_lnl_batch_host.restype = c_int
@@ -547,6 +551,31 @@ def chi2_grid_baseline(flux_d, inv_var_d, grid_d, wbasis_d, minv, secdepth_d=Non
                                 and coef_out.is_contiguous())
     return _chi2_rows("trx_chi2_grid_baseline", flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out, wbasis_d.data_ptr(),
                       k, minv.ctypes.data, coef_out.data_ptr() if coef_out is not None else None)
+
+
+def chi2_grid_ou(flux_d, grid_d, alpha_d, beta_d, omega_d, secdepth=None, sec_limit=float("inf"), out=None):
+    """chi2_grid_weighted for a light curve with white plus exponential (Ornstein-Uhlenbeck) noise (trxn_chi2_grid_ou,
+    include/trx_noise.h): per row 0.5 sum_n omega[n] (y_n - g_n)^2, y = flux - grid[r], g_0 = 0,
+    g_n = alpha[n] g_(n-1) + beta[n] y_(n-1).  alpha_d, beta_d, omega_d: [n_time] fp64 device tensors
+    (datasets.ou_system).  The other arguments are chi2_grid_weighted's."""
+    require_gpu()
+    n, nt = grid_d.shape
+    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    for v in (flux_d, alpha_d, beta_d, omega_d):
+        assert v.numel() == nt and v.dtype == torch.float64 and v.is_contiguous()
+    assert secdepth is None or (secdepth.numel() == n and secdepth.is_contiguous())
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
+    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
+    if n == 0:
+        return out                     # (an empty tensor has no address to pass)
+    with torch.cuda.device(grid_d.device):
+        check(lib().trxn_chi2_grid_ou(flux_d.data_ptr(), grid_d.data_ptr(), nt, n,
+                                      secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
+                                      int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
+                                      omega_d.data_ptr(), _stream(grid_d)))
+    return out
 
 
 def log_mean_exp(logw_d, n_total):

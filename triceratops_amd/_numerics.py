@@ -139,6 +139,25 @@ def baseline_halfchi2(resid, w, basis, sigmas=None):
     return np.maximum(0.5 * (S2 - q), 0.0)
 
 
+def ou_halfchi2(y, alpha, beta, omega, dtype=np.float64):
+    """chi^2/2 of a light curve's residuals under white plus exponential (Ornstein-Uhlenbeck) noise (DESIGN.md section
+    14), on the host: the statement of what trxn_chi2_grid_ou computes per row,
+        g_0 = 0,  g_n = alpha_n g_(n-1) + beta_n y_(n-1),   h = 0.5 sum_n omega_n (y_n - g_n)^2 = 0.5 y^T K^-1 y,
+    alpha, beta, omega [T] from datasets.ou_system; the determinant of K depends on the dataset only and is dropped.
+    y: [..., T] residuals.  A sequential loop over T, vectorised over the rows, in `dtype` (np.longdouble: the tests'
+    reference)."""
+    y = np.asarray(y, dtype=dtype)
+    alpha, beta, omega = (np.asarray(v, dtype=dtype) for v in (alpha, beta, omega))
+    g = np.zeros(y.shape[:-1], dtype=dtype)
+    h = np.zeros(y.shape[:-1], dtype=dtype)
+    for n in range(y.shape[-1]):
+        if n > 0:
+            g = alpha[n] * g + beta[n] * y[..., n - 1]
+        z = y[..., n] - g
+        h = h + omega[n] * z * z
+    return h * dtype(0.5)
+
+
 def warp_identity():
     """the identity grid: [WARP_DIMS][WARP_BINS + 1] edges b / 64 (the map returns its input, ln J = 0, exactly)"""
     return np.tile(np.arange(WARP_BINS + 1) / WARP_BINS, (WARP_DIMS, 1))

@@ -1,6 +1,6 @@
 // libtrx.so: the host side of the likelihood path and the C ABI (include/trx.h) for gfx950.
 //
-// The kernels live in two headers that only this file includes:
+// The kernels live in three headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
 //                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
@@ -9,6 +9,8 @@
 //                    device share (RowsArgs, batch_rows, batch_plan, set_scratch)
 //   trx_reduce.hpp   chi2_grid_kernel, chi2_rows_kernel<STAGE, Terms> (row reductions over a materialised grid; one launcher
 //                    here, chi2_rows_launch) and the log-mean-exp kernels, HBM bound
+//   trx_noise.hpp    chi2_ou_kernel<ONE> (the row reduction under correlated noise: a scan along the row; chi2_ou_launch
+//                    here; include/trx_noise.h)
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
 // lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
@@ -29,6 +31,7 @@
 #include <vector>
 
 #include "../../include/trx.h"
+#include "../../include/trx_noise.h"
 #include "trx_device.hpp"
 #include "trx_internal.hpp"
 #include "trx_knobs.hpp"
@@ -56,6 +59,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 
 #include "trx_cells.hpp"
 #include "trx_reduce.hpp"
+#include "trx_noise.hpp"
 #include "trx_bands.hpp"
 
 namespace {
@@ -1000,6 +1004,20 @@ void chi2_rows_launch(const double* flux, const double* inv_var, const double* m
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, st, flux, inv_var, model_grid, n_time, n, secdepth,
                        sec_limit, accumulate, out, terms);
 }
+
+// One launch of chi2_ou_kernel<ONE> (trxn_chi2_grid_ou): ONE while a row is a single trip of kOuTrip stamps.  No LDS, so
+// the registers bound what stays resident: 4 blocks of 256 threads a CU at up to 128 VGPRs, on 256 CUs; the rows behind
+// that cap are the second row of a wave's pass and its further passes.
+void chi2_ou_launch(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                    double sec_limit, int accumulate, double* out, const double* alpha, const double* beta,
+                    const double* omega, hipStream_t st)
+{
+    long blocks = (n + 3) / 4;
+    if (blocks > 256L * 4) blocks = 256L * 4;
+    const auto kernel = n_time <= kOuTrip ? chi2_ou_kernel<true> : chi2_ou_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
+                       accumulate, out, alpha, beta, omega);
+}
 }  // namespace
 
 // =========================================================================================
@@ -1092,6 +1110,19 @@ int trx_chi2_grid_offset(const double* flux, const double* inv_var, const double
     if (n == 0) return TRX_OK;
     chi2_rows_launch(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2,
                      Chi2Offset{sum_w, prior_prec, offset_out}, static_cast<hipStream_t>(stream));
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trxn_chi2_grid_ou(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                      double sec_limit, int accumulate, double* out_halfchi2, const double* alpha, const double* beta,
+                      const double* omega, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (!flux || !model_grid || !out_halfchi2 || !alpha || !beta || !omega) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    if (n == 0) return TRX_OK;
+    chi2_ou_launch(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
+                   static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

@@ -4,9 +4,11 @@ A dataset is one light curve with its own cadence: `time`, `flux`, `flux_err` (o
 `exptime` and `nsamples`, and optionally `offset_sigma`: the standard deviation of a Gaussian prior on a constant
 baseline offset of that light curve, marginalised per draw (inf: a flat prior), and `baseline` / `baseline_sigma`: up to
 MAX_BASELINE_TERMS columns B_k[t] of a linear baseline model sum_k c_k B_k[t] with priors c_k ~ N(0, s_k^2), marginalised
-the same way (baseline_system).  This module is host side and numpy only: validation, the reference noise sigma_bar and the
-per-star renormalisation.  A `Datasets` object is what the lnZ_* functions receive in place of `time` (with
-flux = None and sigma = sigma_bar); only the device sampling modes evaluate it (fused._Scenario).
+the same way (baseline_system), or `red_sigma` / `red_timescale`: correlated noise of standard deviation s_r with an
+exponential kernel of time scale tau next to the white errors (ou_system).  This module is host side and numpy only:
+validation, the reference noise sigma_bar and the per-star renormalisation.  A `Datasets` object is what the lnZ_*
+functions receive in place of `time` (with flux = None and sigma = sigma_bar); only the device sampling modes evaluate it
+(fused._Scenario).
 """
 import math
 from typing import NamedTuple
@@ -30,6 +32,8 @@ class Dataset(NamedTuple):
     offset_sigma: float = None    # prior sigma of a constant baseline offset (inf: flat); None: no offset
     baseline: np.ndarray = None         # [K_b][T] columns of the linear baseline model, finite; None: none
     baseline_sigma: np.ndarray = None   # [K_b] prior sigmas of their coefficients (inf: flat); None without baseline
+    red_sigma: float = None       # standard deviation of the correlated (Ornstein-Uhlenbeck) noise, flux units; None: white
+    red_timescale: float = None   # its time scale, in the units of `time` (inf allowed); None without red_sigma
 
 
 class BaselineSystem(NamedTuple):
@@ -140,6 +144,57 @@ def _baseline(i, value, sigma, n_given, keep):
     return np.ascontiguousarray(B), np.ascontiguousarray(s)
 
 
+def _red_noise(i, sigma, timescale, time, others):
+    """a dataset's "red_sigma" and "red_timescale" -> (s_r, tau) or (None, None); time: the kept stamps; others: whether
+    the dataset marginalises an offset or a baseline as well"""
+    if sigma is None and timescale is None:
+        return None, None
+    if sigma is None or timescale is None:
+        raise ValueError("dataset %d: red_sigma and red_timescale are given together or not at all" % i)
+    for name, value in (("red_sigma", sigma), ("red_timescale", timescale)):
+        if isinstance(value, (bool, str, bytes)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise ValueError("dataset %d: %s must be a number > 0 (got %r)" % (i, name, value))
+    sigma, timescale = float(sigma), float(timescale)
+    if not (sigma > 0 and math.isfinite(sigma)):              # (also NaN)
+        raise ValueError("dataset %d: red_sigma must be a finite number > 0 (got %r)" % (i, sigma))
+    if not timescale > 0:
+        raise ValueError("dataset %d: red_timescale must be a number > 0 or inf (got %r)" % (i, timescale))
+    if others:
+        raise ValueError("dataset %d: red_sigma together with offset_sigma or baseline is not built (a generalised "
+                         "least-squares problem): give the correlated noise or the marginalised terms" % i)
+    if np.any(np.diff(time) < 0):
+        raise ValueError("dataset %d: red_sigma needs time in non-decreasing order: the noise model is a process in "
+                         "time and follows the stamps as given (a folded light curve is not sorted silently)" % i)
+    return sigma, timescale
+
+
+def ou_system(dataset):
+    """(alpha, beta, omega), float64 [T] each: the Kalman form of a Dataset's noise covariance
+    K = diag(flux_err^2) + red_sigma^2 exp(-|t_i - t_j| / red_timescale), stamps in time order -- the one place that forms
+    them, for the device path (fused._Dataset) and for the numpy statement (_numerics.ou_halfchi2).  With P_0 = s_r^2 and
+    phi_n = exp(-(t_n - t_(n-1)) / tau):
+        D_n = P_n + sigma_n^2,  kappa_n = P_n / D_n,  omega_n = 1 / D_n,
+        alpha_n = phi_n (1 - kappa_(n-1)),  beta_n = phi_n kappa_(n-1)   (alpha_0 = beta_0 = 0),
+        P_n = phi_n^2 (1 - kappa_(n-1)) P_(n-1) + s_r^2 (1 - phi_n^2)    (1 - phi^2 as -expm1(-2 dt / tau)),
+    so that 0.5 y^T K^-1 y = 0.5 sum_n omega_n (y_n - g_n)^2, g_0 = 0, g_n = alpha_n g_(n-1) + beta_n y_(n-1)."""
+    t, var = dataset.time, dataset.flux_err * dataset.flux_err
+    s2, tau = float(dataset.red_sigma) ** 2, float(dataset.red_timescale)
+    T = t.size
+    alpha, beta, omega = np.zeros(T), np.zeros(T), np.zeros(T)
+    P, kappa = s2, 0.0
+    for n in range(T):
+        if n > 0:
+            dt = float(t[n] - t[n - 1])
+            phi = math.exp(-dt / tau)
+            alpha[n] = phi * (1.0 - kappa)
+            beta[n] = phi * kappa
+            P = phi * phi * (1.0 - kappa) * P + s2 * -math.expm1(-2.0 * dt / tau)
+        D = P + float(var[n])
+        kappa = P / D
+        omega[n] = 1.0 / D
+    return alpha, beta, omega
+
+
 def _check_baseline(i, dataset):
     """the limits of a dataset's baseline terms: their number and the conditioning of the scaled system"""
     n_terms = (dataset.offset_sigma is not None) + (0 if dataset.baseline is None else dataset.baseline.shape[0])
@@ -160,11 +215,13 @@ def _check_baseline(i, dataset):
 
 def validate(datasets):
     """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
-    baseline_sigma]} -> a list of Dataset.  Points with a NaN time or flux are dropped together with their error and their
+    baseline_sigma, red_sigma, red_timescale]} -> a list of Dataset.  Points with a NaN time or flux are dropped together with their error and their
     baseline entries; a scalar flux_err is broadcast.  ValueError for an empty list, too many datasets, mismatched
     lengths, an error that is not finite or not positive, a dataset without points, an offset_sigma that is not None, a
     number > 0 or inf, a baseline that is not [K][len(time)] and finite at the kept points, a baseline_sigma that is not
-    > 0 or inf per column (or has no baseline), more than MAX_BASELINE_TERMS terms, or collinear terms."""
+    > 0 or inf per column (or has no baseline), more than MAX_BASELINE_TERMS terms, or collinear terms; for red_sigma
+    without red_timescale or the reverse, a red_sigma that is not a finite number > 0, a red_timescale that is not > 0 or
+    inf, either of them next to offset_sigma or baseline, or with kept stamps that are not in non-decreasing order."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -173,7 +230,8 @@ def validate(datasets):
         raise ValueError("at most %d datasets (got %d)" % (MAX_DATASETS, len(datasets)))
     out = []
     for i, d in enumerate(datasets):
-        unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"}
+        unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma",
+                            "red_sigma", "red_timescale"}
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -201,9 +259,12 @@ def validate(datasets):
         if nsamples < 1:
             raise ValueError("dataset %d: nsamples must be >= 1" % i)
         baseline, baseline_sigma = _baseline(i, d.get("baseline"), d.get("baseline_sigma"), n_given, keep)
+        offset_sigma = _offset_sigma(i, d.get("offset_sigma"))
+        red_sigma, red_timescale = _red_noise(i, d.get("red_sigma"), d.get("red_timescale"), time,
+                                              offset_sigma is not None or baseline is not None)
         out.append(Dataset(np.ascontiguousarray(time), np.ascontiguousarray(flux), np.ascontiguousarray(err),
                            float(d.get("exptime", DEFAULT_EXPTIME)), nsamples,
-                           _offset_sigma(i, d.get("offset_sigma")), baseline, baseline_sigma))
+                           offset_sigma, baseline, baseline_sigma, red_sigma, red_timescale))
         _check_baseline(i, out[-1])
     return out
 
@@ -244,6 +305,10 @@ class Datasets:
         return any(s.baseline is not None for s in self.sets)
 
     @property
+    def has_red_noise(self):
+        return any(s.red_sigma is not None for s in self.sets)
+
+    @property
     def size(self):
         """points of all datasets together"""
         return sum(s.time.size for s in self.sets)
@@ -253,7 +318,9 @@ class Datasets:
         offset_sigma is an error in flux units and is divided by the flux ratio as the errors are: s^2 sum(1 / err^2) --
         and with it the factor of the marginal that the evidence drops -- is the same for every
         star.  So is every finite baseline_sigma (flux units per unit of its column); the columns are left alone: the scaled
-        system matrix of baseline_system is then the same for every star."""
+        system matrix of baseline_system is then the same for every star.  A red_sigma is in flux units too and is divided
+        the same way: alpha and beta of ou_system do not change, omega scales with the square of the flux ratio, and the
+        determinant ratio that the evidence drops is the same for every star."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
@@ -263,6 +330,9 @@ class Datasets:
             bsig = s.baseline_sigma
             if bsig is not None:
                 bsig = np.where(np.isfinite(bsig), bsig / star_fluxratio, bsig)
+            red = s.red_sigma
+            if red is not None:
+                red = red / star_fluxratio
             out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err), offset_sigma=off,
-                                  baseline_sigma=bsig))
+                                  baseline_sigma=bsig, red_sigma=red))
         return Datasets(out)

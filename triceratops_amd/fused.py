@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, funcs
-from .datasets import Datasets, baseline_system
+from .datasets import Datasets, baseline_system, ou_system
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
@@ -229,6 +229,8 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # term 0 of the same system (datasets.baseline_system) -- marginalised per draw by trx_chi2_grid_baseline.
 # DATASET_BASELINES = {}: every such call leaves {work unit: [per branch, a list per dataset: None or the [K_b] posterior-
 # mean coefficients of the branch's best draw]} there, in the call's normalisation (target.dataset_baselines).
+# A dataset with `red_sigma` / `red_timescale` has correlated (Ornstein-Uhlenbeck) noise next to its white errors: its
+# reduction is trxn_chi2_grid_ou on the alpha, beta, omega of datasets.ou_system (grid evaluation only).
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
@@ -762,11 +764,15 @@ class _Dataset(NamedTuple):
     nsamples: int
     offset: Optional[tuple] = None           # (sum_w, 1 / s^2)
     baseline: Optional[_Baseline] = None
+    ou: Optional[tuple] = None               # (alpha, beta, omega) on the device: correlated noise (datasets.ou_system)
 
     @classmethod
     def upload(cls, d, dev):
         inv_var = 1.0 / (d.flux_err * d.flux_err)
         rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
+        if d.red_sigma is not None:
+            # (validate refuses an offset or a baseline next to it)
+            return rec._replace(ou=tuple(_on_device(v, dev) for v in ou_system(d)))
         if d.baseline is not None:
             system = baseline_system(d)
             return rec._replace(baseline=_Baseline(_on_device(system.g, dev), system.minv, np.sqrt(system.D),
@@ -780,8 +786,10 @@ class _Dataset(NamedTuple):
     def halfchi2(self, grid, secdepth=None, sec_limit=float("inf"), out=None, offset_out=None, coef_out=None):
         """this dataset's weighted chi^2/2 of every row of a model grid [n][T], written or added to `out`; +inf where
         secdepth >= sec_limit.  The one place that picks the reduction: trx_chi2_grid_baseline for baseline columns (coef_out:
-        the rows' scaled coefficients), trx_chi2_grid_offset for an offset alone (offset_out: the rows' offsets), else
-        trx_chi2_grid_weighted."""
+        the rows' scaled coefficients), trx_chi2_grid_offset for an offset alone (offset_out: the rows' offsets),
+        trxn_chi2_grid_ou for correlated noise, else trx_chi2_grid_weighted."""
+        if self.ou is not None:
+            return _lib.chi2_grid_ou(self.flux, grid, *self.ou, secdepth, sec_limit, out=out)
         if self.baseline is not None:
             return _lib.chi2_grid_baseline(self.flux, self.inv_var, grid, self.baseline.g, self.baseline.minv, secdepth,
                                            sec_limit, out=out, coef_out=coef_out)
@@ -1187,6 +1195,9 @@ class _Scenario:
         if DATASET_EVALUATION == "fused" and any(d.baseline is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: the fused kernel "
                                       "carries no sums of basis * residual; use evaluation='grid'")
+        if DATASET_EVALUATION == "fused" and any(d.ou is not None for d in self.datasets):
+            raise NotImplementedError("evaluation='fused' with a red_sigma dataset is not built: the fused kernel "
+                                      "carries no recurrence along the row; use evaluation='grid'")
         n = int(block.shape[1])
         h = torch.zeros(n, dtype=F64, device=self.dev)         # (0 + x = x: every reduction accumulates)
         if n == 0:

@@ -86,13 +86,15 @@ def polynomial_baseline(time, order: int):
 
 def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int = 50,
                     exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None,
-                    baseline_order: int = 0, baseline_sigma=None):
+                    baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
     {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
     empty bins are dropped.
     offset_sigma (None: no offset; a number > 0 or inf) is passed through: the prior of the dataset's baseline offset.
     baseline_order > 0: "baseline" = polynomial_baseline(kept bins' times, baseline_order), with baseline_sigma (a number
     or one per column; None: flat) passed through; 0: both keys are None.
+    red_sigma, red_timescale (both or neither): the dataset's correlated noise, passed through as the keys of those names
+    when given.
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -106,6 +108,9 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     head = yb[:n_sigma]
     scatter = float(np.sqrt(np.mean(count[:n_sigma] * (head - np.mean(head)) ** 2)))
     baseline = polynomial_baseline(tb, baseline_order) if int(baseline_order) > 0 else None
-    return {"time": tb, "flux": yb, "flux_err": scatter / np.sqrt(count), "exptime": float(exptime),
-            "nsamples": int(nsamples), "offset_sigma": offset_sigma, "baseline": baseline,
-            "baseline_sigma": baseline_sigma}
+    out = {"time": tb, "flux": yb, "flux_err": scatter / np.sqrt(count), "exptime": float(exptime),
+           "nsamples": int(nsamples), "offset_sigma": offset_sigma, "baseline": baseline,
+           "baseline_sigma": baseline_sigma}
+    if red_sigma is not None or red_timescale is not None:
+        out["red_sigma"], out["red_timescale"] = red_sigma, red_timescale
+    return out

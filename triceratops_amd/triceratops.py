@@ -279,6 +279,8 @@ class target:
             raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: use evaluation='grid'")
         if ds.has_baselines and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: use evaluation='grid'")
+        if ds.has_red_noise and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with a red_sigma dataset is not built: use evaluation='grid'")
         with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, **dataset_switches):
             rows = sharding.run_units(units, verbose=verbose, as_rows=True)
         return units, rows, n_scen
@@ -328,7 +330,20 @@ class target:
         A^-1 b of the scenario's best draw in the target's normalisation (NaN without a finite lnZ), None for a dataset
         without "baseline"; the whole attribute is None when no dataset has one.  `.dataset_offsets` reports the offset of
         a baseline dataset that has offset_sigma as well.  Not built: a multiplicative normalisation, baselines in the
-        fused evaluation, calc_probs_many with datasets."""
+        fused evaluation, calc_probs_many with datasets.
+
+        A dataset may carry "red_sigma": s_r, finite and > 0, in flux units, and "red_timescale": tau > 0 (inf allowed),
+        in the units of its time -- both or neither: correlated noise next to the white errors, with the covariance
+        K = diag(sigma_t^2) + s_r^2 exp(-|t_i - t_j| / tau) (one Ornstein-Uhlenbeck term).  The dataset's term of the
+        log-weight is then 0.5 y^T K^-1 y, y_t = flux_t - model_t, evaluated exactly in O(len(time)) per draw by the
+        process' Kalman recurrence (datasets.ou_system, trxn_chi2_grid_ou).  det K depends on the dataset only -- s_r
+        scales with the errors when a light curve is renormalised to a star -- and is dropped as the offset's factor is.
+        sigma_bar, the secondary-eclipse rule and the best draw (the smallest sum of the datasets' terms) are formed as
+        without the keys.  tau -> 0: white noise with sigma_t^2 + s_r^2; tau = inf: offset_sigma = s_r.  The kept
+        stamps must be in non-decreasing order (ValueError otherwise: the model is a process in time), and the keys do
+        not combine with offset_sigma or baseline on the same dataset (ValueError).  Grid evaluation only:
+        evaluation="fused" with such a dataset raises NotImplementedError.  Not built: fitting s_r and tau, more than
+        one term."""
         ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
         best_offsets = {} if ds.has_offsets else None
         best_baselines = {} if ds.has_baselines else None
