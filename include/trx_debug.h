@@ -84,6 +84,31 @@ int trx_debug_whole_trips(long* whole, long* walked, int reset);
  * had post_rows > 0.  Host counters; they cannot change a result.  Any pointer may be NULL. */
 int trx_debug_chain_counts(long* chains, long* calls_in_chains, long* posterior_calls_in_chains, int reset);
 
+/* The selection stage of ONE branch of a scenario call on the caller's numbers: exactly what trx_scenario_enqueue runs
+ * behind the branch's likelihood kernels -- lme_partial_kernel<SCEN> with the branch's final stage (the evidence, the
+ * best draw and its columns, the masked count, the tie count, the status, the moments, the largest log-weight for the
+ * posterior resampler), then, for K > 1, table_kernel -- with the arguments a real call builds, on the stream's scenario
+ * scratch behind its persistent block, which is left at zero.  No kernel of its own; it waits for the stream.
+ *   halfchi2   DEVICE [n], chi^2/2 of the masked draws in list order; 16-byte aligned (TRX_ERR_ARG otherwise)
+ *   lnprior    DEVICE [N] or NULL, stored densely like the columns: row r at r, with twin != 0 at N - 1 - r
+ *   cols       DEVICE [ncol][N], the masked draws' columns, stored the same way
+ *   cols_pad   DEVICE [ncol][max(K, 1)]: the stand-in draws 0 .. K - 1 (the record of a branch without rows, the table's
+ *              spare rows)
+ *   n, N       the masked count -- handed to the kernels through a `long` on the device, as in a real call -- and the
+ *              draws the launch is sized for (n_upper = N: the blocks beyond lme_blocks(n) exist and leave);
+ *              N >= max(n, K, 1)
+ *   n_total    the divisor of the evidence (>= 1); ncol 11 or 14; twin 0 / 1 (ScenFinal.branch, TableArgs.branch)
+ *   K          0: no table, or 2 .. TRX_TABLE_MAX_ROWS; moments 0 / 1: a record of TRX_SCENARIO_OUT /
+ *              TRX_SCENARIO_OUT_MOMENTS doubles
+ *   out_record   HOST, the branch record (include/trx.h); slots no kernel writes read 0x7f7f7f7f7f7f7f7f (1.38e306)
+ *   out_post_x   HOST [1], the largest log-weight the final stage leaves in the scratch
+ *   out_table    HOST [TRX_TABLE_BRANCH(K)] (K > 1; else may be NULL)
+ * No bounded evaluation (no row-constant header: the -90 floor is not applied). */
+int trx_debug_select_from_halfchi2(const double* halfchi2, const double* lnprior, const double* cols,
+                                   const double* cols_pad, long n, long N, long n_total, int ncol, int twin, int K,
+                                   int moments, double lnsigma, double* out_record, double* out_post_x,
+                                   double* out_table, void* stream);
+
 /* scratch buffers of calls captured into hipGraphs: how many a live graph still owns, how many wait in the library's
  * pool for reuse (trx_release_scratch frees those) */
 int trx_debug_capture_buffers(long* live, long* idle);

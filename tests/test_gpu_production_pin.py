@@ -144,6 +144,62 @@ def test_hundred_row_table_in_device_mode_equals_the_operator_chain():
         triceratops_amd.set_sampling("numpy")
 
 
+def _deferred(name, N, K):
+    """lnZ_<name> in device mode as a deferred call of the library's chain, so that the raw record and the table block
+    can be read (tests/test_gpu_posterior.py, _native): (record, table [2][15][K + 1], columns, branches)"""
+    import triceratops_amd
+    from triceratops_amd import _lib, fused
+    s = [float(v) for v in G["star"]]
+    old = (fused.POSTERIOR_ROWS, fused.TABLE_ROWS)
+    sink = _lib.moments_swap(None)
+    triceratops_amd.set_sampling("device")
+    try:
+        fused.POSTERIOR_ROWS, fused.TABLE_ROWS = 0, K
+        fused.set_thread_seed(11)
+        fused.begin_deferred(1)
+        pend = getattr(fused, "lnZ_" + name)(G["time"], G["flux"], float(G["sigma"][0]), 3.3, s[0], s[1], s[2], 0.0,
+                                             N=N, parallel=True)
+        assert isinstance(pend, fused.Pending) and pend.stride == fused.SCENARIO_OUT and pend.table_rows == K
+        fused.flush()
+        torch.cuda.synchronize()
+        rec = pend.out.numpy().copy()
+        table = pend.table.numpy().copy().reshape(2, 15, K + 1)
+    finally:
+        fused.end_deferred()
+        fused.set_thread_seed(None)
+        _lib.moments_swap(sink)
+        fused.POSTERIOR_ROWS, fused.TABLE_ROWS = old
+        triceratops_amd.set_sampling("numpy")
+    return rec, table, pend.ncol, 1 if pend.ncol == 11 else 2
+
+
+@pytest.mark.parametrize("K", [2, 100, 127])
+def test_record_and_table_of_one_call_agree(K):
+    """what the final stage of the evidence (the record) and table_kernel (the table) say about the same chi^2 values of a
+    call must fit together, whatever those values are: the table's first row is the record's best draw, byte for byte;
+    slot 14 -- the K + 1 smallest chi^2 -- does not decrease, NaN last; and the record's tie count, capped at K + 1, is the
+    number of leading slot-14 entries equal to the first"""
+    from triceratops_amd import fused
+    for name in ("TTP", "TEB"):
+        for N in (700, 60000):
+            rec, table, ncol, nbr = _deferred(name, N, K)
+            W = fused.SCENARIO_OUT
+            for b in range(nbr):
+                r, t = rec[b * W:(b + 1) * W], table[b]
+                n = int(r[ncol + 1])
+                assert 0 <= n <= N and r[fused.SCEN_STATUS] == 0.0, (name, N, b, r)
+                assert t[:ncol, 0].tobytes() == r[:ncol].tobytes(), (name, N, b, t[:ncol, 0], r[:ncol])
+                v = t[14]
+                nan = np.isnan(v)
+                assert not np.any(nan[:-1] & ~nan[1:]), (name, N, b, v)
+                assert np.all(v[~nan][1:] >= v[~nan][:-1]), (name, N, b, v)
+                m = min(n, K + 1)
+                assert nan[m:].all(), (name, N, b, v)               # no such draw: NaN
+                same = (v[:m] == v[0]) | (np.isnan(v[:m]) & np.isnan(v[0]))
+                lead = m if same.all() else int(np.argmin(same))
+                assert min(int(r[fused.SCEN_TIES]), K + 1) == lead, (name, N, b, r[fused.SCEN_TIES], v[:8])
+
+
 FULL = gold("reference_full.npz") if os.path.exists(os.path.join(GOLD, "reference_full.npz")) else None
 RUNS = [str(r) for r in FULL["runs"]] if FULL is not None else []
 

@@ -49,6 +49,7 @@ DEBUG_SYMBOLS = (
     "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison", "trx_set_debug_bug",
     "trx_set_probe_rows", "trx_set_star_chain", "trx_debug_capture_buffers", "trx_debug_chain_counts",
     "trx_set_row_order", "trx_debug_row_order", "trx_set_whole_trips", "trx_debug_whole_trips",
+    "trx_debug_select_from_halfchi2",
 )
 
 
@@ -217,6 +218,9 @@ def _load(path, testing):
         L.trx_debug_row_order.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long), _vp, _vp, _vp]
         L.trx_debug_whole_trips.restype = c_int
         L.trx_debug_whole_trips.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long), c_int]
+        L.trx_debug_select_from_halfchi2.restype = c_int
+        L.trx_debug_select_from_halfchi2.argtypes = [_vp, _vp, _vp, _vp, c_long, c_long, c_long, c_int, c_int, c_int, c_int,
+                                                     c_double, _vp, _vp, _vp, _vp]
     return L
 
 

@@ -723,4 +723,75 @@ extern "C" int trx_set_debug_poison(int on)
     trx::g_knob_poison = on ? 1 : 0;
     return TRX_OK;
 }
+
+// trx_debug_select_from_halfchi2 (include/trx_debug.h): what enqueue() runs for ONE branch behind its likelihood kernels
+// -- lme_draws with the ScenFinal of branch_final, then table_kernel with enqueue()'s TableArgs -- on the caller's chi^2/2,
+// prior and columns.  The scratch is the stream's scenario scratch (slot 1) behind its persistent block, as in enqueue().
+extern "C" int trx_debug_select_from_halfchi2(const double* halfchi2, const double* lnprior, const double* cols,
+                                              const double* cols_pad, long n, long N, long n_total, int ncol, int twin, int K,
+                                              int moments, double lnsigma, double* out_record, double* out_post_x,
+                                              double* out_table, void* stream)
+{
+    const int n_pad = K ? K : 1;
+    if (!halfchi2 || ((uintptr_t)halfchi2 % 16) != 0 || !cols || !cols_pad || !out_record || !out_post_x) return TRX_ERR_ARG;
+    if ((ncol != 11 && ncol != 14) || (twin != 0 && twin != 1) || (moments != 0 && moments != 1)) return TRX_ERR_ARG;
+    if (K != 0 && (K < 2 || K > TRX_TABLE_MAX_ROWS || !out_table)) return TRX_ERR_ARG;
+    if (n < 0 || N < 1 || N > 0x7fffffffL || n > N || N < n_pad || n_total < 1) return TRX_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    trx::StreamLock turn(st);
+    const int stride = moments ? TRX_SCENARIO_OUT_MOMENTS : TRX_SCENARIO_OUT;
+    const size_t rec_bytes = sizeof(double) * (2 * TRX_SCENARIO_OUT_MOMENTS + 1);
+    const size_t table_bytes = K ? sizeof(double) * TRX_TABLE_BRANCH(K) : 0;
+
+    Arena A;
+    const size_t o_state = A.reserve(trx::kScratchZeroed);     // persistent, as in enqueue(): left at zero
+    const size_t o_n = A.reserve(2 * sizeof(long));
+    const size_t o_res = A.reserve(rec_bytes);
+    const size_t o_ws = A.reserve(sizeof(double) * trx::kLmePart * kLmeParts);
+    const size_t o_pv = A.reserve(sizeof(double) * kLmeParts);
+    const size_t o_pi = A.reserve(sizeof(long) * 2 * kLmeParts);
+    const size_t o_idx = A.reserve(sizeof(int) * (size_t)N);    // (dense columns: the list is handed on, never read)
+    const size_t o_px = A.reserve(sizeof(double));
+    const size_t o_table = A.reserve(table_bytes);
+    TRXS_HIP(trx::stream_scratch(st, 1, A.used, reinterpret_cast<void**>(&A.base)));
+    unsigned* state = A.at<unsigned>(o_state);
+    long* n_dev = A.at<long>(o_n);
+    double* res = A.at<double>(o_res);
+    // the count goes to the device, where the kernels read it; what no kernel writes shows as 0x7f7f...: 1.38e306
+    TRXS_HIP(hipMemsetAsync(n_dev, 0, 2 * sizeof(long), st));
+    TRXS_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(n_dev), (int)n, 1, st));
+    TRXS_HIP(hipMemsetAsync(A.at<int>(o_idx), 0, sizeof(int) * (size_t)N, st));
+    TRXS_HIP(hipMemsetAsync(res, 0x7f, rec_bytes, st));
+    TRXS_HIP(hipMemsetAsync(A.at<double>(o_px), 0x7f, sizeof(double), st));
+    if (K) TRXS_HIP(hipMemsetAsync(A.at<double>(o_table), 0x7f, table_bytes, st));
+
+    trx::ScenFinal f{};
+    f.idx = A.at<int>(o_idx); f.cols = cols; f.cols0 = cols_pad; f.cols0_stride = n_pad; f.dense = 1;
+    f.N = N; f.n_total = n_total; f.ncol = ncol; f.branch = twin; f.last_branch = 1;
+    f.stride = stride;
+    f.res = res + (size_t)twin * stride;
+    f.flag_out = (twin == 0) ? res + 2 * stride : nullptr;
+    f.state = state;
+    f.post_x = A.at<double>(o_px);
+    auto bail = [&](int rc) {
+        (void)hipMemsetAsync(state, 0, trx::kScratchZeroed, st);
+        return rc;
+    };
+    if (int rc = trx::lme_draws(halfchi2, lnprior, lnsigma, N, n_dev, f.idx, A.at<double>(o_ws), A.at<double>(o_pv),
+                                A.at<long>(o_pi), nullptr, f, st))
+        return bail(rc);
+    if (K) {
+        TableArgs t{};
+        t.h = halfchi2; t.n_dev = n_dev; t.cols = cols; t.cols_pad = cols_pad; t.N = N;
+        t.ncol = ncol; t.branch = twin; t.K = K;
+        t.table = A.at<double>(o_table);
+        hipLaunchKernelGGL(table_kernel, dim3(1), dim3(256), 0, st, t);
+        if (hipGetLastError() != hipSuccess) return bail(TRX_ERR_HIP);
+    }
+    TRXS_HIP(hipMemcpyAsync(out_record, f.res, sizeof(double) * (size_t)stride, hipMemcpyDeviceToHost, st));
+    TRXS_HIP(hipMemcpyAsync(out_post_x, f.post_x, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (K) TRXS_HIP(hipMemcpyAsync(out_table, A.at<double>(o_table), table_bytes, hipMemcpyDeviceToHost, st));
+    TRXS_HIP(hipStreamSynchronize(st));
+    return TRX_OK;
+}
 #endif
