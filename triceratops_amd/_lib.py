@@ -42,6 +42,8 @@ ABI_SYMBOLS = (
 WARP_SYMBOLS = ("trxw_hist_from_halfchi2",)
 # ... include/trx_noise.h (both libraries: the row reduction under correlated noise, prefix trxn_)
 NOISE_SYMBOLS = ("trxn_chi2_grid_ou",)
+# ... include/trx_mix.h (both libraries: the same over a grid of candidate noise models, prefix trxm_)
+MIX_SYMBOLS = ("trxm_chi2_grid_ou_mix",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -186,6 +188,9 @@ def _load(path, testing):
     L.trxw_hist_from_halfchi2.argtypes = [_vp, _vp, _vp, _vp, c_long, c_double, _vp, _vp, c_size_t, _vp]
     L.trxn_chi2_grid_ou.restype = c_int
     L.trxn_chi2_grid_ou.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, _vp]
+    L.trxm_chi2_grid_ou_mix.restype = c_int
+    L.trxm_chi2_grid_ou_mix.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp,
+                                        _vp]
     L.trx_grid_quantiles.restype = c_int
     L.trx_grid_quantiles.argtypes = [_vp, c_long, c_int, _vp, _vp, c_long, _vp, c_int, _vp, _vp]
     L.trx_lnl_batch_host.restype = c_int
@@ -579,6 +584,38 @@ def chi2_grid_ou(flux_d, grid_d, alpha_d, beta_d, omega_d, secdepth=None, sec_li
                                       secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
                                       int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
                                       omega_d.data_ptr(), _stream(grid_d)))
+    return out
+
+
+def chi2_grid_ou_mix(flux_d, grid_d, alpha_d, beta_d, omega_d, lnc, secdepth=None, sec_limit=float("inf"), out=None,
+                     cand_out=None):
+    """chi2_grid_ou over J candidate noise models in one pass over the grid (trxm_chi2_grid_ou_mix, include/trx_mix.h): per
+    row T = -ln sum_j exp(lnc[j] - h_j), h_j what chi2_grid_ou gives on row j of alpha_d, beta_d, omega_d ([J][n_time] fp64
+    device tensors; datasets.ou_mix_system), clamped at 0.  lnc: [J] float64 on the host.  cand_out: an [n][J] fp64 device
+    tensor that receives the h_j, or None.  The other arguments are chi2_grid_weighted's."""
+    require_gpu()
+    n, nt = grid_d.shape
+    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    assert flux_d.numel() == nt and flux_d.dtype == torch.float64 and flux_d.is_contiguous()
+    lnc = np.ascontiguousarray(lnc, dtype=np.float64)
+    assert lnc.ndim == 1
+    j = int(lnc.size)
+    for v in (alpha_d, beta_d, omega_d):
+        assert v.shape == (j, nt) and v.dtype == torch.float64 and v.is_contiguous()
+    assert secdepth is None or (secdepth.numel() == n and secdepth.is_contiguous())
+    assert cand_out is None or (cand_out.shape == (n, j) and cand_out.dtype == torch.float64 and cand_out.is_contiguous())
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
+    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
+    if n == 0:
+        return out                     # (an empty tensor has no address to pass)
+    with torch.cuda.device(grid_d.device):
+        check(lib().trxm_chi2_grid_ou_mix(flux_d.data_ptr(), grid_d.data_ptr(), nt, n,
+                                          secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
+                                          int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
+                                          omega_d.data_ptr(), j, lnc.ctypes.data,
+                                          cand_out.data_ptr() if cand_out is not None else None, _stream(grid_d)))
     return out
 
 

@@ -158,6 +158,28 @@ def ou_halfchi2(y, alpha, beta, omega, dtype=np.float64):
     return h * dtype(0.5)
 
 
+def ou_mix_halfchi2(y, alpha, beta, omega, lnc, dtype=np.float64, return_candidates=False):
+    """A dataset's term of the log-weight with the amplitude and time scale of its correlated noise marginalised over J
+    candidates, on the host: the statement of what trxm_chi2_grid_ou_mix computes per row,
+        h_j = ou_halfchi2(y, alpha[j], beta[j], omega[j]),  a_j = h_j - lnc_j,  m = min_j a_j,
+        T = m - ln sum_j exp(m - a_j) = -ln sum_j exp(lnc_j - h_j),   stored as 0 where rounding drives it below,
+    alpha, beta, omega [J][T] and lnc [J] from datasets.ou_mix_system; the terms are summed in ascending j.  y: [..., T]
+    residuals.  In `dtype` (np.longdouble: the tests' reference).  J = 1 with lnc = 0 gives ou_halfchi2's bits.
+    return_candidates: (T, h [..., J])."""
+    lnc = np.asarray(lnc, dtype=dtype)
+    h = np.stack([ou_halfchi2(y, alpha[j], beta[j], omega[j], dtype=dtype) for j in range(lnc.size)], axis=-1)
+    a = h - lnc
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        m = np.fmin.reduce(a, axis=-1)
+        s = np.zeros(m.shape, dtype=dtype)
+        for j in range(lnc.size):
+            s = s + np.exp(m - a[..., j])
+        t = np.where(m < np.inf, m - np.log(s), m)                # (every candidate +inf, or a NaN row: no inf - inf)
+        t = np.where(t < 0, dtype(0.0), t)                        # (a NaN stays a NaN)
+    t = np.asarray(t, dtype=dtype)
+    return (t, h) if return_candidates else t
+
+
 def warp_identity():
     """the identity grid: [WARP_DIMS][WARP_BINS + 1] edges b / 64 (the map returns its input, ln J = 0, exactly)"""
     return np.tile(np.arange(WARP_BINS + 1) / WARP_BINS, (WARP_DIMS, 1))

@@ -1,6 +1,6 @@
 // libtrx.so: the host side of the likelihood path and the C ABI (include/trx.h) for gfx950.
 //
-// The kernels live in three headers that only this file includes:
+// The kernels live in four headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
 //                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
@@ -11,6 +11,8 @@
 //                    here, chi2_rows_launch) and the log-mean-exp kernels, HBM bound
 //   trx_noise.hpp    chi2_ou_kernel<ONE> (the row reduction under correlated noise: a scan along the row; chi2_ou_launch
 //                    here; include/trx_noise.h)
+//   trx_noise_mix.hpp  ou_mix_kernel<ONE, J> (the same for J candidate noise models in one pass, their soft minimum per
+//                    row; ou_mix_launch here; include/trx_mix.h)
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
 // lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
@@ -32,6 +34,7 @@
 
 #include "../../include/trx.h"
 #include "../../include/trx_noise.h"
+#include "../../include/trx_mix.h"
 #include "trx_device.hpp"
 #include "trx_internal.hpp"
 #include "trx_knobs.hpp"
@@ -60,6 +63,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 #include "trx_cells.hpp"
 #include "trx_reduce.hpp"
 #include "trx_noise.hpp"
+#include "trx_noise_mix.hpp"
 #include "trx_bands.hpp"
 
 namespace {
@@ -1018,6 +1022,28 @@ void chi2_ou_launch(const double* flux, const double* model_grid, int n_time, lo
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
                        accumulate, out, alpha, beta, omega);
 }
+
+// One launch of ou_mix_kernel<ONE, J> (trxm_chi2_grid_ou_mix): ONE as for chi2_ou_kernel, J = n_cand.  Up to J = 2 the
+// kernel stays within 128 VGPRs and 4 blocks of 256 threads a CU are resident, as for chi2_ou_kernel; past that it holds two
+// waves a SIMD (at most 256 VGPRs, and up to 52 KB of LDS a block): 2 blocks a CU, on 256 CUs.  The rows behind that cap are
+// the second row of a wave's pass and its further passes.
+template <int J>
+void ou_mix_launch_j(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                     double sec_limit, int accumulate, double* out, const double* alpha, const double* beta,
+                     const double* omega, int n_cand, const OuMixLnc& lnc, double* cand_out, hipStream_t st)
+{
+    if constexpr (J < kOuMixMax) {
+        if (n_cand != J)
+            return ou_mix_launch_j<J + 1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out, alpha, beta,
+                                          omega, n_cand, lnc, cand_out, st);
+    }
+    long blocks = (n + 3) / 4;
+    const long resident = 256L * (J <= 2 ? 4 : 2);
+    if (blocks > resident) blocks = resident;
+    const auto kernel = n_time <= kOuTrip ? ou_mix_kernel<true, J> : ou_mix_kernel<false, J>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
+                       accumulate, out, alpha, beta, omega, lnc, cand_out);
+}
 }  // namespace
 
 // =========================================================================================
@@ -1123,6 +1149,27 @@ int trxn_chi2_grid_ou(const double* flux, const double* model_grid, int n_time, 
     if (n == 0) return TRX_OK;
     chi2_ou_launch(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
                    static_cast<hipStream_t>(stream));
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trxm_chi2_grid_ou_mix(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                          double sec_limit, int accumulate, double* out_halfchi2, const double* alpha, const double* beta,
+                          const double* omega, int n_cand, const double* lnc, double* cand_out, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (n_cand < 1 || n_cand > TRXM_MAX_CANDIDATES) return fail(TRX_ERR_ARG, "n_cand outside 1 .. 8%s (n_cand=%ld)", "", n_cand);
+    if (!flux || !model_grid || !out_halfchi2 || !alpha || !beta || !omega || !lnc)
+        return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    static_assert(TRXM_MAX_CANDIDATES == kOuMixMax, "the header's limit is the kernel's");
+    OuMixLnc c = {};
+    for (int j = 0; j < n_cand; ++j) {
+        if (!(lnc[j] < INFINITY)) return fail(TRX_ERR_ARG, "lnc is NaN or +inf%s (candidate %ld)", "", j);
+        c.v[j] = lnc[j];
+    }
+    if (n == 0) return TRX_OK;
+    ou_mix_launch_j<1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
+                       n_cand, c, cand_out, static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

@@ -5,7 +5,8 @@ A dataset is one light curve with its own cadence: `time`, `flux`, `flux_err` (o
 baseline offset of that light curve, marginalised per draw (inf: a flat prior), and `baseline` / `baseline_sigma`: up to
 MAX_BASELINE_TERMS columns B_k[t] of a linear baseline model sum_k c_k B_k[t] with priors c_k ~ N(0, s_k^2), marginalised
 the same way (baseline_system), or `red_sigma` / `red_timescale`: correlated noise of standard deviation s_r with an
-exponential kernel of time scale tau next to the white errors (ou_system).  This module is host side and numpy only:
+exponential kernel of time scale tau next to the white errors (ou_system), or `red_grid`: up to MAX_RED_CANDIDATES
+weighted candidates (s_r, tau) of that noise, marginalised per draw (ou_mix_system).  This module is host side and numpy only:
 validation, the reference noise sigma_bar and the per-star renormalisation.  A `Datasets` object is what the lnZ_*
 functions receive in place of `time` (with flux = None and sigma = sigma_bar); only the device sampling modes evaluate it
 (fused._Scenario).
@@ -20,6 +21,7 @@ from .funcs import renorm_flux
 MAX_DATASETS = 16
 MAX_BASELINE_TERMS = 4          # terms of a dataset's linear baseline model, the offset_sigma term included
 MIN_BASELINE_EIGENVALUE = 1e-6  # of the scaled system matrix: below it the columns count as collinear
+MAX_RED_CANDIDATES = 8          # candidate (s_r, tau) pairs of a dataset's red_grid
 DEFAULT_EXPTIME, DEFAULT_NSAMPLES = 0.00139, 20
 
 
@@ -32,6 +34,7 @@ class Dataset(NamedTuple):
     offset_sigma: float = None    # prior sigma of a constant baseline offset (inf: flat); None: no offset
     baseline: np.ndarray = None         # [K_b][T] columns of the linear baseline model, finite; None: none
     baseline_sigma: np.ndarray = None   # [K_b] prior sigmas of their coefficients (inf: flat); None without baseline
+    red_grid: np.ndarray = None         # [J][3] candidates (s_r, tau, weight) of the correlated noise, weights sum to 1; None
     red_sigma: float = None       # standard deviation of the correlated (Ornstein-Uhlenbeck) noise, flux units; None: white
     red_timescale: float = None   # its time scale, in the units of `time` (inf allowed); None without red_sigma
 
@@ -168,6 +171,37 @@ def _red_noise(i, sigma, timescale, time, others):
     return sigma, timescale
 
 
+def _red_grid(i, value, time, others):
+    """a dataset's "red_grid" -> [J][3] float64 rows (s_r, tau, weight), the weights normalised to sum 1, or None; time:
+    the kept stamps; others: whether the dataset has red_sigma / red_timescale, an offset or a baseline as well"""
+    if value is None:
+        return None
+    msg = ("dataset %d: red_grid must be 1 ... %d triples (s_r, tau, weight): s_r finite and > 0, tau > 0 or inf, weight "
+           "finite and > 0 (got %r)" % (i, MAX_RED_CANDIDATES, value))
+    if isinstance(value, (bool, str, bytes)):
+        raise ValueError(msg)
+    try:
+        g = np.array(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(msg) from None
+    if g.ndim != 2 or g.shape[1] != 3 or not 1 <= g.shape[0] <= MAX_RED_CANDIDATES:
+        raise ValueError(msg)
+    s_r, tau, weight = g[:, 0], g[:, 1], g[:, 2]
+    if not (np.all(np.isfinite(s_r) & (s_r > 0)) and np.all(tau > 0) and np.all(np.isfinite(weight) & (weight > 0))):
+        raise ValueError(msg)                                     # (also NaN)
+    if others:
+        raise ValueError("dataset %d: red_grid together with red_sigma / red_timescale, offset_sigma or baseline is not "
+                         "built: give the candidates alone (a single pair is a red_grid of one row)" % i)
+    if np.any(np.diff(time) < 0):
+        raise ValueError("dataset %d: red_grid needs time in non-decreasing order: the noise model is a process in "
+                         "time and follows the stamps as given (a folded light curve is not sorted silently)" % i)
+    total = math.fsum(weight.tolist())
+    if not (math.isfinite(total) and total > 0):
+        raise ValueError(msg)
+    g[:, 2] = weight / total
+    return np.ascontiguousarray(g)
+
+
 def ou_system(dataset):
     """(alpha, beta, omega), float64 [T] each: the Kalman form of a Dataset's noise covariance
     K = diag(flux_err^2) + red_sigma^2 exp(-|t_i - t_j| / red_timescale), stamps in time order -- the one place that forms
@@ -195,6 +229,28 @@ def ou_system(dataset):
     return alpha, beta, omega
 
 
+def ou_mix_system(dataset):
+    """(alpha [J][T], beta [J][T], omega [J][T], lnc [J]), float64: ou_system of every candidate (s_j, tau_j, pi_j) of a
+    Dataset's red_grid, and the candidates' log-weights
+        lnc_j = ln pi_j + 0.5 sum_n ln omega_j[n] - logsumexp_j(the same),     ln det K_j = -sum_n ln omega_j[n],
+    so that sum_j exp(lnc_j) = 1 and the dataset's term of the log-weight is -ln sum_j exp(lnc_j - h_j), h_j = 0.5 y^T K_j^-1 y
+    (_numerics.ou_mix_halfchi2, trxm_chi2_grid_ou_mix).  The sums are math.fsum's; the normaliser that is dropped,
+    sum_j pi_j |K_j|^(-1/2), depends on the dataset alone."""
+    grid = dataset.red_grid
+    tables, raw = [], []
+    for s_r, tau, weight in grid:
+        abw = ou_system(dataset._replace(red_grid=None, red_sigma=float(s_r), red_timescale=float(tau)))
+        tables.append(abw)
+        raw.append(math.log(weight) + 0.5 * math.fsum(np.log(abw[2]).tolist()))
+    # (the raw values are large -- half a log-determinant --, their differences are not: normalise the differences)
+    top = max(raw)
+    diff = [v - top for v in raw]
+    norm = math.log(math.fsum(math.exp(v) for v in diff))
+    lnc = np.array([v - norm for v in diff])
+    alpha, beta, omega = (np.ascontiguousarray(np.stack([t[k] for t in tables])) for k in range(3))
+    return alpha, beta, omega, lnc
+
+
 def _check_baseline(i, dataset):
     """the limits of a dataset's baseline terms: their number and the conditioning of the scaled system"""
     n_terms = (dataset.offset_sigma is not None) + (0 if dataset.baseline is None else dataset.baseline.shape[0])
@@ -215,13 +271,16 @@ def _check_baseline(i, dataset):
 
 def validate(datasets):
     """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
-    baseline_sigma, red_sigma, red_timescale]} -> a list of Dataset.  Points with a NaN time or flux are dropped together with their error and their
+    baseline_sigma, red_sigma, red_timescale, red_grid]} -> a list of Dataset.  Points with a NaN time or flux are dropped together with their error and their
     baseline entries; a scalar flux_err is broadcast.  ValueError for an empty list, too many datasets, mismatched
     lengths, an error that is not finite or not positive, a dataset without points, an offset_sigma that is not None, a
     number > 0 or inf, a baseline that is not [K][len(time)] and finite at the kept points, a baseline_sigma that is not
     > 0 or inf per column (or has no baseline), more than MAX_BASELINE_TERMS terms, or collinear terms; for red_sigma
     without red_timescale or the reverse, a red_sigma that is not a finite number > 0, a red_timescale that is not > 0 or
-    inf, either of them next to offset_sigma or baseline, or with kept stamps that are not in non-decreasing order."""
+    inf, either of them next to offset_sigma or baseline, or with kept stamps that are not in non-decreasing order; for a
+    red_grid that is not 1 ... MAX_RED_CANDIDATES triples (s_r finite > 0, tau > 0 or inf, weight finite > 0; the weights are
+    normalised to sum 1, repeated pairs are allowed), that stands next to red_sigma / red_timescale, offset_sigma or
+    baseline, or whose kept stamps are not in non-decreasing order."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -231,7 +290,7 @@ def validate(datasets):
     out = []
     for i, d in enumerate(datasets):
         unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma",
-                            "red_sigma", "red_timescale"}
+                            "red_sigma", "red_timescale", "red_grid"}
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -262,9 +321,11 @@ def validate(datasets):
         offset_sigma = _offset_sigma(i, d.get("offset_sigma"))
         red_sigma, red_timescale = _red_noise(i, d.get("red_sigma"), d.get("red_timescale"), time,
                                               offset_sigma is not None or baseline is not None)
+        red_grid = _red_grid(i, d.get("red_grid"), time,
+                             offset_sigma is not None or baseline is not None or red_sigma is not None)
         out.append(Dataset(np.ascontiguousarray(time), np.ascontiguousarray(flux), np.ascontiguousarray(err),
                            float(d.get("exptime", DEFAULT_EXPTIME)), nsamples,
-                           offset_sigma, baseline, baseline_sigma, red_sigma, red_timescale))
+                           offset_sigma, baseline, baseline_sigma, red_grid, red_sigma, red_timescale))
         _check_baseline(i, out[-1])
     return out
 
@@ -306,7 +367,7 @@ class Datasets:
 
     @property
     def has_red_noise(self):
-        return any(s.red_sigma is not None for s in self.sets)
+        return any(s.red_sigma is not None or s.red_grid is not None for s in self.sets)
 
     @property
     def size(self):
@@ -320,7 +381,8 @@ class Datasets:
         star.  So is every finite baseline_sigma (flux units per unit of its column); the columns are left alone: the scaled
         system matrix of baseline_system is then the same for every star.  A red_sigma is in flux units too and is divided
         the same way: alpha and beta of ou_system do not change, omega scales with the square of the flux ratio, and the
-        determinant ratio that the evidence drops is the same for every star."""
+        determinant ratio that the evidence drops is the same for every star.  The s_r column of a red_grid is divided
+        likewise: every candidate's determinant gains the same factor, so the lnc of ou_mix_system do not change."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
@@ -333,6 +395,10 @@ class Datasets:
             red = s.red_sigma
             if red is not None:
                 red = red / star_fluxratio
+            grid = s.red_grid
+            if grid is not None:
+                grid = grid.copy()
+                grid[:, 0] = grid[:, 0] / star_fluxratio
             out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err), offset_sigma=off,
-                                  baseline_sigma=bsig, red_sigma=red))
+                                  baseline_sigma=bsig, red_sigma=red, red_grid=grid))
         return Datasets(out)

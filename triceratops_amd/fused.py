@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, funcs
-from .datasets import Datasets, baseline_system, ou_system
+from .datasets import Datasets, baseline_system, ou_mix_system, ou_system
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
@@ -231,11 +231,16 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # mean coefficients of the branch's best draw]} there, in the call's normalisation (target.dataset_baselines).
 # A dataset with `red_sigma` / `red_timescale` has correlated (Ornstein-Uhlenbeck) noise next to its white errors: its
 # reduction is trxn_chi2_grid_ou on the alpha, beta, omega of datasets.ou_system (grid evaluation only).
+# A dataset with a `red_grid` has that noise's amplitude and time scale marginalised over its candidates per draw: its
+# reduction is trxm_chi2_grid_ou_mix on the tables and log-weights of datasets.ou_mix_system (grid evaluation only).
+# DATASET_RED_NOISE = {}: every such call leaves {work unit: [per branch, a list per dataset: None or the [J] posterior
+# weights of the candidates at the branch's best draw, softmax_j(lnc_j - h_j)]} there (target.dataset_red_noise).
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
 DATASET_OFFSETS = None
 DATASET_BASELINES = None
+DATASET_RED_NOISE = None
 # An importance map (WARP_GRIDS) applies to a datasets call as to any other: its draws are trx_draw_scenario's.  The weight
 # histogram of the library's own chain (WARP_HIST) does not exist here -- chi^2/2 is computed outside that chain -- so
 # DATASET_WARP_HIST = {}: every datasets call leaves {work unit: [branches][WARP_BRANCH] uint64 words} there, one
@@ -246,7 +251,7 @@ DATASET_WARP_HIST = None
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -746,6 +751,21 @@ def _on_device(a, device):
     return _cached(_lc_cache, (a.shape, hash(a.tobytes()), device.index), 32, lambda: _lib.dev(a, device))
 
 
+_mix_cache = {}
+
+
+def _mix_on_device(d, device):
+    """(alpha, beta, omega [J][T] on the device, lnc [J] on the host) of a red_grid dataset (datasets.ou_mix_system): formed
+    once per content of its stamps, errors and candidates -- J * T steps of a Python loop -- for the lnZ_* calls of a star
+    (a cache of its own: _lc_cache's entries decide where a star's launch chain splits)"""
+    key = (tuple(hash(a.tobytes()) for a in (d.time, d.flux_err, d.red_grid)), d.red_grid.shape, device.index)
+
+    def build():
+        alpha, beta, omega, lnc = ou_mix_system(d)
+        return _lib.dev(alpha, device), _lib.dev(beta, device), _lib.dev(omega, device), lnc
+    return _cached(_mix_cache, key, 32, build)
+
+
 class _Baseline(NamedTuple):
     """the system of a dataset with baseline columns (datasets.baseline_system)"""
     g: torch.Tensor              # the scaled columns [K][T], on the device
@@ -765,11 +785,15 @@ class _Dataset(NamedTuple):
     offset: Optional[tuple] = None           # (sum_w, 1 / s^2)
     baseline: Optional[_Baseline] = None
     ou: Optional[tuple] = None               # (alpha, beta, omega) on the device: correlated noise (datasets.ou_system)
+    mix: Optional[tuple] = None              # (alpha, beta, omega [J][T] on the device, lnc [J] on the host): ou_mix_system
 
     @classmethod
     def upload(cls, d, dev):
         inv_var = 1.0 / (d.flux_err * d.flux_err)
         rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
+        if d.red_grid is not None:
+            # (validate refuses anything else next to it)
+            return rec._replace(mix=_mix_on_device(d, dev))
         if d.red_sigma is not None:
             # (validate refuses an offset or a baseline next to it)
             return rec._replace(ou=tuple(_on_device(v, dev) for v in ou_system(d)))
@@ -783,11 +807,15 @@ class _Dataset(NamedTuple):
                                          0.0 if math.isinf(d.offset_sigma) else 1.0 / (d.offset_sigma * d.offset_sigma)))
         return rec
 
-    def halfchi2(self, grid, secdepth=None, sec_limit=float("inf"), out=None, offset_out=None, coef_out=None):
+    def halfchi2(self, grid, secdepth=None, sec_limit=float("inf"), out=None, offset_out=None, coef_out=None,
+                 cand_out=None):
         """this dataset's weighted chi^2/2 of every row of a model grid [n][T], written or added to `out`; +inf where
         secdepth >= sec_limit.  The one place that picks the reduction: trx_chi2_grid_baseline for baseline columns (coef_out:
         the rows' scaled coefficients), trx_chi2_grid_offset for an offset alone (offset_out: the rows' offsets),
-        trxn_chi2_grid_ou for correlated noise, else trx_chi2_grid_weighted."""
+        trxn_chi2_grid_ou for correlated noise, trxm_chi2_grid_ou_mix for a grid of its candidates (cand_out: the rows'
+        per-candidate chi^2/2), else trx_chi2_grid_weighted."""
+        if self.mix is not None:
+            return _lib.chi2_grid_ou_mix(self.flux, grid, *self.mix, secdepth, sec_limit, out=out, cand_out=cand_out)
         if self.ou is not None:
             return _lib.chi2_grid_ou(self.flux, grid, *self.ou, secdepth, sec_limit, out=out)
         if self.baseline is not None:
@@ -1066,6 +1094,7 @@ class _Scenario:
         flags = self._flags(is_host)
         offsets = []       # (DATASET_OFFSETS: per branch the best draw's offsets, still on the device)
         coefs = []         # (DATASET_BASELINES: per branch and dataset the best draw's scaled coefficients, likewise)
+        cands = []         # (DATASET_RED_NOISE: per branch and dataset the best draw's per-candidate chi^2/2, likewise)
         hists = None       # (DATASET_WARP_HIST: per branch the weight histogram of its evidence, likewise)
         if self.datasets is not None and DATASET_WARP_HIST is not None:
             if not self.philox:
@@ -1096,10 +1125,11 @@ class _Scenario:
                 _lib.moments_emit(mom[1], mom[2])
             best = self._best(h, idx, n)
             if self.datasets is not None and ((DATASET_OFFSETS is not None and any(d.offset is not None for d in self.datasets))
-                                              or self._any_baseline()):
-                o, c = self._best_offsets(model, flags, cols, best, twin, nblk) if n else (None, None)
+                                              or self._any_baseline() or self._any_mix()):
+                o, c, hc = self._best_offsets(model, flags, cols, best, twin, nblk) if n else (None, None, None)
                 offsets.append(o)
                 coefs.append(c)
+                cands.append(hc)
             post = None
             if POSTERIOR_ROWS:
                 # the same selection on this chain's chi^2/2 values (trx_posterior_from_halfchi2; the twin branch draws
@@ -1123,7 +1153,7 @@ class _Scenario:
             if POSTERIOR_ROWS:
                 res[-1]["posterior"] = None if post is None else self._posterior_dict(post.cpu().numpy(), ncol, twin)
         if offsets:
-            self._leave_best_terms(offsets, coefs)
+            self._leave_best_terms(offsets, coefs, cands)
         if hists is not None:
             DATASET_WARP_HIST[getattr(_tls, "unit", None)] = torch.stack(hists).cpu().numpy().view(np.uint64)
         return res[0] if a.planet else (res[0], res[1])
@@ -1133,11 +1163,32 @@ class _Scenario:
         return ((DATASET_BASELINES is not None or DATASET_OFFSETS is not None)
                 and any(d.baseline is not None for d in self.datasets))
 
-    def _leave_best_terms(self, offsets, coefs):
+    def _any_mix(self):
+        """whether a red_grid dataset's candidate weights are wanted back (DATASET_RED_NOISE)"""
+        return DATASET_RED_NOISE is not None and any(d.mix is not None for d in self.datasets)
+
+    def _leave_best_terms(self, offsets, coefs, cands):
         """the branches' best-draw offsets and baseline coefficients, from the device to DATASET_OFFSETS / DATASET_BASELINES
-        under this thread's work unit, in the call's normalisation: c_k = c~_k / sqrt(D_k)"""
+        under this thread's work unit, in the call's normalisation: c_k = c~_k / sqrt(D_k); and the posterior weights of a
+        red_grid dataset's candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_RED_NOISE (NaN without a draw)"""
         L = len(self.datasets)
         unit = getattr(_tls, "unit", None)
+        if DATASET_RED_NOISE is not None:
+            red = []
+            for hc in cands:
+                per = [None] * L
+                for l, d in enumerate(self.datasets):
+                    if d.mix is None:
+                        continue
+                    lnc = d.mix[3]
+                    if hc is None:
+                        per[l] = np.full(lnc.size, np.nan)
+                        continue
+                    x = lnc - hc[l].cpu().numpy().reshape(-1)
+                    w = np.exp(x - np.max(x))
+                    per[l] = w / w.sum()
+                red.append(per)
+            DATASET_RED_NOISE[unit] = red
         offs, base = [], []
         for o, c in zip(offsets, coefs):
             o = np.full(L, np.nan) if o is None else o.cpu().numpy()
@@ -1158,26 +1209,30 @@ class _Scenario:
             DATASET_BASELINES[unit] = base
 
     def _best_offsets(self, model, flags, cols, best, twin, nblk):
-        """([L] device tensor, list per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
+        """([L] device tensor, list per dataset, list per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
         S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
-        baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them).  The one row is
-        evaluated again -- trx_flux_grid on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out or
-        coef_out -- so nothing of size n x L is kept."""
+        baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them); and None or the
+        [1][J] device tensor of a red_grid dataset's per-candidate chi^2/2.  The one row is evaluated again -- trx_flux_grid
+        on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out, coef_out or cand_out -- so nothing of
+        size n x L is kept."""
         out = torch.full((len(self.datasets),), float("nan"), dtype=F64, device=self.dev)
         coefs = [None] * len(self.datasets)
+        cands = [None] * len(self.datasets)
         row = cols[:nblk].index_select(1, best[:1]).contiguous()
         if twin:
             row[2] *= 2.0
             row[4] = cols[11].index_select(0, best[:1])
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL
         for l, d in enumerate(self.datasets):
-            if d.offset is None and d.baseline is None:
+            if d.offset is None and d.baseline is None and (d.mix is None or DATASET_RED_NOISE is None):
                 continue
             grid, _ = _lib.flux_grid(model, flags, d.time, row, d.exptime, d.nsamples, want_secdepth=False)
             if d.baseline is not None:
                 coefs[l] = torch.empty((1, int(d.baseline.g.shape[0])), dtype=F64, device=self.dev)
-            d.halfchi2(grid, offset_out=out[l:l + 1], coef_out=coefs[l])
-        return out, coefs
+            if d.mix is not None:
+                cands[l] = torch.empty((1, int(d.mix[3].size)), dtype=F64, device=self.dev)
+            d.halfchi2(grid, offset_out=out[l:l + 1], coef_out=coefs[l], cand_out=cands[l])
+        return out, coefs, cands
 
     def _datasets_halfchi2(self, model, flags, block):
         """sum over the datasets of the weighted chi^2/2 of every row of `block` ([n_param][n], the masked draws of one
@@ -1197,6 +1252,9 @@ class _Scenario:
                                       "carries no sums of basis * residual; use evaluation='grid'")
         if DATASET_EVALUATION == "fused" and any(d.ou is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a red_sigma dataset is not built: the fused kernel "
+                                      "carries no recurrence along the row; use evaluation='grid'")
+        if DATASET_EVALUATION == "fused" and any(d.mix is not None for d in self.datasets):
+            raise NotImplementedError("evaluation='fused' with a red_grid dataset is not built: the fused kernel "
                                       "carries no recurrence along the row; use evaluation='grid'")
         n = int(block.shape[1])
         h = torch.zeros(n, dtype=F64, device=self.dev)         # (0 + x = x: every reduction accumulates)

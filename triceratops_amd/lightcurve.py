@@ -84,9 +84,29 @@ def polynomial_baseline(time, order: int):
     return np.stack([u ** p for p in range(1, order + 1)])
 
 
+def red_noise_grid(sigmas, timescales, weights=None):
+    """The product grid of candidate red-noise amplitudes and time scales as a dataset's "red_grid": a float64 array
+    [len(sigmas) * len(timescales)][3] of rows (s_r, tau, weight), sigmas-major.  weights: None (equal), or an array
+    [len(sigmas)][len(timescales)] of prior weights > 0; they are normalised to sum 1.  datasets.validate checks the
+    values and the number of candidates (datasets.MAX_RED_CANDIDATES)."""
+    s = np.atleast_1d(np.asarray(sigmas, dtype=np.float64))
+    tau = np.atleast_1d(np.asarray(timescales, dtype=np.float64))
+    if s.ndim != 1 or tau.ndim != 1 or s.size == 0 or tau.size == 0:
+        raise ValueError("sigmas and timescales must be non-empty 1-d sequences")
+    w = np.ones((s.size, tau.size)) if weights is None else np.asarray(weights, dtype=np.float64)
+    if w.shape != (s.size, tau.size):
+        raise ValueError("weights must have the shape (len(sigmas), len(timescales)) = %s (got %s)"
+                         % ((s.size, tau.size), w.shape))
+    if not np.all(np.isfinite(w) & (w > 0)):
+        raise ValueError("every weight must be finite and > 0")
+    ss, tt = np.meshgrid(s, tau, indexing="ij")
+    return np.ascontiguousarray(np.stack([ss.ravel(), tt.ravel(), w.ravel() / w.sum()], axis=1))
+
+
 def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int = 50,
                     exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None,
-                    baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None):
+                    baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None,
+                    red_grid=None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
     {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
     empty bins are dropped.
@@ -94,7 +114,8 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     baseline_order > 0: "baseline" = polynomial_baseline(kept bins' times, baseline_order), with baseline_sigma (a number
     or one per column; None: flat) passed through; 0: both keys are None.
     red_sigma, red_timescale (both or neither): the dataset's correlated noise, passed through as the keys of those names
-    when given.
+    when given.  red_grid (red_noise_grid's result, or any list of (s_r, tau, weight)): candidates of that noise to
+    marginalise, passed through as the key "red_grid" when given.
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -113,4 +134,6 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
            "baseline_sigma": baseline_sigma}
     if red_sigma is not None or red_timescale is not None:
         out["red_sigma"], out["red_timescale"] = red_sigma, red_timescale
+    if red_grid is not None:
+        out["red_grid"] = red_grid
     return out

@@ -272,7 +272,8 @@ class target:
 
     def _datasets_pass(self, ds, P_orb, kw, verbose, evaluation, n_samples=0, **dataset_switches):
         """one pass of the datasets path over the target's work units: (units, rows, n_scen) for _finish.
-        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_WARP_HIST for the length of the pass."""
+        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_WARP_HIST for the length
+        of the pass."""
         from . import fused
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
         if ds.has_offsets and evaluation == "fused":
@@ -280,7 +281,8 @@ class target:
         if ds.has_baselines and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: use evaluation='grid'")
         if ds.has_red_noise and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with a red_sigma dataset is not built: use evaluation='grid'")
+            raise NotImplementedError("evaluation='fused' with a red_sigma or red_grid dataset is not built: use "
+                                      "evaluation='grid'")
         with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, **dataset_switches):
             rows = sharding.run_units(units, verbose=verbose, as_rows=True)
         return units, rows, n_scen
@@ -342,13 +344,30 @@ class target:
         without the keys.  tau -> 0: white noise with sigma_t^2 + s_r^2; tau = inf: offset_sigma = s_r.  The kept
         stamps must be in non-decreasing order (ValueError otherwise: the model is a process in time), and the keys do
         not combine with offset_sigma or baseline on the same dataset (ValueError).  Grid evaluation only:
-        evaluation="fused" with such a dataset raises NotImplementedError.  Not built: fitting s_r and tau, more than
-        one term."""
+        evaluation="fused" with such a dataset raises NotImplementedError.
+
+        Where s_r and tau are not known, a dataset may carry "red_grid" in their place: 1 to 8 candidates (s_r, tau, weight)
+        -- lightcurve.red_noise_grid makes a product grid --, s_r finite and > 0, tau > 0 or inf, the prior weights > 0
+        (normalised to sum 1; repeated pairs are allowed).  The pair is then integrated out per draw, determinants
+        included: with h_j = 0.5 y^T K_j^-1 y of candidate j and c_j proportional to weight_j |K_j|^(-1/2), sum_j c_j = 1
+        (datasets.ou_mix_system), the dataset's term of the log-weight is -ln sum_j c_j exp(-h_j), in one pass over the
+        model grid for all candidates (trxm_chi2_grid_ou_mix).  The normaliser sum_j weight_j |K_j|^(-1/2) depends on the
+        dataset only (every s_r scales with the errors under renormalisation, so the c_j are the same for every star) and is
+        dropped as det K is.  One candidate of weight 1 gives the bits of red_sigma / red_timescale.  The same conditions:
+        stamps in non-decreasing order, not next to red_sigma / red_timescale, offset_sigma or baseline on the same dataset
+        (ValueError), grid evaluation only.  `.dataset_red_noise` is then a list per scenario of a list per dataset: None
+        for a dataset without "red_grid", else {"grid": the [J][3] candidates as validated (s_r, tau, normalised prior
+        weight, in the units given), "weight": the [J] posterior weights of the candidates at the scenario's best draw,
+        softmax_j(ln c_j - h_j) (NaN without a finite lnZ)}; the whole attribute is None when no dataset has a grid.
+        Not built: per-draw candidate posteriors, a continuous fit of s_r and tau, more than one term, red noise next to
+        offset or baseline."""
         ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
         best_offsets = {} if ds.has_offsets else None
         best_baselines = {} if ds.has_baselines else None
+        best_red = {} if any(s.red_grid is not None for s in ds.sets) else None
         units, rows, n_scen = self._datasets_pass(ds, P_orb, kw, verbose, evaluation, n_samples,
-                                                  DATASET_OFFSETS=best_offsets, DATASET_BASELINES=best_baselines)
+                                                  DATASET_OFFSETS=best_offsets, DATASET_BASELINES=best_baselines,
+                                                  DATASET_RED_NOISE=best_red)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
@@ -371,6 +390,19 @@ class target:
                     if np.isfinite(self.lnZ[u.first_row + i]):
                         rows_[u.first_row + i] = [None if c is None else c * share[u.group[1]] for c in per]
             self.dataset_baselines = rows_
+        self.dataset_red_noise = None
+        if best_red is not None:
+            # (the weights are pure numbers: the same in every star's normalisation)
+            def entry(s, w=None):
+                if s.red_grid is None:
+                    return None
+                return {"grid": s.red_grid.copy(), "weight": np.full(s.red_grid.shape[0], np.nan) if w is None else w}
+            rows_ = [[entry(s) for s in ds.sets] for _ in range(n_scen)]
+            for k, u in enumerate(sharding.as_units(units)):
+                for i, per in enumerate(best_red.get(k, ())):
+                    if np.isfinite(self.lnZ[u.first_row + i]):
+                        rows_[u.first_row + i] = [entry(s, w) for s, w in zip(ds.sets, per)]
+            self.dataset_red_noise = rows_
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
@@ -469,7 +501,7 @@ class target:
         uniforms from the chi^2/2 values of that pass (trxw_hist_from_halfchi2, fused.DATASET_WARP_HIST) and refine
         the map; best-draw offsets and baselines are not computed in them.  The final pass is calc_probs_datasets under
         the maps the adaptation left: it fills `.probs`, `.FPP`, `.lnZ_err`, `.posterior` (n_samples > 0), `.sigma_ref`,
-        `.dataset_offsets` and `.dataset_baselines` as calc_probs_datasets does, and only it enters the result, so the
+        `.dataset_offsets`, `.dataset_baselines` and `.dataset_red_noise` as calc_probs_datasets does, and only it enters the result, so the
         estimate is unbiased.  `.refine_history` holds, per pass, the rows' lnZ, ess and w_max_frac.  n_adapt = 0 is
         calc_probs_datasets, bit for bit.  Both evaluations ("grid", "fused") feed the histogram the same way.
 
