@@ -44,6 +44,8 @@ WARP_SYMBOLS = ("trxw_hist_from_halfchi2",)
 NOISE_SYMBOLS = ("trxn_chi2_grid_ou",)
 # ... include/trx_mix.h (both libraries: the same over a grid of candidate noise models, prefix trxm_)
 MIX_SYMBOLS = ("trxm_chi2_grid_ou_mix",)
+# ... include/trx_shift.h (both libraries: the soft minimum over the nodes of a transit-time shift grid, prefix trxt_)
+SHIFT_SYMBOLS = ("trxt_softmin_rows",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -191,6 +193,8 @@ def _load(path, testing):
     L.trxm_chi2_grid_ou_mix.restype = c_int
     L.trxm_chi2_grid_ou_mix.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp,
                                         _vp]
+    L.trxt_softmin_rows.restype = c_int
+    L.trxt_softmin_rows.argtypes = [_vp, c_long, c_long, c_int, _vp, c_int, _vp, _vp]
     L.trx_grid_quantiles.restype = c_int
     L.trx_grid_quantiles.argtypes = [_vp, c_long, c_int, _vp, _vp, c_long, _vp, c_int, _vp, _vp]
     L.trx_lnl_batch_host.restype = c_int
@@ -616,6 +620,31 @@ def chi2_grid_ou_mix(flux_d, grid_d, alpha_d, beta_d, omega_d, lnc, secdepth=Non
                                           int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
                                           omega_d.data_ptr(), j, lnc.ctypes.data,
                                           cand_out.data_ptr() if cand_out is not None else None, _stream(grid_d)))
+    return out
+
+
+def softmin_rows(cand_d, lnc, out=None):
+    """The soft minimum over the J rows of cand_d (trxt_softmin_rows, include/trx_shift.h): per column r
+    T = -ln sum_j exp(lnc[j] - cand_d[j][r]), clamped at 0.  cand_d: a [J][n] fp64 device tensor whose rows are contiguous
+    (any row stride >= n); lnc: [J] float64 on the host.  out: an [n] fp64 device tensor that T is added to; None: a new
+    tensor that receives T."""
+    require_gpu()
+    assert cand_d.dim() == 2 and cand_d.dtype == torch.float64
+    j, n = (int(v) for v in cand_d.shape)
+    stride = int(cand_d.stride(0)) if j > 1 else n       # (a single row has no next row to reach)
+    assert n <= 1 or cand_d.stride(1) == 1
+    assert n == 0 or stride >= n
+    lnc = np.ascontiguousarray(lnc, dtype=np.float64)
+    assert lnc.shape == (j,)
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=cand_d.device)
+    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
+    if n == 0:
+        return out                     # (an empty tensor has no address to pass)
+    with torch.cuda.device(cand_d.device):
+        check(lib().trxt_softmin_rows(cand_d.data_ptr(), stride, n, j, lnc.ctypes.data, int(accumulate), out.data_ptr(),
+                                      _stream(cand_d)))
     return out
 
 

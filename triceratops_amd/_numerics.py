@@ -180,6 +180,31 @@ def ou_mix_halfchi2(y, alpha, beta, omega, lnc, dtype=np.float64, return_candida
     return (t, h) if return_candidates else t
 
 
+def t0_mix_halfchi2(h, lnpi):
+    """A dataset's term of the log-weight with a transit-time shift marginalised over J nodes, on the
+    host: the statement of what trxt_softmin_rows computes per row,
+        a_j = h_j - lnpi_j,  m = min_j a_j,  T = m - ln sum_j exp(m - a_j) = -ln sum_j exp(lnpi_j - h_j),
+    stored as 0 where rounding drives it below; m = +inf (every node excluded) or NaN is stored as it is.  h: [J][n] (or
+    [J]), node j's term on the stamps time + shift_j; lnpi: [J] log prior weights (-inf: a node switched off).  The minimum
+    and the sum run in ascending j.  In h's dtype (np.longdouble: the tests' reference).  J = 1 with lnpi = 0 returns
+    h[0]'s bits."""
+    h = np.asarray(h)
+    dtype = h.dtype.type
+    lnpi = np.asarray(lnpi, dtype=dtype)
+    assert h.shape[0] == lnpi.size and lnpi.ndim == 1
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        a = [h[j] - lnpi[j] for j in range(lnpi.size)]
+        m = a[0]
+        for j in range(1, lnpi.size):
+            m = np.fmin(m, a[j])
+        s = np.zeros(np.shape(m), dtype=dtype)
+        for j in range(lnpi.size):
+            s = s + np.exp(m - a[j])
+        t = np.where(m < np.inf, m - np.log(s), m)                # (every node +inf, or a NaN row: no inf - inf)
+        t = np.where(t < 0, dtype(0.0), t)                        # (a NaN stays a NaN)
+    return np.asarray(t, dtype=dtype)
+
+
 def warp_identity():
     """the identity grid: [WARP_DIMS][WARP_BINS + 1] edges b / 64 (the map returns its input, ln J = 0, exactly)"""
     return np.tile(np.arange(WARP_BINS + 1) / WARP_BINS, (WARP_DIMS, 1))

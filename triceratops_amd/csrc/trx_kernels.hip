@@ -1,6 +1,6 @@
 // libtrx.so: the host side of the likelihood path and the C ABI (include/trx.h) for gfx950.
 //
-// The kernels live in four headers that only this file includes:
+// The kernels live in five headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
 //                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
@@ -13,6 +13,8 @@
 //                    here; include/trx_noise.h)
 //   trx_noise_mix.hpp  ou_mix_kernel<ONE, J> (the same for J candidate noise models in one pass, their soft minimum per
 //                    row; ou_mix_launch here; include/trx_mix.h)
+//   trx_softmin.hpp  softmin_rows_kernel<J> (the soft minimum of J candidate values per row, one lane a row;
+//                    softmin_launch_j here; include/trx_shift.h)
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
 // lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
@@ -35,6 +37,7 @@
 #include "../../include/trx.h"
 #include "../../include/trx_noise.h"
 #include "../../include/trx_mix.h"
+#include "../../include/trx_shift.h"
 #include "trx_device.hpp"
 #include "trx_internal.hpp"
 #include "trx_knobs.hpp"
@@ -64,6 +67,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 #include "trx_reduce.hpp"
 #include "trx_noise.hpp"
 #include "trx_noise_mix.hpp"
+#include "trx_softmin.hpp"
 #include "trx_bands.hpp"
 
 namespace {
@@ -1044,6 +1048,21 @@ void ou_mix_launch_j(const double* flux, const double* model_grid, int n_time, l
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
                        accumulate, out, alpha, beta, omega, lnc, cand_out);
 }
+
+// One launch of softmin_rows_kernel<J> (trxt_softmin_rows), J = n_cand: one lane per row, and as many blocks as the draw
+// kernel's cap -- 16 of 256 threads a CU, on 256 CUs; the rows behind that cap are a lane's further trips.
+template <int J>
+void softmin_launch_j(const double* cand, long stride, long n, int n_cand, const SoftminLnc& lnc, int accumulate,
+                      double* out, hipStream_t st)
+{
+    if constexpr (J < kSoftminMax) {
+        if (n_cand != J) return softmin_launch_j<J + 1>(cand, stride, n, n_cand, lnc, accumulate, out, st);
+    }
+    long blocks = (n + 255) / 256;
+    if (blocks > 256L * 16) blocks = 256L * 16;
+    hipLaunchKernelGGL(softmin_rows_kernel<J>, dim3((unsigned)blocks), dim3(256), 0, st, cand, stride, n, lnc, accumulate,
+                       out);
+}
 }  // namespace
 
 // =========================================================================================
@@ -1170,6 +1189,24 @@ int trxm_chi2_grid_ou_mix(const double* flux, const double* model_grid, int n_ti
     if (n == 0) return TRX_OK;
     ou_mix_launch_j<1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
                        n_cand, c, cand_out, static_cast<hipStream_t>(stream));
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trxt_softmin_rows(const double* cand, long stride, long n, int n_cand, const double* lnc, int accumulate, double* out,
+                      void* stream)
+{
+    if (!cand || !lnc || !out) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    if (n < 0 || stride < n) return fail(TRX_ERR_ARG, "n < 0 or stride < n%s (n=%ld)", "", n);
+    if (n_cand < 1 || n_cand > TRXT_MAX_NODES) return fail(TRX_ERR_ARG, "n_cand outside 1 .. 8%s (n_cand=%ld)", "", n_cand);
+    static_assert(TRXT_MAX_NODES == kSoftminMax, "the header's limit is the kernel's");
+    SoftminLnc c = {};
+    for (int j = 0; j < n_cand; ++j) {
+        if (!(lnc[j] < INFINITY)) return fail(TRX_ERR_ARG, "lnc is NaN or +inf%s (node %ld)", "", j);
+        c.v[j] = lnc[j];
+    }
+    if (n == 0) return TRX_OK;
+    softmin_launch_j<1>(cand, stride, n, n_cand, c, accumulate, out, static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

@@ -6,7 +6,8 @@ baseline offset of that light curve, marginalised per draw (inf: a flat prior), 
 MAX_BASELINE_TERMS columns B_k[t] of a linear baseline model sum_k c_k B_k[t] with priors c_k ~ N(0, s_k^2), marginalised
 the same way (baseline_system), or `red_sigma` / `red_timescale`: correlated noise of standard deviation s_r with an
 exponential kernel of time scale tau next to the white errors (ou_system), or `red_grid`: up to MAX_RED_CANDIDATES
-weighted candidates (s_r, tau) of that noise, marginalised per draw (ou_mix_system).  This module is host side and numpy only:
+weighted candidates (s_r, tau) of that noise, marginalised per draw (ou_mix_system); and next to any of these `t0_grid`: up
+to MAX_T0_NODES weighted shifts of its stamps, marginalised per draw (t0_grids).  This module is host side and numpy only:
 validation, the reference noise sigma_bar and the per-star renormalisation.  A `Datasets` object is what the lnZ_*
 functions receive in place of `time` (with flux = None and sigma = sigma_bar); only the device sampling modes evaluate it
 (fused._Scenario).
@@ -22,6 +23,7 @@ MAX_DATASETS = 16
 MAX_BASELINE_TERMS = 4          # terms of a dataset's linear baseline model, the offset_sigma term included
 MIN_BASELINE_EIGENVALUE = 1e-6  # of the scaled system matrix: below it the columns count as collinear
 MAX_RED_CANDIDATES = 8          # candidate (s_r, tau) pairs of a dataset's red_grid
+MAX_T0_NODES = 8                # nodes (shift, weight) of a dataset's t0_grid
 DEFAULT_EXPTIME, DEFAULT_NSAMPLES = 0.00139, 20
 
 
@@ -202,6 +204,49 @@ def _red_grid(i, value, time, others):
     return np.ascontiguousarray(g)
 
 
+def _t0_grid(i, value):
+    """a dataset's "t0_grid" -> [J][2] float64 rows (shift, weight), the weights normalised to sum 1, or None"""
+    if value is None:
+        return None
+    msg = ("dataset %d: t0_grid must be 1 ... %d pairs (shift, weight): the shifts finite and all different, the weights "
+           "finite and > 0 (got %r)" % (i, MAX_T0_NODES, value))
+    if isinstance(value, (bool, str, bytes)):
+        raise ValueError(msg)
+    try:
+        if not isinstance(value, np.ndarray) or value.dtype.kind not in "iuf":
+            # (a bool or a string among the entries would convert silently)
+            if any(isinstance(x, (bool, np.bool_, str, bytes)) for x in np.asarray(value, dtype=object).ravel()):
+                raise TypeError
+        g = np.array(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(msg) from None
+    if g.ndim != 2 or g.shape[1] != 2 or not 1 <= g.shape[0] <= MAX_T0_NODES:
+        raise ValueError(msg)
+    shift, weight = g[:, 0], g[:, 1]
+    if not (np.all(np.isfinite(shift)) and np.all(np.isfinite(weight) & (weight > 0))):
+        raise ValueError(msg)                                     # (also NaN)
+    if np.unique(shift).size != shift.size:
+        raise ValueError(msg)
+    total = math.fsum(weight.tolist())
+    if not (math.isfinite(total) and total > 0):
+        raise ValueError(msg)
+    g[:, 1] = weight / total
+    return np.ascontiguousarray(g)
+
+
+def t0_grids(dicts, sets):
+    """The "t0_grid" keys of the dicts that validate() turned into `sets`: per dataset None, or a contiguous float64 [J][2]
+    array of J = 1 ... MAX_T0_NODES rows (shift_j, weight_j) -- shifts in the units of `time`, finite and all different;
+    weights finite and > 0, normalised to sum 1 (math.fsum).  The dataset's term of the log-weight, h_j on the stamps
+    time + shift_j, becomes -ln sum_j weight_j exp(-h_j) (_numerics.t0_mix_halfchi2).  The key stands next to any other key
+    of the dataset: a shift leaves the stamp differences, the index-aligned baseline columns and the determinants as they
+    are.  ValueError for a wrong shape, too many rows, a value that is not finite, repeated shifts, a weight <= 0, a bool
+    or a string.  Dataset itself has no field for the key: the grids travel in Datasets.t0_grids."""
+    if len(dicts) != len(sets):
+        raise ValueError("t0_grids: %d dicts for %d datasets" % (len(dicts), len(sets)))
+    return [_t0_grid(i, d.get("t0_grid")) for i, d in enumerate(dicts)]
+
+
 def ou_system(dataset):
     """(alpha, beta, omega), float64 [T] each: the Kalman form of a Dataset's noise covariance
     K = diag(flux_err^2) + red_sigma^2 exp(-|t_i - t_j| / red_timescale), stamps in time order -- the one place that forms
@@ -271,7 +316,8 @@ def _check_baseline(i, dataset):
 
 def validate(datasets):
     """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
-    baseline_sigma, red_sigma, red_timescale, red_grid]} -> a list of Dataset.  Points with a NaN time or flux are dropped together with their error and their
+    baseline_sigma, red_sigma, red_timescale, red_grid, t0_grid]} -> a list of Dataset ("t0_grid" is allowed here and read by
+    t0_grids: no field of Dataset holds it).  Points with a NaN time or flux are dropped together with their error and their
     baseline entries; a scalar flux_err is broadcast.  ValueError for an empty list, too many datasets, mismatched
     lengths, an error that is not finite or not positive, a dataset without points, an offset_sigma that is not None, a
     number > 0 or inf, a baseline that is not [K][len(time)] and finite at the kept points, a baseline_sigma that is not
@@ -290,7 +336,7 @@ def validate(datasets):
     out = []
     for i, d in enumerate(datasets):
         unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma",
-                            "red_sigma", "red_timescale", "red_grid"}
+                            "red_sigma", "red_timescale", "red_grid", "t0_grid"}
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -348,11 +394,15 @@ def sigma_bar(errs):
 
 
 class Datasets:
-    """validated datasets in one star's normalisation, and their sigma_bar"""
+    """validated datasets in one star's normalisation, their sigma_bar, and per dataset None or its transit-time shift
+    grid (t0_grids)"""
 
-    def __init__(self, sets):
+    def __init__(self, sets, t0_grids=None):
         self.sets = tuple(sets)
         self.sigma_ref = sigma_ref(self.sets)
+        self.t0_grids = (None,) * len(self.sets) if t0_grids is None else tuple(t0_grids)
+        if len(self.t0_grids) != len(self.sets):
+            raise ValueError("t0_grids: %d grids for %d datasets" % (len(self.t0_grids), len(self.sets)))
 
     def __len__(self):
         return len(self.sets)
@@ -370,6 +420,10 @@ class Datasets:
         return any(s.red_sigma is not None or s.red_grid is not None for s in self.sets)
 
     @property
+    def has_t0_grids(self):
+        return any(g is not None for g in self.t0_grids)
+
+    @property
     def size(self):
         """points of all datasets together"""
         return sum(s.time.size for s in self.sets)
@@ -382,7 +436,8 @@ class Datasets:
         system matrix of baseline_system is then the same for every star.  A red_sigma is in flux units too and is divided
         the same way: alpha and beta of ou_system do not change, omega scales with the square of the flux ratio, and the
         determinant ratio that the evidence drops is the same for every star.  The s_r column of a red_grid is divided
-        likewise: every candidate's determinant gains the same factor, so the lnc of ou_mix_system do not change."""
+        likewise: every candidate's determinant gains the same factor, so the lnc of ou_mix_system do not change.  The t0_grids are times and
+        pure weights: carried through as they are."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
@@ -401,4 +456,4 @@ class Datasets:
                 grid[:, 0] = grid[:, 0] / star_fluxratio
             out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err), offset_sigma=off,
                                   baseline_sigma=bsig, red_sigma=red, red_grid=grid))
-        return Datasets(out)
+        return Datasets(out, self.t0_grids)

@@ -235,12 +235,18 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # reduction is trxm_chi2_grid_ou_mix on the tables and log-weights of datasets.ou_mix_system (grid evaluation only).
 # DATASET_RED_NOISE = {}: every such call leaves {work unit: [per branch, a list per dataset: None or the [J] posterior
 # weights of the candidates at the branch's best draw, softmax_j(lnc_j - h_j)]} there (target.dataset_red_noise).
+# A dataset with a `t0_grid` (Datasets.t0_grids) has a transit-time shift marginalised over its nodes per draw: its model grid
+# and its reduction -- whichever of the above -- run once per node on the stamps time + shift_j, and trxt_softmin_rows folds
+# the nodes' terms into one (grid evaluation only).  DATASET_T0 = {}: every such call leaves {work unit: [per branch, a list
+# per dataset: None or the [J] posterior weights of the nodes at the branch's best draw, softmax_j(ln pi_j - h_j)]} there
+# (target.dataset_t0); the offsets, baselines and red-noise weights of such a dataset are those of its heaviest node.
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
 DATASET_OFFSETS = None
 DATASET_BASELINES = None
 DATASET_RED_NOISE = None
+DATASET_T0 = None
 # An importance map (WARP_GRIDS) applies to a datasets call as to any other: its draws are trx_draw_scenario's.  The weight
 # histogram of the library's own chain (WARP_HIST) does not exist here -- chi^2/2 is computed outside that chain -- so
 # DATASET_WARP_HIST = {}: every datasets call leaves {work unit: [branches][WARP_BRANCH] uint64 words} there, one
@@ -251,7 +257,7 @@ DATASET_WARP_HIST = None
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -766,6 +772,22 @@ def _mix_on_device(d, device):
     return _cached(_mix_cache, key, 32, build)
 
 
+_shift_cache = {}
+
+
+def _shift_on_device(d, grid, device):
+    """(the J device tensors time + shift_j, ln pi [J] on the host, the same on the device) of a dataset with a t0_grid
+    [J][2]: the sums are float64, formed once on the host per content of the stamps and the grid (a cache of its own, as
+    _mix_on_device's).  The device copy of ln pi serves the best draw's choice of a node: an upload per branch would make
+    the host wait for the device there."""
+    key = (hash(d.time.tobytes()), hash(grid.tobytes()), d.time.shape, grid.shape, device.index)
+
+    def build():
+        lnpi = np.log(grid[:, 1])
+        return [_lib.dev(np.ascontiguousarray(d.time + shift), device) for shift in grid[:, 0]], lnpi, _lib.dev(lnpi, device)
+    return _cached(_shift_cache, key, 32, build)
+
+
 class _Baseline(NamedTuple):
     """the system of a dataset with baseline columns (datasets.baseline_system)"""
     g: torch.Tensor              # the scaled columns [K][T], on the device
@@ -776,7 +798,8 @@ class _Baseline(NamedTuple):
 
 class _Dataset(NamedTuple):
     """one light curve of a Datasets call on the device, and what its reduction marginalises: nothing, a constant offset,
-    or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then"""
+    or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then --, or correlated
+    noise; and, next to any of these, the nodes of a transit-time shift (`shift`: the reduction then runs once per node)"""
     time: torch.Tensor
     flux: torch.Tensor
     inv_var: torch.Tensor
@@ -786,11 +809,15 @@ class _Dataset(NamedTuple):
     baseline: Optional[_Baseline] = None
     ou: Optional[tuple] = None               # (alpha, beta, omega) on the device: correlated noise (datasets.ou_system)
     mix: Optional[tuple] = None              # (alpha, beta, omega [J][T] on the device, lnc [J] on the host): ou_mix_system
+    shift: Optional[tuple] = None            # (J device tensors time + shift_j, ln pi [J] on the host, ln pi on the device)
 
     @classmethod
-    def upload(cls, d, dev):
+    def upload(cls, d, dev, t0_grid=None):
         inv_var = 1.0 / (d.flux_err * d.flux_err)
         rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
+        if t0_grid is not None:
+            # (next to whatever else the dataset marginalises: a shift leaves all of that as it is)
+            rec = rec._replace(shift=_shift_on_device(d, t0_grid, dev))
         if d.red_grid is not None:
             # (validate refuses anything else next to it)
             return rec._replace(mix=_mix_on_device(d, dev))
@@ -836,7 +863,7 @@ class _Scenario:
         self.datasets = None
         if isinstance(time, Datasets):
             # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
-            self.datasets = [_Dataset.upload(d, self.dev) for d in time.sets]
+            self.datasets = [_Dataset.upload(d, self.dev, g) for d, g in zip(time.sets, time.t0_grids)]
             sigma = time.sigma_ref
             self.time, self.flux = self.datasets[0].time, self.datasets[0].flux
         else:
@@ -1095,6 +1122,7 @@ class _Scenario:
         offsets = []       # (DATASET_OFFSETS: per branch the best draw's offsets, still on the device)
         coefs = []         # (DATASET_BASELINES: per branch and dataset the best draw's scaled coefficients, likewise)
         cands = []         # (DATASET_RED_NOISE: per branch and dataset the best draw's per-candidate chi^2/2, likewise)
+        nodes = []         # (DATASET_T0: per branch and dataset the best draw's per-node terms, likewise)
         hists = None       # (DATASET_WARP_HIST: per branch the weight histogram of its evidence, likewise)
         if self.datasets is not None and DATASET_WARP_HIST is not None:
             if not self.philox:
@@ -1125,11 +1153,12 @@ class _Scenario:
                 _lib.moments_emit(mom[1], mom[2])
             best = self._best(h, idx, n)
             if self.datasets is not None and ((DATASET_OFFSETS is not None and any(d.offset is not None for d in self.datasets))
-                                              or self._any_baseline() or self._any_mix()):
-                o, c, hc = self._best_offsets(model, flags, cols, best, twin, nblk) if n else (None, None, None)
+                                              or self._any_baseline() or self._any_mix() or self._any_shift()):
+                o, c, hc, hn = self._best_offsets(model, flags, cols, best, twin, nblk) if n else (None, None, None, None)
                 offsets.append(o)
                 coefs.append(c)
                 cands.append(hc)
+                nodes.append(hn)
             post = None
             if POSTERIOR_ROWS:
                 # the same selection on this chain's chi^2/2 values (trx_posterior_from_halfchi2; the twin branch draws
@@ -1153,7 +1182,7 @@ class _Scenario:
             if POSTERIOR_ROWS:
                 res[-1]["posterior"] = None if post is None else self._posterior_dict(post.cpu().numpy(), ncol, twin)
         if offsets:
-            self._leave_best_terms(offsets, coefs, cands)
+            self._leave_best_terms(offsets, coefs, cands, nodes)
         if hists is not None:
             DATASET_WARP_HIST[getattr(_tls, "unit", None)] = torch.stack(hists).cpu().numpy().view(np.uint64)
         return res[0] if a.planet else (res[0], res[1])
@@ -1167,12 +1196,33 @@ class _Scenario:
         """whether a red_grid dataset's candidate weights are wanted back (DATASET_RED_NOISE)"""
         return DATASET_RED_NOISE is not None and any(d.mix is not None for d in self.datasets)
 
-    def _leave_best_terms(self, offsets, coefs, cands):
+    def _any_shift(self):
+        """whether a t0_grid dataset's node weights are wanted back (DATASET_T0)"""
+        return DATASET_T0 is not None and any(d.shift is not None for d in self.datasets)
+
+    def _leave_best_terms(self, offsets, coefs, cands, nodes):
         """the branches' best-draw offsets and baseline coefficients, from the device to DATASET_OFFSETS / DATASET_BASELINES
         under this thread's work unit, in the call's normalisation: c_k = c~_k / sqrt(D_k); and the posterior weights of a
-        red_grid dataset's candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_RED_NOISE (NaN without a draw)"""
+        red_grid dataset's candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_RED_NOISE (NaN without a draw); and
+        those of a t0_grid dataset's nodes, softmax_j(ln pi_j - h_j), to DATASET_T0 (likewise)"""
         L = len(self.datasets)
         unit = getattr(_tls, "unit", None)
+        if DATASET_T0 is not None:
+            t0 = []
+            for hn in nodes:
+                per = [None] * L
+                for l, d in enumerate(self.datasets):
+                    if d.shift is None:
+                        continue
+                    lnpi = d.shift[1]
+                    if hn is None:
+                        per[l] = np.full(lnpi.size, np.nan)
+                        continue
+                    x = lnpi - hn[l].cpu().numpy().reshape(-1)
+                    w = np.exp(x - np.max(x))
+                    per[l] = w / w.sum()
+                t0.append(per)
+            DATASET_T0[unit] = t0
         if DATASET_RED_NOISE is not None:
             red = []
             for hc in cands:
@@ -1209,37 +1259,56 @@ class _Scenario:
             DATASET_BASELINES[unit] = base
 
     def _best_offsets(self, model, flags, cols, best, twin, nblk):
-        """([L] device tensor, list per dataset, list per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
+        """([L] device tensor and three lists per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
         S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
         baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them); and None or the
         [1][J] device tensor of a red_grid dataset's per-candidate chi^2/2.  The one row is evaluated again -- trx_flux_grid
         on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out, coef_out or cand_out -- so nothing of
-        size n x L is kept."""
+        size n x L is kept.  A t0_grid dataset has the row evaluated on every node: the fourth list holds None or the [J]
+        device tensor of its per-node terms h_j, and its offset, coefficients and candidates are those of the node of
+        largest ln pi_j - h_j (on a tie the first), picked on the device."""
         out = torch.full((len(self.datasets),), float("nan"), dtype=F64, device=self.dev)
         coefs = [None] * len(self.datasets)
         cands = [None] * len(self.datasets)
+        nodes = [None] * len(self.datasets)
         row = cols[:nblk].index_select(1, best[:1]).contiguous()
         if twin:
             row[2] *= 2.0
             row[4] = cols[11].index_select(0, best[:1])
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL
         for l, d in enumerate(self.datasets):
-            if d.offset is None and d.baseline is None and (d.mix is None or DATASET_RED_NOISE is None):
+            if (d.offset is None and d.baseline is None and (d.mix is None or DATASET_RED_NOISE is None)
+                    and (d.shift is None or DATASET_T0 is None)):
                 continue
-            grid, _ = _lib.flux_grid(model, flags, d.time, row, d.exptime, d.nsamples, want_secdepth=False)
+            stamps = [d.time] if d.shift is None else d.shift[0]
+            J = len(stamps)
+            off = out[l:l + 1] if d.shift is None else torch.full((J,), float("nan"), dtype=F64, device=self.dev)
             if d.baseline is not None:
-                coefs[l] = torch.empty((1, int(d.baseline.g.shape[0])), dtype=F64, device=self.dev)
+                coefs[l] = torch.empty((J, int(d.baseline.g.shape[0])), dtype=F64, device=self.dev)
             if d.mix is not None:
-                cands[l] = torch.empty((1, int(d.mix[3].size)), dtype=F64, device=self.dev)
-            d.halfchi2(grid, offset_out=out[l:l + 1], coef_out=coefs[l], cand_out=cands[l])
-        return out, coefs, cands
+                cands[l] = torch.empty((J, int(d.mix[3].size)), dtype=F64, device=self.dev)
+            hs = []
+            for j, t in enumerate(stamps):
+                grid, _ = _lib.flux_grid(model, flags, t, row, d.exptime, d.nsamples, want_secdepth=False)
+                hs.append(d.halfchi2(grid, offset_out=off[j:j + 1], coef_out=None if coefs[l] is None else coefs[l][j:j + 1],
+                                     cand_out=None if cands[l] is None else cands[l][j:j + 1]))
+            if d.shift is not None:
+                nodes[l] = torch.cat(hs)
+                top = torch.argmax(d.shift[2] - nodes[l]).reshape(1)   # (the first of equal maxima)
+                out[l:l + 1] = off.index_select(0, top)
+                coefs[l] = None if coefs[l] is None else coefs[l].index_select(0, top)
+                cands[l] = None if cands[l] is None else cands[l].index_select(0, top)
+        return out, coefs, cands, nodes
 
     def _datasets_halfchi2(self, model, flags, block):
         """sum over the datasets of the weighted chi^2/2 of every row of `block` ([n_param][n], the masked draws of one
         branch): per chunk of rows and per dataset one trx_flux_grid and the dataset's accumulating reduction
-        (_Dataset.halfchi2: trx_chi2_grid_weighted, or what marginalises its offset or baseline columns).  The EB
+        (_Dataset.halfchi2: trx_chi2_grid_weighted, or what marginalises its offset or baseline columns); for a dataset
+        with a t0_grid, J of each on the stamps time + shift_j into a zeroed [J][rows] buffer, then one trxt_softmin_rows that
+        adds -ln sum_j pi_j exp(-h_j).  The EB
         branch's secondary-eclipse rule (secdepth >= 1.5 sigma_bar -> +inf) rides in the first dataset's reduction: the
-        depth does not depend on the time stamps.  A row's value does not depend on the chunk it falls in.
+        depth does not depend on the time stamps (asked for once; with a t0_grid on the first dataset it rides every node's
+        reduction: all nodes +inf give +inf).  A row's value does not depend on the chunk it falls in.
         DATASET_EVALUATION = "fused": one trx_lnl_batch_weighted per dataset over the whole block instead -- no grid, no
         chunks; the rule rides in the first dataset's call as its sec_limit.  It has no offset form."""
         if DATASET_EVALUATION not in DATASET_EVALUATIONS:
@@ -1256,6 +1325,9 @@ class _Scenario:
         if DATASET_EVALUATION == "fused" and any(d.mix is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a red_grid dataset is not built: the fused kernel "
                                       "carries no recurrence along the row; use evaluation='grid'")
+        if DATASET_EVALUATION == "fused" and any(d.shift is not None for d in self.datasets):
+            raise NotImplementedError("evaluation='fused' with a t0_grid dataset is not built: the nodes' terms are folded "
+                                      "from the grid reductions; use evaluation='grid'")
         n = int(block.shape[1])
         h = torch.zeros(n, dtype=F64, device=self.dev)         # (0 + x = x: every reduction accumulates)
         if n == 0:
@@ -1277,14 +1349,27 @@ class _Scenario:
                 blk = block if (r0 == 0 and r1 == n) else block[:, r0:r1].contiguous()
                 for l, d in enumerate(self.datasets):
                     nt = int(d.time.numel())
+                    if d.shift is not None:
+                        stamps, lnpi = d.shift[:2]
+                        cand = torch.zeros((len(stamps), r1 - r0), dtype=F64, device=self.dev)
+                        sec = None
+                        for j, t in enumerate(stamps):
+                            grid, s = _lib.flux_grid(model, flags, t, blk, d.exptime, d.nsamples,
+                                                     want_secdepth=eb and l == 0 and j == 0,
+                                                     out=buf[:(r1 - r0) * nt].view(r1 - r0, nt))
+                            sec = s if j == 0 else sec
+                            d.halfchi2(grid, sec, 1.5 * self.sigma, out=cand[j])
+                        _lib.softmin_rows(cand, lnpi, out=h[r0:r1])
+                        continue
                     grid, sec = _lib.flux_grid(model, flags, d.time, blk, d.exptime, d.nsamples, want_secdepth=eb and l == 0,
                                                out=buf[:(r1 - r0) * nt].view(r1 - r0, nt))
                     d.halfchi2(grid, sec, 1.5 * self.sigma, out=h[r0:r1])
         with _stats_lock:
             # (the masked draws once, every (draw, time stamp) cell of every dataset)
             _lib.STATS["rows"] += n
-            _lib.STATS["cells"] += n * sum(int(d.time.numel()) for d in self.datasets)
-            _lib.STATS["launches"] += len(self.datasets) * chunks
+            nodes = [1 if d.shift is None else len(d.shift[0]) for d in self.datasets]
+            _lib.STATS["cells"] += n * sum(j * int(d.time.numel()) for j, d in zip(nodes, self.datasets))
+            _lib.STATS["launches"] += sum(nodes) * chunks
         return h
 
     def _run_native(self, is_host, ncol):

@@ -9,6 +9,8 @@ Bin edges follow lightkurve 2.x's fixed-width binning [recollection -- lightkurv
 image]: bins of `time_bin_size` start at the first time stamp, each bin reports its centre and the
 nan-mean of its fluxes, an empty bin reports NaN.
 """
+import math
+
 import numpy as np
 
 
@@ -103,10 +105,27 @@ def red_noise_grid(sigmas, timescales, weights=None):
     return np.ascontiguousarray(np.stack([ss.ravel(), tt.ravel(), w.ravel() / w.sum()], axis=1))
 
 
+def t0_shift_grid(sigma, n: int = 5, span: float = 3.0):
+    """A Gaussian prior on a dataset's transit-time shift as its "t0_grid": a float64 array [n][2] of rows (shift, weight),
+    n odd, the shifts equally spaced over -span * sigma ... +span * sigma (the middle one exactly 0, the others mirror
+    images), the weights proportional to exp(-0.5 (shift / sigma)^2) and normalised to sum 1.  sigma: the propagated
+    ephemeris error sqrt(sigma_T0^2 + E^2 sigma_P^2), in the units of `time`.  n = 1: the single node 0."""
+    sigma, span, n = float(sigma), float(span), int(n)
+    if not (sigma > 0 and math.isfinite(sigma)) or not (span > 0 and math.isfinite(span)):
+        raise ValueError("sigma and span must be finite and > 0")
+    if n < 1 or n % 2 == 0:
+        raise ValueError("n must be odd and >= 1 (got %d): the middle node is no shift" % n)
+    half = n // 2
+    k = np.arange(-half, half + 1, dtype=np.float64)
+    u = k * (span / half) if half else k                          # (shift / sigma; symmetric in bits)
+    w = np.exp(-0.5 * u * u)
+    return np.ascontiguousarray(np.stack([u * sigma, w / math.fsum(w.tolist())], axis=1))
+
+
 def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int = 50,
                     exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None,
                     baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None,
-                    red_grid=None):
+                    red_grid=None, t0_grid=None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
     {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
     empty bins are dropped.
@@ -115,7 +134,8 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     or one per column; None: flat) passed through; 0: both keys are None.
     red_sigma, red_timescale (both or neither): the dataset's correlated noise, passed through as the keys of those names
     when given.  red_grid (red_noise_grid's result, or any list of (s_r, tau, weight)): candidates of that noise to
-    marginalise, passed through as the key "red_grid" when given.
+    marginalise, passed through as the key "red_grid" when given.  t0_grid (t0_shift_grid's result, or any list of (shift,
+    weight)): nodes of a transit-time shift to marginalise, passed through as the key "t0_grid" when given.
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -136,4 +156,6 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
         out["red_sigma"], out["red_timescale"] = red_sigma, red_timescale
     if red_grid is not None:
         out["red_grid"] = red_grid
+    if t0_grid is not None:
+        out["t0_grid"] = t0_grid
     return out

@@ -27,7 +27,7 @@ from scipy.special import ndtr
 from . import _lib
 from ._numerics import _mc_errors, _normalize_probabilities
 from .constants import G, Msun, pi
-from .datasets import Datasets, validate as _validate_datasets
+from .datasets import Datasets, t0_grids as _t0_grids, validate as _validate_datasets
 from .funcs import renorm_flux
 from .marginal_likelihoods import *  # noqa: F401,F403  (reference re-exports the lnZ_* names)
 from .marginal_likelihoods import (lnZ_BEB, lnZ_BTP, lnZ_DEB, lnZ_DTP, lnZ_PEB, lnZ_PTP, lnZ_SEB,
@@ -258,7 +258,8 @@ class target:
         for k in ("exptime", "nsamples"):
             if k in calc_probs_kwargs:
                 raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
-        ds = Datasets(_validate_datasets(datasets))
+        sets = _validate_datasets(datasets)
+        ds = Datasets(sets, _t0_grids(datasets, sets))
         n_samples = int(n_samples)
         if not 0 <= n_samples <= fused.POST_MAX_ROWS:
             raise ValueError("n_samples must lie in [0, %d]" % fused.POST_MAX_ROWS)
@@ -272,8 +273,8 @@ class target:
 
     def _datasets_pass(self, ds, P_orb, kw, verbose, evaluation, n_samples=0, **dataset_switches):
         """one pass of the datasets path over the target's work units: (units, rows, n_scen) for _finish.
-        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_WARP_HIST for the length
-        of the pass."""
+        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_WARP_HIST for
+        the length of the pass."""
         from . import fused
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
         if ds.has_offsets and evaluation == "fused":
@@ -283,6 +284,8 @@ class target:
         if ds.has_red_noise and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a red_sigma or red_grid dataset is not built: use "
                                       "evaluation='grid'")
+        if ds.has_t0_grids and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with a t0_grid dataset is not built: use evaluation='grid'")
         with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, **dataset_switches):
             rows = sharding.run_units(units, verbose=verbose, as_rows=True)
         return units, rows, n_scen
@@ -360,14 +363,30 @@ class target:
         weight, in the units given), "weight": the [J] posterior weights of the candidates at the scenario's best draw,
         softmax_j(ln c_j - h_j) (NaN without a finite lnZ)}; the whole attribute is None when no dataset has a grid.
         Not built: per-draw candidate posteriors, a continuous fit of s_r and tau, more than one term, red noise next to
-        offset or baseline."""
+        offset or baseline.
+
+        Where the transit time of a dataset is uncertain -- a follow-up night long after the ephemeris was measured --
+        the dataset may carry "t0_grid" next to any of the keys above: 1 to 8 nodes (shift, weight), the shifts in the units
+        of `time`, finite and all different, the prior weights > 0 (normalised to sum 1); lightcurve.t0_shift_grid makes
+        the nodes of a Gaussian prior.  With h_j the dataset's term of the log-weight on the stamps time + shift_j -- by
+        whichever reduction the dataset uses --, its term becomes -ln sum_j weight_j exp(-h_j): J model grids and J
+        reductions per draw, folded by trxt_softmin_rows.  Nothing is dropped: the weights sum to 1, and a shift leaves the
+        stamp differences, the baseline columns (they follow the points, not the shifted stamps) and the determinants as
+        they are.  One node (d, 1) gives the bits of the same dataset with time + d.  Grid evaluation only.
+        `.dataset_t0` is then a list per scenario of a list per dataset: None for a dataset without the key, else
+        {"shift": the [J] shifts, "weight": the [J] posterior weights of the nodes at the scenario's best draw,
+        softmax_j(ln weight_j - h_j) (NaN without a finite lnZ), "mean": sum_j weight_j shift_j}; the whole attribute is
+        None when no dataset has the key.  `.dataset_offsets`, `.dataset_baselines` and `.dataset_red_noise` of such a
+        dataset are those of its node of largest weight (the first of equal ones).  Not built: a shift shared between
+        datasets, a continuous fit of the shift, per-draw shift posteriors."""
         ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
         best_offsets = {} if ds.has_offsets else None
         best_baselines = {} if ds.has_baselines else None
         best_red = {} if any(s.red_grid is not None for s in ds.sets) else None
+        best_t0 = {} if ds.has_t0_grids else None
         units, rows, n_scen = self._datasets_pass(ds, P_orb, kw, verbose, evaluation, n_samples,
                                                   DATASET_OFFSETS=best_offsets, DATASET_BASELINES=best_baselines,
-                                                  DATASET_RED_NOISE=best_red)
+                                                  DATASET_RED_NOISE=best_red, DATASET_T0=best_t0)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
@@ -403,6 +422,20 @@ class target:
                     if np.isfinite(self.lnZ[u.first_row + i]):
                         rows_[u.first_row + i] = [entry(s, w) for s, w in zip(ds.sets, per)]
             self.dataset_red_noise = rows_
+        self.dataset_t0 = None
+        if best_t0 is not None:
+            # (shifts are times and the weights pure numbers: the same in every star's normalisation)
+            def node(g, w=None):
+                if g is None:
+                    return None
+                w = np.full(g.shape[0], np.nan) if w is None else w
+                return {"shift": g[:, 0].copy(), "weight": w, "mean": float(np.sum(w * g[:, 0]))}
+            rows_ = [[node(g) for g in ds.t0_grids] for _ in range(n_scen)]
+            for k, u in enumerate(sharding.as_units(units)):
+                for i, per in enumerate(best_t0.get(k, ())):
+                    if np.isfinite(self.lnZ[u.first_row + i]):
+                        rows_[u.first_row + i] = [node(g, w) for g, w in zip(ds.t0_grids, per)]
+            self.dataset_t0 = rows_
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
@@ -501,7 +534,7 @@ class target:
         uniforms from the chi^2/2 values of that pass (trxw_hist_from_halfchi2, fused.DATASET_WARP_HIST) and refine
         the map; best-draw offsets and baselines are not computed in them.  The final pass is calc_probs_datasets under
         the maps the adaptation left: it fills `.probs`, `.FPP`, `.lnZ_err`, `.posterior` (n_samples > 0), `.sigma_ref`,
-        `.dataset_offsets`, `.dataset_baselines` and `.dataset_red_noise` as calc_probs_datasets does, and only it enters the result, so the
+        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise` and `.dataset_t0` as calc_probs_datasets does, and only it enters the result, so the
         estimate is unbiased.  `.refine_history` holds, per pass, the rows' lnZ, ess and w_max_frac.  n_adapt = 0 is
         calc_probs_datasets, bit for bit.  Both evaluations ("grid", "fused") feed the histogram the same way.
 
