@@ -74,6 +74,14 @@ int trx_debug_row_order(long* n_rows, long* segment_capacity, int* counts, int* 
  * filing the trips that lie wholly inside a transit window as they stand (default 1).  No output depends on it, bit
  * for bit: the in-window list holds the same cells in the same order. */
 int trx_set_whole_trips(int on);
+/* How the one-row kernels of the full evaluation (with and without the stencil) take the cells next to a limb contact:
+ * 1 (default, what the production library does): the likelihood kernels evaluate them in the chunk that planned them,
+ * the flux grid files them for a second sweep over the in-window list, as the bounded and the batched kernels do;
+ * 0: the likelihood kernels take the second sweep too; 2: the flux grid and its evaluation census take the one sweep
+ * too.  The evaluations per cell do not depend on it; a contact cell's value and chi^2/2 may move in the last bits (its
+ * centre solution comes from another plan trip, and its chi^2 term is added by another lane).  TRX_ERR_ARG for another
+ * value. */
+int trx_set_one_sweep(int mode);
 /* the 64-cell trips of pass 1 that the stencil instantiation's waves on the current device filed whole and those they
  * walked cell by cell since the library was loaded (or since the last call with reset != 0, which returns the counts and
  * then zeroes them); the trips that cannot hold an in-window cell are in neither.  It waits for the device.  Device

@@ -52,7 +52,7 @@ DEBUG_SYMBOLS = (
     "trx_set_stencil", "trx_set_skip_excluded", "trx_set_debug_node_counts", "trx_set_kepler_stepping",
     "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison", "trx_set_debug_bug",
     "trx_set_probe_rows", "trx_set_star_chain", "trx_debug_capture_buffers", "trx_debug_chain_counts",
-    "trx_set_row_order", "trx_debug_row_order", "trx_set_whole_trips", "trx_debug_whole_trips",
+    "trx_set_row_order", "trx_debug_row_order", "trx_set_whole_trips", "trx_debug_whole_trips", "trx_set_one_sweep",
     "trx_debug_select_from_halfchi2",
 )
 
@@ -217,7 +217,7 @@ def _load(path, testing):
                      "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison",
                      "trx_set_debug_bug", "trx_set_star_chain", "trx_set_probe_rows", "trx_set_stencil",
                      "trx_set_supersample_tiers", "trx_set_debug_node_counts", "trx_set_cell_packing_below",
-                     "trx_set_row_order", "trx_set_whole_trips"):
+                     "trx_set_row_order", "trx_set_whole_trips", "trx_set_one_sweep"):
             fn = getattr(L, name)
             fn.restype = c_int
             fn.argtypes = [c_int]

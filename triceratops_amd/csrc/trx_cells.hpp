@@ -91,6 +91,7 @@ struct RowsArgs {
     double sec_limit;
     int accumulate;
     int whole_trips;   // trx_set_whole_trips (read by the testing library's kernels only): see window_trips
+    int one_sweep;     // trx_set_one_sweep (likewise): 0 two sweeps, 1 one in the likelihood kernels, 2 in the flux grid's too
     // Cost-ordered rows (one row per wave, full evaluation of a likelihood launch; null: rows as they come): rowc_kernel
     // files every row under its cost bucket, cells_kernel's position v takes the v-th row of that order (row_order_at)
     int* order;        // [kOrderSegs counters, kOrderStride ints apart | kOrderSegs lists of order_cap(n) row numbers]
@@ -207,9 +208,11 @@ __device__ __forceinline__ void add_trip_stat(int which, unsigned count)
     if (count) atomicAdd(&g_trip_stats[which][(blockIdx.x + 41u * blockIdx.y) & (kStatShards - 1)][0], (unsigned long long)count);
 }
 __device__ __forceinline__ bool whole_trips_on(const RowsArgs& a) { return a.whole_trips != 0; }
+__device__ __forceinline__ bool one_sweep_on(const RowsArgs& a, bool lnl) { return a.one_sweep >= (lnl ? 1 : 2); }
 #define TRX_TRIP_STAT(var) ++var
 #else
 __device__ __forceinline__ bool whole_trips_on(const RowsArgs&) { return true; }
+__device__ __forceinline__ bool one_sweep_on(const RowsArgs&, bool lnl) { return lnl; }
 #define TRX_TRIP_STAT(var)
 #endif
 
@@ -244,8 +247,9 @@ __device__ __forceinline__ double k_rule(double k, bool scalar_rule)
 //     chunk are dealt to all 64 lanes: a pair steps the orbit from its cell's centre solution,
 //     evaluates the Mandel-Agol flux and adds its term to the cell's sum in LDS.  Every stage runs
 //     full lanes whatever the mix of node counts.  Cells next to a limb contact (all S
-//     sub-exposures, some of them off the disc) are filed again and take a second sweep, so that
-//     the first sweep's pairs are all on the disc;
+//     sub-exposures, some of them off the disc) ride in their chunk's pair table like any other cell where a
+//     wave has one row and evaluates its likelihood in full (kOneSweep); in the flux grid, the bounded and the
+//     batched instantiations they are filed again and take a second sweep;
 //   * batches: a lane's row constants come from the row blocks in LDS (cells of different rows share
 //     a wave); chi^2 of a row = chi^2 of the flat model (every cell exactly 1: one number per
 //     launch) + the corrections ((f-m)^2 - (f-1)^2)/sigma^2 of its in-window cells, added to one
@@ -297,6 +301,14 @@ __host__ __device__ constexpr int cells_waves(bool long_rows) { return long_rows
 #endif
 #ifndef TRX_CELLS_PAIRS
 #define TRX_CELLS_PAIRS 640
+#endif
+// 1: one row per wave, full evaluation: a contact cell is evaluated in the chunk that planned it (cells_body, pass 2)
+#ifndef TRX_ONE_SWEEP
+#define TRX_ONE_SWEEP 1
+#endif
+// (side arm of profiles/one_sweep: 1 = the batched instantiations of the full evaluation too)
+#ifndef TRX_ONE_SWEEP_BATCH
+#define TRX_ONE_SWEEP_BATCH 0
 #endif
 #ifndef TRX_CELLS_WINDOW
 #define TRX_CELLS_WINDOW 2048
@@ -1624,11 +1636,22 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
             wave_sync();
             TRX_TOCK(1, t_p1);
             // pass 2: the in-window cells, 64 at a time.  A cell next to a limb contact evaluates
-            // all S sub-exposures, the others 3-9 nodes: the first sweep only files those cells
-            // (back into the list, behind the read cursor) and a second sweep takes them, so that
-            // pairs that may turn out to be off the disc stay out of the first sweep's trips.
+            // all S sub-exposures, the others 3-9 nodes.  Two sweeps (bounded, batched): the first only files
+            // those cells (back into the list, behind the read cursor) and a second sweep takes them.
+            // One row per wave, full evaluation (kOneSweep): ONE sweep.  A contact cell keeps the plan it was given and
+            // its S pairs ride in the pair table of the chunk that planned it, behind its left neighbour's; it is
+            // finalised with that chunk.  (The off-disc lanes of its pairs idle in disc_flux either way; the second
+            // sweep planned such a cell again -- another Kepler step from conjunction --, built a pair table of its own
+            // and finalised in a trip of its own, all with half the lanes: DESIGN 4.1, "one sweep".)  The bounded and the
+            // batched instantiations keep two sweeps, and so does the flux grid: a contact cell's centre solution then
+            // comes from another plan trip (kepler_step_wide without FREEZE: a lane takes the steps its trip-mates need),
+            // which moves the cell's last bit or two on eccentric orbits, and the flux grid's values are on record bit
+            // for bit (tests/golden/window_trips.npz).  The testing library can send the flux grid and its census through
+            // the one sweep as well (trx_set_one_sweep(2)): the same code, cell by cell, for tests/test_gpu_one_sweep.py.
+            constexpr bool kOneSweep = TRX_ONE_SWEEP && (LONG || TRX_ONE_SWEEP_BATCH) && !PRUNE;
+            const bool one = kOneSweep && one_sweep_on(a, MODE == MODE_LNL);
             int nheavy = 0;
-            for (int sweep = 0; sweep < 2; ++sweep) {
+            for (int sweep = 0; sweep < (one ? 1 : 2); ++sweep) {
             const int count = sweep ? nheavy : nw;
             // With the centre-value stencil the chunks of the first sweep overlap by kStM cells: a chunk finalises
             // its first 64 - kStM lanes and only lends the centre values of the last kStM, which the next chunk owns;
@@ -1709,12 +1732,20 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                         pl.anchored = true;
                     }
                 }
+                // `planned`: a cell of this sweep that is no contact cell -- what counts as a neighbour for the stencil and
+                // may take a centre value.  One sweep: the contact cell stays `valid` (its owner evaluates and finalises it
+                // here, all S sub-exposures from the plan it has); two sweeps: it is filed for the second and leaves this one.
+                bool planned = valid;
                 if (sweep == 0 && a.use_tiers) {
                     const bool heavy = valid && !pl.lazy && pl.tier < 0 && pl.n > 0;
-                    const unsigned long long mh = __ballot(heavy && owned);       // filed once, by its owner
-                    if (heavy && owned) winlist[nheavy + lanes_below(mh)] = (unsigned short)rel;
-                    if (heavy) { pl.n = 0; valid = false; }
-                    nheavy += __popcll(mh);
+                    if (one) {
+                        planned = valid && !heavy;
+                    } else {
+                        const unsigned long long mh = __ballot(heavy && owned);       // filed once, by its owner
+                        if (heavy && owned) winlist[nheavy + lanes_below(mh)] = (unsigned short)rel;
+                        if (heavy) { pl.n = 0; valid = false; planned = false; }
+                        nheavy += __popcll(mh);
+                    }
                 }
                 int tier = pl.tier;
                 int nodes = (valid && owned) ? pl.n : 0;
@@ -1729,27 +1760,27 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                     const int jleft = __shfl(carry_j, 64 - 2 * kStM + lane, 64), jhere = __shfl(j, lane - kStM, 64);
                     const int jm = (lane < kStM) ? jleft : jhere;
                     const int jp = __shfl(j, lane + kStM, 64);
-                    const unsigned long long mok = __ballot(valid);
+                    const unsigned long long mok = __ballot(planned);
                     const unsigned long long left = (carry_ok >> (64 - 2 * kStM)) & ((1ull << kStM) - 1ull);
                     const bool inner = (lane >= kStM || (halo && w0 > 0)) && lane + kStM < 64;
                     constexpr unsigned long long kAll = (1ull << (2 * kStM + 1)) - 1ull;
                     // the 2 kStM + 1 "planned cell" bits around the lane (the lowest ones from the previous chunk)
                     const unsigned long long field = (lane >= kStM) ? (mok >> (lane - kStM)) : (((mok << kStM) | left) >> lane);
-                    st = inner && owned && valid && pl.n > 0 && pl.st_ok && jm == j - kStM && jp == j + kStM &&
+                    st = inner && owned && planned && pl.n > 0 && pl.st_ok && jm == j - kStM && jp == j + kStM &&
                          (field & kAll) == kAll;
                     const unsigned long long mst = __ballot(st);
                     unsigned long long dil = mst;
 #pragma unroll
                     for (int i = 1; i <= kStM; ++i) dil |= (mst << i) | (mst >> i);
-                    centre = valid && ((dil >> lane) & 1ull);
+                    centre = planned && ((dil >> lane) & 1ull);
                     // (the next chunk's first cells may take their stencil through this one's last owned cells; one whose
                     // exposure is off the disc altogether has the value 1 without an evaluation)
                     // -- and only a cell that a stencil cell of the next chunk can reach: lane 64 - 2 kStM + k is within
                     // kStM of the next chunk's cells 0 .. k, this chunk's lanes 64 - kStM .. 64 - kStM + k, which can take
                     // the stencil only where their own plan allows it)
-                    const unsigned long long mnext = __ballot(valid && pl.n > 0 && pl.st_ok) >> (64 - kStM);
+                    const unsigned long long mnext = __ballot(planned && pl.n > 0 && pl.st_ok) >> (64 - kStM);
                     const int kk = lane - (64 - 2 * kStM);
-                    if (halo && !last_chunk && valid && !centre && kk >= 0 && kk < kStM && (mnext & ((2ull << kk) - 1ull)) != 0) {
+                    if (halo && !last_chunk && planned && !centre && kk >= 0 && kk < kStM && (mnext & ((2ull << kk) - 1ull)) != 0) {
                         if (pl.n > 0) centre = true;
                         else ss.fc[kStM + lane] = 1.0;
                     }
@@ -1807,29 +1838,57 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                 }
                 TRX_TOCK(2, t_plan);
                 TRX_TICK(t_a);
-                // The (cell, node) pairs of the chunk, cell by cell, dealt to all lanes: a pass
+                // The (cell, node) pairs of the chunk, cell by cell, dealt to all lanes.  Two sweeps: a pass
                 // takes as many nodes of every cell as fit the pair table (a first-sweep chunk in
                 // one pass; 64 contact cells x S = 20 sub-exposures in two).
+                // One sweep: a chunk whose pairs all fit the table -- centres included, whatever the mix of counts -- is one
+                // pass; one that does not fit (both ingress contacts in one chunk, a grazing row, every sub-exposure asked
+                // for) is split by CELLS: a pass takes the cells, in lane order, whose pairs end within the table, the
+                // next pass goes on behind them.  Every pass but the last is full, a cell's nodes sit in consecutive lanes
+                // of one pass, and a cell's sum is still added in node order.  (A cell with more nodes than the table
+                // holds -- S >= kCellsPairs -- can only be split by nodes: then as with two sweeps.)
                 int ldone = 64;                    // lanes [0, ldone) are done with this chunk, the others are carried on
                 const int ncells = __popcll(__ballot(nodes > 0 || (ST && centre)));
+                const bool by_cells = one && a.S < kCellsPairs;
+                // (two sweeps: the centre's slot is reserved in the second sweep too, which has no centres -- with 31-32
+                // contact cells `per` is 19 and the chunk takes two passes.  It stays: other passes mean other trip-mates
+                // for the pairs' Kepler steps, and the values of these instantiations are on record bit for bit)
                 int per = ncells > 0 ? kCellsPairs / ncells - (ST ? 1 : 0) : kCellsPairs;
                 per = per > 1000 ? 1000 : (per < 1 ? 1 : per);
-                for (int s0 = 0; !direct && __any(s0 < nodes || (ST && s0 == 0 && centre)); s0 += per) {
+                if (by_cells) per = kCellsPairs;
+                int lane0 = ncells > 0 ? 0 : 64;   // by cells: the first lane whose cell is still to be taken
+                for (int s0 = 0; !direct && (by_cells ? lane0 < 64 : __any(s0 < nodes || (ST && s0 == 0 && centre)));
+                     s0 += by_cells ? 0 : per) {
                     int cnt = nodes - s0;
                     cnt = cnt < 0 ? 0 : (cnt > per ? per : cnt);
                     TRX_CENSUS_ADD(kCenPass, 1);
-                    const int extra = (ST && s0 == 0 && centre) ? 1 : 0;      // the centre rides in the first pass
-                    // (first sweep: at most 9 nodes + the centre per cell -- four ballots; contact cells: up to S)
+                    int extra = (ST && s0 == 0 && centre) ? 1 : 0;            // the centre rides in the first pass
+                    if (by_cells && lane < lane0) { cnt = 0; extra = 0; }     // (taken by an earlier pass)
+                    // (first sweep of two: at most 9 nodes + the centre per cell -- four ballots; contact cells: up to S;
+                    // one sweep: up to S + 1 per cell -- five ballots up to S = 30)
                     int total;
-                    const int off = (sweep == 0 && a.use_tiers) ? lane_prefix<4>(cnt + extra, total)
-                                                                : lane_prefix<10>(cnt + extra, total);
+                    int off;
+                    if (one) off = (a.S + 1 < 32) ? lane_prefix<5>(cnt + extra, total) : lane_prefix<10>(cnt + extra, total);
+                    else off = (sweep == 0 && a.use_tiers) ? lane_prefix<4>(cnt + extra, total) : lane_prefix<10>(cnt + extra, total);
+                    if (by_cells) {
+                        // (off ascends: the cells that still fit are a run of lanes from lane0 on, and the first of them
+                        // -- at most S + 1 <= kCellsPairs pairs from offset 0 -- always fits)
+                        const unsigned long long mover = __ballot(off + cnt + extra > kCellsPairs);
+                        lane0 = 64;
+                        if (mover) {
+                            lane0 = __ffsll((long long)mover) - 1;
+                            total = __builtin_amdgcn_readlane(off, lane0);
+                            if (lane >= lane0) { cnt = 0; extra = 0; }
+                        }
+                    }
                     for (int si = 0; si < cnt; ++si) pdesc[off + si] = (unsigned short)(lane | (si << 6));
                     if (extra) pdesc[off + cnt] = (unsigned short)(lane | (kCentreNode << 6));
                     wave_sync();
                     // (carried cells: with more of the list to come and every cell's pairs in this one pass, the cells
                     // whose pairs end within the whole trips are processed, the others handed on -- when the last trip's
                     // empty lanes outnumber the cells that then have to wait)
-                    if (kCarry && !(ST && halo) && s0 == 0 && w0 + step < count && total >= 64 && !__any(nodes > per)) {
+                    if (kCarry && !(ST && halo) && s0 == 0 && w0 + step < count && total >= 64 && !__any(nodes > per) &&
+                        (!by_cells || lane0 == 64)) {
                         const int whole = total & ~63;
                         const int l0 = __popcll(__ballot(off + cnt + extra <= whole));      // (a prefix of the lanes: off ascends)
                         if (l0 >= 1 && l0 < 64 && (64 - (total - whole)) > (64 - l0)) {

@@ -346,6 +346,7 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
     a.nbatch = 8 * batch_plan(a.n, a.B).P;          // wave positions of the launch (batch_plan)
     a.debug_bug = knob_debug_bug();
     a.whole_trips = knob_whole_trips();
+    a.one_sweep = knob_one_sweep();
     a.mark_unwritten = (MODE == MODE_LNL && !a.inv_var) ? 1 : 0;     // (a weighted launch may ADD to out[]: never marked)
     bool tiers_ok = false;
     if (tier_device(a.S, a.tiers, &a.tier_xw, &tiers_ok)) return fail(TRX_ERR_HIP, "tier table upload failed%s", "", 0);
@@ -1533,6 +1534,14 @@ int trx_set_row_order(int on)
 int trx_set_whole_trips(int on)
 {
     g_knob_whole_trips = on ? 1 : 0;
+    return TRX_OK;
+}
+
+/* (tests) 0: the one-row likelihood kernels take their contact cells in a second sweep; 2: one sweep in the flux grid too */
+int trx_set_one_sweep(int mode)
+{
+    if (mode < 0 || mode > 2) return fail(TRX_ERR_ARG, "trx_set_one_sweep: mode must be 0, 1 or 2%s (got %ld)", "", (long)mode);
+    g_knob_one_sweep = mode;
     return TRX_OK;
 }
 
