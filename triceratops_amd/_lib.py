@@ -46,6 +46,8 @@ NOISE_SYMBOLS = ("trxn_chi2_grid_ou",)
 MIX_SYMBOLS = ("trxm_chi2_grid_ou_mix",)
 # ... include/trx_shift.h (both libraries: the soft minimum over the nodes of a transit-time shift grid, prefix trxt_)
 SHIFT_SYMBOLS = ("trxt_softmin_rows",)
+# ... include/trx_robust.h (both libraries: the outlier-tolerant row reduction, prefix trxr_)
+ROBUST_SYMBOLS = ("trxr_chi2_grid_robust",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -195,6 +197,9 @@ def _load(path, testing):
                                         _vp]
     L.trxt_softmin_rows.restype = c_int
     L.trxt_softmin_rows.argtypes = [_vp, c_long, c_long, c_int, _vp, c_int, _vp, _vp]
+    L.trxr_chi2_grid_robust.restype = c_int
+    L.trxr_chi2_grid_robust.argtypes = [_vp, _vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, c_double, c_double, c_double,
+                                        _vp]
     L.trx_grid_quantiles.restype = c_int
     L.trx_grid_quantiles.argtypes = [_vp, c_long, c_int, _vp, _vp, c_long, _vp, c_int, _vp, _vp]
     L.trx_lnl_batch_host.restype = c_int
@@ -564,6 +569,16 @@ def chi2_grid_baseline(flux_d, inv_var_d, grid_d, wbasis_d, minv, secdepth_d=Non
                                 and coef_out.is_contiguous())
     return _chi2_rows("trx_chi2_grid_baseline", flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out, wbasis_d.data_ptr(),
                       k, minv.ctypes.data, coef_out.data_ptr() if coef_out is not None else None)
+
+
+def chi2_grid_robust(flux_d, inv_var_d, grid_d, c0, c1, k2, secdepth=None, sec_limit=float("inf"), out=None):
+    """chi2_grid_weighted with every point a two-component mixture -- its stated error, or with probability eps a Gaussian
+    kappa times wider --, the membership integrated out per point (trxr_chi2_grid_robust, include/trx_robust.h): per row
+    sum_t (lo_t - log1p(exp(-|A_t - B_t|))), A_t = a_t + c0, B_t = a_t k2 + c1, lo_t = min(A_t, B_t),
+    a_t = 0.5 inv_var[t] (flux[t] - grid[r][t])^2, clamped at 0 and not halved.  c0, c1, k2: datasets.robust_constants.  The
+    other arguments are chi2_grid_weighted's."""
+    return _chi2_rows("trxr_chi2_grid_robust", flux_d, inv_var_d, grid_d, secdepth, sec_limit, out, float(c0), float(c1),
+                      float(k2))
 
 
 def chi2_grid_ou(flux_d, grid_d, alpha_d, beta_d, omega_d, secdepth=None, sec_limit=float("inf"), out=None):

@@ -205,6 +205,40 @@ def t0_mix_halfchi2(h, lnpi):
     return np.asarray(t, dtype=dtype)
 
 
+def _robust_terms(resid, inv_var, c0, c1, k2):
+    """(A, B) of robust_halfchi2, in resid's dtype"""
+    d = np.asarray(resid)
+    dtype = d.dtype.type if d.dtype.kind == "f" else np.float64
+    d = np.asarray(d, dtype=dtype)
+    w = np.asarray(inv_var, dtype=dtype)
+    a = (dtype(0.5) * (w * d)) * d
+    return a + dtype(c0), a * dtype(k2) + dtype(c1)
+
+
+def robust_halfchi2(resid, inv_var, c0, c1, k2):
+    """A dataset's term of the log-weight under the outlier mixture, on the host: the statement of
+    what trxr_chi2_grid_robust computes per row.  With d = resid [..., T] (flux - model), w = inv_var [T] and the constants
+    of datasets.robust_constants,
+        a_t = 0.5 w_t d_t^2,  A_t = a_t + c0,  B_t = a_t k2 + c1,  lo_t = min(A_t, B_t),
+        h = sum_t (lo_t - log1p(exp(-|A_t - B_t|)))  =  sum_t -ln[(1 - eps) e^(-a_t) + (eps / kappa) e^(-a_t / kappa^2)],
+    stored as 0 where rounding drives the total below; a NaN stays a NaN.  Not halved: the terms are log-weights already.
+    In resid's dtype (np.longdouble: the tests' reference)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        A, B = _robust_terms(resid, inv_var, c0, c1, k2)
+        lo = np.minimum(A, B)
+        h = np.sum(lo - np.log1p(np.exp(-np.abs(A - B))), axis=-1)
+        h = np.where(h < 0, A.dtype.type(0.0), h)                 # (a NaN stays a NaN)
+    return np.asarray(h, dtype=A.dtype)
+
+
+def robust_responsibility(resid, inv_var, c0, c1, k2):
+    """The posterior probability that each point is an outlier under robust_halfchi2's mixture, given the residuals:
+    p_t = 1 / (1 + exp(B_t - A_t)), in resid's shape and dtype."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        A, B = _robust_terms(resid, inv_var, c0, c1, k2)
+        return np.asarray(1.0 / (1.0 + np.exp(B - A)), dtype=A.dtype)
+
+
 def warp_identity():
     """the identity grid: [WARP_DIMS][WARP_BINS + 1] edges b / 64 (the map returns its input, ln J = 0, exactly)"""
     return np.tile(np.arange(WARP_BINS + 1) / WARP_BINS, (WARP_DIMS, 1))

@@ -1,6 +1,6 @@
 // libtrx.so: the host side of the likelihood path and the C ABI (include/trx.h) for gfx950.
 //
-// The kernels live in five headers that only this file includes:
+// The kernels live in six headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
 //                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
@@ -15,6 +15,8 @@
 //                    row; ou_mix_launch here; include/trx_mix.h)
 //   trx_softmin.hpp  softmin_rows_kernel<J> (the soft minimum of J candidate values per row, one lane a row;
 //                    softmin_launch_j here; include/trx_shift.h)
+//   trx_robust.hpp   chi2_robust_kernel<STAGE> (the outlier-tolerant row reduction: a two-component mixture per point, one
+//                    exp and one log1p a value; chi2_robust_launch here; include/trx_robust.h)
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
 // lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
@@ -38,6 +40,7 @@
 #include "../../include/trx_noise.h"
 #include "../../include/trx_mix.h"
 #include "../../include/trx_shift.h"
+#include "../../include/trx_robust.h"
 #include "trx_device.hpp"
 #include "trx_internal.hpp"
 #include "trx_knobs.hpp"
@@ -68,6 +71,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 #include "trx_noise.hpp"
 #include "trx_noise_mix.hpp"
 #include "trx_softmin.hpp"
+#include "trx_robust.hpp"
 #include "trx_bands.hpp"
 
 namespace {
@@ -1050,6 +1054,27 @@ void ou_mix_launch_j(const double* flux, const double* model_grid, int n_time, l
                        accumulate, out, alpha, beta, omega, lnc, cand_out);
 }
 
+// One launch of chi2_robust_kernel<STAGE> (trxr_chi2_grid_robust): STAGE while flux and inv_var fit the LDS budget of
+// chi2_rows_kernel, and chi2_rows_launch's cap of blocks -- 8 of 256 threads a CU, fewer where the staged vectors fill the
+// 160 KB of LDS, on 256 CUs.  The registers decide how many of them are resident at once (six at the 80 VGPRs the kernel
+// takes, four at the 128 its test allows); the others wait their turn, which measured faster than a cap of 4 at 100 stamps
+// (0.48 - 0.49 against 0.54 ms of a 512 MiB grid) and the same at 2048 (0.35 - 0.36 ms).  The rows behind the cap are the second row of a
+// wave's pass and its further passes.
+void chi2_robust_launch(const double* flux, const double* inv_var, const double* model_grid, int n_time, long n,
+                        const double* secdepth, double sec_limit, int accumulate, double* out, const RobustC& c,
+                        hipStream_t st)
+{
+    const bool stage = n_time <= kChi2wStageMax;
+    const size_t lds = stage ? 2 * (size_t)((n_time + 1) & ~1) * sizeof(double) : 0;
+    long per_cu = lds ? (long)((160u * 1024u) / lds) : 8;
+    per_cu = per_cu > 8 ? 8 : per_cu;
+    long blocks = (n + 3) / 4;
+    if (blocks > 256L * per_cu) blocks = 256L * per_cu;
+    const auto kernel = stage ? chi2_robust_kernel<true> : chi2_robust_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, st, flux, inv_var, model_grid, n_time, n, secdepth,
+                       sec_limit, accumulate, out, c);
+}
+
 // One launch of softmin_rows_kernel<J> (trxt_softmin_rows), J = n_cand: one lane per row, and as many blocks as the draw
 // kernel's cap -- 16 of 256 threads a CU, on 256 CUs; the rows behind that cap are a lane's further trips.
 template <int J>
@@ -1208,6 +1233,22 @@ int trxt_softmin_rows(const double* cand, long stride, long n, int n_cand, const
     }
     if (n == 0) return TRX_OK;
     softmin_launch_j<1>(cand, stride, n, n_cand, c, accumulate, out, static_cast<hipStream_t>(stream));
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trxr_chi2_grid_robust(const double* flux, const double* inv_var, const double* model_grid, int n_time, long n,
+                          const double* secdepth, double sec_limit, int accumulate, double* out_halfchi2, double c0,
+                          double c1, double k2, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (!flux || !inv_var || !model_grid || !out_halfchi2) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    if (!(c0 >= 0.0) || c0 == INFINITY) return fail(TRX_ERR_ARG, "c0 must be finite and >= 0%s", "", 0);     // (also NaN)
+    if (!(c1 - c1 == 0.0)) return fail(TRX_ERR_ARG, "c1 must be finite%s", "", 0);                            // (NaN or +-inf)
+    if (!(k2 > 0.0 && k2 < 1.0)) return fail(TRX_ERR_ARG, "k2 must lie in (0, 1)%s", "", 0);
+    if (n == 0) return TRX_OK;
+    chi2_robust_launch(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2,
+                       RobustC{c0, c1, k2}, static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

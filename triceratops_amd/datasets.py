@@ -7,7 +7,9 @@ MAX_BASELINE_TERMS columns B_k[t] of a linear baseline model sum_k c_k B_k[t] wi
 the same way (baseline_system), or `red_sigma` / `red_timescale`: correlated noise of standard deviation s_r with an
 exponential kernel of time scale tau next to the white errors (ou_system), or `red_grid`: up to MAX_RED_CANDIDATES
 weighted candidates (s_r, tau) of that noise, marginalised per draw (ou_mix_system); and next to any of these `t0_grid`: up
-to MAX_T0_NODES weighted shifts of its stamps, marginalised per draw (t0_grids).  This module is host side and numpy only:
+to MAX_T0_NODES weighted shifts of its stamps, marginalised per draw (t0_grids); or, alone or next to `t0_grid`,
+`outlier_frac` / `outlier_scale`: every point is with probability eps an outlier from a Gaussian kappa times wider than its
+error, the membership integrated out per point and per draw (outliers, robust_constants).  This module is host side and numpy only:
 validation, the reference noise sigma_bar and the per-star renormalisation.  A `Datasets` object is what the lnZ_*
 functions receive in place of `time` (with flux = None and sigma = sigma_bar); only the device sampling modes evaluate it
 (fused._Scenario).
@@ -247,6 +249,54 @@ def t0_grids(dicts, sets):
     return [_t0_grid(i, d.get("t0_grid")) for i, d in enumerate(dicts)]
 
 
+OUTLIER_KEYS = ("outlier_frac", "outlier_scale")
+
+
+def _outliers(i, d, dataset):
+    """a dataset's "outlier_frac" and "outlier_scale" -> (frac, scale) as Python floats, or None; dataset: the validated
+    Dataset of the same dict (what else it marginalises)"""
+    frac, scale = d.get("outlier_frac"), d.get("outlier_scale")
+    if frac is None and scale is None:
+        return None
+    if frac is None or scale is None:
+        raise ValueError("dataset %d: outlier_frac and outlier_scale are given together or not at all" % i)
+    for name, value in (("outlier_frac", frac), ("outlier_scale", scale)):
+        if isinstance(value, (bool, np.bool_, str, bytes)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise ValueError("dataset %d: %s must be a number (got %r)" % (i, name, value))
+    frac, scale = float(frac), float(scale)
+    if not 0.0 < frac <= 0.5:                                     # (also NaN)
+        raise ValueError("dataset %d: outlier_frac must lie in (0, 0.5] (got %r)" % (i, frac))
+    if not (scale > 1.0 and math.isfinite(scale)):                # (also NaN)
+        raise ValueError("dataset %d: outlier_scale must be a finite number > 1 (got %r)" % (i, scale))
+    if (dataset.offset_sigma is not None or dataset.baseline is not None or dataset.red_sigma is not None
+            or dataset.red_grid is not None):
+        raise ValueError("dataset %d: outlier_frac / outlier_scale together with offset_sigma, baseline, red_sigma / "
+                         "red_timescale or red_grid is not built: the mixture has no closed form next to a marginalised "
+                         "linear term or a correlated residual" % i)
+    return frac, scale
+
+
+def outliers(dicts, sets):
+    """The "outlier_frac" / "outlier_scale" keys of the dicts that validate() turned into `sets`: per dataset None, or the
+    tuple (frac, scale) of Python floats -- both keys or neither; 0 < frac <= 0.5: the prior probability eps that a point is
+    an outlier; scale finite and > 1: the factor kappa by which an outlier's Gaussian is wider than the point's flux_err.
+    The dataset's term of the log-weight, 0.5 sum_t w_t d_t^2, becomes sum_t -ln[(1 - eps) e^(-a_t) + (eps / kappa)
+    e^(-a_t / kappa^2)], a_t = 0.5 w_t d_t^2 (_numerics.robust_halfchi2 on robust_constants).  The keys stand alone or next to
+    t0_grid; next to offset_sigma, baseline, red_sigma / red_timescale or red_grid they are a ValueError, as is a bool, a
+    string, an array, a NaN or an inf.  Dataset itself has no field for the keys: the pairs travel in Datasets.outliers."""
+    if len(dicts) != len(sets):
+        raise ValueError("outliers: %d dicts for %d datasets" % (len(dicts), len(sets)))
+    return [_outliers(i, d, s) for i, (d, s) in enumerate(zip(dicts, sets))]
+
+
+def robust_constants(frac, scale):
+    """(c0, c1, k2) of a dataset's outlier mixture: c0 = -log1p(-eps) >= 0, c1 = ln kappa - ln eps > 0, k2 = 1 / kappa^2 --
+    the one place that forms them, for the device path (fused._Dataset) and for the numpy statement
+    (_numerics.robust_halfchi2).  Pure numbers: the same in every star's normalisation."""
+    frac, scale = float(frac), float(scale)
+    return -math.log1p(-frac), math.log(scale) - math.log(frac), 1.0 / (scale * scale)
+
+
 def ou_system(dataset):
     """(alpha, beta, omega), float64 [T] each: the Kalman form of a Dataset's noise covariance
     K = diag(flux_err^2) + red_sigma^2 exp(-|t_i - t_j| / red_timescale), stamps in time order -- the one place that forms
@@ -316,8 +366,9 @@ def _check_baseline(i, dataset):
 
 def validate(datasets):
     """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
-    baseline_sigma, red_sigma, red_timescale, red_grid, t0_grid]} -> a list of Dataset ("t0_grid" is allowed here and read by
-    t0_grids: no field of Dataset holds it).  Points with a NaN time or flux are dropped together with their error and their
+    baseline_sigma, red_sigma, red_timescale, red_grid, t0_grid, outlier_frac, outlier_scale]} -> a list of Dataset ("t0_grid"
+    is allowed here and read by t0_grids, "outlier_frac" / "outlier_scale" are checked here and returned by outliers: no field
+    of Dataset holds them).  Points with a NaN time or flux are dropped together with their error and their
     baseline entries; a scalar flux_err is broadcast.  ValueError for an empty list, too many datasets, mismatched
     lengths, an error that is not finite or not positive, a dataset without points, an offset_sigma that is not None, a
     number > 0 or inf, a baseline that is not [K][len(time)] and finite at the kept points, a baseline_sigma that is not
@@ -326,7 +377,9 @@ def validate(datasets):
     inf, either of them next to offset_sigma or baseline, or with kept stamps that are not in non-decreasing order; for a
     red_grid that is not 1 ... MAX_RED_CANDIDATES triples (s_r finite > 0, tau > 0 or inf, weight finite > 0; the weights are
     normalised to sum 1, repeated pairs are allowed), that stands next to red_sigma / red_timescale, offset_sigma or
-    baseline, or whose kept stamps are not in non-decreasing order."""
+    baseline, or whose kept stamps are not in non-decreasing order; for outlier_frac without outlier_scale or the reverse, an
+    outlier_frac outside (0, 0.5], an outlier_scale that is not a finite number > 1, or either of them next to
+    offset_sigma, baseline, red_sigma / red_timescale or red_grid."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -336,7 +389,7 @@ def validate(datasets):
     out = []
     for i, d in enumerate(datasets):
         unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma",
-                            "red_sigma", "red_timescale", "red_grid", "t0_grid"}
+                            "red_sigma", "red_timescale", "red_grid", "t0_grid", "outlier_frac", "outlier_scale"}
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -373,6 +426,7 @@ def validate(datasets):
                            float(d.get("exptime", DEFAULT_EXPTIME)), nsamples,
                            offset_sigma, baseline, baseline_sigma, red_grid, red_sigma, red_timescale))
         _check_baseline(i, out[-1])
+        _outliers(i, d, out[-1])
     return out
 
 
@@ -395,14 +449,17 @@ def sigma_bar(errs):
 
 class Datasets:
     """validated datasets in one star's normalisation, their sigma_bar, and per dataset None or its transit-time shift
-    grid (t0_grids)"""
+    grid (t0_grids) and None or its outlier pair (frac, scale) (outliers)"""
 
-    def __init__(self, sets, t0_grids=None):
+    def __init__(self, sets, t0_grids=None, outliers=None):
         self.sets = tuple(sets)
         self.sigma_ref = sigma_ref(self.sets)
         self.t0_grids = (None,) * len(self.sets) if t0_grids is None else tuple(t0_grids)
         if len(self.t0_grids) != len(self.sets):
             raise ValueError("t0_grids: %d grids for %d datasets" % (len(self.t0_grids), len(self.sets)))
+        self.outliers = (None,) * len(self.sets) if outliers is None else tuple(outliers)
+        if len(self.outliers) != len(self.sets):
+            raise ValueError("outliers: %d pairs for %d datasets" % (len(self.outliers), len(self.sets)))
 
     def __len__(self):
         return len(self.sets)
@@ -424,6 +481,10 @@ class Datasets:
         return any(g is not None for g in self.t0_grids)
 
     @property
+    def has_outliers(self):
+        return any(o is not None for o in self.outliers)
+
+    @property
     def size(self):
         """points of all datasets together"""
         return sum(s.time.size for s in self.sets)
@@ -437,7 +498,8 @@ class Datasets:
         the same way: alpha and beta of ou_system do not change, omega scales with the square of the flux ratio, and the
         determinant ratio that the evidence drops is the same for every star.  The s_r column of a red_grid is divided
         likewise: every candidate's determinant gains the same factor, so the lnc of ou_mix_system do not change.  The t0_grids are times and
-        pure weights: carried through as they are."""
+        pure weights: carried through as they are.  So are the outlier pairs: only z_t = d_t / sigma_t enters the mixture,
+        and renorm_flux leaves it alone."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
@@ -456,4 +518,4 @@ class Datasets:
                 grid[:, 0] = grid[:, 0] / star_fluxratio
             out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err), offset_sigma=off,
                                   baseline_sigma=bsig, red_sigma=red, red_grid=grid))
-        return Datasets(out, self.t0_grids)
+        return Datasets(out, self.t0_grids, self.outliers)

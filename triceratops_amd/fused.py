@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, funcs
-from .datasets import Datasets, baseline_system, ou_mix_system, ou_system
+from .datasets import Datasets, baseline_system, ou_mix_system, ou_system, robust_constants
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
@@ -240,6 +240,11 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # the nodes' terms into one (grid evaluation only).  DATASET_T0 = {}: every such call leaves {work unit: [per branch, a list
 # per dataset: None or the [J] posterior weights of the nodes at the branch's best draw, softmax_j(ln pi_j - h_j)]} there
 # (target.dataset_t0); the offsets, baselines and red-noise weights of such a dataset are those of its heaviest node.
+# A dataset with `outlier_frac` / `outlier_scale` (Datasets.outliers) has every point's membership in a kappa times wider
+# outlier component integrated out per draw: its reduction is trxr_chi2_grid_robust on the constants of
+# datasets.robust_constants (grid evaluation only).  DATASET_OUTLIERS = {}: every such call leaves {work unit: [per branch, a
+# list per dataset: None or the [T] posterior outlier probabilities of the points at the branch's best draw
+# (_numerics.robust_responsibility; with a t0_grid on its heaviest node)]} there (target.dataset_outliers).
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
@@ -247,6 +252,7 @@ DATASET_OFFSETS = None
 DATASET_BASELINES = None
 DATASET_RED_NOISE = None
 DATASET_T0 = None
+DATASET_OUTLIERS = None
 # An importance map (WARP_GRIDS) applies to a datasets call as to any other: its draws are trx_draw_scenario's.  The weight
 # histogram of the library's own chain (WARP_HIST) does not exist here -- chi^2/2 is computed outside that chain -- so
 # DATASET_WARP_HIST = {}: every datasets call leaves {work unit: [branches][WARP_BRANCH] uint64 words} there, one
@@ -257,7 +263,7 @@ DATASET_WARP_HIST = None
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_OUTLIERS, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -799,7 +805,8 @@ class _Baseline(NamedTuple):
 class _Dataset(NamedTuple):
     """one light curve of a Datasets call on the device, and what its reduction marginalises: nothing, a constant offset,
     or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then --, or correlated
-    noise; and, next to any of these, the nodes of a transit-time shift (`shift`: the reduction then runs once per node)"""
+    noise, or the outlier mixture of its points; and, next to any of these, the nodes of a transit-time shift (`shift`: the
+    reduction then runs once per node)"""
     time: torch.Tensor
     flux: torch.Tensor
     inv_var: torch.Tensor
@@ -810,11 +817,15 @@ class _Dataset(NamedTuple):
     ou: Optional[tuple] = None               # (alpha, beta, omega) on the device: correlated noise (datasets.ou_system)
     mix: Optional[tuple] = None              # (alpha, beta, omega [J][T] on the device, lnc [J] on the host): ou_mix_system
     shift: Optional[tuple] = None            # (J device tensors time + shift_j, ln pi [J] on the host, ln pi on the device)
+    robust: Optional[tuple] = None           # (c0, c1, k2): the outlier mixture of the points (datasets.robust_constants)
 
     @classmethod
-    def upload(cls, d, dev, t0_grid=None):
+    def upload(cls, d, dev, t0_grid=None, outliers=None):
         inv_var = 1.0 / (d.flux_err * d.flux_err)
         rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
+        if outliers is not None:
+            # (validate refuses anything but a t0_grid next to it)
+            rec = rec._replace(robust=robust_constants(*outliers))
         if t0_grid is not None:
             # (next to whatever else the dataset marginalises: a shift leaves all of that as it is)
             rec = rec._replace(shift=_shift_on_device(d, t0_grid, dev))
@@ -840,7 +851,9 @@ class _Dataset(NamedTuple):
         secdepth >= sec_limit.  The one place that picks the reduction: trx_chi2_grid_baseline for baseline columns (coef_out:
         the rows' scaled coefficients), trx_chi2_grid_offset for an offset alone (offset_out: the rows' offsets),
         trxn_chi2_grid_ou for correlated noise, trxm_chi2_grid_ou_mix for a grid of its candidates (cand_out: the rows'
-        per-candidate chi^2/2), else trx_chi2_grid_weighted."""
+        per-candidate chi^2/2), trxr_chi2_grid_robust for the outlier mixture, else trx_chi2_grid_weighted."""
+        if self.robust is not None:
+            return _lib.chi2_grid_robust(self.flux, self.inv_var, grid, *self.robust, secdepth, sec_limit, out=out)
         if self.mix is not None:
             return _lib.chi2_grid_ou_mix(self.flux, grid, *self.mix, secdepth, sec_limit, out=out, cand_out=cand_out)
         if self.ou is not None:
@@ -863,7 +876,7 @@ class _Scenario:
         self.datasets = None
         if isinstance(time, Datasets):
             # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
-            self.datasets = [_Dataset.upload(d, self.dev, g) for d, g in zip(time.sets, time.t0_grids)]
+            self.datasets = [_Dataset.upload(d, self.dev, g, o) for d, g, o in zip(time.sets, time.t0_grids, time.outliers)]
             sigma = time.sigma_ref
             self.time, self.flux = self.datasets[0].time, self.datasets[0].flux
         else:
@@ -1123,6 +1136,7 @@ class _Scenario:
         coefs = []         # (DATASET_BASELINES: per branch and dataset the best draw's scaled coefficients, likewise)
         cands = []         # (DATASET_RED_NOISE: per branch and dataset the best draw's per-candidate chi^2/2, likewise)
         nodes = []         # (DATASET_T0: per branch and dataset the best draw's per-node terms, likewise)
+        probs = []         # (DATASET_OUTLIERS: per branch and dataset the best draw's model row, likewise)
         hists = None       # (DATASET_WARP_HIST: per branch the weight histogram of its evidence, likewise)
         if self.datasets is not None and DATASET_WARP_HIST is not None:
             if not self.philox:
@@ -1153,12 +1167,15 @@ class _Scenario:
                 _lib.moments_emit(mom[1], mom[2])
             best = self._best(h, idx, n)
             if self.datasets is not None and ((DATASET_OFFSETS is not None and any(d.offset is not None for d in self.datasets))
-                                              or self._any_baseline() or self._any_mix() or self._any_shift()):
-                o, c, hc, hn = self._best_offsets(model, flags, cols, best, twin, nblk) if n else (None, None, None, None)
+                                              or self._any_baseline() or self._any_mix() or self._any_shift()
+                                              or self._any_robust()):
+                o, c, hc, hn, mr = (self._best_offsets(model, flags, cols, best, twin, nblk) if n
+                                    else (None, None, None, None, None))
                 offsets.append(o)
                 coefs.append(c)
                 cands.append(hc)
                 nodes.append(hn)
+                probs.append(mr)
             post = None
             if POSTERIOR_ROWS:
                 # the same selection on this chain's chi^2/2 values (trx_posterior_from_halfchi2; the twin branch draws
@@ -1182,7 +1199,7 @@ class _Scenario:
             if POSTERIOR_ROWS:
                 res[-1]["posterior"] = None if post is None else self._posterior_dict(post.cpu().numpy(), ncol, twin)
         if offsets:
-            self._leave_best_terms(offsets, coefs, cands, nodes)
+            self._leave_best_terms(offsets, coefs, cands, nodes, probs)
         if hists is not None:
             DATASET_WARP_HIST[getattr(_tls, "unit", None)] = torch.stack(hists).cpu().numpy().view(np.uint64)
         return res[0] if a.planet else (res[0], res[1])
@@ -1200,13 +1217,34 @@ class _Scenario:
         """whether a t0_grid dataset's node weights are wanted back (DATASET_T0)"""
         return DATASET_T0 is not None and any(d.shift is not None for d in self.datasets)
 
-    def _leave_best_terms(self, offsets, coefs, cands, nodes):
+    def _any_robust(self):
+        """whether a robust dataset's outlier probabilities are wanted back (DATASET_OUTLIERS)"""
+        return DATASET_OUTLIERS is not None and any(d.robust is not None for d in self.datasets)
+
+    def _leave_best_terms(self, offsets, coefs, cands, nodes, probs):
         """the branches' best-draw offsets and baseline coefficients, from the device to DATASET_OFFSETS / DATASET_BASELINES
         under this thread's work unit, in the call's normalisation: c_k = c~_k / sqrt(D_k); and the posterior weights of a
         red_grid dataset's candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_RED_NOISE (NaN without a draw); and
-        those of a t0_grid dataset's nodes, softmax_j(ln pi_j - h_j), to DATASET_T0 (likewise)"""
+        those of a t0_grid dataset's nodes, softmax_j(ln pi_j - h_j), to DATASET_T0 (likewise); and the posterior outlier
+        probabilities of a robust dataset's points at that draw, _numerics.robust_responsibility on the draw's model row, to
+        DATASET_OUTLIERS (likewise)"""
         L = len(self.datasets)
         unit = getattr(_tls, "unit", None)
+        if DATASET_OUTLIERS is not None:
+            from ._numerics import robust_responsibility
+            out = []
+            for mr in probs:
+                per = [None] * L
+                for l, d in enumerate(self.datasets):
+                    if d.robust is None:
+                        continue
+                    if mr is None:
+                        per[l] = np.full(int(d.flux.numel()), np.nan)
+                        continue
+                    resid = d.flux.cpu().numpy() - mr[l].cpu().numpy().reshape(-1)
+                    per[l] = robust_responsibility(resid, d.inv_var.cpu().numpy(), *d.robust)
+                out.append(per)
+            DATASET_OUTLIERS[unit] = out
         if DATASET_T0 is not None:
             t0 = []
             for hn in nodes:
@@ -1259,18 +1297,20 @@ class _Scenario:
             DATASET_BASELINES[unit] = base
 
     def _best_offsets(self, model, flags, cols, best, twin, nblk):
-        """([L] device tensor and three lists per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
+        """([L] device tensor and four lists per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
         S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
         baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them); and None or the
         [1][J] device tensor of a red_grid dataset's per-candidate chi^2/2.  The one row is evaluated again -- trx_flux_grid
         on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out, coef_out or cand_out -- so nothing of
         size n x L is kept.  A t0_grid dataset has the row evaluated on every node: the fourth list holds None or the [J]
         device tensor of its per-node terms h_j, and its offset, coefficients and candidates are those of the node of
-        largest ln pi_j - h_j (on a tie the first), picked on the device."""
+        largest ln pi_j - h_j (on a tie the first), picked on the device.  The fifth list holds None or, for a robust
+        dataset under DATASET_OUTLIERS, the [1][T] device tensor of the draw's model row (on that node)."""
         out = torch.full((len(self.datasets),), float("nan"), dtype=F64, device=self.dev)
         coefs = [None] * len(self.datasets)
         cands = [None] * len(self.datasets)
         nodes = [None] * len(self.datasets)
+        rows = [None] * len(self.datasets)
         row = cols[:nblk].index_select(1, best[:1]).contiguous()
         if twin:
             row[2] *= 2.0
@@ -1278,8 +1318,10 @@ class _Scenario:
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL
         for l, d in enumerate(self.datasets):
             if (d.offset is None and d.baseline is None and (d.mix is None or DATASET_RED_NOISE is None)
-                    and (d.shift is None or DATASET_T0 is None)):
+                    and (d.shift is None or DATASET_T0 is None) and (d.robust is None or DATASET_OUTLIERS is None)):
                 continue
+            keep = d.robust is not None and DATASET_OUTLIERS is not None
+            grids = []
             stamps = [d.time] if d.shift is None else d.shift[0]
             J = len(stamps)
             off = out[l:l + 1] if d.shift is None else torch.full((J,), float("nan"), dtype=F64, device=self.dev)
@@ -1290,6 +1332,8 @@ class _Scenario:
             hs = []
             for j, t in enumerate(stamps):
                 grid, _ = _lib.flux_grid(model, flags, t, row, d.exptime, d.nsamples, want_secdepth=False)
+                if keep:
+                    grids.append(grid)
                 hs.append(d.halfchi2(grid, offset_out=off[j:j + 1], coef_out=None if coefs[l] is None else coefs[l][j:j + 1],
                                      cand_out=None if cands[l] is None else cands[l][j:j + 1]))
             if d.shift is not None:
@@ -1298,7 +1342,11 @@ class _Scenario:
                 out[l:l + 1] = off.index_select(0, top)
                 coefs[l] = None if coefs[l] is None else coefs[l].index_select(0, top)
                 cands[l] = None if cands[l] is None else cands[l].index_select(0, top)
-        return out, coefs, cands, nodes
+                if keep:
+                    rows[l] = torch.cat(grids).index_select(0, top)
+            elif keep:
+                rows[l] = grids[0]
+        return out, coefs, cands, nodes, rows
 
     def _datasets_halfchi2(self, model, flags, block):
         """sum over the datasets of the weighted chi^2/2 of every row of `block` ([n_param][n], the masked draws of one
@@ -1328,6 +1376,9 @@ class _Scenario:
         if DATASET_EVALUATION == "fused" and any(d.shift is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a t0_grid dataset is not built: the nodes' terms are folded "
                                       "from the grid reductions; use evaluation='grid'")
+        if DATASET_EVALUATION == "fused" and any(d.robust is not None for d in self.datasets):
+            raise NotImplementedError("evaluation='fused' with an outlier_frac dataset is not built: the fused kernel "
+                                      "carries no exp and log1p per point; use evaluation='grid'")
         n = int(block.shape[1])
         h = torch.zeros(n, dtype=F64, device=self.dev)         # (0 + x = x: every reduction accumulates)
         if n == 0:

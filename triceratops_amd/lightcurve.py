@@ -125,7 +125,7 @@ def t0_shift_grid(sigma, n: int = 5, span: float = 3.0):
 def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int = 50,
                     exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None,
                     baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None,
-                    red_grid=None, t0_grid=None):
+                    red_grid=None, t0_grid=None, outlier_frac: float = None, outlier_scale: float = None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
     {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
     empty bins are dropped.
@@ -136,6 +136,8 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     when given.  red_grid (red_noise_grid's result, or any list of (s_r, tau, weight)): candidates of that noise to
     marginalise, passed through as the key "red_grid" when given.  t0_grid (t0_shift_grid's result, or any list of (shift,
     weight)): nodes of a transit-time shift to marginalise, passed through as the key "t0_grid" when given.
+    outlier_frac, outlier_scale (both or neither): the outlier-tolerant likelihood of the dataset's points, passed through
+    as the keys of those names when given.
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -158,4 +160,6 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
         out["red_grid"] = red_grid
     if t0_grid is not None:
         out["t0_grid"] = t0_grid
+    if outlier_frac is not None or outlier_scale is not None:
+        out["outlier_frac"], out["outlier_scale"] = outlier_frac, outlier_scale
     return out

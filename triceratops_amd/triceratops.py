@@ -27,7 +27,7 @@ from scipy.special import ndtr
 from . import _lib
 from ._numerics import _mc_errors, _normalize_probabilities
 from .constants import G, Msun, pi
-from .datasets import Datasets, t0_grids as _t0_grids, validate as _validate_datasets
+from .datasets import Datasets, outliers as _outliers, t0_grids as _t0_grids, validate as _validate_datasets
 from .funcs import renorm_flux
 from .marginal_likelihoods import *  # noqa: F401,F403  (reference re-exports the lnZ_* names)
 from .marginal_likelihoods import (lnZ_BEB, lnZ_BTP, lnZ_DEB, lnZ_DTP, lnZ_PEB, lnZ_PTP, lnZ_SEB,
@@ -259,7 +259,7 @@ class target:
             if k in calc_probs_kwargs:
                 raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
         sets = _validate_datasets(datasets)
-        ds = Datasets(sets, _t0_grids(datasets, sets))
+        ds = Datasets(sets, _t0_grids(datasets, sets), _outliers(datasets, sets))
         n_samples = int(n_samples)
         if not 0 <= n_samples <= fused.POST_MAX_ROWS:
             raise ValueError("n_samples must lie in [0, %d]" % fused.POST_MAX_ROWS)
@@ -273,7 +273,7 @@ class target:
 
     def _datasets_pass(self, ds, P_orb, kw, verbose, evaluation, n_samples=0, **dataset_switches):
         """one pass of the datasets path over the target's work units: (units, rows, n_scen) for _finish.
-        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_WARP_HIST for
+        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_OUTLIERS / DATASET_WARP_HIST for
         the length of the pass."""
         from . import fused
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
@@ -286,6 +286,8 @@ class target:
                                       "evaluation='grid'")
         if ds.has_t0_grids and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a t0_grid dataset is not built: use evaluation='grid'")
+        if ds.has_outliers and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with an outlier_frac dataset is not built: use evaluation='grid'")
         with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, **dataset_switches):
             rows = sharding.run_units(units, verbose=verbose, as_rows=True)
         return units, rows, n_scen
@@ -378,15 +380,34 @@ class target:
         softmax_j(ln weight_j - h_j) (NaN without a finite lnZ), "mean": sum_j weight_j shift_j}; the whole attribute is
         None when no dataset has the key.  `.dataset_offsets`, `.dataset_baselines` and `.dataset_red_noise` of such a
         dataset are those of its node of largest weight (the first of equal ones).  Not built: a shift shared between
-        datasets, a continuous fit of the shift, per-draw shift posteriors."""
+        datasets, a continuous fit of the shift, per-draw shift posteriors.
+
+        Where single points of a dataset may be off by far more than their errors -- a passing cloud, a cosmic ray --, the
+        dataset may carry "outlier_frac": eps, 0 < eps <= 0.5, and "outlier_scale": kappa, finite and > 1 -- both or
+        neither: every point is then, with prior probability eps, an outlier from a Gaussian kappa times wider than its
+        flux_err, and its membership is integrated out per point and per draw.  With a_t = 0.5 (flux_t - model_t)^2 /
+        sigma_t^2 the dataset's term of the log-weight is sum_t -ln[(1 - eps) exp(-a_t) + (eps / kappa) exp(-a_t / kappa^2)]
+        in place of sum_t a_t (_numerics.robust_halfchi2, trxr_chi2_grid_robust): an 8 sigma point costs about
+        ln(kappa / eps) + 32 / kappa^2 instead of 32.  Only the common factor prod_t (sigma_t sqrt(2 pi))^-1 is dropped, as it
+        is without the keys; only (flux_t - model_t) / sigma_t enters, so the term is the same in every star's
+        normalisation.  sigma_bar and the secondary-eclipse rule use flux_err as given.  The keys stand next to "t0_grid"
+        but not next to offset_sigma, baseline, red_sigma / red_timescale or red_grid on the same dataset (ValueError).
+        Grid evaluation only.  `.dataset_outliers` is then a list per scenario of a list per dataset: None for a dataset
+        without the keys, else {"frac", "scale", "prob": the [len(kept points)] posterior probabilities
+        1 / (1 + (1 - eps) kappa / eps exp(-a_t (1 - 1 / kappa^2))) that each point is an outlier at the scenario's best draw
+        (NaN without a finite lnZ; with a t0_grid on its node of largest weight)}; the whole attribute is None when no
+        dataset has the keys.  Not built: the keys next to offset, baseline or red noise, a Student-t form, a fit of eps,
+        per-draw outlier probabilities, the scalar calc_probs path."""
         ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
         best_offsets = {} if ds.has_offsets else None
         best_baselines = {} if ds.has_baselines else None
         best_red = {} if any(s.red_grid is not None for s in ds.sets) else None
         best_t0 = {} if ds.has_t0_grids else None
+        best_outliers = {} if ds.has_outliers else None
         units, rows, n_scen = self._datasets_pass(ds, P_orb, kw, verbose, evaluation, n_samples,
                                                   DATASET_OFFSETS=best_offsets, DATASET_BASELINES=best_baselines,
-                                                  DATASET_RED_NOISE=best_red, DATASET_T0=best_t0)
+                                                  DATASET_RED_NOISE=best_red, DATASET_T0=best_t0,
+                                                  DATASET_OUTLIERS=best_outliers)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
@@ -436,6 +457,19 @@ class target:
                     if np.isfinite(self.lnZ[u.first_row + i]):
                         rows_[u.first_row + i] = [node(g, w) for g, w in zip(ds.t0_grids, per)]
             self.dataset_t0 = rows_
+        self.dataset_outliers = None
+        if best_outliers is not None:
+            # (only (flux - model) / sigma enters: the same in every star's normalisation)
+            def points(s, o, p=None):
+                if o is None:
+                    return None
+                return {"frac": o[0], "scale": o[1], "prob": np.full(s.time.size, np.nan) if p is None else p}
+            rows_ = [[points(s, o) for s, o in zip(ds.sets, ds.outliers)] for _ in range(n_scen)]
+            for k, u in enumerate(sharding.as_units(units)):
+                for i, per in enumerate(best_outliers.get(k, ())):
+                    if np.isfinite(self.lnZ[u.first_row + i]):
+                        rows_[u.first_row + i] = [points(s, o, p) for s, o, p in zip(ds.sets, ds.outliers, per)]
+            self.dataset_outliers = rows_
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
@@ -534,7 +568,7 @@ class target:
         uniforms from the chi^2/2 values of that pass (trxw_hist_from_halfchi2, fused.DATASET_WARP_HIST) and refine
         the map; best-draw offsets and baselines are not computed in them.  The final pass is calc_probs_datasets under
         the maps the adaptation left: it fills `.probs`, `.FPP`, `.lnZ_err`, `.posterior` (n_samples > 0), `.sigma_ref`,
-        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise` and `.dataset_t0` as calc_probs_datasets does, and only it enters the result, so the
+        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise`, `.dataset_t0` and `.dataset_outliers` as calc_probs_datasets does, and only it enters the result, so the
         estimate is unbiased.  `.refine_history` holds, per pass, the rows' lnZ, ess and w_max_frac.  n_adapt = 0 is
         calc_probs_datasets, bit for bit.  Both evaluations ("grid", "fused") feed the histogram the same way.
 
