@@ -48,6 +48,8 @@ MIX_SYMBOLS = ("trxm_chi2_grid_ou_mix",)
 SHIFT_SYMBOLS = ("trxt_softmin_rows",)
 # ... include/trx_robust.h (both libraries: the outlier-tolerant row reduction, prefix trxr_)
 ROBUST_SYMBOLS = ("trxr_chi2_grid_robust",)
+# ... include/trx_gls.h (both libraries: a linear baseline marginalised under correlated noise, prefix trxg_)
+GLS_SYMBOLS = ("trxg_chi2_grid_ou_baseline",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -200,6 +202,9 @@ def _load(path, testing):
     L.trxr_chi2_grid_robust.restype = c_int
     L.trxr_chi2_grid_robust.argtypes = [_vp, _vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, c_double, c_double, c_double,
                                         _vp]
+    L.trxg_chi2_grid_ou_baseline.restype = c_int
+    L.trxg_chi2_grid_ou_baseline.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, _vp, c_int,
+                                             _vp, _vp, _vp]
     L.trx_grid_quantiles.restype = c_int
     L.trx_grid_quantiles.argtypes = [_vp, c_long, c_int, _vp, _vp, c_long, _vp, c_int, _vp, _vp]
     L.trx_lnl_batch_host.restype = c_int
@@ -603,6 +608,41 @@ def chi2_grid_ou(flux_d, grid_d, alpha_d, beta_d, omega_d, secdepth=None, sec_li
                                       secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
                                       int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
                                       omega_d.data_ptr(), _stream(grid_d)))
+    return out
+
+
+def chi2_grid_ou_baseline(flux_d, grid_d, alpha_d, beta_d, omega_d, cols_d, minv, secdepth=None, sec_limit=float("inf"),
+                          out=None, coef_out=None):
+    """chi2_grid_ou with a linear baseline sum_k c_k B_k[t] of the light curve marginalised per row under the same noise
+    (trxg_chi2_grid_ou_baseline, include/trx_gls.h): 0.5 * max(S2 - sum_ij M_ij b_i b_j, 0), S2 what chi2_grid_ou sums and
+    b_k = sum_n cols[k][n] z_n over the same innovations z.  cols_d: [K][n_time] fp64 device tensor, the whitened scaled
+    columns; minv: the K (K + 1) / 2 entries of the upper triangle of M by rows, on the host (datasets.ou_baseline_system);
+    K = 1 .. 4.  coef_out: an [n][K] fp64 device tensor that receives the scaled posterior-mean coefficients M b, or None.
+    The other arguments are chi2_grid_ou's."""
+    require_gpu()
+    n, nt = grid_d.shape
+    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    for v in (flux_d, alpha_d, beta_d, omega_d):
+        assert v.numel() == nt and v.dtype == torch.float64 and v.is_contiguous()
+    assert cols_d.dim() == 2 and cols_d.shape[1] == nt and cols_d.dtype == torch.float64 and cols_d.is_contiguous()
+    k = int(cols_d.shape[0])
+    assert 1 <= k <= 4, "1 .. 4 columns (got %d)" % k
+    minv = np.ascontiguousarray(minv, dtype=np.float64).reshape(-1)
+    assert minv.size == k * (k + 1) // 2, "minv: the packed upper triangle of a %d x %d matrix" % (k, k)
+    assert secdepth is None or (secdepth.numel() == n and secdepth.is_contiguous())
+    assert coef_out is None or (coef_out.shape == (n, k) and coef_out.dtype == torch.float64 and coef_out.is_contiguous())
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
+    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
+    if n == 0:
+        return out                     # (an empty tensor has no address to pass)
+    with torch.cuda.device(grid_d.device):
+        check(lib().trxg_chi2_grid_ou_baseline(flux_d.data_ptr(), grid_d.data_ptr(), nt, n,
+                                               secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
+                                               int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
+                                               omega_d.data_ptr(), cols_d.data_ptr(), k, minv.ctypes.data,
+                                               coef_out.data_ptr() if coef_out is not None else None, _stream(grid_d)))
     return out
 
 

@@ -158,6 +158,50 @@ def ou_halfchi2(y, alpha, beta, omega, dtype=np.float64):
     return h * dtype(0.5)
 
 
+def ou_innovations(x, alpha, beta, dtype=np.float64):
+    """The innovations of x [..., T] under the Kalman recurrence of datasets.ou_system: z_n = x_n - g_n, g_0 = 0,
+    g_n = alpha_n g_(n-1) + beta_n x_(n-1) -- what ou_halfchi2 squares, and what whitens a baseline column as it whitens
+    the residuals: x^T K^-1 x' = sum_n omega_n z[x]_n z[x']_n.  In `dtype`, the operations of ou_halfchi2 in its order."""
+    x = np.asarray(x, dtype=dtype)
+    alpha, beta = np.asarray(alpha, dtype=dtype), np.asarray(beta, dtype=dtype)
+    z = np.empty(x.shape, dtype=dtype)
+    g = np.zeros(x.shape[:-1], dtype=dtype)
+    for n in range(x.shape[-1]):
+        if n > 0:
+            g = alpha[n] * g + beta[n] * x[..., n - 1]
+        z[..., n] = x[..., n] - g
+    return z
+
+
+def ou_baseline_halfchi2(y, system, dtype=np.float64, return_coef=False):
+    """chi^2/2 of a light curve's residuals with a linear baseline sum_k c_k B_k[t], c_k ~ N(0, s_k^2) independent,
+    marginalised under white plus exponential noise K, on the host: the statement of what
+    trxg_chi2_grid_ou_baseline computes per row,
+        h = 0.5 [y^T K^-1 y - b^T A^-1 b],   b = B^T K^-1 y,   A = B^T K^-1 B + diag(1 / s_k^2),
+    (for finite priors 0.5 y^T (K + B diag(s^2) B^T)^-1 y) in the innovations z = ou_innovations(y) and the scaled form of
+    `system` (datasets.ou_baseline_system: omega, c, M):
+        S2 = sum_n omega_n z_n^2,   b~_k = sum_n c_k[n] z_n,   h = 0.5 max(S2 - b~^T M b~, 0).
+    The factors det K and det(I + diag(s^2) B^T K^-1 B) depend on the dataset alone and are dropped.  y: [..., T]
+    residuals; in `dtype` (np.longdouble: the tests' reference).  S2 is summed as ou_halfchi2 sums it: M = 0 gives its
+    bits.  return_coef: (h, coef~ [..., K]), coef~ = M b~ the scaled posterior-mean coefficients, c_k = coef~_k / sqrt(D_k)."""
+    z = ou_innovations(y, system.alpha, system.beta, dtype)
+    omega = np.asarray(system.omega, dtype=dtype)
+    c = np.asarray(system.c, dtype=dtype)
+    M = np.asarray(system.M, dtype=dtype)
+    S2 = np.zeros(z.shape[:-1], dtype=dtype)
+    for n in range(z.shape[-1]):                                  # (ou_halfchi2's order: its bits at M = 0)
+        zn = z[..., n]
+        S2 = S2 + omega[n] * zn * zn
+    b = z @ c.T
+    coef = b @ M                                                  # (M is symmetric)
+    q = np.sum(b * coef, axis=-1)
+    with np.errstate(invalid="ignore"):
+        tot = S2 - q
+        h = np.where(tot < 0, dtype(0.0), tot) * dtype(0.5)       # (a NaN stays a NaN)
+    h = np.asarray(h, dtype=dtype)
+    return (h, coef) if return_coef else h
+
+
 def ou_mix_halfchi2(y, alpha, beta, omega, lnc, dtype=np.float64, return_candidates=False):
     """A dataset's term of the log-weight with the amplitude and time scale of its correlated noise marginalised over J
     candidates, on the host: the statement of what trxm_chi2_grid_ou_mix computes per row,

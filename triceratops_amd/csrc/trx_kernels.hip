@@ -1,6 +1,6 @@
 // libtrx.so: the host side of the likelihood path and the C ABI (include/trx.h) for gfx950.
 //
-// The kernels live in six headers that only this file includes:
+// The kernels live in seven headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
 //                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
@@ -17,6 +17,8 @@
 //                    softmin_launch_j here; include/trx_shift.h)
 //   trx_robust.hpp   chi2_robust_kernel<STAGE> (the outlier-tolerant row reduction: a two-component mixture per point, one
 //                    exp and one log1p a value; chi2_robust_launch here; include/trx_robust.h)
+//   trx_gls.hpp      gls_ou_kernel<ONE, K> (chi2_ou_kernel's scan with K baseline columns marginalised under the same noise;
+//                    gls_ou_launch here; include/trx_gls.h)
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
 // lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
@@ -41,6 +43,7 @@
 #include "../../include/trx_mix.h"
 #include "../../include/trx_shift.h"
 #include "../../include/trx_robust.h"
+#include "../../include/trx_gls.h"
 #include "trx_device.hpp"
 #include "trx_internal.hpp"
 #include "trx_knobs.hpp"
@@ -72,6 +75,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 #include "trx_noise_mix.hpp"
 #include "trx_softmin.hpp"
 #include "trx_robust.hpp"
+#include "trx_gls.hpp"
 #include "trx_bands.hpp"
 
 namespace {
@@ -1054,6 +1058,30 @@ void ou_mix_launch_j(const double* flux, const double* model_grid, int n_time, l
                        accumulate, out, alpha, beta, omega, lnc, cand_out);
 }
 
+// One launch of gls_ou_kernel<ONE, K> (trxg_chi2_grid_ou_baseline): ONE as for chi2_ou_kernel, K = n_terms.  No LDS, so the
+// registers bound what stays resident: below kGlsWideFrom columns the kernel stays within 128 VGPRs and 4 blocks of 256
+// threads a CU are resident, from there on it would hold two waves a SIMD (at most 256 VGPRs): 2 blocks a CU, on 256 CUs.
+// As built every K = 1 .. 4 is within 128 (trx_gls.hpp).  The rows behind that cap are the second row of a wave's pass and
+// its further passes.
+template <int K>
+void gls_ou_launch(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                   double sec_limit, int accumulate, double* out, const double* alpha, const double* beta,
+                   const double* omega, const double* columns, int n_terms, const Chi2bM& M, double* coef_out,
+                   hipStream_t st)
+{
+    if constexpr (K < kChi2bMaxTerms) {
+        if (n_terms != K)
+            return gls_ou_launch<K + 1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out, alpha, beta,
+                                        omega, columns, n_terms, M, coef_out, st);
+    }
+    long blocks = (n + 3) / 4;
+    const long resident = 256L * (K < kGlsWideFrom ? 4 : 2);
+    if (blocks > resident) blocks = resident;
+    const auto kernel = n_time <= kOuTrip ? gls_ou_kernel<true, K> : gls_ou_kernel<false, K>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
+                       accumulate, out, alpha, beta, omega, columns, M, coef_out);
+}
+
 // One launch of chi2_robust_kernel<STAGE> (trxr_chi2_grid_robust): STAGE while flux and inv_var fit the LDS budget of
 // chi2_rows_kernel, and chi2_rows_launch's cap of blocks -- 8 of 256 threads a CU, fewer where the staged vectors fill the
 // 160 KB of LDS, on 256 CUs.  The registers decide how many of them are resident at once (six at the 80 VGPRs the kernel
@@ -1215,6 +1243,30 @@ int trxm_chi2_grid_ou_mix(const double* flux, const double* model_grid, int n_ti
     if (n == 0) return TRX_OK;
     ou_mix_launch_j<1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
                        n_cand, c, cand_out, static_cast<hipStream_t>(stream));
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trxg_chi2_grid_ou_baseline(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                               double sec_limit, int accumulate, double* out_halfchi2, const double* alpha,
+                               const double* beta, const double* omega, const double* columns, int n_terms,
+                               const double* minv, double* coef_out, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (n_terms < 1 || n_terms > TRXG_MAX_TERMS)
+        return fail(TRX_ERR_ARG, "n_terms must lie in [1, 4]%s (got %ld)", "", (long)n_terms);
+    if (!flux || !model_grid || !out_halfchi2 || !alpha || !beta || !omega || !columns || !minv)
+        return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    static_assert(TRXG_MAX_TERMS == kChi2bMaxTerms, "the header's limit is the kernel's");
+    Chi2bM M{};
+    for (int i = 0; i < n_terms * (n_terms + 1) / 2; ++i) {
+        if (!(minv[i] - minv[i] == 0.0))                    // (NaN or +-inf)
+            return fail(TRX_ERR_ARG, "minv must be finite%s (entry %ld)", "", (long)i);
+        M.m[i] = minv[i];
+    }
+    if (n == 0) return TRX_OK;
+    gls_ou_launch<1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
+                     columns, n_terms, M, coef_out, static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

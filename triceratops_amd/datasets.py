@@ -7,7 +7,9 @@ MAX_BASELINE_TERMS columns B_k[t] of a linear baseline model sum_k c_k B_k[t] wi
 the same way (baseline_system), or `red_sigma` / `red_timescale`: correlated noise of standard deviation s_r with an
 exponential kernel of time scale tau next to the white errors (ou_system), or `red_grid`: up to MAX_RED_CANDIDATES
 weighted candidates (s_r, tau) of that noise, marginalised per draw (ou_mix_system); and next to any of these `t0_grid`: up
-to MAX_T0_NODES weighted shifts of its stamps, marginalised per draw (t0_grids); or, alone or next to `t0_grid`,
+to MAX_T0_NODES weighted shifts of its stamps, marginalised per draw (t0_grids); next to `red_sigma` / `red_timescale` (and
+`t0_grid`) alone `red_baseline` / `red_baseline_sigma`: up to MAX_BASELINE_TERMS baseline columns marginalised under that
+correlated noise (red_baselines, ou_baseline_system); or, alone or next to `t0_grid`,
 `outlier_frac` / `outlier_scale`: every point is with probability eps an outlier from a Gaussian kappa times wider than its
 error, the membership integrated out per point and per draw (outliers, robust_constants).  This module is host side and numpy only:
 validation, the reference noise sigma_bar and the per-star renormalisation.  A `Datasets` object is what the lnZ_*
@@ -116,25 +118,26 @@ def _offset_sigma(i, value):
     return value
 
 
-def _baseline(i, value, sigma, n_given, keep):
-    """a dataset's "baseline" and "baseline_sigma" -> ([K_b][T kept] columns, [K_b] sigmas), or (None, None)"""
+def _baseline(i, value, sigma, n_given, keep, name="baseline"):
+    """a dataset's "baseline" and "baseline_sigma" -> ([K_b][T kept] columns, [K_b] sigmas), or (None, None); name: the
+    key the messages speak of ("red_baseline": the same rules for the columns under correlated noise)"""
     if value is None:
         if sigma is not None:
-            raise ValueError("dataset %d: baseline_sigma without baseline" % i)
+            raise ValueError("dataset %d: %s_sigma without %s" % (i, name, name))
         return None, None
     try:
         B = np.asarray(value, dtype=np.float64)
     except (TypeError, ValueError):
-        raise ValueError("dataset %d: baseline must be an array [K][len(time)] or [len(time)]" % i) from None
+        raise ValueError("dataset %d: %s must be an array [K][len(time)] or [len(time)]" % (i, name)) from None
     if B.ndim == 1:
         B = B[None, :]
     if B.ndim != 2 or B.shape[0] < 1 or B.shape[1] != n_given:
-        raise ValueError("dataset %d: baseline must be an array [K][len(time)] or [len(time)], len(time) = %d (got shape %s)"
-                         % (i, n_given, np.shape(value)))
+        raise ValueError("dataset %d: %s must be an array [K][len(time)] or [len(time)], len(time) = %d (got shape %s)"
+                         % (i, name, n_given, np.shape(value)))
     B = B[:, keep]
     if not np.all(np.isfinite(B)):
-        raise ValueError("dataset %d: every baseline entry of a kept point must be finite" % i)
-    msg = "dataset %d: baseline_sigma must be a number or %d numbers, each > 0 or inf (got %r)" % (i, B.shape[0], sigma)
+        raise ValueError("dataset %d: every %s entry of a kept point must be finite" % (i, name))
+    msg = "dataset %d: %s_sigma must be a number or %d numbers, each > 0 or inf (got %r)" % (i, name, B.shape[0], sigma)
     if sigma is None:
         s = np.full(B.shape[0], np.inf)
     else:
@@ -289,6 +292,87 @@ def outliers(dicts, sets):
     return [_outliers(i, d, s) for i, (d, s) in enumerate(zip(dicts, sets))]
 
 
+RED_BASELINE_KEYS = ("red_baseline", "red_baseline_sigma")
+
+
+class OuBaselineSystem(NamedTuple):
+    """the noise tables of a dataset and the linear system of its baseline columns under that noise (ou_baseline_system)"""
+    alpha: np.ndarray         # [T] of ou_system
+    beta: np.ndarray          # [T]
+    omega: np.ndarray         # [T]
+    c: np.ndarray             # [K][T] c_k[n] = omega_n z[B_k]_n / sqrt(D_k), z[x] the innovations of x
+    D: np.ndarray             # [K] D_k = sum_n omega_n z[B_k]_n^2 = B_k^T K^-1 B_k
+    A: np.ndarray             # [K][K] A~ = D^(-1/2) (B^T K^-1 B + diag(1 / s_k^2)) D^(-1/2)
+    M: np.ndarray             # [K][K] A~^(-1), symmetric; None where A~ is singular
+    lambda_min: float         # smallest eigenvalue of A~
+
+    @property
+    def minv(self):
+        """M's upper triangle packed by rows: the `minv` of trxg_chi2_grid_ou_baseline"""
+        return np.ascontiguousarray(self.M[np.triu_indices(self.M.shape[0])])
+
+
+def ou_baseline_system(dataset, B, sigmas):
+    """OuBaselineSystem of the columns B [K][T] with prior sigmas [K] (inf: flat) under the noise of a Dataset with
+    red_sigma / red_timescale -- the one place that forms them, for the device path (fused._Dataset) and for the numpy
+    statement (_numerics.ou_baseline_halfchi2).  The Kalman recurrence of ou_system whitens the columns as it whitens the
+    residuals: with z[x]_n = x_n - g_n (_numerics.ou_innovations), B_k^T K^-1 B_l = sum_n omega_n z[B_k]_n z[B_l]_n, so the
+    scaled system is linear_system's on the weights omega and the columns z[B_k].  ValueError for a column whose D_k is 0
+    (or not finite); a singular A~ gives lambda_min <= 0 and M = None."""
+    from ._numerics import ou_innovations
+    alpha, beta, omega = ou_system(dataset)
+    Z = ou_innovations(np.atleast_2d(np.asarray(B, dtype=np.float64)), alpha, beta, np.float64)
+    system = linear_system(omega, Z, sigmas)
+    return OuBaselineSystem(alpha, beta, omega, system.g, system.D, system.A, system.M, system.lambda_min)
+
+
+def _red_baseline(i, d, dataset):
+    """a dataset's "red_baseline" and "red_baseline_sigma" -> ([K_b][T kept] columns, [K_b] sigmas), or None; dataset: the
+    validated Dataset of the same dict (its noise, and what else it marginalises)"""
+    value, sigma = d.get("red_baseline"), d.get("red_baseline_sigma")
+    time = np.atleast_1d(np.asarray(d["time"], dtype=np.float64))
+    keep = ~np.isnan(time) & ~np.isnan(np.atleast_1d(np.asarray(d["flux"], dtype=np.float64)))
+    B, s = _baseline(i, value, sigma, time.size, keep, name="red_baseline")
+    if B is None:
+        return None
+    if B.shape[0] > MAX_BASELINE_TERMS:
+        raise ValueError("dataset %d: at most %d red_baseline columns (got %d)" % (i, MAX_BASELINE_TERMS, B.shape[0]))
+    if (dataset.offset_sigma is not None or dataset.baseline is not None or dataset.red_grid is not None
+            or d.get("outlier_frac") is not None or d.get("outlier_scale") is not None):
+        raise ValueError("dataset %d: red_baseline together with offset_sigma, baseline, red_grid or outlier_frac / "
+                         "outlier_scale is not built: the columns stand next to red_sigma / red_timescale (and t0_grid) "
+                         "alone; a column of ones is the constant" % i)
+    if dataset.red_sigma is None:
+        raise ValueError("dataset %d: red_baseline needs red_sigma / red_timescale: under white noise give the columns as "
+                         "baseline" % i)
+    try:
+        system = ou_baseline_system(dataset, B, s)
+    except ValueError as e:
+        raise ValueError("dataset %d: red_baseline term %s" % (i, e)) from None
+    if not system.lambda_min >= MIN_BASELINE_EIGENVALUE:
+        raise ValueError("dataset %d: the red_baseline terms are collinear under the dataset's noise (smallest eigenvalue of "
+                         "the scaled system %.3g < %g): drop a column, or give finite priors"
+                         % (i, system.lambda_min, MIN_BASELINE_EIGENVALUE))
+    return B, s
+
+
+def red_baselines(dicts, sets):
+    """The "red_baseline" / "red_baseline_sigma" keys of the dicts that validate() turned into `sets`: per dataset None, or
+    the pair (B, sigmas) -- B a contiguous float64 [K_b][kept points] array of K_b = 1 ... MAX_BASELINE_TERMS columns of a
+    linear baseline model sum_k c_k B_k[t], aligned with `time` (entries of NaN-dropped points dropped with them, every
+    kept entry finite), sigmas [K_b] the prior sigmas of c_k ~ N(0, s_k^2), each > 0 or inf (absent: flat) -- marginalised
+    per draw under the dataset's correlated noise: its term of the log-weight becomes 0.5 [y^T K^-1 y - b^T A^-1 b]
+    (_numerics.ou_baseline_halfchi2 on ou_baseline_system).  A column of ones is how the constant is given.  The keys stand
+    only next to red_sigma / red_timescale, and may stand next to t0_grid (the columns follow the points); ValueError next
+    to offset_sigma, baseline, red_grid or outlier_frac / outlier_scale, without the two red keys, for a sigma without
+    columns, a wrong shape, more than MAX_BASELINE_TERMS columns, a kept entry that is not finite, a zero column, or
+    columns that are collinear under the noise (smallest eigenvalue of the scaled system < MIN_BASELINE_EIGENVALUE).
+    Dataset itself has no field for the keys: the pairs travel in Datasets.red_baselines."""
+    if len(dicts) != len(sets):
+        raise ValueError("red_baselines: %d dicts for %d datasets" % (len(dicts), len(sets)))
+    return [_red_baseline(i, d, s) for i, (d, s) in enumerate(zip(dicts, sets))]
+
+
 def robust_constants(frac, scale):
     """(c0, c1, k2) of a dataset's outlier mixture: c0 = -log1p(-eps) >= 0, c1 = ln kappa - ln eps > 0, k2 = 1 / kappa^2 --
     the one place that forms them, for the device path (fused._Dataset) and for the numpy statement
@@ -366,8 +450,10 @@ def _check_baseline(i, dataset):
 
 def validate(datasets):
     """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
-    baseline_sigma, red_sigma, red_timescale, red_grid, t0_grid, outlier_frac, outlier_scale]} -> a list of Dataset ("t0_grid"
-    is allowed here and read by t0_grids, "outlier_frac" / "outlier_scale" are checked here and returned by outliers: no field
+    baseline_sigma, red_sigma, red_timescale, red_grid, t0_grid, outlier_frac, outlier_scale, red_baseline,
+    red_baseline_sigma]} -> a list of Dataset ("t0_grid"
+    is allowed here and read by t0_grids, "outlier_frac" / "outlier_scale" are checked here and returned by outliers,
+    "red_baseline" / "red_baseline_sigma" are checked here and returned by red_baselines: no field
     of Dataset holds them).  Points with a NaN time or flux are dropped together with their error and their
     baseline entries; a scalar flux_err is broadcast.  ValueError for an empty list, too many datasets, mismatched
     lengths, an error that is not finite or not positive, a dataset without points, an offset_sigma that is not None, a
@@ -379,7 +465,7 @@ def validate(datasets):
     normalised to sum 1, repeated pairs are allowed), that stands next to red_sigma / red_timescale, offset_sigma or
     baseline, or whose kept stamps are not in non-decreasing order; for outlier_frac without outlier_scale or the reverse, an
     outlier_frac outside (0, 0.5], an outlier_scale that is not a finite number > 1, or either of them next to
-    offset_sigma, baseline, red_sigma / red_timescale or red_grid."""
+    offset_sigma, baseline, red_sigma / red_timescale or red_grid; and for what red_baselines lists."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -389,7 +475,8 @@ def validate(datasets):
     out = []
     for i, d in enumerate(datasets):
         unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma",
-                            "red_sigma", "red_timescale", "red_grid", "t0_grid", "outlier_frac", "outlier_scale"}
+                            "red_sigma", "red_timescale", "red_grid", "t0_grid", "outlier_frac", "outlier_scale",
+                            "red_baseline", "red_baseline_sigma"}
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -426,6 +513,7 @@ def validate(datasets):
                            float(d.get("exptime", DEFAULT_EXPTIME)), nsamples,
                            offset_sigma, baseline, baseline_sigma, red_grid, red_sigma, red_timescale))
         _check_baseline(i, out[-1])
+        _red_baseline(i, d, out[-1])
         _outliers(i, d, out[-1])
     return out
 
@@ -449,9 +537,10 @@ def sigma_bar(errs):
 
 class Datasets:
     """validated datasets in one star's normalisation, their sigma_bar, and per dataset None or its transit-time shift
-    grid (t0_grids) and None or its outlier pair (frac, scale) (outliers)"""
+    grid (t0_grids), None or its outlier pair (frac, scale) (outliers) and None or the pair (columns, sigmas) of its
+    baseline under correlated noise (red_baselines)"""
 
-    def __init__(self, sets, t0_grids=None, outliers=None):
+    def __init__(self, sets, t0_grids=None, outliers=None, red_baselines=None):
         self.sets = tuple(sets)
         self.sigma_ref = sigma_ref(self.sets)
         self.t0_grids = (None,) * len(self.sets) if t0_grids is None else tuple(t0_grids)
@@ -460,6 +549,9 @@ class Datasets:
         self.outliers = (None,) * len(self.sets) if outliers is None else tuple(outliers)
         if len(self.outliers) != len(self.sets):
             raise ValueError("outliers: %d pairs for %d datasets" % (len(self.outliers), len(self.sets)))
+        self.red_baselines = (None,) * len(self.sets) if red_baselines is None else tuple(red_baselines)
+        if len(self.red_baselines) != len(self.sets):
+            raise ValueError("red_baselines: %d pairs for %d datasets" % (len(self.red_baselines), len(self.sets)))
 
     def __len__(self):
         return len(self.sets)
@@ -485,6 +577,10 @@ class Datasets:
         return any(o is not None for o in self.outliers)
 
     @property
+    def has_red_baselines(self):
+        return any(b is not None for b in self.red_baselines)
+
+    @property
     def size(self):
         """points of all datasets together"""
         return sum(s.time.size for s in self.sets)
@@ -499,7 +595,10 @@ class Datasets:
         determinant ratio that the evidence drops is the same for every star.  The s_r column of a red_grid is divided
         likewise: every candidate's determinant gains the same factor, so the lnc of ou_mix_system do not change.  The t0_grids are times and
         pure weights: carried through as they are.  So are the outlier pairs: only z_t = d_t / sigma_t enters the mixture,
-        and renorm_flux leaves it alone."""
+        and renorm_flux leaves it alone.  A finite sigma of a red_baselines pair is in flux units per unit of its column
+        and is divided by the flux ratio; the columns are left alone: with red_sigma and the errors scaled alike, D_k of
+        ou_baseline_system scales with the square of the flux ratio, s_k^2 D_k and the scaled system matrix are the same
+        for every star, and so is the determinant that the evidence drops."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
@@ -518,4 +617,6 @@ class Datasets:
                 grid[:, 0] = grid[:, 0] / star_fluxratio
             out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err), offset_sigma=off,
                                   baseline_sigma=bsig, red_sigma=red, red_grid=grid))
-        return Datasets(out, self.t0_grids, self.outliers)
+        red = [None if p is None else (p[0], np.where(np.isfinite(p[1]), p[1] / star_fluxratio, p[1]))
+               for p in self.red_baselines]
+        return Datasets(out, self.t0_grids, self.outliers, red)

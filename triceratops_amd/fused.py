@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, funcs
-from .datasets import Datasets, baseline_system, ou_mix_system, ou_system, robust_constants
+from .datasets import Datasets, baseline_system, ou_baseline_system, ou_mix_system, ou_system, robust_constants
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
@@ -245,6 +245,11 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # datasets.robust_constants (grid evaluation only).  DATASET_OUTLIERS = {}: every such call leaves {work unit: [per branch, a
 # list per dataset: None or the [T] posterior outlier probabilities of the points at the branch's best draw
 # (_numerics.robust_responsibility; with a t0_grid on its heaviest node)]} there (target.dataset_outliers).
+# A dataset with `red_baseline` (Datasets.red_baselines) has the columns' coefficients marginalised per draw under its
+# red_sigma / red_timescale noise: its reduction is trxg_chi2_grid_ou_baseline on the tables of datasets.ou_baseline_system
+# (grid evaluation only).  DATASET_RED_BASELINES = {}: every such call leaves {work unit: [per branch, a list per dataset:
+# None or the [K_b] posterior-mean coefficients at the branch's best draw, in the call's normalisation (with a t0_grid on
+# its heaviest node)]} there (target.dataset_red_baselines).
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
@@ -253,6 +258,7 @@ DATASET_BASELINES = None
 DATASET_RED_NOISE = None
 DATASET_T0 = None
 DATASET_OUTLIERS = None
+DATASET_RED_BASELINES = None
 # An importance map (WARP_GRIDS) applies to a datasets call as to any other: its draws are trx_draw_scenario's.  The weight
 # histogram of the library's own chain (WARP_HIST) does not exist here -- chi^2/2 is computed outside that chain -- so
 # DATASET_WARP_HIST = {}: every datasets call leaves {work unit: [branches][WARP_BRANCH] uint64 words} there, one
@@ -263,7 +269,7 @@ DATASET_WARP_HIST = None
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_OUTLIERS, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_OUTLIERS, DATASET_RED_BASELINES, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -778,6 +784,24 @@ def _mix_on_device(d, device):
     return _cached(_mix_cache, key, 32, build)
 
 
+_gls_cache = {}
+
+
+def _gls_on_device(d, pair, device):
+    """the _Gls record of a dataset with red_baseline columns (datasets.ou_baseline_system): formed once per content of its
+    stamps, errors, noise keys, columns and prior sigmas -- (1 + K) * T steps of a Python loop and a K x K eigenproblem --
+    for the lnZ_* calls of a star (a cache of its own, as _mix_on_device's)"""
+    B, sigmas = pair
+    key = (tuple(hash(np.ascontiguousarray(a).tobytes()) for a in (d.time, d.flux_err, B, sigmas)), B.shape,
+           float(d.red_sigma), float(d.red_timescale), device.index)
+
+    def build():
+        system = ou_baseline_system(d, B, sigmas)
+        return _Gls(tuple(_lib.dev(v, device) for v in (system.alpha, system.beta, system.omega)),
+                    _lib.dev(system.c, device), system.minv, np.sqrt(system.D))
+    return _cached(_gls_cache, key, 32, build)
+
+
 _shift_cache = {}
 
 
@@ -802,10 +826,19 @@ class _Baseline(NamedTuple):
     has_offset: bool             # term 0 is the dataset's offset
 
 
+class _Gls(NamedTuple):
+    """the system of a dataset with red_baseline columns (datasets.ou_baseline_system)"""
+    ou: tuple                    # (alpha, beta, omega) on the device
+    c: torch.Tensor              # the whitened scaled columns [K][T], on the device
+    minv: np.ndarray             # M's packed upper triangle
+    sqrt_d: np.ndarray           # sqrt(D): c_k = c~_k / sqrt(D_k)
+
+
 class _Dataset(NamedTuple):
     """one light curve of a Datasets call on the device, and what its reduction marginalises: nothing, a constant offset,
     or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then --, or correlated
-    noise, or the outlier mixture of its points; and, next to any of these, the nodes of a transit-time shift (`shift`: the
+    noise -- alone (`ou`) or with baseline columns under it (`gls`: `ou` is None then) --, or the outlier mixture of its
+    points; and, next to any of these, the nodes of a transit-time shift (`shift`: the
     reduction then runs once per node)"""
     time: torch.Tensor
     flux: torch.Tensor
@@ -818,9 +851,10 @@ class _Dataset(NamedTuple):
     mix: Optional[tuple] = None              # (alpha, beta, omega [J][T] on the device, lnc [J] on the host): ou_mix_system
     shift: Optional[tuple] = None            # (J device tensors time + shift_j, ln pi [J] on the host, ln pi on the device)
     robust: Optional[tuple] = None           # (c0, c1, k2): the outlier mixture of the points (datasets.robust_constants)
+    gls: Optional[_Gls] = None               # baseline columns under correlated noise (datasets.ou_baseline_system)
 
     @classmethod
-    def upload(cls, d, dev, t0_grid=None, outliers=None):
+    def upload(cls, d, dev, t0_grid=None, outliers=None, red_baseline=None):
         inv_var = 1.0 / (d.flux_err * d.flux_err)
         rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
         if outliers is not None:
@@ -832,6 +866,9 @@ class _Dataset(NamedTuple):
         if d.red_grid is not None:
             # (validate refuses anything else next to it)
             return rec._replace(mix=_mix_on_device(d, dev))
+        if red_baseline is not None:
+            # (validate wants red_sigma / red_timescale next to it and refuses an offset, a baseline or a red_grid)
+            return rec._replace(gls=_gls_on_device(d, red_baseline, dev))
         if d.red_sigma is not None:
             # (validate refuses an offset or a baseline next to it)
             return rec._replace(ou=tuple(_on_device(v, dev) for v in ou_system(d)))
@@ -851,11 +888,15 @@ class _Dataset(NamedTuple):
         secdepth >= sec_limit.  The one place that picks the reduction: trx_chi2_grid_baseline for baseline columns (coef_out:
         the rows' scaled coefficients), trx_chi2_grid_offset for an offset alone (offset_out: the rows' offsets),
         trxn_chi2_grid_ou for correlated noise, trxm_chi2_grid_ou_mix for a grid of its candidates (cand_out: the rows'
-        per-candidate chi^2/2), trxr_chi2_grid_robust for the outlier mixture, else trx_chi2_grid_weighted."""
+        per-candidate chi^2/2), trxg_chi2_grid_ou_baseline for baseline columns under correlated noise (coef_out likewise),
+        trxr_chi2_grid_robust for the outlier mixture, else trx_chi2_grid_weighted."""
         if self.robust is not None:
             return _lib.chi2_grid_robust(self.flux, self.inv_var, grid, *self.robust, secdepth, sec_limit, out=out)
         if self.mix is not None:
             return _lib.chi2_grid_ou_mix(self.flux, grid, *self.mix, secdepth, sec_limit, out=out, cand_out=cand_out)
+        if self.gls is not None:
+            return _lib.chi2_grid_ou_baseline(self.flux, grid, *self.gls.ou, self.gls.c, self.gls.minv, secdepth, sec_limit,
+                                              out=out, coef_out=coef_out)
         if self.ou is not None:
             return _lib.chi2_grid_ou(self.flux, grid, *self.ou, secdepth, sec_limit, out=out)
         if self.baseline is not None:
@@ -876,7 +917,8 @@ class _Scenario:
         self.datasets = None
         if isinstance(time, Datasets):
             # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
-            self.datasets = [_Dataset.upload(d, self.dev, g, o) for d, g, o in zip(time.sets, time.t0_grids, time.outliers)]
+            self.datasets = [_Dataset.upload(d, self.dev, g, o, b)
+                             for d, g, o, b in zip(time.sets, time.t0_grids, time.outliers, time.red_baselines)]
             sigma = time.sigma_ref
             self.time, self.flux = self.datasets[0].time, self.datasets[0].flux
         else:
@@ -1168,7 +1210,7 @@ class _Scenario:
             best = self._best(h, idx, n)
             if self.datasets is not None and ((DATASET_OFFSETS is not None and any(d.offset is not None for d in self.datasets))
                                               or self._any_baseline() or self._any_mix() or self._any_shift()
-                                              or self._any_robust()):
+                                              or self._any_robust() or self._any_gls()):
                 o, c, hc, hn, mr = (self._best_offsets(model, flags, cols, best, twin, nblk) if n
                                     else (None, None, None, None, None))
                 offsets.append(o)
@@ -1221,15 +1263,30 @@ class _Scenario:
         """whether a robust dataset's outlier probabilities are wanted back (DATASET_OUTLIERS)"""
         return DATASET_OUTLIERS is not None and any(d.robust is not None for d in self.datasets)
 
+    def _any_gls(self):
+        """whether a red_baseline dataset's coefficients are wanted back (DATASET_RED_BASELINES)"""
+        return DATASET_RED_BASELINES is not None and any(d.gls is not None for d in self.datasets)
+
     def _leave_best_terms(self, offsets, coefs, cands, nodes, probs):
         """the branches' best-draw offsets and baseline coefficients, from the device to DATASET_OFFSETS / DATASET_BASELINES
         under this thread's work unit, in the call's normalisation: c_k = c~_k / sqrt(D_k); and the posterior weights of a
         red_grid dataset's candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_RED_NOISE (NaN without a draw); and
         those of a t0_grid dataset's nodes, softmax_j(ln pi_j - h_j), to DATASET_T0 (likewise); and the posterior outlier
         probabilities of a robust dataset's points at that draw, _numerics.robust_responsibility on the draw's model row, to
-        DATASET_OUTLIERS (likewise)"""
+        DATASET_OUTLIERS (likewise); and the coefficients of a red_baseline dataset's columns at that draw,
+        c_k = c~_k / sqrt(D_k), to DATASET_RED_BASELINES (likewise)"""
         L = len(self.datasets)
         unit = getattr(_tls, "unit", None)
+        if DATASET_RED_BASELINES is not None:
+            out = []
+            for c in coefs:
+                per = [None] * L
+                for l, d in enumerate(self.datasets):
+                    if d.gls is not None:
+                        per[l] = (np.full(d.gls.sqrt_d.size, np.nan) if c is None
+                                  else c[l].cpu().numpy().reshape(-1) / d.gls.sqrt_d)
+                out.append(per)
+            DATASET_RED_BASELINES[unit] = out
         if DATASET_OUTLIERS is not None:
             from ._numerics import robust_responsibility
             out = []
@@ -1299,7 +1356,8 @@ class _Scenario:
     def _best_offsets(self, model, flags, cols, best, twin, nblk):
         """([L] device tensor and four lists per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
         S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
-        baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them); and None or the
+        baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them; likewise for a
+        red_baseline dataset under DATASET_RED_BASELINES); and None or the
         [1][J] device tensor of a red_grid dataset's per-candidate chi^2/2.  The one row is evaluated again -- trx_flux_grid
         on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out, coef_out or cand_out -- so nothing of
         size n x L is kept.  A t0_grid dataset has the row evaluated on every node: the fourth list holds None or the [J]
@@ -1318,7 +1376,8 @@ class _Scenario:
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL
         for l, d in enumerate(self.datasets):
             if (d.offset is None and d.baseline is None and (d.mix is None or DATASET_RED_NOISE is None)
-                    and (d.shift is None or DATASET_T0 is None) and (d.robust is None or DATASET_OUTLIERS is None)):
+                    and (d.shift is None or DATASET_T0 is None) and (d.robust is None or DATASET_OUTLIERS is None)
+                    and (d.gls is None or DATASET_RED_BASELINES is None)):
                 continue
             keep = d.robust is not None and DATASET_OUTLIERS is not None
             grids = []
@@ -1327,6 +1386,8 @@ class _Scenario:
             off = out[l:l + 1] if d.shift is None else torch.full((J,), float("nan"), dtype=F64, device=self.dev)
             if d.baseline is not None:
                 coefs[l] = torch.empty((J, int(d.baseline.g.shape[0])), dtype=F64, device=self.dev)
+            if d.gls is not None and DATASET_RED_BASELINES is not None:
+                coefs[l] = torch.empty((J, int(d.gls.c.shape[0])), dtype=F64, device=self.dev)
             if d.mix is not None:
                 cands[l] = torch.empty((J, int(d.mix[3].size)), dtype=F64, device=self.dev)
             hs = []
@@ -1367,6 +1428,9 @@ class _Scenario:
         if DATASET_EVALUATION == "fused" and any(d.baseline is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: the fused kernel "
                                       "carries no sums of basis * residual; use evaluation='grid'")
+        if DATASET_EVALUATION == "fused" and any(d.gls is not None for d in self.datasets):
+            raise NotImplementedError("evaluation='fused' with a red_baseline dataset is not built: the fused kernel "
+                                      "carries no recurrence along the row; use evaluation='grid'")
         if DATASET_EVALUATION == "fused" and any(d.ou is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a red_sigma dataset is not built: the fused kernel "
                                       "carries no recurrence along the row; use evaluation='grid'")

@@ -86,6 +86,21 @@ def polynomial_baseline(time, order: int):
     return np.stack([u ** p for p in range(1, order + 1)])
 
 
+def trend_columns(time, order: int, constant: bool = True):
+    """[order + 1][T] columns u^0 ... u^order of a polynomial trend for a dataset's "red_baseline" key (constant=False:
+    [order][T], u^1 ... u^order), u as in polynomial_baseline.  The column of ones is how the constant is given there: no
+    offset_sigma stands next to red_baseline.  order = 0 (with the constant): the ones alone.  A NaN time gives NaN entries
+    (dropped with the point), also in the constant."""
+    time = np.asarray(time, dtype=np.float64)
+    order = int(order)
+    if time.ndim != 1 or order < 0 or (order == 0 and not constant):
+        raise ValueError("trend_columns needs a 1-d time array and order >= 0 (>= 1 without the constant)")
+    cols = polynomial_baseline(time, order) if order > 0 else np.empty((0, time.size))
+    if constant:
+        cols = np.concatenate([np.where(np.isnan(time), np.nan, 1.0)[None, :], cols])
+    return np.ascontiguousarray(cols)
+
+
 def red_noise_grid(sigmas, timescales, weights=None):
     """The product grid of candidate red-noise amplitudes and time scales as a dataset's "red_grid": a float64 array
     [len(sigmas) * len(timescales)][3] of rows (s_r, tau, weight), sigmas-major.  weights: None (equal), or an array
@@ -125,7 +140,8 @@ def t0_shift_grid(sigma, n: int = 5, span: float = 3.0):
 def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_sigma: int = 50,
                     exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None,
                     baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None,
-                    red_grid=None, t0_grid=None, outlier_frac: float = None, outlier_scale: float = None):
+                    red_grid=None, t0_grid=None, outlier_frac: float = None, outlier_scale: float = None,
+                    red_baseline_order: int = None, red_baseline_sigma=None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
     {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
     empty bins are dropped.
@@ -138,6 +154,9 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     weight)): nodes of a transit-time shift to marginalise, passed through as the key "t0_grid" when given.
     outlier_frac, outlier_scale (both or neither): the outlier-tolerant likelihood of the dataset's points, passed through
     as the keys of those names when given.
+    red_baseline_order (None: no such key; >= 0): "red_baseline" = trend_columns(kept bins' times, red_baseline_order), the
+    trend marginalised under the dataset's red_sigma / red_timescale, with red_baseline_sigma (a number or one per column;
+    None: flat) passed through.
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -162,4 +181,8 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
         out["t0_grid"] = t0_grid
     if outlier_frac is not None or outlier_scale is not None:
         out["outlier_frac"], out["outlier_scale"] = outlier_frac, outlier_scale
+    if red_baseline_order is not None:
+        out["red_baseline"] = trend_columns(tb, red_baseline_order)
+    if red_baseline_sigma is not None:
+        out["red_baseline_sigma"] = red_baseline_sigma
     return out

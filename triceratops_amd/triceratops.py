@@ -27,7 +27,8 @@ from scipy.special import ndtr
 from . import _lib
 from ._numerics import _mc_errors, _normalize_probabilities
 from .constants import G, Msun, pi
-from .datasets import Datasets, outliers as _outliers, t0_grids as _t0_grids, validate as _validate_datasets
+from .datasets import (Datasets, outliers as _outliers, red_baselines as _red_baselines, t0_grids as _t0_grids,
+                       validate as _validate_datasets)
 from .funcs import renorm_flux
 from .marginal_likelihoods import *  # noqa: F401,F403  (reference re-exports the lnZ_* names)
 from .marginal_likelihoods import (lnZ_BEB, lnZ_BTP, lnZ_DEB, lnZ_DTP, lnZ_PEB, lnZ_PTP, lnZ_SEB,
@@ -259,7 +260,7 @@ class target:
             if k in calc_probs_kwargs:
                 raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
         sets = _validate_datasets(datasets)
-        ds = Datasets(sets, _t0_grids(datasets, sets), _outliers(datasets, sets))
+        ds = Datasets(sets, _t0_grids(datasets, sets), _outliers(datasets, sets), _red_baselines(datasets, sets))
         n_samples = int(n_samples)
         if not 0 <= n_samples <= fused.POST_MAX_ROWS:
             raise ValueError("n_samples must lie in [0, %d]" % fused.POST_MAX_ROWS)
@@ -273,7 +274,7 @@ class target:
 
     def _datasets_pass(self, ds, P_orb, kw, verbose, evaluation, n_samples=0, **dataset_switches):
         """one pass of the datasets path over the target's work units: (units, rows, n_scen) for _finish.
-        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_OUTLIERS / DATASET_WARP_HIST for
+        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_OUTLIERS / DATASET_RED_BASELINES / DATASET_WARP_HIST for
         the length of the pass."""
         from . import fused
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
@@ -281,6 +282,8 @@ class target:
             raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: use evaluation='grid'")
         if ds.has_baselines and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: use evaluation='grid'")
+        if ds.has_red_baselines and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with a red_baseline dataset is not built: use evaluation='grid'")
         if ds.has_red_noise and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a red_sigma or red_grid dataset is not built: use "
                                       "evaluation='grid'")
@@ -397,17 +400,36 @@ class target:
         1 / (1 + (1 - eps) kappa / eps exp(-a_t (1 - 1 / kappa^2))) that each point is an outlier at the scenario's best draw
         (NaN without a finite lnZ; with a t0_grid on its node of largest weight)}; the whole attribute is None when no
         dataset has the keys.  Not built: the keys next to offset, baseline or red noise, a Student-t form, a fit of eps,
-        per-draw outlier probabilities, the scalar calc_probs path."""
+        per-draw outlier probabilities, the scalar calc_probs path.
+
+        A dataset with red_sigma / red_timescale may carry a trend as well: "red_baseline": 1 ... 4 columns B_k
+        [K_b][len(time)] (or [len(time)]) aligned with `time`, finite at the kept points, and "red_baseline_sigma": the
+        prior sigmas of their coefficients c_k ~ N(0, s_k^2), a number or [K_b], each > 0 or inf (absent: flat).  A column
+        of ones is how the constant is given (lightcurve.trend_columns); no offset_sigma stands next to these keys.  The
+        coefficients are marginalised per draw under the correlated noise K: the dataset's term of the log-weight is
+        0.5 [y^T K^-1 y - b^T A^-1 b], b = B^T K^-1 y, A = B^T K^-1 B + diag(1 / s_k^2) -- for finite priors
+        0.5 y^T (K + B diag(s^2) B^T)^-1 y -- in the Kalman form of ou_system that whitens residuals and columns alike
+        (datasets.ou_baseline_system, _numerics.ou_baseline_halfchi2, trxg_chi2_grid_ou_baseline).  The dropped factors
+        det K and det(I + diag(s^2) B^T K^-1 B) depend on the dataset alone and are the same for every star: red_sigma and
+        every finite s_k scale with the errors.  The keys stand only next to red_sigma / red_timescale and may stand next
+        to "t0_grid"; next to offset_sigma, baseline, red_grid or the outlier keys, without the two red keys, with a zero
+        column or with columns that are collinear under the noise they are a ValueError.  Grid evaluation only.
+        `.dataset_red_baselines` is then a list per scenario of a list per dataset: None for a dataset without the keys,
+        else the [K_b] posterior-mean coefficients at the scenario's best draw, in flux units per unit of the column (NaN
+        without a finite lnZ; with a t0_grid on its node of largest weight); the whole attribute is None when no dataset
+        has the keys.  Not built: red_grid next to a baseline, the outlier keys next to any marginalised term, the fused
+        evaluation, more than one noise term, the scalar calc_probs path."""
         ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
         best_offsets = {} if ds.has_offsets else None
         best_baselines = {} if ds.has_baselines else None
         best_red = {} if any(s.red_grid is not None for s in ds.sets) else None
         best_t0 = {} if ds.has_t0_grids else None
         best_outliers = {} if ds.has_outliers else None
+        best_gls = {} if ds.has_red_baselines else None
         units, rows, n_scen = self._datasets_pass(ds, P_orb, kw, verbose, evaluation, n_samples,
                                                   DATASET_OFFSETS=best_offsets, DATASET_BASELINES=best_baselines,
                                                   DATASET_RED_NOISE=best_red, DATASET_T0=best_t0,
-                                                  DATASET_OUTLIERS=best_outliers)
+                                                  DATASET_OUTLIERS=best_outliers, DATASET_RED_BASELINES=best_gls)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
@@ -470,6 +492,16 @@ class target:
                     if np.isfinite(self.lnZ[u.first_row + i]):
                         rows_[u.first_row + i] = [points(s, o, p) for s, o, p in zip(ds.sets, ds.outliers, per)]
             self.dataset_outliers = rows_
+        self.dataset_red_baselines = None
+        if best_gls is not None:
+            # (as dataset_baselines: c_k multiplies a column that is left alone, so c = fr c')
+            sizes = [None if p is None else p[0].shape[0] for p in ds.red_baselines]
+            rows_ = [[None if m is None else np.full(m, np.nan) for m in sizes] for _ in range(n_scen)]
+            for k, u in enumerate(sharding.as_units(units)):
+                for i, per in enumerate(best_gls.get(k, ())):
+                    if np.isfinite(self.lnZ[u.first_row + i]):
+                        rows_[u.first_row + i] = [None if c is None else c * share[u.group[1]] for c in per]
+            self.dataset_red_baselines = rows_
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
@@ -568,7 +600,7 @@ class target:
         uniforms from the chi^2/2 values of that pass (trxw_hist_from_halfchi2, fused.DATASET_WARP_HIST) and refine
         the map; best-draw offsets and baselines are not computed in them.  The final pass is calc_probs_datasets under
         the maps the adaptation left: it fills `.probs`, `.FPP`, `.lnZ_err`, `.posterior` (n_samples > 0), `.sigma_ref`,
-        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise`, `.dataset_t0` and `.dataset_outliers` as calc_probs_datasets does, and only it enters the result, so the
+        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise`, `.dataset_t0`, `.dataset_outliers` and `.dataset_red_baselines` as calc_probs_datasets does, and only it enters the result, so the
         estimate is unbiased.  `.refine_history` holds, per pass, the rows' lnZ, ess and w_max_frac.  n_adapt = 0 is
         calc_probs_datasets, bit for bit.  Both evaluations ("grid", "fused") feed the histogram the same way.
 
