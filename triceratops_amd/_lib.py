@@ -50,6 +50,8 @@ SHIFT_SYMBOLS = ("trxt_softmin_rows",)
 ROBUST_SYMBOLS = ("trxr_chi2_grid_robust",)
 # ... include/trx_gls.h (both libraries: a linear baseline marginalised under correlated noise, prefix trxg_)
 GLS_SYMBOLS = ("trxg_chi2_grid_ou_baseline",)
+# ... include/trx_ss.h (both libraries: the row reduction under correlated noise with a two-dimensional state, prefix trxs_)
+SS_SYMBOLS = ("trxs_chi2_grid_ss2",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -205,6 +207,8 @@ def _load(path, testing):
     L.trxg_chi2_grid_ou_baseline.restype = c_int
     L.trxg_chi2_grid_ou_baseline.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, _vp, c_int,
                                              _vp, _vp, _vp]
+    L.trxs_chi2_grid_ss2.restype = c_int
+    L.trxs_chi2_grid_ss2.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, _vp]
     L.trx_grid_quantiles.restype = c_int
     L.trx_grid_quantiles.argtypes = [_vp, c_long, c_int, _vp, _vp, c_long, _vp, c_int, _vp, _vp]
     L.trx_lnl_batch_host.restype = c_int
@@ -608,6 +612,31 @@ def chi2_grid_ou(flux_d, grid_d, alpha_d, beta_d, omega_d, secdepth=None, sec_li
                                       secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
                                       int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
                                       omega_d.data_ptr(), _stream(grid_d)))
+    return out
+
+
+def chi2_grid_ss2(flux_d, grid_d, A_d, g_d, omega_d, secdepth=None, sec_limit=float("inf"), out=None):
+    """chi2_grid_ou for correlated noise whose Kalman filter carries two states -- a Matern-3/2 term, two exponential terms
+    -- (trxs_chi2_grid_ss2, include/trx_ss.h): per row 0.5 sum_n omega[n] z_n^2, y = flux - grid[r], u_(-1) = 0,
+    z_n = y_n - u_(n-1)[0], u_n = A[n] u_(n-1) + g[n] y_n.  A_d [n_time][2][2], g_d [n_time][2], omega_d [n_time]: fp64 device
+    tensors (datasets.ss2_system).  The other arguments are chi2_grid_weighted's."""
+    require_gpu()
+    n, nt = grid_d.shape
+    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    for v, per in ((flux_d, 1), (A_d, 4), (g_d, 2), (omega_d, 1)):
+        assert v.numel() == per * nt and v.dtype == torch.float64 and v.is_contiguous()
+    assert secdepth is None or (secdepth.numel() == n and secdepth.is_contiguous())
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
+    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
+    if n == 0:
+        return out                     # (an empty tensor has no address to pass)
+    with torch.cuda.device(grid_d.device):
+        check(lib().trxs_chi2_grid_ss2(flux_d.data_ptr(), grid_d.data_ptr(), nt, n,
+                                       secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
+                                       int(accumulate), out.data_ptr(), A_d.data_ptr(), g_d.data_ptr(),
+                                       omega_d.data_ptr(), _stream(grid_d)))
     return out
 
 

@@ -158,6 +158,31 @@ def ou_halfchi2(y, alpha, beta, omega, dtype=np.float64):
     return h * dtype(0.5)
 
 
+def ss2_halfchi2(y, A, g, omega, dtype=np.float64):
+    """chi^2/2 of a light curve's residuals under white noise plus a process with a two-dimensional state -- a Matern-3/2
+    term, two exponential terms -- (DESIGN.md section 14), on the host: the statement of what trxs_chi2_grid_ss2 computes
+    per row,
+        u_(-1) = 0,  z_n = y_n - u_(n-1)[0],  u_n = A_n u_(n-1) + g_n y_n,   h = 0.5 sum_n omega_n z_n^2 = 0.5 y^T K^-1 y,
+    A [T][2][2], g [T][2], omega [T] from datasets.ss2_system; the determinant of K depends on the dataset only and is
+    dropped.  y: [..., T] residuals.  A sequential loop over T, vectorised over the rows, in `dtype` (np.longdouble: the
+    tests' reference)."""
+    y = np.asarray(y, dtype=dtype)
+    T = y.shape[-1]
+    A = np.asarray(A, dtype=dtype).reshape(T, 2, 2)
+    g = np.asarray(g, dtype=dtype).reshape(T, 2)
+    omega = np.asarray(omega, dtype=dtype).reshape(T)
+    u0 = np.zeros(y.shape[:-1], dtype=dtype)
+    u1 = np.zeros(y.shape[:-1], dtype=dtype)
+    h = np.zeros(y.shape[:-1], dtype=dtype)
+    for n in range(T):
+        yn = y[..., n]
+        z = yn - u0
+        h = h + omega[n] * z * z
+        u0, u1 = (A[n, 0, 0] * u0 + A[n, 0, 1] * u1 + g[n, 0] * yn,
+                  A[n, 1, 0] * u0 + A[n, 1, 1] * u1 + g[n, 1] * yn)
+    return h * dtype(0.5)
+
+
 def ou_innovations(x, alpha, beta, dtype=np.float64):
     """The innovations of x [..., T] under the Kalman recurrence of datasets.ou_system: z_n = x_n - g_n, g_0 = 0,
     g_n = alpha_n g_(n-1) + beta_n x_(n-1) -- what ou_halfchi2 squares, and what whitens a baseline column as it whitens

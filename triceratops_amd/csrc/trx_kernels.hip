@@ -1,6 +1,6 @@
 // libtrx.so: the host side of the likelihood path and the C ABI (include/trx.h) for gfx950.
 //
-// The kernels live in seven headers that only this file includes:
+// The kernels live in eight headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
 //                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
@@ -19,6 +19,8 @@
 //                    exp and one log1p a value; chi2_robust_launch here; include/trx_robust.h)
 //   trx_gls.hpp      gls_ou_kernel<ONE, K> (chi2_ou_kernel's scan with K baseline columns marginalised under the same noise;
 //                    gls_ou_launch here; include/trx_gls.h)
+//   trx_ss2.hpp      ss2_kernel<ONE> (chi2_ou_kernel's layout for noise with a two-dimensional state: 2 x 2 affine maps in
+//                    the scan; ss2_launch here; include/trx_ss.h)
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
 // lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
@@ -44,6 +46,7 @@
 #include "../../include/trx_shift.h"
 #include "../../include/trx_robust.h"
 #include "../../include/trx_gls.h"
+#include "../../include/trx_ss.h"
 #include "trx_device.hpp"
 #include "trx_internal.hpp"
 #include "trx_knobs.hpp"
@@ -76,6 +79,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 #include "trx_softmin.hpp"
 #include "trx_robust.hpp"
 #include "trx_gls.hpp"
+#include "trx_ss2.hpp"
 #include "trx_bands.hpp"
 
 namespace {
@@ -1082,6 +1086,19 @@ void gls_ou_launch(const double* flux, const double* model_grid, int n_time, lon
                        accumulate, out, alpha, beta, omega, columns, M, coef_out);
 }
 
+// One launch of ss2_kernel<ONE> (trxs_chi2_grid_ss2): ONE as for chi2_ou_kernel.  No LDS, so the registers bound what stays
+// resident: 4 blocks of 256 threads a CU at up to 128 VGPRs (tests/test_build_resources_ss2.py), on 256 CUs; the rows
+// behind that cap are the second row of a wave's pass and its further passes.
+void ss2_launch(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth, double sec_limit,
+                int accumulate, double* out, const double* A, const double* g, const double* omega, hipStream_t st)
+{
+    long blocks = (n + 3) / 4;
+    if (blocks > 256L * 4) blocks = 256L * 4;
+    const auto kernel = n_time <= kOuTrip ? ss2_kernel<true> : ss2_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
+                       accumulate, out, A, g, omega);
+}
+
 // One launch of chi2_robust_kernel<STAGE> (trxr_chi2_grid_robust): STAGE while flux and inv_var fit the LDS budget of
 // chi2_rows_kernel, and chi2_rows_launch's cap of blocks -- 8 of 256 threads a CU, fewer where the staged vectors fill the
 // 160 KB of LDS, on 256 CUs.  The registers decide how many of them are resident at once (six at the 80 VGPRs the kernel
@@ -1267,6 +1284,19 @@ int trxg_chi2_grid_ou_baseline(const double* flux, const double* model_grid, int
     if (n == 0) return TRX_OK;
     gls_ou_launch<1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
                      columns, n_terms, M, coef_out, static_cast<hipStream_t>(stream));
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trxs_chi2_grid_ss2(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                       double sec_limit, int accumulate, double* out_halfchi2, const double* A, const double* g,
+                       const double* omega, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (!flux || !model_grid || !out_halfchi2 || !A || !g || !omega) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    if (n == 0) return TRX_OK;
+    ss2_launch(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, A, g, omega,
+               static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

@@ -5,7 +5,8 @@ A dataset is one light curve with its own cadence: `time`, `flux`, `flux_err` (o
 baseline offset of that light curve, marginalised per draw (inf: a flat prior), and `baseline` / `baseline_sigma`: up to
 MAX_BASELINE_TERMS columns B_k[t] of a linear baseline model sum_k c_k B_k[t] with priors c_k ~ N(0, s_k^2), marginalised
 the same way (baseline_system), or `red_sigma` / `red_timescale`: correlated noise of standard deviation s_r with an
-exponential kernel of time scale tau next to the white errors (ou_system), or `red_grid`: up to MAX_RED_CANDIDATES
+exponential kernel of time scale tau next to the white errors (ou_system) -- with `red_kernel` = "matern32" a Matern-3/2
+kernel, with "ou2" two exponential terms (ss2_system) --, or `red_grid`: up to MAX_RED_CANDIDATES
 weighted candidates (s_r, tau) of that noise, marginalised per draw (ou_mix_system); and next to any of these `t0_grid`: up
 to MAX_T0_NODES weighted shifts of its stamps, marginalised per draw (t0_grids); next to `red_sigma` / `red_timescale` (and
 `t0_grid`) alone `red_baseline` / `red_baseline_sigma`: up to MAX_BASELINE_TERMS baseline columns marginalised under that
@@ -43,6 +44,27 @@ class Dataset(NamedTuple):
     red_grid: np.ndarray = None         # [J][3] candidates (s_r, tau, weight) of the correlated noise, weights sum to 1; None
     red_sigma: float = None       # standard deviation of the correlated (Ornstein-Uhlenbeck) noise, flux units; None: white
     red_timescale: float = None   # its time scale, in the units of `time` (inf allowed); None without red_sigma
+
+    # The kernel of the correlated noise: None, the one exponential term of ou_system.  It is no field -- the fields are
+    # what a Dataset of today's keys compares by -- but the record's type: validate returns a Matern32Dataset or an
+    # Ou2Dataset for the other two kernels, and _replace (Datasets.renorm) keeps the type.
+    red_kernel = None
+
+
+class Matern32Dataset(Dataset):
+    """a Dataset whose correlated noise is a Matern-3/2 term: red_sigma = s, red_timescale = l, both finite floats"""
+    __slots__ = ()
+    red_kernel = "matern32"
+
+
+class Ou2Dataset(Dataset):
+    """a Dataset whose correlated noise is two exponential terms: red_sigma = (s_1, s_2), red_timescale = (tau_1, tau_2),
+    float64 arrays of two, all finite"""
+    __slots__ = ()
+    red_kernel = "ou2"
+
+
+RED_KERNELS = {"matern32": Matern32Dataset, "ou2": Ou2Dataset}
 
 
 class BaselineSystem(NamedTuple):
@@ -176,6 +198,46 @@ def _red_noise(i, sigma, timescale, time, others):
         raise ValueError("dataset %d: red_sigma needs time in non-decreasing order: the noise model is a process in "
                          "time and follows the stamps as given (a folded light curve is not sorted silently)" % i)
     return sigma, timescale
+
+
+def _red_kernel(i, value):
+    """a dataset's "red_kernel" -> None (absent, None or "ou": the one exponential term), "matern32" or "ou2" (the others)"""
+    if value is None or (isinstance(value, str) and value == "ou"):
+        return None
+    if not isinstance(value, str) or value not in RED_KERNELS:
+        raise ValueError("dataset %d: red_kernel must be None, 'ou', 'matern32' or 'ou2' (got %r)" % (i, value))
+    return value
+
+
+def _red_terms(i, kernel, sigma, timescale, time, others):
+    """a dataset's "red_sigma" and "red_timescale" under red_kernel = "matern32" (two finite numbers > 0) or "ou2" (two
+    arrays of two, every entry finite and > 0) -> (sigma, timescale) as floats or contiguous float64 arrays; time: the kept
+    stamps; others: the names of the keys of the dataset that do not stand next to these kernels"""
+    n = {"matern32": 0, "ou2": 2}[kernel]
+    want = "a finite number > 0" if n == 0 else "two finite numbers > 0"
+    out = []
+    for name, value in (("red_sigma", sigma), ("red_timescale", timescale)):
+        msg = "dataset %d: %s must be %s with red_kernel = %r (got %r)" % (i, name, want, kernel, value)
+        if value is None or isinstance(value, (bool, np.bool_, str, bytes)):
+            raise ValueError(msg)
+        try:
+            if not isinstance(value, np.ndarray) or value.dtype.kind not in "iuf":
+                # (a bool or a string among the entries would convert silently)
+                if any(isinstance(x, (bool, np.bool_, str, bytes)) for x in np.asarray(value, dtype=object).ravel()):
+                    raise TypeError
+            v = np.array(value, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(msg) from None
+        if v.shape != ((n,) if n else ()) or not np.all(np.isfinite(v) & (v > 0)):       # (also NaN)
+            raise ValueError(msg)
+        out.append(np.ascontiguousarray(v) if n else float(v))
+    if others:
+        raise ValueError("dataset %d: red_kernel = %r together with %s is not built: the kernel stands next to red_sigma / "
+                         "red_timescale and t0_grid alone" % (i, kernel, ", ".join(others)))
+    if np.any(np.diff(time) < 0):
+        raise ValueError("dataset %d: red_sigma needs time in non-decreasing order: the noise model is a process in "
+                         "time and follows the stamps as given (a folded light curve is not sorted silently)" % i)
+    return out[0], out[1]
 
 
 def _red_grid(i, value, time, others):
@@ -408,6 +470,72 @@ def ou_system(dataset):
     return alpha, beta, omega
 
 
+def ss2_system(dataset):
+    """(A [T][2][2], g [T][2], omega [T]), float64: the Kalman form of the noise covariance of a Dataset with red_kernel =
+    "matern32" or "ou2", K = diag(flux_err^2) + k(|t_i - t_j|), stamps in time order -- the one place that forms them, for the
+    device path (fused._Dataset) and for the numpy statement (_numerics.ss2_halfchi2).  The process has a state of dimension
+    two, written in a basis whose first component is what is observed, with the stationary covariance Pinf and the
+    transition Phi(dt):
+        matern32, k = s^2 (1 + lam dt) exp(-lam dt), lam = sqrt(3) / l, state (x, x' / lam):
+            Pinf = s^2 I,   Phi = exp(-lam dt) [[1 + lam dt, lam dt], [-lam dt, 1 - lam dt]];
+        ou2, k = s_1^2 exp(-dt / tau_1) + s_2^2 exp(-dt / tau_2), state (x_1 + x_2, x_2), a_i = exp(-dt / tau_i):
+            Pinf = [[s_1^2 + s_2^2, s_2^2], [s_2^2, s_2^2]],   Phi = [[a_1, a_2 - a_1], [0, a_2]].
+    The covariance recursion with the observation vector e_0 = (1, 0), from P_0 = Pinf:
+        S_n = P_n[0][0] + sigma_n^2,  k_n = P_n[:, 0] / S_n,  omega_n = 1 / S_n,  P_n+ = P_n - S_n k_n k_n^T,
+        P_(n+1) = Phi P_n+ Phi^T + Q,  Q = Pinf - Phi Pinf Phi^T,  Phi = Phi(t_(n+1) - t_n),
+        A_n = Phi (I - k_n e_0^T),  g_n = Phi k_n     (both zero for the last stamp),
+    so that 0.5 y^T K^-1 y = 0.5 sum_n omega_n z_n^2, z_n = y_n - u_(n-1)[0], u_(-1) = 0, u_n = A_n u_(n-1) + g_n y_n, and
+    ln det K = sum_n ln S_n.  Q is formed without the subtraction of near-equal matrices where a closed form allows it:
+    for ou2 from 1 - a_i^2 = -expm1(-2 dt / tau_i), as ou_system forms it."""
+    kernel = dataset.red_kernel
+    if kernel not in RED_KERNELS:
+        raise ValueError("ss2_system: a dataset with red_kernel 'matern32' or 'ou2' (got %r)" % (kernel,))
+    t, var = dataset.time, dataset.flux_err * dataset.flux_err
+    T = t.size
+    if kernel == "matern32":
+        s2, lam = float(dataset.red_sigma) ** 2, math.sqrt(3.0) / float(dataset.red_timescale)
+        p00, p01, p11 = s2, 0.0, s2
+
+        def step(dt):
+            x = lam * dt
+            e = math.exp(-x)
+            if e == 0.0:                                          # (also x = inf: no 0 * inf below)
+                return (0.0, 0.0, 0.0, 0.0), (s2, 0.0, s2)
+            e2 = math.exp(-2.0 * x)
+            # Q = s^2 (I - Phi Phi^T), Phi Phi^T = exp(-2 x) [[1 + 2 x + 2 x^2, -2 x^2], [-2 x^2, 1 - 2 x + 2 x^2]]
+            q00 = s2 * (-math.expm1(-2.0 * x) - e2 * (2.0 * x + 2.0 * x * x))
+            q01 = s2 * (e2 * 2.0 * x * x)
+            q11 = s2 * (-math.expm1(-2.0 * x) - e2 * (2.0 * x * x - 2.0 * x))
+            return (e * (1.0 + x), e * x, -(e * x), e * (1.0 - x)), (q00, q01, q11)
+    else:
+        s1, s2_ = (float(v) ** 2 for v in dataset.red_sigma)
+        tau1, tau2 = (float(v) for v in dataset.red_timescale)
+        p00, p01, p11 = s1 + s2_, s2_, s2_
+
+        def step(dt):
+            a1, a2 = math.exp(-dt / tau1), math.exp(-dt / tau2)
+            q1, q2 = s1 * -math.expm1(-2.0 * dt / tau1), s2_ * -math.expm1(-2.0 * dt / tau2)
+            return (a1, a2 - a1, 0.0, a2), (q1 + q2, q2, q2)
+    A, g, omega = np.zeros((T, 2, 2)), np.zeros((T, 2)), np.zeros(T)
+    for n in range(T):
+        S = p00 + float(var[n])
+        k0, k1 = p00 / S, p01 / S
+        omega[n] = 1.0 / S
+        if n == T - 1:
+            break
+        (f00, f01, f10, f11), (q00, q01, q11) = step(float(t[n + 1] - t[n]))
+        A[n] = ((f00 * (1.0 - k0) - f01 * k1, f01), (f10 * (1.0 - k0) - f11 * k1, f11))
+        g[n] = (f00 * k0 + f01 * k1, f10 * k0 + f11 * k1)
+        # P+ = P - S k k^T, then Phi P+ Phi^T + Q
+        u00, u01, u11 = (1.0 - k0) * p00, (1.0 - k0) * p01, p11 - p01 * k1
+        m00, m01 = f00 * u00 + f01 * u01, f00 * u01 + f01 * u11
+        m10, m11 = f10 * u00 + f11 * u01, f10 * u01 + f11 * u11
+        p00 = m00 * f00 + m01 * f01 + q00
+        p01 = m00 * f10 + m01 * f11 + q01
+        p11 = m10 * f10 + m11 * f11 + q11
+    return A, g, omega
+
+
 def ou_mix_system(dataset):
     """(alpha [J][T], beta [J][T], omega [J][T], lnc [J]), float64: ou_system of every candidate (s_j, tau_j, pi_j) of a
     Dataset's red_grid, and the candidates' log-weights
@@ -450,8 +578,9 @@ def _check_baseline(i, dataset):
 
 def validate(datasets):
     """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
-    baseline_sigma, red_sigma, red_timescale, red_grid, t0_grid, outlier_frac, outlier_scale, red_baseline,
-    red_baseline_sigma]} -> a list of Dataset ("t0_grid"
+    baseline_sigma, red_sigma, red_timescale, red_kernel, red_grid, t0_grid, outlier_frac, outlier_scale, red_baseline,
+    red_baseline_sigma]} -> a list of Dataset ("red_kernel" = "matern32" / "ou2" gives a Matern32Dataset / an Ou2Dataset: the
+    same fields, red_sigma and red_timescale two finite numbers / two arrays of two finite entries, all > 0; "t0_grid"
     is allowed here and read by t0_grids, "outlier_frac" / "outlier_scale" are checked here and returned by outliers,
     "red_baseline" / "red_baseline_sigma" are checked here and returned by red_baselines: no field
     of Dataset holds them).  Points with a NaN time or flux are dropped together with their error and their
@@ -465,7 +594,10 @@ def validate(datasets):
     normalised to sum 1, repeated pairs are allowed), that stands next to red_sigma / red_timescale, offset_sigma or
     baseline, or whose kept stamps are not in non-decreasing order; for outlier_frac without outlier_scale or the reverse, an
     outlier_frac outside (0, 0.5], an outlier_scale that is not a finite number > 1, or either of them next to
-    offset_sigma, baseline, red_sigma / red_timescale or red_grid; and for what red_baselines lists."""
+    offset_sigma, baseline, red_sigma / red_timescale or red_grid; for a red_kernel that is not None, "ou", "matern32" or
+    "ou2", and with the last two for a red_sigma or red_timescale of the wrong shape or with an entry that is not finite and
+    > 0, for stamps out of order, or for offset_sigma, baseline, red_grid, red_baseline or the outlier keys next to them; and
+    for what red_baselines lists."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -476,7 +608,7 @@ def validate(datasets):
     for i, d in enumerate(datasets):
         unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma",
                             "red_sigma", "red_timescale", "red_grid", "t0_grid", "outlier_frac", "outlier_scale",
-                            "red_baseline", "red_baseline_sigma"}
+                            "red_baseline", "red_baseline_sigma", "red_kernel"}
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -505,13 +637,20 @@ def validate(datasets):
             raise ValueError("dataset %d: nsamples must be >= 1" % i)
         baseline, baseline_sigma = _baseline(i, d.get("baseline"), d.get("baseline_sigma"), n_given, keep)
         offset_sigma = _offset_sigma(i, d.get("offset_sigma"))
-        red_sigma, red_timescale = _red_noise(i, d.get("red_sigma"), d.get("red_timescale"), time,
-                                              offset_sigma is not None or baseline is not None)
+        red_kernel = _red_kernel(i, d.get("red_kernel"))
+        if red_kernel is None:
+            red_sigma, red_timescale = _red_noise(i, d.get("red_sigma"), d.get("red_timescale"), time,
+                                                  offset_sigma is not None or baseline is not None)
+        else:
+            others = [k for k in ("offset_sigma", "baseline", "red_grid", "red_baseline", "red_baseline_sigma") + OUTLIER_KEYS
+                      if d.get(k) is not None]
+            red_sigma, red_timescale = _red_terms(i, red_kernel, d.get("red_sigma"), d.get("red_timescale"), time, others)
         red_grid = _red_grid(i, d.get("red_grid"), time,
                              offset_sigma is not None or baseline is not None or red_sigma is not None)
-        out.append(Dataset(np.ascontiguousarray(time), np.ascontiguousarray(flux), np.ascontiguousarray(err),
-                           float(d.get("exptime", DEFAULT_EXPTIME)), nsamples,
-                           offset_sigma, baseline, baseline_sigma, red_grid, red_sigma, red_timescale))
+        record = Dataset if red_kernel is None else RED_KERNELS[red_kernel]
+        out.append(record(np.ascontiguousarray(time), np.ascontiguousarray(flux), np.ascontiguousarray(err),
+                          float(d.get("exptime", DEFAULT_EXPTIME)), nsamples,
+                          offset_sigma, baseline, baseline_sigma, red_grid, red_sigma, red_timescale))
         _check_baseline(i, out[-1])
         _red_baseline(i, d, out[-1])
         _outliers(i, d, out[-1])

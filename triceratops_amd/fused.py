@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from . import _lib, funcs
-from .datasets import Datasets, baseline_system, ou_baseline_system, ou_mix_system, ou_system, robust_constants
+from .datasets import (Datasets, baseline_system, ou_baseline_system, ou_mix_system, ou_system, robust_constants,
+                       ss2_system)
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
@@ -231,6 +232,8 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # mean coefficients of the branch's best draw]} there, in the call's normalisation (target.dataset_baselines).
 # A dataset with `red_sigma` / `red_timescale` has correlated (Ornstein-Uhlenbeck) noise next to its white errors: its
 # reduction is trxn_chi2_grid_ou on the alpha, beta, omega of datasets.ou_system (grid evaluation only).
+# With `red_kernel` = "matern32" or "ou2" next to them the noise is a Matern-3/2 term or two exponential terms: a process with
+# a two-dimensional state, reduced by trxs_chi2_grid_ss2 on the A, g, omega of datasets.ss2_system (grid evaluation only).
 # A dataset with a `red_grid` has that noise's amplitude and time scale marginalised over its candidates per draw: its
 # reduction is trxm_chi2_grid_ou_mix on the tables and log-weights of datasets.ou_mix_system (grid evaluation only).
 # DATASET_RED_NOISE = {}: every such call leaves {work unit: [per branch, a list per dataset: None or the [J] posterior
@@ -784,6 +787,18 @@ def _mix_on_device(d, device):
     return _cached(_mix_cache, key, 32, build)
 
 
+_ss2_cache = {}
+
+
+def _ss2_on_device(d, device):
+    """(A [T][2][2], g [T][2], omega [T]) on the device of a dataset with red_kernel "matern32" or "ou2"
+    (datasets.ss2_system): formed once per content of its stamps, errors and noise keys -- T steps of a Python loop -- for
+    the lnZ_* calls of a star (a cache of its own, as _mix_on_device's)"""
+    terms = tuple(tuple(np.ravel(np.asarray(v, dtype=np.float64)).tolist()) for v in (d.red_sigma, d.red_timescale))
+    key = (tuple(hash(a.tobytes()) for a in (d.time, d.flux_err)), d.time.shape, d.red_kernel, terms, device.index)
+    return _cached(_ss2_cache, key, 32, lambda: tuple(_lib.dev(np.ascontiguousarray(v), device) for v in ss2_system(d)))
+
+
 _gls_cache = {}
 
 
@@ -837,7 +852,8 @@ class _Gls(NamedTuple):
 class _Dataset(NamedTuple):
     """one light curve of a Datasets call on the device, and what its reduction marginalises: nothing, a constant offset,
     or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then --, or correlated
-    noise -- alone (`ou`) or with baseline columns under it (`gls`: `ou` is None then) --, or the outlier mixture of its
+    noise -- one exponential term alone (`ou`) or with baseline columns under it (`gls`: `ou` is None then), or a term with
+    a two-dimensional state (`ss2`: `ou` is None then) --, or the outlier mixture of its
     points; and, next to any of these, the nodes of a transit-time shift (`shift`: the
     reduction then runs once per node)"""
     time: torch.Tensor
@@ -852,6 +868,7 @@ class _Dataset(NamedTuple):
     shift: Optional[tuple] = None            # (J device tensors time + shift_j, ln pi [J] on the host, ln pi on the device)
     robust: Optional[tuple] = None           # (c0, c1, k2): the outlier mixture of the points (datasets.robust_constants)
     gls: Optional[_Gls] = None               # baseline columns under correlated noise (datasets.ou_baseline_system)
+    ss2: Optional[tuple] = None              # (A, g, omega) on the device: red_kernel matern32 / ou2 (datasets.ss2_system)
 
     @classmethod
     def upload(cls, d, dev, t0_grid=None, outliers=None, red_baseline=None):
@@ -869,6 +886,9 @@ class _Dataset(NamedTuple):
         if red_baseline is not None:
             # (validate wants red_sigma / red_timescale next to it and refuses an offset, a baseline or a red_grid)
             return rec._replace(gls=_gls_on_device(d, red_baseline, dev))
+        if d.red_kernel is not None:
+            # (validate refuses anything but a t0_grid next to it)
+            return rec._replace(ss2=_ss2_on_device(d, dev))
         if d.red_sigma is not None:
             # (validate refuses an offset or a baseline next to it)
             return rec._replace(ou=tuple(_on_device(v, dev) for v in ou_system(d)))
@@ -889,7 +909,8 @@ class _Dataset(NamedTuple):
         the rows' scaled coefficients), trx_chi2_grid_offset for an offset alone (offset_out: the rows' offsets),
         trxn_chi2_grid_ou for correlated noise, trxm_chi2_grid_ou_mix for a grid of its candidates (cand_out: the rows'
         per-candidate chi^2/2), trxg_chi2_grid_ou_baseline for baseline columns under correlated noise (coef_out likewise),
-        trxr_chi2_grid_robust for the outlier mixture, else trx_chi2_grid_weighted."""
+        trxs_chi2_grid_ss2 for correlated noise with a two-dimensional state, trxr_chi2_grid_robust for the outlier mixture,
+        else trx_chi2_grid_weighted."""
         if self.robust is not None:
             return _lib.chi2_grid_robust(self.flux, self.inv_var, grid, *self.robust, secdepth, sec_limit, out=out)
         if self.mix is not None:
@@ -897,6 +918,8 @@ class _Dataset(NamedTuple):
         if self.gls is not None:
             return _lib.chi2_grid_ou_baseline(self.flux, grid, *self.gls.ou, self.gls.c, self.gls.minv, secdepth, sec_limit,
                                               out=out, coef_out=coef_out)
+        if self.ss2 is not None:
+            return _lib.chi2_grid_ss2(self.flux, grid, *self.ss2, secdepth, sec_limit, out=out)
         if self.ou is not None:
             return _lib.chi2_grid_ou(self.flux, grid, *self.ou, secdepth, sec_limit, out=out)
         if self.baseline is not None:
@@ -1433,6 +1456,9 @@ class _Scenario:
                                       "carries no recurrence along the row; use evaluation='grid'")
         if DATASET_EVALUATION == "fused" and any(d.ou is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a red_sigma dataset is not built: the fused kernel "
+                                      "carries no recurrence along the row; use evaluation='grid'")
+        if DATASET_EVALUATION == "fused" and any(d.ss2 is not None for d in self.datasets):
+            raise NotImplementedError("evaluation='fused' with a red_kernel dataset is not built: the fused kernel "
                                       "carries no recurrence along the row; use evaluation='grid'")
         if DATASET_EVALUATION == "fused" and any(d.mix is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a red_grid dataset is not built: the fused kernel "

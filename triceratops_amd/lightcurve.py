@@ -141,7 +141,7 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
                     exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None,
                     baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None,
                     red_grid=None, t0_grid=None, outlier_frac: float = None, outlier_scale: float = None,
-                    red_baseline_order: int = None, red_baseline_sigma=None):
+                    red_baseline_order: int = None, red_baseline_sigma=None, red_kernel: str = None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
     {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
     empty bins are dropped.
@@ -149,7 +149,8 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     baseline_order > 0: "baseline" = polynomial_baseline(kept bins' times, baseline_order), with baseline_sigma (a number
     or one per column; None: flat) passed through; 0: both keys are None.
     red_sigma, red_timescale (both or neither): the dataset's correlated noise, passed through as the keys of those names
-    when given.  red_grid (red_noise_grid's result, or any list of (s_r, tau, weight)): candidates of that noise to
+    when given; red_kernel ("ou", "matern32" or "ou2": the kernel of that noise, the last with two amplitudes and two time
+    scales) is passed through as the key "red_kernel" when given.  red_grid (red_noise_grid's result, or any list of (s_r, tau, weight)): candidates of that noise to
     marginalise, passed through as the key "red_grid" when given.  t0_grid (t0_shift_grid's result, or any list of (shift,
     weight)): nodes of a transit-time shift to marginalise, passed through as the key "t0_grid" when given.
     outlier_frac, outlier_scale (both or neither): the outlier-tolerant likelihood of the dataset's points, passed through
@@ -175,6 +176,8 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
            "baseline_sigma": baseline_sigma}
     if red_sigma is not None or red_timescale is not None:
         out["red_sigma"], out["red_timescale"] = red_sigma, red_timescale
+    if red_kernel is not None:
+        out["red_kernel"] = red_kernel
     if red_grid is not None:
         out["red_grid"] = red_grid
     if t0_grid is not None:

@@ -367,8 +367,8 @@ class target:
         for a dataset without "red_grid", else {"grid": the [J][3] candidates as validated (s_r, tau, normalised prior
         weight, in the units given), "weight": the [J] posterior weights of the candidates at the scenario's best draw,
         softmax_j(ln c_j - h_j) (NaN without a finite lnZ)}; the whole attribute is None when no dataset has a grid.
-        Not built: per-draw candidate posteriors, a continuous fit of s_r and tau, more than one term, red noise next to
-        offset or baseline.
+        Not built: per-draw candidate posteriors, a continuous fit of s_r and tau, candidates of another kernel than the
+        one exponential term, red noise next to offset or baseline.
 
         Where the transit time of a dataset is uncertain -- a follow-up night long after the ephemeris was measured --
         the dataset may carry "t0_grid" next to any of the keys above: 1 to 8 nodes (shift, weight), the shifts in the units
@@ -418,7 +418,24 @@ class target:
         else the [K_b] posterior-mean coefficients at the scenario's best draw, in flux units per unit of the column (NaN
         without a finite lnZ; with a t0_grid on its node of largest weight); the whole attribute is None when no dataset
         has the keys.  Not built: red_grid next to a baseline, the outlier keys next to any marginalised term, the fused
-        evaluation, more than one noise term, the scalar calc_probs path."""
+        evaluation, the columns under another kernel than the one exponential term, the scalar calc_probs path.
+
+        A dataset with red_sigma / red_timescale may name the kernel of that noise: "red_kernel": "ou", None or absent is
+        the one exponential term above, with its calls and its bits.  "matern32": red_sigma = s and red_timescale = l, both
+        finite and > 0, K = diag(sigma_t^2) + s^2 (1 + sqrt(3) D / l) exp(-sqrt(3) D / l), D = |t_i - t_j| -- smooth sample
+        paths, as airmass, seeing and drift are.  "ou2": red_sigma = (s_1, s_2) and red_timescale = (tau_1, tau_2), arrays
+        of two, every entry finite and > 0, K = diag(sigma_t^2) + s_1^2 exp(-D / tau_1) + s_2^2 exp(-D / tau_2) -- two time
+        scales, minutes and hours.  The dataset's term of the log-weight is 0.5 y^T K^-1 y as before, exact in O(len(time))
+        per draw: both processes have a state of dimension two, and the innovation form of their Kalman filter needs
+        per-stamp tables A [T][2][2], g [T][2], omega [T] that depend on the dataset alone (datasets.ss2_system,
+        _numerics.ss2_halfchi2, trxs_chi2_grid_ss2).  det K depends on the dataset only -- every s scales with the errors
+        when a light curve is renormalised to a star -- and is dropped as for the one term.  The stamps must be in
+        non-decreasing order; with these two kernels the dataset may stand next to "t0_grid" only: next to offset_sigma,
+        baseline, red_grid, red_baseline or the outlier keys, for a red_kernel that is none of the four values, for shapes
+        that do not fit the kernel or an entry that is not finite and > 0 (tau = inf stays the one term's business) it is a
+        ValueError.  Grid evaluation only: evaluation="fused" raises NotImplementedError.  Nothing new is reported per
+        best draw.  Not built: these kernels next to a baseline, red_grid or the outlier keys, a quasi-periodic (SHO) term,
+        more than two exponential terms, the fused evaluation, the scalar calc_probs path."""
         ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
         best_offsets = {} if ds.has_offsets else None
         best_baselines = {} if ds.has_baselines else None
