@@ -256,28 +256,28 @@ def ou_kernels():
 
 def ou_summary(trace):
     """per-launch times of the `ou_kernels` step from rocprofv3's kernel trace, by kernel, each shape's first (warm-up)
-    launch left out, and the ratio of chi2_ou_kernel to the plain reduction on the same grid"""
+    launch left out, and the ratio of scan_rows_kernel<ONE, OuFilter> to the plain reduction on the same grid"""
     lines, avg = [], {}
     for f in glob.glob(os.path.join(trace, "**", "*kernel_trace.csv"), recursive=True):
         groups = {}
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
-            if "chi2_rows_kernel" in name or "chi2_ou_kernel" in name:
+            if "chi2_rows_kernel" in name or "OuFilter>" in name:
                 groups.setdefault(name, []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
         for name, ns in groups.items():
-            # (the staged plain reduction runs on both shapes, six launches each, the large grid first; chi2_ou_kernel<false>
+            # (the staged plain reduction runs on both shapes, six launches each, the large grid first; the OU filter's <false>
             # on the large grid only, <true> -- one trip -- at 100 stamps only)
             shapes = ((N_GRID, N_TIME), (1_000_000, 100))
-            if "chi2_ou" in name:
+            if "OuFilter>" in name:
                 shapes = shapes[1:] if "<true" in name else shapes[:1]
             for part, (rows, nt) in zip((ns[i:i + 6] for i in range(0, len(ns), 6)), shapes):
-                avg[("ou" if "chi2_ou" in name else "plain", nt)] = a = sum(part[1:]) / max(len(part) - 1, 1)
+                avg[("ou" if "OuFilter>" in name else "plain", nt)] = a = sum(part[1:]) / max(len(part) - 1, 1)
                 gb = (rows * nt * 8 + rows * 8) / 1e9
                 lines.append("rocprofv3 %-44s %d x %d  %d launches  %.1f us  %.2f TB/s  (%.2f GB)\n"
                              % (name[:44], rows, nt, len(part) - 1, a * 1e-3, gb / (a * 1e-9) / 1e3, gb))
     for nt in (N_TIME, 100):
         if ("ou", nt) in avg and ("plain", nt) in avg:
-            lines.append("rocprofv3 chi2_ou_kernel / chi2_rows_kernel<Chi2Plain> at %d stamps: %.2f\n"
+            lines.append("rocprofv3 scan_rows_kernel<OuFilter> / chi2_rows_kernel<Chi2Plain> at %d stamps: %.2f\n"
                          % (nt, avg[("ou", nt)] / avg[("plain", nt)]))
     return "".join(lines)
 

@@ -1,10 +1,10 @@
 """Measurements of DESIGN.md section 14, baseline terms marginalised under red noise (`red_baseline` next to `red_sigma` /
-`red_timescale`, gls_ou_kernel).
+`red_timescale`, scan_rows_kernel<ONE, OuColsFilter<K>>).
 
   python profiles/gls/measure.py            the whole job: each GPU step a child process under its own time limit, the next
                                             one only after the last ended well; writes profiles/gls/results.txt (or --out FILE)
-  python profiles/gls/measure.py kernels    (a) gls_ou_kernel<ONE, K> (_lib.chi2_grid_ou_baseline) at K = 1, 2, 4 columns on a
-                                            512 MiB grid at n_time = 100 and 2048 against chi2_ou_kernel (_lib.chi2_grid_ou) on
+  python profiles/gls/measure.py kernels    (a) the OuColsFilter<K> kernel (_lib.chi2_grid_ou_baseline) at K = 1, 2, 4 columns on a
+                                            512 MiB grid at n_time = 100 and 2048 against the OuFilter kernel (_lib.chi2_grid_ou) on
                                             the same grid and tables: the same bytes, K more fmas a value and K more butterflies
                                             a row.  Nothing else in the library computes the column sums, so there is no operator
                                             alternative to hold against.  One warm-up of each, then five rounds in which the four

@@ -1,17 +1,17 @@
 """Measurements of DESIGN.md section 14, correlated noise with a two-dimensional state (`red_kernel` = "matern32" / "ou2" next
-to `red_sigma` / `red_timescale`, ss2_kernel).
+to `red_sigma` / `red_timescale`, scan_rows_kernel<ONE, Ss2Filter>).
 
   python profiles/ss2/measure.py            the whole job: each GPU step a child process under its own time limit, the next
                                             one only after the last ended well; writes profiles/ss2/results.txt (or --out FILE)
-  python profiles/ss2/measure.py kernels    (a) ss2_kernel<ONE> (_lib.chi2_grid_ss2) with a Matern-3/2 and a two-term table on
-                                            a 512 MiB grid at n_time = 100 and 2048 against chi2_ou_kernel (_lib.chi2_grid_ou) on
+  python profiles/ss2/measure.py kernels    (a) the Ss2Filter kernel (_lib.chi2_grid_ss2) with a Matern-3/2 and a two-term table on
+                                            a 512 MiB grid at n_time = 100 and 2048 against the OuFilter kernel (_lib.chi2_grid_ou) on
                                             the same grid: the same bytes, about four times the scan's arithmetic.  One warm-up
                                             of each, then five rounds in which they take turns, each run timed with device
                                             events; the best of the five
   python profiles/ss2/measure.py dense      (b) the only alternative without the kernel: torch.linalg.cholesky of K once, then
                                             torch.cholesky_solve on the residual matrix of the same grid and the row sums of
                                             r * K^-1 r; the factorisation is not timed
-  python profiles/ss2/measure.py pmc        (d) which resource bounds ss2_kernel: one rocprofv3 --pmc child (counters alone, no
+  python profiles/ss2/measure.py pmc        (d) which resource bounds the Ss2Filter kernel: one rocprofv3 --pmc child (counters alone, no
                                             tracing) of `once` -- every kernel of (a) launched twice on the same grids --, the
                                             SQ counters per dispatch summed by kernel.  Not part of the whole job: run it on
                                             its own (--out FILE appends the lines to FILE)
@@ -135,10 +135,11 @@ def pmc(path=None):
     for name in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         for row in csv.DictReader(open(name)):
             kernel = row["Kernel_Name"]
-            which = "ss2_kernel" if "ss2_kernel" in kernel else "chi2_ou_kernel" if "chi2_ou_kernel" in kernel else None
-            if which is None:
+            # (scan_rows_kernel<ONE, Ss2Filter> and <ONE, OuFilter>; the lines keep the names results.txt has)
+            which = "ss2_kernel" if "Ss2Filter" in kernel else "chi2_ou_kernel" if "OuFilter" in kernel else None
+            if which is None or "scan_rows_kernel" not in kernel:
                 continue
-            key = (which + ("<ONE> 100 stamps" if ("<true>" in kernel or "ILb1E" in kernel) else " 2048 stamps"))
+            key = (which + ("<ONE> 100 stamps" if ("<true" in kernel or "ILb1E" in kernel) else " 2048 stamps"))
             total.setdefault(key, {}).setdefault(row["Counter_Name"], 0.0)
             total[key][row["Counter_Name"]] += float(row["Counter_Value"])
             count.setdefault(key, set()).add(row["Dispatch_Id"])

@@ -7,6 +7,7 @@ import re
 import shutil
 import struct
 import subprocess
+import tempfile
 
 import pytest
 
@@ -32,6 +33,33 @@ def _device_objects(path):
             if "gfx950" in name and s:
                 out.append(blob[i + o:i + o + s])
         at = i + len(magic)
+
+
+def kernel_resources(path):
+    """{mangled kernel name: (VGPRs, SGPRs, bytes of scratch a lane, bytes of static LDS)} of the gfx950 code objects in
+    the library at `path`, from their notes."""
+    objs = _device_objects(path)
+    assert objs, "no gfx950 code object in %s" % path
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for k, obj in enumerate(objs):
+            f = os.path.join(tmp, "dev%d.co" % k)
+            with open(f, "wb") as fh:
+                fh.write(obj)
+            notes = subprocess.run([READELF, "--notes", f], capture_output=True, text=True, check=True).stdout
+            for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?"
+                                 r"\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.sgpr_count:\s+(\d+)\n(?:.*\n)*?"
+                                 r"\s+\.vgpr_count:\s+(\d+)", notes):
+                out[m.group(2)] = (int(m.group(5)), int(m.group(4)), int(m.group(3)), int(m.group(1)))
+    return out
+
+
+def instantiations(resources, kernel, *tags):
+    """The entries of a kernel_resources table whose name is an instantiation of `kernel` and holds every one of `tags`.
+    Names are Itanium-mangled, every identifier behind its length: "16scan_rows_kernel" and "8OuFilter" match that
+    identifier alone, not a longer one that ends in it."""
+    want = ["%d%s" % (len(t), t) for t in (kernel,) + tags]
+    return {name: r for name, r in resources.items() if all(w in name for w in want)}
 
 
 @pytest.mark.skipif(not os.path.exists(READELF), reason="llvm-readelf not installed")

@@ -519,14 +519,15 @@ def chi2_grid(flux_d, grid_d, sigma):
     return out
 
 
-def _chi2_rows(entry, flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out, *extra):
-    """What chi2_grid_weighted, chi2_grid_offset and chi2_grid_baseline share: the checks of the grid, the light curve, the
-    secondary depths and `out`, a fresh `out` unless one is given to add to, and the call of libtrx's `entry` -- `extra`:
-    its arguments between out_halfchi2 and the stream."""
+def _chi2_rows(entry, curve, grid_d, secdepth_d, sec_limit, out, *extra):
+    """What the row reductions of a materialised grid share: the checks of the grid, the light curve, the secondary depths
+    and `out`, a fresh `out` unless one is given to add to, and the call of libtrx's `entry`.  curve: the [n_time] vectors
+    of the light curve that `entry` takes in front of the grid, (flux, inv_var) or (flux,); `extra`: its arguments between
+    out_halfchi2 and the stream."""
     require_gpu()
     n, nt = grid_d.shape
     assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
-    assert flux_d.numel() == nt and inv_var_d.numel() == nt and flux_d.is_contiguous() and inv_var_d.is_contiguous()
+    assert all(v.numel() == nt and v.is_contiguous() for v in curve)
     assert secdepth_d is None or (secdepth_d.numel() == n and secdepth_d.is_contiguous())
     accumulate = out is not None
     if out is None:
@@ -535,7 +536,7 @@ def _chi2_rows(entry, flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out, *ex
     if n == 0:
         return out                     # (an empty tensor has no address to pass)
     with torch.cuda.device(grid_d.device):
-        check(getattr(lib(), entry)(flux_d.data_ptr(), inv_var_d.data_ptr(), grid_d.data_ptr(), nt, n,
+        check(getattr(lib(), entry)(*(v.data_ptr() for v in curve), grid_d.data_ptr(), nt, n,
                                     secdepth_d.data_ptr() if secdepth_d is not None else None, float(sec_limit),
                                     int(accumulate), out.data_ptr(), *extra, _stream(grid_d)))
     return out
@@ -545,7 +546,7 @@ def chi2_grid_weighted(flux_d, inv_var_d, grid_d, secdepth_d=None, sec_limit=flo
     """0.5 * sum_t inv_var[t] (flux[t] - grid[r][t])^2 per row of an [n][n_time] device grid (trx_chi2_grid_weighted);
     +inf where secdepth_d[r] >= sec_limit.  out: an [n] fp64 device tensor to ADD the rows' values to (the next light
     curve of an evidence over several); None: a fresh tensor.  Rows may start at any 8-byte boundary (a view's offset)."""
-    return _chi2_rows("trx_chi2_grid_weighted", flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out)
+    return _chi2_rows("trx_chi2_grid_weighted", (flux_d, inv_var_d), grid_d, secdepth_d, sec_limit, out)
 
 
 def chi2_grid_offset(flux_d, inv_var_d, grid_d, sum_w, prior_prec, secdepth_d=None, sec_limit=float("inf"), out=None,
@@ -557,7 +558,7 @@ def chi2_grid_offset(flux_d, inv_var_d, grid_d, sum_w, prior_prec, secdepth_d=No
     chi2_grid_weighted's."""
     assert offset_out is None or (offset_out.shape == (grid_d.shape[0],) and offset_out.dtype == torch.float64
                                   and offset_out.is_contiguous())
-    return _chi2_rows("trx_chi2_grid_offset", flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out, float(sum_w),
+    return _chi2_rows("trx_chi2_grid_offset", (flux_d, inv_var_d), grid_d, secdepth_d, sec_limit, out, float(sum_w),
                       float(prior_prec), offset_out.data_ptr() if offset_out is not None else None)
 
 
@@ -576,7 +577,7 @@ def chi2_grid_baseline(flux_d, inv_var_d, grid_d, wbasis_d, minv, secdepth_d=Non
     assert minv.size == k * (k + 1) // 2, "minv: the packed upper triangle of a %d x %d matrix" % (k, k)
     assert coef_out is None or (coef_out.shape == (n, k) and coef_out.dtype == torch.float64
                                 and coef_out.is_contiguous())
-    return _chi2_rows("trx_chi2_grid_baseline", flux_d, inv_var_d, grid_d, secdepth_d, sec_limit, out, wbasis_d.data_ptr(),
+    return _chi2_rows("trx_chi2_grid_baseline", (flux_d, inv_var_d), grid_d, secdepth_d, sec_limit, out, wbasis_d.data_ptr(),
                       k, minv.ctypes.data, coef_out.data_ptr() if coef_out is not None else None)
 
 
@@ -586,7 +587,7 @@ def chi2_grid_robust(flux_d, inv_var_d, grid_d, c0, c1, k2, secdepth=None, sec_l
     sum_t (lo_t - log1p(exp(-|A_t - B_t|))), A_t = a_t + c0, B_t = a_t k2 + c1, lo_t = min(A_t, B_t),
     a_t = 0.5 inv_var[t] (flux[t] - grid[r][t])^2, clamped at 0 and not halved.  c0, c1, k2: datasets.robust_constants.  The
     other arguments are chi2_grid_weighted's."""
-    return _chi2_rows("trxr_chi2_grid_robust", flux_d, inv_var_d, grid_d, secdepth, sec_limit, out, float(c0), float(c1),
+    return _chi2_rows("trxr_chi2_grid_robust", (flux_d, inv_var_d), grid_d, secdepth, sec_limit, out, float(c0), float(c1),
                       float(k2))
 
 
@@ -595,24 +596,11 @@ def chi2_grid_ou(flux_d, grid_d, alpha_d, beta_d, omega_d, secdepth=None, sec_li
     include/trx_noise.h): per row 0.5 sum_n omega[n] (y_n - g_n)^2, y = flux - grid[r], g_0 = 0,
     g_n = alpha[n] g_(n-1) + beta[n] y_(n-1).  alpha_d, beta_d, omega_d: [n_time] fp64 device tensors
     (datasets.ou_system).  The other arguments are chi2_grid_weighted's."""
-    require_gpu()
-    n, nt = grid_d.shape
-    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    nt = grid_d.shape[1]
     for v in (flux_d, alpha_d, beta_d, omega_d):
         assert v.numel() == nt and v.dtype == torch.float64 and v.is_contiguous()
-    assert secdepth is None or (secdepth.numel() == n and secdepth.is_contiguous())
-    accumulate = out is not None
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
-    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
-    if n == 0:
-        return out                     # (an empty tensor has no address to pass)
-    with torch.cuda.device(grid_d.device):
-        check(lib().trxn_chi2_grid_ou(flux_d.data_ptr(), grid_d.data_ptr(), nt, n,
-                                      secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
-                                      int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
-                                      omega_d.data_ptr(), _stream(grid_d)))
-    return out
+    return _chi2_rows("trxn_chi2_grid_ou", (flux_d,), grid_d, secdepth, sec_limit, out, alpha_d.data_ptr(),
+                      beta_d.data_ptr(), omega_d.data_ptr())
 
 
 def chi2_grid_ss2(flux_d, grid_d, A_d, g_d, omega_d, secdepth=None, sec_limit=float("inf"), out=None):
@@ -620,24 +608,11 @@ def chi2_grid_ss2(flux_d, grid_d, A_d, g_d, omega_d, secdepth=None, sec_limit=fl
     -- (trxs_chi2_grid_ss2, include/trx_ss.h): per row 0.5 sum_n omega[n] z_n^2, y = flux - grid[r], u_(-1) = 0,
     z_n = y_n - u_(n-1)[0], u_n = A[n] u_(n-1) + g[n] y_n.  A_d [n_time][2][2], g_d [n_time][2], omega_d [n_time]: fp64 device
     tensors (datasets.ss2_system).  The other arguments are chi2_grid_weighted's."""
-    require_gpu()
-    n, nt = grid_d.shape
-    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
+    nt = grid_d.shape[1]
     for v, per in ((flux_d, 1), (A_d, 4), (g_d, 2), (omega_d, 1)):
         assert v.numel() == per * nt and v.dtype == torch.float64 and v.is_contiguous()
-    assert secdepth is None or (secdepth.numel() == n and secdepth.is_contiguous())
-    accumulate = out is not None
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
-    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
-    if n == 0:
-        return out                     # (an empty tensor has no address to pass)
-    with torch.cuda.device(grid_d.device):
-        check(lib().trxs_chi2_grid_ss2(flux_d.data_ptr(), grid_d.data_ptr(), nt, n,
-                                       secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
-                                       int(accumulate), out.data_ptr(), A_d.data_ptr(), g_d.data_ptr(),
-                                       omega_d.data_ptr(), _stream(grid_d)))
-    return out
+    return _chi2_rows("trxs_chi2_grid_ss2", (flux_d,), grid_d, secdepth, sec_limit, out, A_d.data_ptr(), g_d.data_ptr(),
+                      omega_d.data_ptr())
 
 
 def chi2_grid_ou_baseline(flux_d, grid_d, alpha_d, beta_d, omega_d, cols_d, minv, secdepth=None, sec_limit=float("inf"),
@@ -648,9 +623,7 @@ def chi2_grid_ou_baseline(flux_d, grid_d, alpha_d, beta_d, omega_d, cols_d, minv
     columns; minv: the K (K + 1) / 2 entries of the upper triangle of M by rows, on the host (datasets.ou_baseline_system);
     K = 1 .. 4.  coef_out: an [n][K] fp64 device tensor that receives the scaled posterior-mean coefficients M b, or None.
     The other arguments are chi2_grid_ou's."""
-    require_gpu()
     n, nt = grid_d.shape
-    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
     for v in (flux_d, alpha_d, beta_d, omega_d):
         assert v.numel() == nt and v.dtype == torch.float64 and v.is_contiguous()
     assert cols_d.dim() == 2 and cols_d.shape[1] == nt and cols_d.dtype == torch.float64 and cols_d.is_contiguous()
@@ -658,21 +631,10 @@ def chi2_grid_ou_baseline(flux_d, grid_d, alpha_d, beta_d, omega_d, cols_d, minv
     assert 1 <= k <= 4, "1 .. 4 columns (got %d)" % k
     minv = np.ascontiguousarray(minv, dtype=np.float64).reshape(-1)
     assert minv.size == k * (k + 1) // 2, "minv: the packed upper triangle of a %d x %d matrix" % (k, k)
-    assert secdepth is None or (secdepth.numel() == n and secdepth.is_contiguous())
     assert coef_out is None or (coef_out.shape == (n, k) and coef_out.dtype == torch.float64 and coef_out.is_contiguous())
-    accumulate = out is not None
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
-    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
-    if n == 0:
-        return out                     # (an empty tensor has no address to pass)
-    with torch.cuda.device(grid_d.device):
-        check(lib().trxg_chi2_grid_ou_baseline(flux_d.data_ptr(), grid_d.data_ptr(), nt, n,
-                                               secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
-                                               int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
-                                               omega_d.data_ptr(), cols_d.data_ptr(), k, minv.ctypes.data,
-                                               coef_out.data_ptr() if coef_out is not None else None, _stream(grid_d)))
-    return out
+    return _chi2_rows("trxg_chi2_grid_ou_baseline", (flux_d,), grid_d, secdepth, sec_limit, out, alpha_d.data_ptr(),
+                      beta_d.data_ptr(), omega_d.data_ptr(), cols_d.data_ptr(), k, minv.ctypes.data,
+                      coef_out.data_ptr() if coef_out is not None else None)
 
 
 def chi2_grid_ou_mix(flux_d, grid_d, alpha_d, beta_d, omega_d, lnc, secdepth=None, sec_limit=float("inf"), out=None,
@@ -681,30 +643,17 @@ def chi2_grid_ou_mix(flux_d, grid_d, alpha_d, beta_d, omega_d, lnc, secdepth=Non
     row T = -ln sum_j exp(lnc[j] - h_j), h_j what chi2_grid_ou gives on row j of alpha_d, beta_d, omega_d ([J][n_time] fp64
     device tensors; datasets.ou_mix_system), clamped at 0.  lnc: [J] float64 on the host.  cand_out: an [n][J] fp64 device
     tensor that receives the h_j, or None.  The other arguments are chi2_grid_weighted's."""
-    require_gpu()
     n, nt = grid_d.shape
-    assert grid_d.dtype == torch.float64 and grid_d.is_contiguous()
-    assert flux_d.numel() == nt and flux_d.dtype == torch.float64 and flux_d.is_contiguous()
+    assert flux_d.dtype == torch.float64
     lnc = np.ascontiguousarray(lnc, dtype=np.float64)
     assert lnc.ndim == 1
     j = int(lnc.size)
     for v in (alpha_d, beta_d, omega_d):
         assert v.shape == (j, nt) and v.dtype == torch.float64 and v.is_contiguous()
-    assert secdepth is None or (secdepth.numel() == n and secdepth.is_contiguous())
     assert cand_out is None or (cand_out.shape == (n, j) and cand_out.dtype == torch.float64 and cand_out.is_contiguous())
-    accumulate = out is not None
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=grid_d.device)
-    assert out.shape == (n,) and out.dtype == torch.float64 and out.is_contiguous()
-    if n == 0:
-        return out                     # (an empty tensor has no address to pass)
-    with torch.cuda.device(grid_d.device):
-        check(lib().trxm_chi2_grid_ou_mix(flux_d.data_ptr(), grid_d.data_ptr(), nt, n,
-                                          secdepth.data_ptr() if secdepth is not None else None, float(sec_limit),
-                                          int(accumulate), out.data_ptr(), alpha_d.data_ptr(), beta_d.data_ptr(),
-                                          omega_d.data_ptr(), j, lnc.ctypes.data,
-                                          cand_out.data_ptr() if cand_out is not None else None, _stream(grid_d)))
-    return out
+    return _chi2_rows("trxm_chi2_grid_ou_mix", (flux_d,), grid_d, secdepth, sec_limit, out, alpha_d.data_ptr(),
+                      beta_d.data_ptr(), omega_d.data_ptr(), j, lnc.ctypes.data,
+                      cand_out.data_ptr() if cand_out is not None else None)
 
 
 def softmin_rows(cand_d, lnc, out=None):

@@ -1,6 +1,6 @@
 // libtrx.so: the host side of the likelihood path and the C ABI (include/trx.h) for gfx950.
 //
-// The kernels live in eight headers that only this file includes:
+// The kernels live in nine headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
 //                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
@@ -9,18 +9,19 @@
 //                    device share (RowsArgs, batch_rows, batch_plan, set_scratch)
 //   trx_reduce.hpp   chi2_grid_kernel, chi2_rows_kernel<STAGE, Terms> (row reductions over a materialised grid; one launcher
 //                    here, chi2_rows_launch) and the log-mean-exp kernels, HBM bound
-//   trx_noise.hpp    chi2_ou_kernel<ONE> (the row reduction under correlated noise: a scan along the row; chi2_ou_launch
-//                    here; include/trx_noise.h)
+//   trx_scan.hpp     scan_rows_kernel<ONE, Filter> (the row reductions under correlated noise: a scan along the row, what
+//                    differs in a Filter; one launcher here, scan_rows_launch) and the pieces its filters and ou_mix_kernel
+//                    share
+//   trx_noise.hpp    OuFilter (one exponential term; include/trx_noise.h)
 //   trx_noise_mix.hpp  ou_mix_kernel<ONE, J> (the same for J candidate noise models in one pass, their soft minimum per
-//                    row; ou_mix_launch here; include/trx_mix.h)
+//                    row: a kernel of its own through scan_rows_launch; include/trx_mix.h)
 //   trx_softmin.hpp  softmin_rows_kernel<J> (the soft minimum of J candidate values per row, one lane a row;
-//                    softmin_launch_j here; include/trx_shift.h)
+//                    softmin_launch here; include/trx_shift.h)
 //   trx_robust.hpp   chi2_robust_kernel<STAGE> (the outlier-tolerant row reduction: a two-component mixture per point, one
 //                    exp and one log1p a value; chi2_robust_launch here; include/trx_robust.h)
-//   trx_gls.hpp      gls_ou_kernel<ONE, K> (chi2_ou_kernel's scan with K baseline columns marginalised under the same noise;
-//                    gls_ou_launch here; include/trx_gls.h)
-//   trx_ss2.hpp      ss2_kernel<ONE> (chi2_ou_kernel's layout for noise with a two-dimensional state: 2 x 2 affine maps in
-//                    the scan; ss2_launch here; include/trx_ss.h)
+//   trx_gls.hpp      OuColsFilter<K> (the OU filter with K baseline columns marginalised under the same noise;
+//                    include/trx_gls.h)
+//   trx_ss2.hpp      Ss2Filter (noise with a two-dimensional state: 2 x 2 affine maps in the scan; include/trx_ss.h)
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
 // lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
@@ -37,6 +38,7 @@
 #include <cstdint>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -74,6 +76,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 
 #include "trx_cells.hpp"
 #include "trx_reduce.hpp"
+#include "trx_scan.hpp"
 #include "trx_noise.hpp"
 #include "trx_noise_mix.hpp"
 #include "trx_softmin.hpp"
@@ -1026,77 +1029,58 @@ void chi2_rows_launch(const double* flux, const double* inv_var, const double* m
                        sec_limit, accumulate, out, terms);
 }
 
-// One launch of chi2_ou_kernel<ONE> (trxn_chi2_grid_ou): ONE while a row is a single trip of kOuTrip stamps.  No LDS, so
-// the registers bound what stays resident: 4 blocks of 256 threads a CU at up to 128 VGPRs, on 256 CUs; the rows behind
-// that cap are the second row of a wave's pass and its further passes.
-void chi2_ou_launch(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
-                    double sec_limit, int accumulate, double* out, const double* alpha, const double* beta,
-                    const double* omega, hipStream_t st)
+// One launch of the red-noise row reductions (trxn_chi2_grid_ou, trxs_chi2_grid_ss2, trxg_chi2_grid_ou_baseline,
+// trxm_chi2_grid_ou_mix): `one` -- scan_rows_kernel<true, Filter>, ou_mix_kernel<true, J> -- while a row is a single trip
+// of kOuTrip stamps, `trips` past that; p: the filter, or ou_mix_kernel's OuMix.  No dynamic LDS, so the registers bound
+// what stays resident: blocks_per_cu = 4 blocks of 256 threads a CU at up to 128 VGPRs, 2 at up to 256 (two waves a SIMD;
+// ou_mix_kernel's up to 52 KB of LDS a block fit as well), on 256 CUs.  The rows behind that cap are the second row of a
+// wave's pass and its further passes.
+template <class P>
+using ScanKernel = void (*)(const double*, const double*, int, long, const double*, double, int, double*, P);
+
+template <class P>
+void scan_rows_launch(ScanKernel<P> one, ScanKernel<P> trips, const double* flux, const double* model_grid, int n_time,
+                      long n, const double* secdepth, double sec_limit, int accumulate, double* out, const P& p,
+                      int blocks_per_cu, hipStream_t st)
 {
     long blocks = (n + 3) / 4;
-    if (blocks > 256L * 4) blocks = 256L * 4;
-    const auto kernel = n_time <= kOuTrip ? chi2_ou_kernel<true> : chi2_ou_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
-                       accumulate, out, alpha, beta, omega);
+    if (blocks > 256L * blocks_per_cu) blocks = 256L * blocks_per_cu;
+    hipLaunchKernelGGL(n_time <= kOuTrip ? one : trips, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time,
+                       n, secdepth, sec_limit, accumulate, out, p);
 }
 
-// One launch of ou_mix_kernel<ONE, J> (trxm_chi2_grid_ou_mix): ONE as for chi2_ou_kernel, J = n_cand.  Up to J = 2 the
-// kernel stays within 128 VGPRs and 4 blocks of 256 threads a CU are resident, as for chi2_ou_kernel; past that it holds two
-// waves a SIMD (at most 256 VGPRs, and up to 52 KB of LDS a block): 2 blocks a CU, on 256 CUs.  The rows behind that cap are
-// the second row of a wave's pass and its further passes.
-template <int J>
-void ou_mix_launch_j(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
-                     double sec_limit, int accumulate, double* out, const double* alpha, const double* beta,
-                     const double* omega, int n_cand, const OuMixLnc& lnc, double* cand_out, hipStream_t st)
+// f(std::integral_constant<int, N>{}) with N = n, for the instantiations of LO .. HI (the callers have checked the range;
+// an n outside it takes HI)
+template <int LO, int HI, class F>
+void dispatch_int(int n, const F& f)
 {
-    if constexpr (J < kOuMixMax) {
-        if (n_cand != J)
-            return ou_mix_launch_j<J + 1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out, alpha, beta,
-                                          omega, n_cand, lnc, cand_out, st);
+    if constexpr (LO < HI) {
+        if (n != LO) return dispatch_int<LO + 1, HI>(n, f);
     }
-    long blocks = (n + 3) / 4;
-    const long resident = 256L * (J <= 2 ? 4 : 2);
-    if (blocks > resident) blocks = resident;
-    const auto kernel = n_time <= kOuTrip ? ou_mix_kernel<true, J> : ou_mix_kernel<false, J>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
-                       accumulate, out, alpha, beta, omega, lnc, cand_out);
+    f(std::integral_constant<int, LO>{});
 }
 
-// One launch of gls_ou_kernel<ONE, K> (trxg_chi2_grid_ou_baseline): ONE as for chi2_ou_kernel, K = n_terms.  No LDS, so the
-// registers bound what stays resident: below kGlsWideFrom columns the kernel stays within 128 VGPRs and 4 blocks of 256
-// threads a CU are resident, from there on it would hold two waves a SIMD (at most 256 VGPRs): 2 blocks a CU, on 256 CUs.
-// As built every K = 1 .. 4 is within 128 (trx_gls.hpp).  The rows behind that cap are the second row of a wave's pass and
-// its further passes.
-template <int K>
-void gls_ou_launch(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
-                   double sec_limit, int accumulate, double* out, const double* alpha, const double* beta,
-                   const double* omega, const double* columns, int n_terms, const Chi2bM& M, double* coef_out,
-                   hipStream_t st)
+// The packed upper triangle of the n_terms x n_terms matrix M from the caller's array, and the log-weights of n_cand
+// candidates (`what`: the caller's word for one): by value in the kernel arguments, so they are checked on the way.
+int pack_minv(const double* minv, int n_terms, Chi2bM& M)
 {
-    if constexpr (K < kChi2bMaxTerms) {
-        if (n_terms != K)
-            return gls_ou_launch<K + 1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out, alpha, beta,
-                                        omega, columns, n_terms, M, coef_out, st);
+    M = Chi2bM{};
+    for (int i = 0; i < n_terms * (n_terms + 1) / 2; ++i) {
+        if (!(minv[i] - minv[i] == 0.0))                    // (NaN or +-inf)
+            return fail(TRX_ERR_ARG, "minv must be finite%s (entry %ld)", "", (long)i);
+        M.m[i] = minv[i];
     }
-    long blocks = (n + 3) / 4;
-    const long resident = 256L * (K < kGlsWideFrom ? 4 : 2);
-    if (blocks > resident) blocks = resident;
-    const auto kernel = n_time <= kOuTrip ? gls_ou_kernel<true, K> : gls_ou_kernel<false, K>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
-                       accumulate, out, alpha, beta, omega, columns, M, coef_out);
+    return TRX_OK;
 }
 
-// One launch of ss2_kernel<ONE> (trxs_chi2_grid_ss2): ONE as for chi2_ou_kernel.  No LDS, so the registers bound what stays
-// resident: 4 blocks of 256 threads a CU at up to 128 VGPRs (tests/test_build_resources_ss2.py), on 256 CUs; the rows
-// behind that cap are the second row of a wave's pass and its further passes.
-void ss2_launch(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth, double sec_limit,
-                int accumulate, double* out, const double* A, const double* g, const double* omega, hipStream_t st)
+int pack_lnc(const double* lnc, int n_cand, const char* what, Lnc8& c)
 {
-    long blocks = (n + 3) / 4;
-    if (blocks > 256L * 4) blocks = 256L * 4;
-    const auto kernel = n_time <= kOuTrip ? ss2_kernel<true> : ss2_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, flux, model_grid, n_time, n, secdepth, sec_limit,
-                       accumulate, out, A, g, omega);
+    c = Lnc8{};
+    for (int j = 0; j < n_cand; ++j) {
+        if (!(lnc[j] < INFINITY)) return fail(TRX_ERR_ARG, "lnc is NaN or +inf (%s %ld)", what, j);
+        c.v[j] = lnc[j];
+    }
+    return TRX_OK;
 }
 
 // One launch of chi2_robust_kernel<STAGE> (trxr_chi2_grid_robust): STAGE while flux and inv_var fit the LDS budget of
@@ -1122,17 +1106,15 @@ void chi2_robust_launch(const double* flux, const double* inv_var, const double*
 
 // One launch of softmin_rows_kernel<J> (trxt_softmin_rows), J = n_cand: one lane per row, and as many blocks as the draw
 // kernel's cap -- 16 of 256 threads a CU, on 256 CUs; the rows behind that cap are a lane's further trips.
-template <int J>
-void softmin_launch_j(const double* cand, long stride, long n, int n_cand, const SoftminLnc& lnc, int accumulate,
-                      double* out, hipStream_t st)
+void softmin_launch(const double* cand, long stride, long n, int n_cand, const Lnc8& lnc, int accumulate, double* out,
+                    hipStream_t st)
 {
-    if constexpr (J < kSoftminMax) {
-        if (n_cand != J) return softmin_launch_j<J + 1>(cand, stride, n, n_cand, lnc, accumulate, out, st);
-    }
     long blocks = (n + 255) / 256;
     if (blocks > 256L * 16) blocks = 256L * 16;
-    hipLaunchKernelGGL(softmin_rows_kernel<J>, dim3((unsigned)blocks), dim3(256), 0, st, cand, stride, n, lnc, accumulate,
-                       out);
+    dispatch_int<1, kSoftminMax>(n_cand, [&](auto j) {
+        hipLaunchKernelGGL(softmin_rows_kernel<decltype(j)::value>, dim3((unsigned)blocks), dim3(256), 0, st, cand, stride,
+                           n, lnc, accumulate, out);
+    });
 }
 }  // namespace
 
@@ -1237,8 +1219,9 @@ int trxn_chi2_grid_ou(const double* flux, const double* model_grid, int n_time, 
     if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
     if (!flux || !model_grid || !out_halfchi2 || !alpha || !beta || !omega) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
     if (n == 0) return TRX_OK;
-    chi2_ou_launch(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
-                   static_cast<hipStream_t>(stream));
+    scan_rows_launch(scan_rows_kernel<true, OuFilter>, scan_rows_kernel<false, OuFilter>, flux, model_grid, n_time, n,
+                     secdepth, sec_limit, accumulate, out_halfchi2, OuFilter{alpha, beta, omega}, 4,
+                     static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }
@@ -1252,14 +1235,15 @@ int trxm_chi2_grid_ou_mix(const double* flux, const double* model_grid, int n_ti
     if (!flux || !model_grid || !out_halfchi2 || !alpha || !beta || !omega || !lnc)
         return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
     static_assert(TRXM_MAX_CANDIDATES == kOuMixMax, "the header's limit is the kernel's");
-    OuMixLnc c = {};
-    for (int j = 0; j < n_cand; ++j) {
-        if (!(lnc[j] < INFINITY)) return fail(TRX_ERR_ARG, "lnc is NaN or +inf%s (candidate %ld)", "", j);
-        c.v[j] = lnc[j];
-    }
+    OuMix mix{alpha, beta, omega, {}, cand_out};
+    if (int rc = pack_lnc(lnc, n_cand, "candidate", mix.lnc)) return rc;
     if (n == 0) return TRX_OK;
-    ou_mix_launch_j<1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
-                       n_cand, c, cand_out, static_cast<hipStream_t>(stream));
+    // (up to J = 2 the kernel stays within 128 VGPRs, as the OU filter's; past that it holds two waves a SIMD)
+    dispatch_int<1, kOuMixMax>(n_cand, [&](auto j) {
+        constexpr int J = decltype(j)::value;
+        scan_rows_launch(ou_mix_kernel<true, J>, ou_mix_kernel<false, J>, flux, model_grid, n_time, n, secdepth, sec_limit,
+                         accumulate, out_halfchi2, mix, J <= 2 ? 4 : 2, static_cast<hipStream_t>(stream));
+    });
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }
@@ -1275,15 +1259,19 @@ int trxg_chi2_grid_ou_baseline(const double* flux, const double* model_grid, int
     if (!flux || !model_grid || !out_halfchi2 || !alpha || !beta || !omega || !columns || !minv)
         return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
     static_assert(TRXG_MAX_TERMS == kChi2bMaxTerms, "the header's limit is the kernel's");
-    Chi2bM M{};
-    for (int i = 0; i < n_terms * (n_terms + 1) / 2; ++i) {
-        if (!(minv[i] - minv[i] == 0.0))                    // (NaN or +-inf)
-            return fail(TRX_ERR_ARG, "minv must be finite%s (entry %ld)", "", (long)i);
-        M.m[i] = minv[i];
-    }
+    Chi2bM M;
+    if (int rc = pack_minv(minv, n_terms, M)) return rc;
     if (n == 0) return TRX_OK;
-    gls_ou_launch<1>(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, alpha, beta, omega,
-                     columns, n_terms, M, coef_out, static_cast<hipStream_t>(stream));
+    // (below kGlsWideFrom columns the kernel stays within 128 VGPRs, from there on it would hold two waves a SIMD; as built
+    // every K = 1 .. 4 is within 128: trx_gls.hpp)
+    dispatch_int<1, kChi2bMaxTerms>(n_terms, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        using Filter = OuColsFilter<K>;
+        scan_rows_launch(scan_rows_kernel<true, Filter>, scan_rows_kernel<false, Filter>, flux, model_grid, n_time, n,
+                         secdepth, sec_limit, accumulate, out_halfchi2,
+                         Filter{alpha, beta, omega, columns, {nullptr, M, coef_out}}, K < kGlsWideFrom ? 4 : 2,
+                         static_cast<hipStream_t>(stream));
+    });
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }
@@ -1295,8 +1283,9 @@ int trxs_chi2_grid_ss2(const double* flux, const double* model_grid, int n_time,
     if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
     if (!flux || !model_grid || !out_halfchi2 || !A || !g || !omega) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
     if (n == 0) return TRX_OK;
-    ss2_launch(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, A, g, omega,
-               static_cast<hipStream_t>(stream));
+    scan_rows_launch(scan_rows_kernel<true, Ss2Filter>, scan_rows_kernel<false, Ss2Filter>, flux, model_grid, n_time, n,
+                     secdepth, sec_limit, accumulate, out_halfchi2, Ss2Filter{A, g, omega}, 4,
+                     static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }
@@ -1308,13 +1297,10 @@ int trxt_softmin_rows(const double* cand, long stride, long n, int n_cand, const
     if (n < 0 || stride < n) return fail(TRX_ERR_ARG, "n < 0 or stride < n%s (n=%ld)", "", n);
     if (n_cand < 1 || n_cand > TRXT_MAX_NODES) return fail(TRX_ERR_ARG, "n_cand outside 1 .. 8%s (n_cand=%ld)", "", n_cand);
     static_assert(TRXT_MAX_NODES == kSoftminMax, "the header's limit is the kernel's");
-    SoftminLnc c = {};
-    for (int j = 0; j < n_cand; ++j) {
-        if (!(lnc[j] < INFINITY)) return fail(TRX_ERR_ARG, "lnc is NaN or +inf%s (node %ld)", "", j);
-        c.v[j] = lnc[j];
-    }
+    Lnc8 c;
+    if (int rc = pack_lnc(lnc, n_cand, "node", c)) return rc;
     if (n == 0) return TRX_OK;
-    softmin_launch_j<1>(cand, stride, n, n_cand, c, accumulate, out, static_cast<hipStream_t>(stream));
+    softmin_launch(cand, stride, n, n_cand, c, accumulate, out, static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }
@@ -1344,23 +1330,13 @@ int trx_chi2_grid_baseline(const double* flux, const double* inv_var, const doub
         return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
     if (n_terms < 1 || n_terms > kChi2bMaxTerms)
         return fail(TRX_ERR_ARG, "n_terms must lie in [1, 4]%s (got %ld)", "", (long)n_terms);
-    Chi2bM M{};
-    for (int i = 0; i < n_terms * (n_terms + 1) / 2; ++i) {
-        if (!(minv[i] - minv[i] == 0.0))                    // (NaN or +-inf)
-            return fail(TRX_ERR_ARG, "minv must be finite%s (entry %ld)", "", (long)i);
-        M.m[i] = minv[i];
-    }
+    Chi2bM M;
+    if (int rc = pack_minv(minv, n_terms, M)) return rc;
     if (n == 0) return TRX_OK;
-    const auto launch = [&](const auto& terms) {
-        chi2_rows_launch(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, terms,
-                         static_cast<hipStream_t>(stream));
-    };
-    switch (n_terms) {
-    case 1: launch(Chi2Baseline<1>{wbasis, M, coef_out}); break;
-    case 2: launch(Chi2Baseline<2>{wbasis, M, coef_out}); break;
-    case 3: launch(Chi2Baseline<3>{wbasis, M, coef_out}); break;
-    default: launch(Chi2Baseline<4>{wbasis, M, coef_out}); break;
-    }
+    dispatch_int<1, kChi2bMaxTerms>(n_terms, [&](auto k) {
+        chi2_rows_launch(flux, inv_var, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2,
+                         Chi2Baseline<decltype(k)::value>{wbasis, M, coef_out}, static_cast<hipStream_t>(stream));
+    });
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

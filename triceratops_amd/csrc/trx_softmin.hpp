@@ -10,18 +10,16 @@
 // One lane per row: the J loads of a wave are 512 contiguous bytes each (non-temporal: every value is read once), then J exp
 // and one log in registers.  No LDS, no scratch, no cross-lane traffic: a row's bits depend on its J values and lnc alone.
 #pragma once
+#include "trx_scan.hpp"
 
 namespace {
 
 constexpr int kSoftminMax = 8;          // candidates (datasets.MAX_T0_NODES)
-
-struct SoftminLnc {
-    double v[kSoftminMax];
-};
+static_assert(kSoftminMax * sizeof(double) <= sizeof(Lnc8), "a log-weight per candidate");
 
 template <int J>
 __global__ __launch_bounds__(256) void softmin_rows_kernel(const double* __restrict__ cand, long stride, long n,
-                                                           SoftminLnc lnc, int accumulate, double* __restrict__ out)
+                                                           Lnc8 lnc, int accumulate, double* __restrict__ out)
 {
     static_assert(J >= 1 && J <= kSoftminMax, "1 .. 8 candidates");
     const long step = (long)gridDim.x * 256;
@@ -41,9 +39,7 @@ __global__ __launch_bounds__(256) void softmin_rows_kernel(const double* __restr
             // issued above, so nothing that hides latency is lost.)
             if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
         }
-        double t = m - log(s);
-        t = m < INFINITY ? t : m;                            // (every candidate +inf, or a NaN row: no inf - inf)
-        t = t < 0.0 ? 0.0 : t;                               // (a NaN stays a NaN)
+        const double t = softmin_tail(m, s);
         out[r] = accumulate ? out[r] + t : t;                // (+inf stays +inf: t is never -inf)
     }
 }

@@ -1,25 +1,19 @@
-// Correlated noise with a state of dimension two: ss2_kernel<ONE> (trxs_chi2_grid_ss2, include/trx_ss.h; DESIGN.md section
-// 14), the row reduction of a materialised grid under white noise plus a process whose Kalman filter carries two states --
-// a Matern-3/2 term, two exponential terms, any other celerite-style term of that size.  Included by trx_kernels.hip
-// only, after trx_noise.hpp.
+// Correlated noise with a state of dimension two: scan_rows_kernel<ONE, Ss2Filter> (trxs_chi2_grid_ss2, include/trx_ss.h;
+// DESIGN.md section 14), the row reduction of a materialised grid under white noise plus a process whose Kalman filter
+// carries two states -- a Matern-3/2 term, two exponential terms, any other celerite-style term of that size.  Included
+// by trx_kernels.hip only.
 //
 // With y_t = flux_t - model[r][t] and the row-independent A [T][2][2], g [T][2], omega [T] of datasets.ss2_system:
 //     u_(-1) = 0,   z_n = y_n - u_(n-1)[0],   u_n = A_n u_(n-1) + g_n y_n,    h[r] = 0.5 sum_n omega_n z_n^2.
 //
-// The layout is chi2_ou_kernel's: one wavefront per row, two rows in flight per wave, trips of kOuTrip = 128 consecutive
-// stamps, lane l the pair (2 l, 2 l + 1) of a trip, every grid value read once (ou_load_pair: one 16-byte non-temporal load
-// where the row's address allows it).  A lane folds its pair into one affine map u -> M u + v, M = A_1 A_0 (the same for
-// every row), v = (A_1 g_0) y_0 + g_1 y_1; the six-step scan over the lanes composes the maps with the DPP moves of
-// ou_scan_source.  The multipliers m[s] -- the M-products of the spans, 2 x 2 each -- and minc, the product from the trip's
-// start, are formed by the same scan on M alone, once per trip for both rows (ONE: n_time <= kOuTrip, once per wave before
-// its first row, in registers for all its rows); a row's scan moves only v: two doubles and four fma a step.  The last
-// lane's u is carried into the next trip.  Stamps past n_time enter as y = 0, A = 0, g = 0, omega = 0.  No LDS, no
-// workspace: flux and the three tables are read through the caches, 16 values per lane and trip.
-//
-// The order of a row's arithmetic is fixed by n_time alone: the trips, the lane of every stamp, the scan's steps and
-// wave_sum's butterfly.  Neither the launch geometry, the row's position, its alignment nor the other rows enter.
+// The layout is scan_rows_kernel's (trx_scan.hpp), Ss2Filter its filter.  A lane folds its pair into one affine map
+// u -> M u + v, M = A_1 A_0 (the same for every row), v = (A_1 g_0) y_0 + g_1 y_1.  The multipliers m[s] -- the M-products
+// of the spans, 2 x 2 each -- and minc, the product from the trip's start, are formed by the scan on M alone; a row's scan
+// moves only v: two doubles and four fma a step.  The last lane's u is carried into the next trip; A = 0, g = 0,
+// omega = 0 past n_time.  16 table values per lane and trip.  The wave reduction is wave_sum's butterfly, the store
+// chi2w_store.
 #pragma once
-#include "trx_noise.hpp"
+#include "trx_scan.hpp"
 
 namespace {
 
@@ -131,68 +125,43 @@ __device__ __forceinline__ Ss2Trip ss2_trip(const double* __restrict__ flux, con
     return t;
 }
 
-__device__ __forceinline__ double ss2_last_lane(double v)
-{
-    const long long b = __double_as_longlong(v);
-    return __longlong_as_double(((long long)__builtin_amdgcn_readlane((int)(b >> 32), 63) << 32) |
-                                (long long)(unsigned)__builtin_amdgcn_readlane((int)b, 63));
-}
 
-// one trip of one row: carry = u before the trip's first stamp, acc the lane's share of sum omega z^2
-__device__ __forceinline__ void ss2_row_trip(const Ss2Trip& t, double m0, double m1, Ss2Vec& carry, double& acc, int lane)
-{
-    const double y0 = t.f0 - m0, y1 = t.f1 - m1;
-    Ss2Vec v;
-    v.x = fma(t.h.x, y0, t.g1.x * y1);
-    v.y = fma(t.h.y, y0, t.g1.y * y1);
-    ss2_scan_v<0>(t.m, v);
-    const Ss2Vec uinc = ss2_apply(t.minc, carry, v);           // u after the lane's second stamp
-    const double uin0 = ou_shift_up1(uinc.x, carry.x, lane);   // ... and before its first
-    const double uin1 = ou_shift_up1(uinc.y, carry.y, lane);
-    const double z0 = y0 - uin0;
-    const double z1 = y1 - fma(t.a00, uin0, fma(t.a01, uin1, t.g00 * y0));
-    acc = fma(t.w0 * z0, z0, acc);
-    acc = fma(t.w1 * z1, z1, acc);
-    carry.x = ss2_last_lane(uinc.x);                           // the last lane's u, to every lane
-    carry.y = ss2_last_lane(uinc.y);
-}
+struct Ss2Row {
+    Ss2Vec carry = {0.0, 0.0};        // u before the trip's first stamp
+    double acc = 0.0;                 // the lane's share of sum omega z^2
+};
 
-template <bool ONE>
-__global__ __launch_bounds__(256) void ss2_kernel(const double* __restrict__ flux, const double* __restrict__ grid,
-                                                  int n_time, long n, const double* __restrict__ secdepth,
-                                                  double sec_limit, int accumulate, double* __restrict__ out,
-                                                  const double* __restrict__ A, const double* __restrict__ g,
-                                                  const double* __restrict__ omega)
-{
-    const int lane = threadIdx.x & 63;
-    const long wave0 = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long nwaves = (long)gridDim.x * 4;
-    Ss2Trip t;
-    if (ONE) t = ss2_trip(flux, A, g, omega, n_time, 0, lane);
-    for (long r = wave0; r < n; r += 2 * nwaves) {
-        // two rows per pass, their loads in flight together; each row's arithmetic is its own
-        const long r2 = r + nwaves;
-        const bool two = r2 < n;
-        const double* row0 = grid + (size_t)r * n_time;
-        const double* row1 = grid + (size_t)(two ? r2 : r) * n_time;
-        const bool vec0 = ((uintptr_t)row0 & 15) == 0, vec1 = ((uintptr_t)row1 & 15) == 0;      // (per row: wave-uniform)
-        Ss2Vec carry0 = {0.0, 0.0}, carry1 = {0.0, 0.0};
-        double acc0 = 0.0, acc1 = 0.0;
-        for (int base = 0; base < n_time; base += kOuTrip) {
-            double a0, a1, b0 = 0.0, b1 = 0.0;
-            ou_load_pair(row0, n_time, base, lane, vec0, a0, a1);
-            if (two) ou_load_pair(row1, n_time, base, lane, vec1, b0, b1);
-            if (!ONE) t = ss2_trip(flux, A, g, omega, n_time, base, lane);
-            ss2_row_trip(t, a0, a1, carry0, acc0, lane);
-            if (two) ss2_row_trip(t, b0, b1, carry1, acc1, lane);
-            if (ONE) break;                                   // (n_time <= kOuTrip)
-        }
-        const double tot0 = wave_sum(acc0), tot1 = wave_sum(acc1);
-        if (lane == 0) {
-            chi2w_store(tot0, r, secdepth, sec_limit, accumulate, out);
-            if (two) chi2w_store(tot1, r2, secdepth, sec_limit, accumulate, out);
-        }
+struct Ss2Filter {
+    using Trip = Ss2Trip;
+    using Row = Ss2Row;
+    const double *A, *g, *omega;
+    __device__ __forceinline__ Ss2Trip trip(const double* __restrict__ flux, int n_time, int base, int lane) const
+    {
+        return ss2_trip(flux, A, g, omega, n_time, base, lane);
     }
-}
+    static __device__ __forceinline__ void row_trip(const Ss2Trip& t, double m0, double m1, Ss2Row& s, int lane)
+    {
+        const double y0 = t.f0 - m0, y1 = t.f1 - m1;
+        Ss2Vec v;
+        v.x = fma(t.h.x, y0, t.g1.x * y1);
+        v.y = fma(t.h.y, y0, t.g1.y * y1);
+        ss2_scan_v<0>(t.m, v);
+        const Ss2Vec uinc = ss2_apply(t.minc, s.carry, v);             // u after the lane's second stamp
+        const double uin0 = ou_shift_up1(uinc.x, s.carry.x, lane);     // ... and before its first
+        const double uin1 = ou_shift_up1(uinc.y, s.carry.y, lane);
+        const double z0 = y0 - uin0;
+        const double z1 = y1 - fma(t.a00, uin0, fma(t.a01, uin1, t.g00 * y0));
+        s.acc = fma(t.w0 * z0, z0, s.acc);
+        s.acc = fma(t.w1 * z1, z1, s.acc);
+        s.carry.x = wave_read_lane<63>(uinc.x);                        // the last lane's u, to every lane
+        s.carry.y = wave_read_lane<63>(uinc.y);
+    }
+    static __device__ __forceinline__ void wave_sums(Ss2Row& s) { s.acc = wave_sum(s.acc); }
+    __device__ __forceinline__ void store(const Ss2Row& s, long r, const double* __restrict__ secdepth, double sec_limit,
+                                          int accumulate, double* __restrict__ out) const
+    {
+        chi2w_store(s.acc, r, secdepth, sec_limit, accumulate, out);
+    }
+};
 
 }  // namespace
