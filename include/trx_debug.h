@@ -82,6 +82,18 @@ int trx_set_whole_trips(int on);
  * centre solution comes from another plan trip, and its chi^2 term is added by another lane).  TRX_ERR_ARG for another
  * value. */
 int trx_set_one_sweep(int mode);
+/* How the stencil instantiation of the one-row kernels chunks the in-window list where it takes the one sweep:
+ * 1 (default, what the production library does): a chunk of the likelihood kernels takes 64 new list entries; a stencil
+ * cell of its last 8 lanes is finalised by the next chunk, which owes it the centre values of its first cells.  The flux
+ * grid keeps the one-sided halo (56 new cells per chunk, the last 8 lanes lent), as the bounded and batched kernels do;
+ * 0: the likelihood kernels keep the halo too; 2: the flux grid and its evaluation census take full chunks too (only
+ * together with trx_set_one_sweep(2)).  A cell's value and chi^2/2 may move in the last bits (other trip-mates in the plan,
+ * another lane and order for its chi^2 term); a cell within 8 lanes of a chunk edge may change between the stencil and
+ * its own nodes.  TRX_ERR_ARG for another value. */
+int trx_set_full_chunks(int mode);
+/* bytes of LDS a workgroup of the one-row kernels (one wave) is launched with, from the function the launch plan uses;
+ * sixteen of them have to fit a CU's 160 KB.  No device is touched. */
+long trx_debug_cells_lds_one_row(void);
 /* the 64-cell trips of pass 1 that the stencil instantiation's waves on the current device filed whole and those they
  * walked cell by cell since the library was loaded (or since the last call with reset != 0, which returns the counts and
  * then zeroes them); the trips that cannot hold an in-window cell are in neither.  It waits for the device.  Device

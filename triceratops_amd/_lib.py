@@ -59,7 +59,7 @@ DEBUG_SYMBOLS = (
     "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison", "trx_set_debug_bug",
     "trx_set_probe_rows", "trx_set_star_chain", "trx_debug_capture_buffers", "trx_debug_chain_counts",
     "trx_set_row_order", "trx_debug_row_order", "trx_set_whole_trips", "trx_debug_whole_trips", "trx_set_one_sweep",
-    "trx_debug_select_from_halfchi2",
+    "trx_set_full_chunks", "trx_debug_cells_lds_one_row", "trx_debug_select_from_halfchi2",
 )
 
 
@@ -231,10 +231,12 @@ def _load(path, testing):
                      "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison",
                      "trx_set_debug_bug", "trx_set_star_chain", "trx_set_probe_rows", "trx_set_stencil",
                      "trx_set_supersample_tiers", "trx_set_debug_node_counts", "trx_set_cell_packing_below",
-                     "trx_set_row_order", "trx_set_whole_trips", "trx_set_one_sweep"):
+                     "trx_set_row_order", "trx_set_whole_trips", "trx_set_one_sweep", "trx_set_full_chunks"):
             fn = getattr(L, name)
             fn.restype = c_int
             fn.argtypes = [c_int]
+        L.trx_debug_cells_lds_one_row.restype = c_long
+        L.trx_debug_cells_lds_one_row.argtypes = []
         L.trx_debug_capture_buffers.restype = c_int
         L.trx_debug_capture_buffers.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long)]
         L.trx_debug_row_order.restype = c_int

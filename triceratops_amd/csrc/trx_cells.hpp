@@ -92,6 +92,7 @@ struct RowsArgs {
     int accumulate;
     int whole_trips;   // trx_set_whole_trips (read by the testing library's kernels only): see window_trips
     int one_sweep;     // trx_set_one_sweep (likewise): 0 two sweeps, 1 one in the likelihood kernels, 2 in the flux grid's too
+    int full_chunks;   // trx_set_full_chunks (likewise): 0 one-sided halo, 1 full stencil chunks in the likelihood kernels, 2 in the flux grid's too
     // Cost-ordered rows (one row per wave, full evaluation of a likelihood launch; null: rows as they come): rowc_kernel
     // files every row under its cost bucket, cells_kernel's position v takes the v-th row of that order (row_order_at)
     int* order;        // [kOrderSegs counters, kOrderStride ints apart | kOrderSegs lists of order_cap(n) row numbers]
@@ -209,10 +210,12 @@ __device__ __forceinline__ void add_trip_stat(int which, unsigned count)
 }
 __device__ __forceinline__ bool whole_trips_on(const RowsArgs& a) { return a.whole_trips != 0; }
 __device__ __forceinline__ bool one_sweep_on(const RowsArgs& a, bool lnl) { return a.one_sweep >= (lnl ? 1 : 2); }
+__device__ __forceinline__ bool full_chunks_on(const RowsArgs& a, bool lnl) { return a.full_chunks >= (lnl ? 1 : 2); }
 #define TRX_TRIP_STAT(var) ++var
 #else
 __device__ __forceinline__ bool whole_trips_on(const RowsArgs&) { return true; }
 __device__ __forceinline__ bool one_sweep_on(const RowsArgs&, bool lnl) { return lnl; }
+__device__ __forceinline__ bool full_chunks_on(const RowsArgs&, bool lnl) { return lnl; }
 #define TRX_TRIP_STAT(var)
 #endif
 
@@ -998,13 +1001,17 @@ struct CellState {
     double facc[64];                        // the cell's sum over its nodes
     unsigned meta[64];                      // row | (tier + 1) << 8 | anchored << 16 (tier -1 = all S sub-exposures): one read per pair
                                             // (| valid << 17 | node count << 18: what a carried cell's next chunk needs, cells_body)
-    unsigned short rel[64];                 // the cell's entry in the window's list
+    union {
+        unsigned short rel[64];             // the cell's entry in the window's list (carried cells: the batched instantiations)
+        double held[2 * kStM];              // one row per wave, full stencil chunks: observed flux [q] and weight [kStM + q] of
+    };                                      // the pending cell of lane 64 - kStM + q, until the next chunk finalises it
 };
 // centre-value stencil (LONG only): the chunk's centre fluxes and the launch's weights
 struct StencilState {
-    double fc[64 + ((kStM + 7) & ~7)];                      // [kStM + h]: the centre flux of lane h; [0, kStM): the previous chunk's last owned cells'
-    double stw[(2 * kStM + 1 + 7) & ~7];
+    double fc[64 + 2 * kStM];                               // [kFcB + h]: the centre flux of lane h; below: the previous chunk's last cells'
+    double stw[2 * kStM + 1];                               // (halo: its last kStM owned cells' in [kStM, kFcB); full chunks: its last 2 kStM in [0, kFcB))
 };
+constexpr int kFcB = 2 * kStM;
 constexpr int kCentreNode = 1023;           // pair table: "the exposure centre itself" in the node field
 
 // What a verdict of the bounded evaluation has to allow for when the cells done so far carry the fp32 flux model
@@ -1660,8 +1667,23 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
             // finds radius 0 and walks the list exactly like the instantiation without the stencil: same chunks,
             // same summation order)
             const bool halo = ST && sweep == 0 && st_radius > 0.0;
+            // Full chunks (the one sweep of the likelihood kernels): every chunk takes 64 new list entries and
+            // owns them all.  A cell of the last kStM lanes whose right neighbours are the next chunk's first cells takes
+            // the stencil on the strength of the list alone -- the entries it needs exist in this pass and continue its
+            // run of time indices -- and is finalised by the next chunk, which OWES a centre value for each of its first
+            // cells that such a "pending" cell reaches, whatever their kind: a planned cell evaluates its centre, an
+            // off-disc cell stores 1, a contact cell adds the centre to its S pairs.  That is sound because among a
+            // stencil cell's neighbours the `planned` bit only ever recorded that a centre value exists: the accuracy
+            // condition is the stencil cell's OWN st_ok, a contact-free disc of >= 13.4 half exposures round its centre, on
+            // which the instantaneous flux is analytic, and the flux at a neighbour's exposure centre is a valid sample of
+            // it whatever node rule that neighbour uses for its own average.  Nothing but scalars and carry_j cross the
+            // back edge: the previous chunk's last 2 kStM centre values sit in ss.fc below the chunk's own.
+            const bool full = halo && one && full_chunks_on(a, MODE == MODE_LNL);
+            const bool lend = halo && !full;       // the one-sided halo: the flux grid, the bounded and batched kernels
             int carry_j = 0;                       // stencil: the time indices of the previous chunk's lanes
             unsigned long long carry_ok = 0;       // ... and which of them were planned cells (no contact cell)
+                                                   // (full chunks: which of them left a centre value in ss.fc)
+            unsigned pendm = 0;                    // full chunks: which of a chunk's last kStM cells are pending (bit q: lane 64 - kStM + q)
             // Carried cells (no stencil).  A chunk's pairs are dealt to the lanes 64 at a time and the last trip is
             // half empty on average -- 54 of 64 lanes per trip at 100 points, and the pair loop is three quarters of
             // the kernel there.  So a chunk with more cells behind it processes only the cells whose pairs fill whole
@@ -1685,7 +1707,15 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                 bool valid = carried ? (cmeta & 0x20000u) != 0 : (w0 + lane - ncarry) < count;
                 int rel = (int)*(carried ? &cs.rel[csrc] : &winlist[valid ? (w0 + lane - ncarry) : (count - 1)]);
                 bool last_chunk = false;
-                if (ST && halo) {
+                const unsigned pend_prev = pendm;          // (0 unless full chunks)
+                if (ST && full) {
+                    // (the lane's number counted afresh, here and below, as in pass 1: what is derived from `lane` itself the
+                    // compiler computes once and keeps in registers for the whole kernel, which this instantiation does not have)
+                    const int ln = lanes_below(~0ull);
+                    if (w0 > 0 && ln < 2 * kStM) ss.fc[ln] = ss.fc[64 + ln];
+                    wave_sync();
+                }
+                if (ST && lend) {
                     // One-sided halo (round 5): a chunk owns its first 64 - kStM lanes and only lends the centre values
                     // of the last kStM -- the next chunk's first cells.  What its own first cells need from the left --
                     // the centre values, time indices and "planned, not a contact cell" bits of the previous chunk's last
@@ -1696,7 +1726,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                     last_chunk = w0 + 64 >= count;
                     step = last_chunk ? 64 : 64 - kStM;
                     owned = lane < step;
-                    if (w0 > 0 && lane < kStM) ss.fc[lane] = ss.fc[kStM + (64 - 2 * kStM) + lane];
+                    if (w0 > 0 && lane < kStM) ss.fc[kFcB - kStM + lane] = ss.fc[kFcB + (64 - 2 * kStM) + lane];
                     wave_sync();
                 }
                 const int cell = win0 + rel;
@@ -1757,22 +1787,59 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                 if (ST && sweep == 0) {
                     // (the kStM cells to the left of this chunk's first: lanes 64 - 2 kStM .. 64 - kStM - 1 of the previous one)
                     // (both shuffles by every lane: a shuffle under a divergent mask reads 0 from the lanes that sit it out)
-                    const int jleft = __shfl(carry_j, 64 - 2 * kStM + lane, 64), jhere = __shfl(j, lane - kStM, 64);
+                    // (full chunks: they are the previous chunk's LAST kStM lanes)
+                    const int lsrc = full ? 64 - kStM : 64 - 2 * kStM;
+                    const int jleft = __shfl(carry_j, lsrc + lane, 64), jhere = __shfl(j, lane - kStM, 64);
                     const int jm = (lane < kStM) ? jleft : jhere;
-                    const int jp = __shfl(j, lane + kStM, 64);
+                    int jp = __shfl(j, lane + kStM, 64);
                     const unsigned long long mok = __ballot(planned);
-                    const unsigned long long left = (carry_ok >> (64 - 2 * kStM)) & ((1ull << kStM) - 1ull);
-                    const bool inner = (lane >= kStM || (halo && w0 > 0)) && lane + kStM < 64;
-                    constexpr unsigned long long kAll = (1ull << (2 * kStM + 1)) - 1ull;
-                    // the 2 kStM + 1 "planned cell" bits around the lane (the lowest ones from the previous chunk)
+                    const unsigned long long left = (carry_ok >> lsrc) & ((1ull << kStM) - 1ull);
+                    // full chunks: the list goes on behind this chunk with nnext (<= kStM) cells that follow its last one in
+                    // step (the list ascends, so the last of them settles it); 0 at the list's end -- a window pass's -- or
+                    // where an epoch ends within them.  Lane 64 - kStM + q needs q + 1 of them.
+                    int nnext = 0;
+                    const int j_last = __builtin_amdgcn_readlane(j, 63);       // (ST: one row per wave, j = win0 + rel)
+                    if (full && w0 + 64 < count) {
+                        const int more = count - (w0 + 64) < kStM ? count - (w0 + 64) : kStM;
+                        if (win0 + (int)winlist[w0 + 63 + more] == j_last + more) nnext = more;
+                    }
+                    constexpr unsigned kAll = (1u << (2 * kStM + 1)) - 1u;
+                    // (a cell of the last kStM lanes: its neighbours up to the last lane, where the run must arrive in step)
+                    unsigned want = kAll;
+                    bool inner = (lane >= kStM || (halo && w0 > 0)) && lane + kStM < 64;
+                    if (nnext > 0) {
+                        const int over = lanes_below(~0ull) - (63 - kStM);
+                        if (over > 0 && over <= nnext) {
+                            jp = j_last + over;
+                            want = kAll >> over;
+                            inner = true;
+                        }
+                    }
+                    // the 2 kStM + 1 "planned cell" bits around the lane (the lowest ones from the previous chunk:
+                    // full chunks, "left a centre value")
                     const unsigned long long field = (lane >= kStM) ? (mok >> (lane - kStM)) : (((mok << kStM) | left) >> lane);
                     st = inner && owned && planned && pl.n > 0 && pl.st_ok && jm == j - kStM && jp == j + kStM &&
-                         (field & kAll) == kAll;
+                         ((unsigned)field & kAll) == want;
                     const unsigned long long mst = __ballot(st);
                     unsigned long long dil = mst;
 #pragma unroll
                     for (int i = 1; i <= kStM; ++i) dil |= (mst << i) | (mst >> i);
                     centre = planned && ((dil >> lane) & 1ull);
+                    pendm = (unsigned)(mst >> (64 - kStM));         // (only full chunks have a stencil cell there)
+                    bool has_value = centre;
+                    if (full) {
+                        // what this chunk owes the previous one's pending cells: a centre value in each of its first
+                        // lanes up to the last such cell's reach (lane q of the last kStM reaches this chunk's lanes 0 .. q)
+                        // (inside a stencil zone the first lanes take a centre value anyway: one vote settles it)
+                        const bool owes = pend_prev != 0 && lanes_below(~0ull) < 32 - __clz((int)pend_prev);
+                        if (__any(owes && !centre)) {
+                            if (owes) {
+                                if (pl.n > 0) centre = true;                      // (a contact cell too: kCentreNode rides with its S pairs)
+                                else if (!centre) ss.fc[kFcB + lane] = 1.0;
+                                has_value = true;
+                            }
+                        }
+                    }
                     // (the next chunk's first cells may take their stencil through this one's last owned cells; one whose
                     // exposure is off the disc altogether has the value 1 without an evaluation)
                     // -- and only a cell that a stencil cell of the next chunk can reach: lane 64 - 2 kStM + k is within
@@ -1780,13 +1847,15 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                     // the stencil only where their own plan allows it)
                     const unsigned long long mnext = __ballot(planned && pl.n > 0 && pl.st_ok) >> (64 - kStM);
                     const int kk = lane - (64 - 2 * kStM);
-                    if (halo && !last_chunk && planned && !centre && kk >= 0 && kk < kStM && (mnext & ((2ull << kk) - 1ull)) != 0) {
+                    if (lend && !last_chunk && planned && !centre && kk >= 0 && kk < kStM && (mnext & ((2ull << kk) - 1ull)) != 0) {
                         if (pl.n > 0) centre = true;
-                        else ss.fc[kStM + lane] = 1.0;
+                        else ss.fc[kFcB + lane] = 1.0;
                     }
                     if (st) nodes = 0;
                     carry_j = j;
-                    carry_ok = mok;
+                    // (full chunks: a first cell of the next chunk takes the stencil only where every left neighbour it
+                    // needs HAS a value; otherwise it takes its own nodes -- no predictor, no second plan)
+                    carry_ok = full ? __ballot(has_value) : mok;
                     if (kLazyTiers) {
                         // the cells that need their own nodes after all (no neighbours on one side: a row's first and
                         // last cells in the window): their tier now (plan_cell<LAZY>)
@@ -1823,7 +1892,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                         } else if (z2 != z2) {
                             f = z2;
                         }
-                        ss.fc[kStM + lane] = f;
+                        ss.fc[kFcB + lane] = f;
                     }
                     wave_sync();
                 }
@@ -1939,7 +2008,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                                 f = z2;
                             }
                             if (at_centre) {
-                                ss.fc[kStM + h] = f;
+                                ss.fc[kFcB + h] = f;
                             } else {
                                 const double term = (ht < 0) ? f : tier_xw[2 * (ht * kTierMaxNodes + s) + 1] * (1.0 - f);
                                 if (ht < 0 || term != 0.0)
@@ -1951,32 +2020,52 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                 }
                 TRX_TOCK(3, t_a);
                 TRX_TICK(t_rest);
+                // Full chunks: a pending cell of the last kStM lanes waits for the next chunk, so its lane has nothing to
+                // finalise now -- and ADOPTS the previous chunk's pending cell of the same lane, whose right neighbours'
+                // centre values are in: the 2 kStM + 1 terms ride in the instructions the chunk's own stencil cells issue
+                // anyway (a block of its own for them cost what the eighth of the chunks saved), its observed flux and
+                // weight wait in cs.held.  In a row's stencil zone every pending cell is adopted; where the row leaves the
+                // zone the cells left over take the block behind this one.
+                const int lq = lanes_below(~0ull) - (64 - kStM);
+                const bool mine_pending = ST && st && pendm != 0 && lq >= 0;
+                // (the same lanes pending as in the previous chunk -- a stencil zone's every chunk but its first and last: each
+                // adopts its predecessor and nothing is left over)
+                bool adopt = mine_pending;
+                unsigned left_over = 0u;
+                if (ST && pend_prev != pendm) {
+                    const bool prev_here = lq >= 0 && ((pend_prev >> lq) & 1u) != 0;
+                    adopt = prev_here && (mine_pending || !valid);
+                    left_over = (unsigned)(__ballot(prev_here && !adopt) >> (64 - kStM));
+                }
                 if (MODE == MODE_GRID && a.debug_nodes) {
                     // bench / test knob: the model evaluations every cell cost, its own and those a
                     // neighbouring chunk spent on its centre value (the cells were zeroed by pass 1)
                     const int spent = nodes + ((ST && centre) ? 1 : 0);
                     if (spent > 0 && lane < ldone) atomicAdd(&a.out[(size_t)base * n_time + cell], (double)spent);
-                } else if (valid && owned && lane < ldone) {
+                } else if ((valid && owned && lane < ldone && !mine_pending) || adopt) {
                     const RowC& c = (LONG && !TRX_LONG_ROWS_IN_LDS) ? cu : rows[rr];
                     double fsum = cs.facc[lane];
-                    if (ST && st) {
+                    if (ST && (st || adopt)) {
                         // the S-point average of the interpolant through the 2 kStM + 1 centre values
+                        // (an adopted cell: lane q - kStM of this chunk as far as ss.fc goes)
+                        const double* fcl = &ss.fc[kFcB + (adopt ? lq - kStM : lane)];
                         fsum = 0.0;
 #pragma unroll
-                        for (int i = -kStM; i <= kStM; ++i) fsum = fma(ss.stw[i + kStM], 1.0 - ss.fc[kStM + lane + i], fsum);
+                        for (int i = -kStM; i <= kStM; ++i) fsum = fma(ss.stw[i + kStM], 1.0 - fcl[i], fsum);
                     }
                     // the cell's flux deficit: nothing, 1 - mean of the S sub-exposures, or the Gauss rule's weighted sum
                     // (a stencil cell's sum is one of deficits like a Gauss rule's -- and its tier may never have been looked for)
-                    const double deficit = (pl.n == 0) ? 0.0 : ((ST && st) ? fsum : ((tier < 0) ? 1.0 - fsum / a.dS : fsum));
+                    const double deficit = (ST && adopt) ? fsum
+                                         : ((pl.n == 0) ? 0.0 : ((ST && st) ? fsum : ((tier < 0) ? 1.0 - fsum / a.dS : fsum)));
                     const RowC& cd = rows[rr];
                     const double m = fma(-deficit, cd.rdil, 1.0);    // dilution(s), :352-357, :427-438
                     if (MODE == MODE_GRID) {
-                        a.out[(size_t)base * n_time + cell] = m;
+                        a.out[(size_t)base * n_time + ((ST && adopt) ? win0 + (int)winlist[w0] - kStM + lq : cell)] = m;
                     } else {
                         if (LONG) {
                             // the row's own lanes sum (f - m)^2 / sigma^2 directly    :486, :537, :586
-                            const double d = fobs - m;
-                            lacc = fma(d * d, wobs, lacc);
+                            const double d = ((ST && adopt) ? cs.held[lq] : fobs) - m;
+                            lacc = fma(d * d, (ST && WT && adopt) ? cs.held[kStM + lq] : wobs, lacc);
                             nonflat = nonflat || (m != 1.0);
                         } else {
                             // (f - m)^2 - (f - 1)^2, exactly 0 for m = 1: one LDS atomic per cell with a
@@ -1993,6 +2082,30 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                             }
                         }
                     }
+                }
+                if (ST && left_over != 0 && !(MODE == MODE_GRID && a.debug_nodes)) {
+                    // The previous chunk's pending cells that no lane could adopt -- where a row leaves its stencil zone,
+                    // once or twice a row --, by the first lanes: the same 2 kStM + 1 terms in the same order.
+                    const int q = lanes_below(~0ull);
+                    if (q < kStM && ((left_over >> q) & 1u)) {
+                        const int jq = win0 + (int)winlist[w0] - kStM + q;
+                        double fsum = 0.0;
+#pragma unroll
+                        for (int i = -kStM; i <= kStM; ++i) fsum = fma(ss.stw[i + kStM], 1.0 - ss.fc[kFcB - kStM + q + i], fsum);
+                        const double m = fma(-fsum, rows[0].rdil, 1.0);
+                        if (MODE == MODE_GRID) {
+                            a.out[(size_t)base * n_time + jq] = m;
+                        } else {
+                            const double d = cs.held[q] - m;
+                            lacc = fma(d * d, WT ? cs.held[kStM + q] : rs2, lacc);
+                            nonflat = nonflat || (m != 1.0);
+                        }
+                    }
+                }
+                if (ST && MODE == MODE_LNL && mine_pending) {
+                    // (after the reads above: lane 64 - kStM + q only ever overwrites what it has just adopted)
+                    cs.held[lq] = fobs;
+                    if (WT) cs.held[kStM + lq] = wobs;
                 }
                 if (kCarry) ncarry = 64 - ldone;          // the cells handed on (read from this chunk's slots by the next)
                 TRX_TOCK(5, t_rest);

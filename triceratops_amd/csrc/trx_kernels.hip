@@ -348,6 +348,21 @@ struct CellsPlan {
 #endif
 constexpr bool kProbeFp32 = TRX_PROBE_FP32 != 0;
 
+// LDS of cells_kernel: [node tables | atan constants | tier head] shared by the workgroup's waves (then, short curves,
+// the staged light curve), and per wave [rows, accumulators | pair table | in-window list | cell state (| stencil state)]
+constexpr size_t cells_tables_bytes()
+{
+    return (size_t)(2 * kTiers * kTierMaxNodes + kAtanRanges * kAtanCols + kTierHeadDoubles) * sizeof(double);
+}
+constexpr size_t cells_wave_bytes(int B, bool long_variant)
+{
+    return (size_t)B * (kRowDoubles + 4) * sizeof(double)
+         + (kCellsPairs + cells_window(long_variant)) * sizeof(unsigned short) + sizeof(CellState)
+         + (long_variant ? sizeof(StencilState) : 0);
+}
+// one row per wave: sixteen one-wave workgroups per CU (four waves per SIMD) share its 160 KB
+static_assert(cells_tables_bytes() + cells_wave_bytes(1, true) <= 160 * 1024 / 16, "LDS of the one-row workgroup");
+
 template <int MODE>
 int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
 {
@@ -362,6 +377,7 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
     a.debug_bug = knob_debug_bug();
     a.whole_trips = knob_whole_trips();
     a.one_sweep = knob_one_sweep();
+    a.full_chunks = knob_full_chunks();
     a.mark_unwritten = (MODE == MODE_LNL && !a.inv_var) ? 1 : 0;     // (a weighted launch may ADD to out[]: never marked)
     bool tiers_ok = false;
     if (tier_device(a.S, a.tiers, &a.tier_xw, &tiers_ok)) return fail(TRX_ERR_HIP, "tier table upload failed%s", "", 0);
@@ -396,12 +412,8 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
     // state (| stencil state)]
     static_assert((kCellsPairs + kCellsWindowLong) % 4 == 0 && (kCellsPairs + kCellsWindowBatch) % 4 == 0 &&
                   sizeof(CellState) % 8 == 0 && sizeof(StencilState) % 8 == 0, "8-byte alignment of the LDS arrays");
-    const size_t tables = (size_t)(2 * kTiers * kTierMaxNodes + kAtanRanges * kAtanCols + kTierHeadDoubles) * sizeof(double);
-    auto wave_bytes = [&](bool long_variant) -> size_t {
-        return (size_t)a.B * (kRowDoubles + 4) * sizeof(double)
-             + (kCellsPairs + cells_window(long_variant)) * sizeof(unsigned short) + sizeof(CellState)
-             + (long_variant ? sizeof(StencilState) : 0);
-    };
+    const size_t tables = cells_tables_bytes();
+    auto wave_bytes = [&](bool long_variant) -> size_t { return cells_wave_bytes(a.B, long_variant); };
     a.tl_off = (int)(tables / sizeof(double));
     size_t shared = tables + (long_rows ? 0 : (size_t)(a.inv_var ? 3 : 2) * a.n_time * sizeof(double));
     size_t lds = shared + cells_waves(long_rows) * wave_bytes(long_rows);
@@ -1642,6 +1654,21 @@ int trx_set_one_sweep(int mode)
     if (mode < 0 || mode > 2) return fail(TRX_ERR_ARG, "trx_set_one_sweep: mode must be 0, 1 or 2%s (got %ld)", "", (long)mode);
     g_knob_one_sweep = mode;
     return TRX_OK;
+}
+
+/* (tests) 0: the one-row likelihood kernels keep the stencil's one-sided halo (56 new cells per chunk); 2: full chunks in
+   the flux grid too, where it takes the one sweep (trx_set_one_sweep(2)) */
+int trx_set_full_chunks(int mode)
+{
+    if (mode < 0 || mode > 2) return fail(TRX_ERR_ARG, "trx_set_full_chunks: mode must be 0, 1 or 2%s (got %ld)", "", (long)mode);
+    g_knob_full_chunks = mode;
+    return TRX_OK;
+}
+
+/* (tests) the LDS a workgroup of the one-row cells_kernel is launched with, as plan_cells computes it */
+long trx_debug_cells_lds_one_row(void)
+{
+    return (long)(cells_tables_bytes() + cells_wave_bytes(1, true));
 }
 
 /* (tests) the pass-1 trips filed whole / walked cell by cell on the current device since the last reset */
