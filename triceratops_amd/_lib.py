@@ -52,6 +52,9 @@ ROBUST_SYMBOLS = ("trxr_chi2_grid_robust",)
 GLS_SYMBOLS = ("trxg_chi2_grid_ou_baseline",)
 # ... include/trx_ss.h (both libraries: the row reduction under correlated noise with a two-dimensional state, prefix trxs_)
 SS_SYMBOLS = ("trxs_chi2_grid_ss2",)
+# ... include/trx_mix.h as well (both libraries: the weighted row reduction over a grid of candidate white-noise models,
+# prefix trxv_)
+WHITE_SYMBOLS = ("trxv_chi2_grid_white_mix",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -199,6 +202,8 @@ def _load(path, testing):
     L.trxm_chi2_grid_ou_mix.restype = c_int
     L.trxm_chi2_grid_ou_mix.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, c_int, _vp, _vp,
                                         _vp]
+    L.trxv_chi2_grid_white_mix.restype = c_int
+    L.trxv_chi2_grid_white_mix.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, c_int, _vp, _vp, _vp]
     L.trxt_softmin_rows.restype = c_int
     L.trxt_softmin_rows.argtypes = [_vp, c_long, c_long, c_int, _vp, c_int, _vp, _vp]
     L.trxr_chi2_grid_robust.restype = c_int
@@ -656,6 +661,33 @@ def chi2_grid_ou_mix(flux_d, grid_d, alpha_d, beta_d, omega_d, lnc, secdepth=Non
     return _chi2_rows("trxm_chi2_grid_ou_mix", (flux_d,), grid_d, secdepth, sec_limit, out, alpha_d.data_ptr(),
                       beta_d.data_ptr(), omega_d.data_ptr(), j, lnc.ctypes.data,
                       cand_out.data_ptr() if cand_out is not None else None)
+
+
+def chi2_grid_white_mix(flux_d, grid_d, w_d, lnc, secdepth=None, sec_limit=float("inf"), out=None, cand_out=None):
+    """chi2_grid_weighted over J candidate white-noise models in one pass over the grid (trxv_chi2_grid_white_mix,
+    include/trx_mix.h): per row T = -ln sum_j exp(lnc[j] - h_j), h_j what chi2_grid_weighted gives with inv_var = row j of w_d
+    (a [J][n_time] fp64 device tensor; datasets.white_mix_system), clamped at 0.  lnc: [J] float64 on the host.  cand_out: an
+    [n][J] fp64 device tensor that receives the h_j, or None.  The other arguments are chi2_grid_weighted's."""
+    n, nt = grid_d.shape
+    assert flux_d.dtype == torch.float64
+    lnc = np.ascontiguousarray(lnc, dtype=np.float64)
+    assert lnc.ndim == 1
+    j = int(lnc.size)
+    assert 1 <= j <= 8, "1 .. 8 candidates (got %d)" % j
+    assert w_d.shape == (j, nt) and w_d.dtype == torch.float64 and w_d.is_contiguous()
+    assert cand_out is None or (cand_out.shape == (n, j) and cand_out.dtype == torch.float64 and cand_out.is_contiguous())
+    return _chi2_rows("trxv_chi2_grid_white_mix", (flux_d,), grid_d, secdepth, sec_limit, out, w_d.data_ptr(), j,
+                      lnc.ctypes.data, cand_out.data_ptr() if cand_out is not None else None)
+
+
+def white_mix_blocks(n, n_time, n_cand):
+    """the blocks trxv_chi2_grid_white_mix launches for n rows of n_time stamps and n_cand candidates (its launcher's cap,
+    for the tests): 4 rows a block, at most 8 blocks a CU -- fewer where the staged [1 + n_cand] vectors fill the 160 KB of
+    LDS -- on 256 CUs; staged up to ((2 * 2048) // (1 + n_cand)) & ~1 stamps"""
+    stage = n_time <= (((2 * 2048) // (1 + n_cand)) & ~1)
+    lds = (1 + n_cand) * ((n_time + 1) & ~1) * 8 if stage else 0
+    per_cu = min((160 * 1024) // lds, 8) if lds else 8
+    return min((n + 3) // 4, 256 * per_cu)
 
 
 def softmin_rows(cand_d, lnc, out=None):

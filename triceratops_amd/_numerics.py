@@ -249,6 +249,31 @@ def ou_mix_halfchi2(y, alpha, beta, omega, lnc, dtype=np.float64, return_candida
     return (t, h) if return_candidates else t
 
 
+def white_mix_halfchi2(y, w, lnc, dtype=np.float64, return_candidates=False):
+    """A dataset's term of the log-weight with the size of its white noise marginalised over J candidates (DESIGN.md section
+    14), on the host: the statement of what trxv_chi2_grid_white_mix computes per row,
+        h_j = 0.5 sum_t w_j[t] y_t^2,  a_j = h_j - lnc_j,  m = min_j a_j,
+        T = m - ln sum_j exp(m - a_j) = -ln sum_j exp(lnc_j - h_j),   stored as 0 where rounding drives it below,
+    w [J][T] and lnc [J] from datasets.white_mix_system; the terms are summed in ascending j.  y: [..., T] residuals.  In
+    `dtype` (np.longdouble: the tests' reference).  J = 1 with lnc = 0 gives the plain weighted chi^2/2,
+    0.5 * sum(w[0] * y * y).  return_candidates: (T, h [..., J])."""
+    y = np.asarray(y, dtype=dtype)
+    w = np.atleast_2d(np.asarray(w, dtype=dtype))
+    lnc = np.asarray(lnc, dtype=dtype)
+    assert w.shape[0] == lnc.size and lnc.ndim == 1
+    h = np.stack([dtype(0.5) * np.sum(w[j] * y * y, axis=-1) for j in range(lnc.size)], axis=-1)
+    a = h - lnc
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        m = np.fmin.reduce(a, axis=-1)
+        s = np.zeros(m.shape, dtype=dtype)
+        for j in range(lnc.size):
+            s = s + np.exp(m - a[..., j])
+        t = np.where(m < np.inf, m - np.log(s), m)                # (every candidate +inf, or a NaN row: no inf - inf)
+        t = np.where(t < 0, dtype(0.0), t)                        # (a NaN stays a NaN)
+    t = np.asarray(t, dtype=dtype)
+    return (t, h) if return_candidates else t
+
+
 def t0_mix_halfchi2(h, lnpi):
     """A dataset's term of the log-weight with a transit-time shift marginalised over J nodes, on the
     host: the statement of what trxt_softmin_rows computes per row,

@@ -1,6 +1,6 @@
 // libtrx.so: the host side of the likelihood path and the C ABI (include/trx.h) for gfx950.
 //
-// The kernels live in nine headers that only this file includes:
+// The kernels live in ten headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
 //                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
@@ -19,6 +19,8 @@
 //                    softmin_launch here; include/trx_shift.h)
 //   trx_robust.hpp   chi2_robust_kernel<STAGE> (the outlier-tolerant row reduction: a two-component mixture per point, one
 //                    exp and one log1p a value; chi2_robust_launch here; include/trx_robust.h)
+//   trx_white_mix.hpp  chi2_white_mix_kernel<STAGE, J> (the weighted row reduction for J candidate white-noise models in
+//                    one pass, their soft minimum per row; chi2_white_mix_launch here; include/trx_mix.h)
 //   trx_gls.hpp      OuColsFilter<K> (the OU filter with K baseline columns marginalised under the same noise;
 //                    include/trx_gls.h)
 //   trx_ss2.hpp      Ss2Filter (noise with a two-dimensional state: 2 x 2 affine maps in the scan; include/trx_ss.h)
@@ -81,6 +83,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 #include "trx_noise_mix.hpp"
 #include "trx_softmin.hpp"
 #include "trx_robust.hpp"
+#include "trx_white_mix.hpp"
 #include "trx_gls.hpp"
 #include "trx_ss2.hpp"
 #include "trx_bands.hpp"
@@ -1116,6 +1119,27 @@ void chi2_robust_launch(const double* flux, const double* inv_var, const double*
                        sec_limit, accumulate, out, c);
 }
 
+// One launch of chi2_white_mix_kernel<STAGE, J> (trxv_chi2_grid_white_mix), J = n_cand: STAGE while flux and the J weight
+// vectors fit the LDS budget of chi2_rows_kernel, and chi2_rows_launch's cap of blocks -- 8 of 256 threads a CU, fewer where
+// the staged vectors fill the 160 KB of LDS, on 256 CUs.  The rows behind the cap are the second row of a wave's pass and
+// its further passes.
+void chi2_white_mix_launch(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                           double sec_limit, int accumulate, double* out, const WhiteMix& mix, int n_cand, hipStream_t st)
+{
+    dispatch_int<1, kWhiteMixMax>(n_cand, [&](auto j) {
+        constexpr int J = decltype(j)::value;
+        const bool stage = n_time <= white_stage_max(J);
+        const size_t lds = stage ? (1 + J) * (size_t)((n_time + 1) & ~1) * sizeof(double) : 0;
+        long per_cu = lds ? (long)((160u * 1024u) / lds) : 8;
+        per_cu = per_cu > 8 ? 8 : per_cu;
+        long blocks = (n + 3) / 4;
+        if (blocks > 256L * per_cu) blocks = 256L * per_cu;
+        const auto kernel = stage ? chi2_white_mix_kernel<true, J> : chi2_white_mix_kernel<false, J>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, st, flux, model_grid, n_time, n, secdepth,
+                           sec_limit, accumulate, out, mix);
+    });
+}
+
 // One launch of softmin_rows_kernel<J> (trxt_softmin_rows), J = n_cand: one lane per row, and as many blocks as the draw
 // kernel's cap -- 16 of 256 threads a CU, on 256 CUs; the rows behind that cap are a lane's further trips.
 void softmin_launch(const double* cand, long stride, long n, int n_cand, const Lnc8& lnc, int accumulate, double* out,
@@ -1256,6 +1280,23 @@ int trxm_chi2_grid_ou_mix(const double* flux, const double* model_grid, int n_ti
         scan_rows_launch(ou_mix_kernel<true, J>, ou_mix_kernel<false, J>, flux, model_grid, n_time, n, secdepth, sec_limit,
                          accumulate, out_halfchi2, mix, J <= 2 ? 4 : 2, static_cast<hipStream_t>(stream));
     });
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trxv_chi2_grid_white_mix(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                             double sec_limit, int accumulate, double* out_halfchi2, const double* weights, int n_cand,
+                             const double* lnc, double* cand_out, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (n_cand < 1 || n_cand > TRXV_MAX_CANDIDATES) return fail(TRX_ERR_ARG, "n_cand outside 1 .. 8%s (n_cand=%ld)", "", n_cand);
+    if (!flux || !model_grid || !out_halfchi2 || !weights || !lnc) return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    static_assert(TRXV_MAX_CANDIDATES == kWhiteMixMax, "the header's limit is the kernel's");
+    WhiteMix mix{weights, {}, cand_out};
+    if (int rc = pack_lnc(lnc, n_cand, "candidate", mix.lnc)) return rc;
+    if (n == 0) return TRX_OK;
+    chi2_white_mix_launch(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, mix, n_cand,
+                          static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

@@ -12,7 +12,9 @@ to MAX_T0_NODES weighted shifts of its stamps, marginalised per draw (t0_grids);
 `t0_grid`) alone `red_baseline` / `red_baseline_sigma`: up to MAX_BASELINE_TERMS baseline columns marginalised under that
 correlated noise (red_baselines, ou_baseline_system); or, alone or next to `t0_grid`,
 `outlier_frac` / `outlier_scale`: every point is with probability eps an outlier from a Gaussian kappa times wider than its
-error, the membership integrated out per point and per draw (outliers, robust_constants).  This module is host side and numpy only:
+error, the membership integrated out per point and per draw (outliers, robust_constants); or, alone or next to `t0_grid`,
+`white_grid`: up to MAX_WHITE_CANDIDATES weighted candidates (error scale k, jitter s) of the white noise's size,
+marginalised per draw (white_grids, white_mix_system).  This module is host side and numpy only:
 validation, the reference noise sigma_bar and the per-star renormalisation.  A `Datasets` object is what the lnZ_*
 functions receive in place of `time` (with flux = None and sigma = sigma_bar); only the device sampling modes evaluate it
 (fused._Scenario).
@@ -29,6 +31,7 @@ MAX_BASELINE_TERMS = 4          # terms of a dataset's linear baseline model, th
 MIN_BASELINE_EIGENVALUE = 1e-6  # of the scaled system matrix: below it the columns count as collinear
 MAX_RED_CANDIDATES = 8          # candidate (s_r, tau) pairs of a dataset's red_grid
 MAX_T0_NODES = 8                # nodes (shift, weight) of a dataset's t0_grid
+MAX_WHITE_CANDIDATES = 8        # candidate (scale, jitter) pairs of a dataset's white_grid
 DEFAULT_EXPTIME, DEFAULT_NSAMPLES = 0.00139, 20
 
 
@@ -354,6 +357,88 @@ def outliers(dicts, sets):
     return [_outliers(i, d, s) for i, (d, s) in enumerate(zip(dicts, sets))]
 
 
+WHITE_GRID_NEIGHBOURS = ("offset_sigma", "baseline", "baseline_sigma", "red_sigma", "red_timescale", "red_grid", "red_kernel",
+                         "red_baseline", "red_baseline_sigma") + OUTLIER_KEYS
+
+
+def _white_grid(i, d):
+    """a dataset's "white_grid" -> [J][3] float64 rows (scale k, jitter s, weight), the weights normalised to sum 1, or
+    None; d: the dataset's dict (what else it asks for)"""
+    value = d.get("white_grid")
+    if value is None:
+        return None
+    msg = ("dataset %d: white_grid must be 1 ... %d triples (scale, jitter, weight): scale finite and > 0, jitter finite and "
+           ">= 0, weight finite and > 0 (got %r)" % (i, MAX_WHITE_CANDIDATES, value))
+    if isinstance(value, (bool, str, bytes)):
+        raise ValueError(msg)
+    try:
+        if not isinstance(value, np.ndarray) or value.dtype.kind not in "iuf":
+            # (a bool or a string among the entries would convert silently)
+            if any(isinstance(x, (bool, np.bool_, str, bytes)) for x in np.asarray(value, dtype=object).ravel()):
+                raise TypeError
+        g = np.array(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(msg) from None
+    if g.ndim != 2 or g.shape[1] != 3 or not 1 <= g.shape[0] <= MAX_WHITE_CANDIDATES:
+        raise ValueError(msg)
+    scale, jitter, weight = g[:, 0], g[:, 1], g[:, 2]
+    if not (np.all(np.isfinite(scale) & (scale > 0)) and np.all(np.isfinite(jitter) & (jitter >= 0))
+            and np.all(np.isfinite(weight) & (weight > 0))):
+        raise ValueError(msg)                                     # (also NaN)
+    others = [k for k in WHITE_GRID_NEIGHBOURS if d.get(k) is not None]
+    if others:
+        raise ValueError("dataset %d: white_grid together with %s is not built: the candidates stand alone or next to t0_grid "
+                         "(a marginalised linear term would need its sums and its determinant per candidate)"
+                         % (i, ", ".join(others)))
+    total = math.fsum(weight.tolist())
+    if not (math.isfinite(total) and total > 0):
+        raise ValueError(msg)
+    g[:, 2] = weight / total
+    return np.ascontiguousarray(g)
+
+
+def white_grids(dicts, sets):
+    """The "white_grid" keys of the dicts that validate() turned into `sets`: per dataset None, or a contiguous float64
+    [J][3] array of J = 1 ... MAX_WHITE_CANDIDATES rows (k_j, s_j, weight_j) -- an error scale k finite and > 0, a jitter s
+    finite and >= 0 in flux units, a prior weight finite and > 0, normalised to sum 1 (math.fsum); repeated pairs are
+    allowed.  Candidate j has the per-point variance k_j^2 flux_err_t^2 + s_j^2, and the dataset's term of the log-weight
+    becomes -ln sum_j c_j exp(-h_j) (_numerics.white_mix_halfchi2 on white_mix_system).  No condition on the order of the
+    stamps.  The key stands alone or next to t0_grid; next to offset_sigma, baseline, red_sigma / red_timescale, red_grid,
+    red_kernel, red_baseline / red_baseline_sigma or the outlier keys it is a ValueError, as is a wrong shape, too many
+    rows, a value that is not finite, a scale <= 0, a jitter < 0, a weight <= 0, a bool or a string.  Dataset itself has no
+    field for the key: the grids travel in Datasets.white_grids."""
+    if len(dicts) != len(sets):
+        raise ValueError("white_grids: %d dicts for %d datasets" % (len(dicts), len(sets)))
+    return [_white_grid(i, d) for i, d in enumerate(dicts)]
+
+
+def white_mix_system(dataset, grid):
+    """(w [J][T], lnc [J]), float64: the per-point weights of every candidate (k_j, s_j, pi_j) of a dataset's white_grid
+    [J][3] and the candidates' log-weights,
+        w_j[t] = 1 / (k_j^2 flux_err_t^2 + s_j^2),
+        lnc_j = ln pi_j + 0.5 sum_t ln w_j[t] - logsumexp_j(the same),
+    so that sum_j exp(lnc_j) = 1 and the dataset's term of the log-weight is -ln sum_j exp(lnc_j - h_j),
+    h_j = 0.5 sum_t w_j[t] y_t^2 (_numerics.white_mix_halfchi2, trxv_chi2_grid_white_mix) -- the one place that forms them,
+    for the device path (fused._Dataset) and for the numpy statement.  The candidate (1, 0) has the bits of
+    1 / (flux_err * flux_err), a power-of-two k those of the same errors scaled.  The sums are math.fsum's; the normaliser
+    that is dropped, sum_j pi_j prod_t w_j[t]^(1/2), depends on the dataset alone."""
+    err = np.asarray(dataset.flux_err, dtype=np.float64)
+    grid = np.asarray(grid, dtype=np.float64)
+    w, terms = [], []
+    for k_j, s_j, weight in grid:
+        k_j, s_j = float(k_j), float(s_j)
+        w_j = 1.0 / ((k_j * k_j) * (err * err) + s_j * s_j)
+        w.append(w_j)
+        terms.append([math.log(weight)] + (0.5 * np.log(w_j)).tolist())
+    # (the raw values are large -- half a log-determinant --, their differences are not: the difference to the largest is
+    # one correctly rounded sum over both candidates' terms, so the spacing of the raw values does not enter)
+    top = [-v for v in max(terms, key=math.fsum)]
+    diff = [math.fsum(t + top) for t in terms]
+    norm = math.log(math.fsum(math.exp(v) for v in diff))
+    lnc = np.array([v - norm for v in diff])
+    return np.ascontiguousarray(np.stack(w)), lnc
+
+
 RED_BASELINE_KEYS = ("red_baseline", "red_baseline_sigma")
 
 
@@ -579,11 +664,11 @@ def _check_baseline(i, dataset):
 def validate(datasets):
     """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
     baseline_sigma, red_sigma, red_timescale, red_kernel, red_grid, t0_grid, outlier_frac, outlier_scale, red_baseline,
-    red_baseline_sigma]} -> a list of Dataset ("red_kernel" = "matern32" / "ou2" gives a Matern32Dataset / an Ou2Dataset: the
+    red_baseline_sigma, white_grid]} -> a list of Dataset ("red_kernel" = "matern32" / "ou2" gives a Matern32Dataset / an Ou2Dataset: the
     same fields, red_sigma and red_timescale two finite numbers / two arrays of two finite entries, all > 0; "t0_grid"
     is allowed here and read by t0_grids, "outlier_frac" / "outlier_scale" are checked here and returned by outliers,
-    "red_baseline" / "red_baseline_sigma" are checked here and returned by red_baselines: no field
-    of Dataset holds them).  Points with a NaN time or flux are dropped together with their error and their
+    "red_baseline" / "red_baseline_sigma" are checked here and returned by red_baselines, "white_grid" is checked here and
+    returned by white_grids: no field of Dataset holds them).  Points with a NaN time or flux are dropped together with their error and their
     baseline entries; a scalar flux_err is broadcast.  ValueError for an empty list, too many datasets, mismatched
     lengths, an error that is not finite or not positive, a dataset without points, an offset_sigma that is not None, a
     number > 0 or inf, a baseline that is not [K][len(time)] and finite at the kept points, a baseline_sigma that is not
@@ -597,7 +682,7 @@ def validate(datasets):
     offset_sigma, baseline, red_sigma / red_timescale or red_grid; for a red_kernel that is not None, "ou", "matern32" or
     "ou2", and with the last two for a red_sigma or red_timescale of the wrong shape or with an entry that is not finite and
     > 0, for stamps out of order, or for offset_sigma, baseline, red_grid, red_baseline or the outlier keys next to them; and
-    for what red_baselines lists."""
+    for what red_baselines and white_grids list."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -608,7 +693,7 @@ def validate(datasets):
     for i, d in enumerate(datasets):
         unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma",
                             "red_sigma", "red_timescale", "red_grid", "t0_grid", "outlier_frac", "outlier_scale",
-                            "red_baseline", "red_baseline_sigma", "red_kernel"}
+                            "red_baseline", "red_baseline_sigma", "red_kernel", "white_grid"}
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -654,6 +739,7 @@ def validate(datasets):
         _check_baseline(i, out[-1])
         _red_baseline(i, d, out[-1])
         _outliers(i, d, out[-1])
+        _white_grid(i, d)
     return out
 
 
@@ -676,10 +762,10 @@ def sigma_bar(errs):
 
 class Datasets:
     """validated datasets in one star's normalisation, their sigma_bar, and per dataset None or its transit-time shift
-    grid (t0_grids), None or its outlier pair (frac, scale) (outliers) and None or the pair (columns, sigmas) of its
-    baseline under correlated noise (red_baselines)"""
+    grid (t0_grids), None or its outlier pair (frac, scale) (outliers), None or the pair (columns, sigmas) of its
+    baseline under correlated noise (red_baselines) and None or its grid of white-noise candidates (white_grids)"""
 
-    def __init__(self, sets, t0_grids=None, outliers=None, red_baselines=None):
+    def __init__(self, sets, t0_grids=None, outliers=None, red_baselines=None, white_grids=None):
         self.sets = tuple(sets)
         self.sigma_ref = sigma_ref(self.sets)
         self.t0_grids = (None,) * len(self.sets) if t0_grids is None else tuple(t0_grids)
@@ -691,6 +777,9 @@ class Datasets:
         self.red_baselines = (None,) * len(self.sets) if red_baselines is None else tuple(red_baselines)
         if len(self.red_baselines) != len(self.sets):
             raise ValueError("red_baselines: %d pairs for %d datasets" % (len(self.red_baselines), len(self.sets)))
+        self.white_grids = (None,) * len(self.sets) if white_grids is None else tuple(white_grids)
+        if len(self.white_grids) != len(self.sets):
+            raise ValueError("white_grids: %d grids for %d datasets" % (len(self.white_grids), len(self.sets)))
 
     def __len__(self):
         return len(self.sets)
@@ -720,6 +809,10 @@ class Datasets:
         return any(b is not None for b in self.red_baselines)
 
     @property
+    def has_white_grids(self):
+        return any(g is not None for g in self.white_grids)
+
+    @property
     def size(self):
         """points of all datasets together"""
         return sum(s.time.size for s in self.sets)
@@ -737,7 +830,9 @@ class Datasets:
         and renorm_flux leaves it alone.  A finite sigma of a red_baselines pair is in flux units per unit of its column
         and is divided by the flux ratio; the columns are left alone: with red_sigma and the errors scaled alike, D_k of
         ou_baseline_system scales with the square of the flux ratio, s_k^2 D_k and the scaled system matrix are the same
-        for every star, and so is the determinant that the evidence drops."""
+        for every star, and so is the determinant that the evidence drops.  The jitter column of a white_grids grid is in
+        flux units and is divided by the flux ratio, the scales are pure numbers: every candidate's weights gain the
+        square of the flux ratio, so the lnc of white_mix_system do not change."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
@@ -758,4 +853,10 @@ class Datasets:
                                   baseline_sigma=bsig, red_sigma=red, red_grid=grid))
         red = [None if p is None else (p[0], np.where(np.isfinite(p[1]), p[1] / star_fluxratio, p[1]))
                for p in self.red_baselines]
-        return Datasets(out, self.t0_grids, self.outliers, red)
+        white = []
+        for g in self.white_grids:
+            if g is not None:
+                g = g.copy()
+                g[:, 1] = g[:, 1] / star_fluxratio
+            white.append(g)
+        return Datasets(out, self.t0_grids, self.outliers, red, white)

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, funcs
-from .datasets import (Datasets, baseline_system, ou_baseline_system, ou_mix_system, ou_system, robust_constants,
+from .datasets import (Datasets, baseline_system, ou_baseline_system, ou_mix_system, ou_system, robust_constants, white_mix_system,
                        ss2_system)
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
@@ -253,6 +253,11 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # (grid evaluation only).  DATASET_RED_BASELINES = {}: every such call leaves {work unit: [per branch, a list per dataset:
 # None or the [K_b] posterior-mean coefficients at the branch's best draw, in the call's normalisation (with a t0_grid on
 # its heaviest node)]} there (target.dataset_red_baselines).
+# A dataset with a `white_grid` (Datasets.white_grids) has the size of its white noise -- an error scale and a jitter --
+# marginalised over its candidates per draw: its reduction is trxv_chi2_grid_white_mix on the weights and log-weights of
+# datasets.white_mix_system (grid evaluation only).  DATASET_WHITE_NOISE = {}: every such call leaves {work unit: [per branch, a
+# list per dataset: None or the [J] posterior weights of the candidates at the branch's best draw, softmax_j(lnc_j - h_j)
+# (with a t0_grid on its heaviest node)]} there (target.dataset_white_noise).
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
@@ -262,6 +267,7 @@ DATASET_RED_NOISE = None
 DATASET_T0 = None
 DATASET_OUTLIERS = None
 DATASET_RED_BASELINES = None
+DATASET_WHITE_NOISE = None
 # An importance map (WARP_GRIDS) applies to a datasets call as to any other: its draws are trx_draw_scenario's.  The weight
 # histogram of the library's own chain (WARP_HIST) does not exist here -- chi^2/2 is computed outside that chain -- so
 # DATASET_WARP_HIST = {}: every datasets call leaves {work unit: [branches][WARP_BRANCH] uint64 words} there, one
@@ -272,7 +278,7 @@ DATASET_WARP_HIST = None
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_OUTLIERS, DATASET_RED_BASELINES, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_OUTLIERS, DATASET_RED_BASELINES, DATASET_WHITE_NOISE, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -787,6 +793,21 @@ def _mix_on_device(d, device):
     return _cached(_mix_cache, key, 32, build)
 
 
+_white_cache = {}
+
+
+def _white_on_device(d, grid, device):
+    """(w [J][T] on the device, lnc [J] on the host) of a dataset with a white_grid [J][3] (datasets.white_mix_system):
+    formed once per content of its errors and candidates for the lnZ_* calls of a star (a cache of its own, as
+    _mix_on_device's)"""
+    key = (hash(d.flux_err.tobytes()), hash(grid.tobytes()), d.flux_err.shape, grid.shape, device.index)
+
+    def build():
+        w, lnc = white_mix_system(d, grid)
+        return _lib.dev(w, device), lnc
+    return _cached(_white_cache, key, 32, build)
+
+
 _ss2_cache = {}
 
 
@@ -854,7 +875,7 @@ class _Dataset(NamedTuple):
     or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then --, or correlated
     noise -- one exponential term alone (`ou`) or with baseline columns under it (`gls`: `ou` is None then), or a term with
     a two-dimensional state (`ss2`: `ou` is None then) --, or the outlier mixture of its
-    points; and, next to any of these, the nodes of a transit-time shift (`shift`: the
+    points, or white noise whose size is marginalised over candidates (`white`); and, next to any of these, the nodes of a transit-time shift (`shift`: the
     reduction then runs once per node)"""
     time: torch.Tensor
     flux: torch.Tensor
@@ -869,9 +890,10 @@ class _Dataset(NamedTuple):
     robust: Optional[tuple] = None           # (c0, c1, k2): the outlier mixture of the points (datasets.robust_constants)
     gls: Optional[_Gls] = None               # baseline columns under correlated noise (datasets.ou_baseline_system)
     ss2: Optional[tuple] = None              # (A, g, omega) on the device: red_kernel matern32 / ou2 (datasets.ss2_system)
+    white: Optional[tuple] = None            # (w [J][T] on the device, lnc [J] on the host): datasets.white_mix_system
 
     @classmethod
-    def upload(cls, d, dev, t0_grid=None, outliers=None, red_baseline=None):
+    def upload(cls, d, dev, t0_grid=None, outliers=None, red_baseline=None, white_grid=None):
         inv_var = 1.0 / (d.flux_err * d.flux_err)
         rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
         if outliers is not None:
@@ -880,6 +902,9 @@ class _Dataset(NamedTuple):
         if t0_grid is not None:
             # (next to whatever else the dataset marginalises: a shift leaves all of that as it is)
             rec = rec._replace(shift=_shift_on_device(d, t0_grid, dev))
+        if white_grid is not None:
+            # (validate refuses anything but a t0_grid next to it)
+            return rec._replace(white=_white_on_device(d, white_grid, dev))
         if d.red_grid is not None:
             # (validate refuses anything else next to it)
             return rec._replace(mix=_mix_on_device(d, dev))
@@ -910,9 +935,11 @@ class _Dataset(NamedTuple):
         trxn_chi2_grid_ou for correlated noise, trxm_chi2_grid_ou_mix for a grid of its candidates (cand_out: the rows'
         per-candidate chi^2/2), trxg_chi2_grid_ou_baseline for baseline columns under correlated noise (coef_out likewise),
         trxs_chi2_grid_ss2 for correlated noise with a two-dimensional state, trxr_chi2_grid_robust for the outlier mixture,
-        else trx_chi2_grid_weighted."""
+        trxv_chi2_grid_white_mix for a grid of white-noise candidates (cand_out likewise), else trx_chi2_grid_weighted."""
         if self.robust is not None:
             return _lib.chi2_grid_robust(self.flux, self.inv_var, grid, *self.robust, secdepth, sec_limit, out=out)
+        if self.white is not None:
+            return _lib.chi2_grid_white_mix(self.flux, grid, *self.white, secdepth, sec_limit, out=out, cand_out=cand_out)
         if self.mix is not None:
             return _lib.chi2_grid_ou_mix(self.flux, grid, *self.mix, secdepth, sec_limit, out=out, cand_out=cand_out)
         if self.gls is not None:
@@ -940,8 +967,9 @@ class _Scenario:
         self.datasets = None
         if isinstance(time, Datasets):
             # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
-            self.datasets = [_Dataset.upload(d, self.dev, g, o, b)
-                             for d, g, o, b in zip(time.sets, time.t0_grids, time.outliers, time.red_baselines)]
+            self.datasets = [_Dataset.upload(d, self.dev, g, o, b, w)
+                             for d, g, o, b, w in zip(time.sets, time.t0_grids, time.outliers, time.red_baselines,
+                                                      time.white_grids)]
             sigma = time.sigma_ref
             self.time, self.flux = self.datasets[0].time, self.datasets[0].flux
         else:
@@ -1199,7 +1227,7 @@ class _Scenario:
         flags = self._flags(is_host)
         offsets = []       # (DATASET_OFFSETS: per branch the best draw's offsets, still on the device)
         coefs = []         # (DATASET_BASELINES: per branch and dataset the best draw's scaled coefficients, likewise)
-        cands = []         # (DATASET_RED_NOISE: per branch and dataset the best draw's per-candidate chi^2/2, likewise)
+        cands = []         # (DATASET_RED_NOISE, DATASET_WHITE_NOISE: per branch and dataset the best draw's per-candidate chi^2/2, likewise)
         nodes = []         # (DATASET_T0: per branch and dataset the best draw's per-node terms, likewise)
         probs = []         # (DATASET_OUTLIERS: per branch and dataset the best draw's model row, likewise)
         hists = None       # (DATASET_WARP_HIST: per branch the weight histogram of its evidence, likewise)
@@ -1233,7 +1261,7 @@ class _Scenario:
             best = self._best(h, idx, n)
             if self.datasets is not None and ((DATASET_OFFSETS is not None and any(d.offset is not None for d in self.datasets))
                                               or self._any_baseline() or self._any_mix() or self._any_shift()
-                                              or self._any_robust() or self._any_gls()):
+                                              or self._any_robust() or self._any_gls() or self._any_white()):
                 o, c, hc, hn, mr = (self._best_offsets(model, flags, cols, best, twin, nblk) if n
                                     else (None, None, None, None, None))
                 offsets.append(o)
@@ -1286,6 +1314,10 @@ class _Scenario:
         """whether a robust dataset's outlier probabilities are wanted back (DATASET_OUTLIERS)"""
         return DATASET_OUTLIERS is not None and any(d.robust is not None for d in self.datasets)
 
+    def _any_white(self):
+        """whether a white_grid dataset's candidate weights are wanted back (DATASET_WHITE_NOISE)"""
+        return DATASET_WHITE_NOISE is not None and any(d.white is not None for d in self.datasets)
+
     def _any_gls(self):
         """whether a red_baseline dataset's coefficients are wanted back (DATASET_RED_BASELINES)"""
         return DATASET_RED_BASELINES is not None and any(d.gls is not None for d in self.datasets)
@@ -1297,9 +1329,26 @@ class _Scenario:
         those of a t0_grid dataset's nodes, softmax_j(ln pi_j - h_j), to DATASET_T0 (likewise); and the posterior outlier
         probabilities of a robust dataset's points at that draw, _numerics.robust_responsibility on the draw's model row, to
         DATASET_OUTLIERS (likewise); and the coefficients of a red_baseline dataset's columns at that draw,
-        c_k = c~_k / sqrt(D_k), to DATASET_RED_BASELINES (likewise)"""
+        c_k = c~_k / sqrt(D_k), to DATASET_RED_BASELINES (likewise); and the posterior weights of a white_grid dataset's
+        candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_WHITE_NOISE (likewise)"""
         L = len(self.datasets)
         unit = getattr(_tls, "unit", None)
+        if DATASET_WHITE_NOISE is not None:
+            white = []
+            for hc in cands:
+                per = [None] * L
+                for l, d in enumerate(self.datasets):
+                    if d.white is None:
+                        continue
+                    lnc = d.white[1]
+                    if hc is None:
+                        per[l] = np.full(lnc.size, np.nan)
+                        continue
+                    x = lnc - hc[l].cpu().numpy().reshape(-1)
+                    w = np.exp(x - np.max(x))
+                    per[l] = w / w.sum()
+                white.append(per)
+            DATASET_WHITE_NOISE[unit] = white
         if DATASET_RED_BASELINES is not None:
             out = []
             for c in coefs:
@@ -1381,7 +1430,7 @@ class _Scenario:
         S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
         baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them; likewise for a
         red_baseline dataset under DATASET_RED_BASELINES); and None or the
-        [1][J] device tensor of a red_grid dataset's per-candidate chi^2/2.  The one row is evaluated again -- trx_flux_grid
+        [1][J] device tensor of a red_grid or white_grid dataset's per-candidate chi^2/2.  The one row is evaluated again -- trx_flux_grid
         on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out, coef_out or cand_out -- so nothing of
         size n x L is kept.  A t0_grid dataset has the row evaluated on every node: the fourth list holds None or the [J]
         device tensor of its per-node terms h_j, and its offset, coefficients and candidates are those of the node of
@@ -1400,7 +1449,8 @@ class _Scenario:
         for l, d in enumerate(self.datasets):
             if (d.offset is None and d.baseline is None and (d.mix is None or DATASET_RED_NOISE is None)
                     and (d.shift is None or DATASET_T0 is None) and (d.robust is None or DATASET_OUTLIERS is None)
-                    and (d.gls is None or DATASET_RED_BASELINES is None)):
+                    and (d.gls is None or DATASET_RED_BASELINES is None)
+                    and (d.white is None or DATASET_WHITE_NOISE is None)):
                 continue
             keep = d.robust is not None and DATASET_OUTLIERS is not None
             grids = []
@@ -1413,6 +1463,8 @@ class _Scenario:
                 coefs[l] = torch.empty((J, int(d.gls.c.shape[0])), dtype=F64, device=self.dev)
             if d.mix is not None:
                 cands[l] = torch.empty((J, int(d.mix[3].size)), dtype=F64, device=self.dev)
+            if d.white is not None:
+                cands[l] = torch.empty((J, int(d.white[1].size)), dtype=F64, device=self.dev)
             hs = []
             for j, t in enumerate(stamps):
                 grid, _ = _lib.flux_grid(model, flags, t, row, d.exptime, d.nsamples, want_secdepth=False)
@@ -1463,6 +1515,9 @@ class _Scenario:
         if DATASET_EVALUATION == "fused" and any(d.mix is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a red_grid dataset is not built: the fused kernel "
                                       "carries no recurrence along the row; use evaluation='grid'")
+        if DATASET_EVALUATION == "fused" and any(d.white is not None for d in self.datasets):
+            raise NotImplementedError("evaluation='fused' with a white_grid dataset is not built: the fused kernel "
+                                      "carries one sum per row, not one per candidate; use evaluation='grid'")
         if DATASET_EVALUATION == "fused" and any(d.shift is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a t0_grid dataset is not built: the nodes' terms are folded "
                                       "from the grid reductions; use evaluation='grid'")

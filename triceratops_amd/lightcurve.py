@@ -120,6 +120,26 @@ def red_noise_grid(sigmas, timescales, weights=None):
     return np.ascontiguousarray(np.stack([ss.ravel(), tt.ravel(), w.ravel() / w.sum()], axis=1))
 
 
+def white_noise_grid(scales, jitters=(0.0,), weights=None):
+    """The product grid of candidate error scales and jitters as a dataset's "white_grid": a float64 array
+    [len(scales) * len(jitters)][3] of rows (scale k, jitter s, weight), scales-major: candidate (k, s) has the per-point
+    variance k^2 flux_err^2 + s^2.  weights: None (equal), or an array [len(scales)][len(jitters)] of prior weights > 0; they
+    are normalised to sum 1.  datasets.validate checks the values and the number of candidates
+    (datasets.MAX_WHITE_CANDIDATES)."""
+    k = np.atleast_1d(np.asarray(scales, dtype=np.float64))
+    s = np.atleast_1d(np.asarray(jitters, dtype=np.float64))
+    if k.ndim != 1 or s.ndim != 1 or k.size == 0 or s.size == 0:
+        raise ValueError("scales and jitters must be non-empty 1-d sequences")
+    w = np.ones((k.size, s.size)) if weights is None else np.asarray(weights, dtype=np.float64)
+    if w.shape != (k.size, s.size):
+        raise ValueError("weights must have the shape (len(scales), len(jitters)) = %s (got %s)"
+                         % ((k.size, s.size), w.shape))
+    if not np.all(np.isfinite(w) & (w > 0)):
+        raise ValueError("every weight must be finite and > 0")
+    kk, ss = np.meshgrid(k, s, indexing="ij")
+    return np.ascontiguousarray(np.stack([kk.ravel(), ss.ravel(), w.ravel() / w.sum()], axis=1))
+
+
 def t0_shift_grid(sigma, n: int = 5, span: float = 3.0):
     """A Gaussian prior on a dataset's transit-time shift as its "t0_grid": a float64 array [n][2] of rows (shift, weight),
     n odd, the shifts equally spaced over -span * sigma ... +span * sigma (the middle one exactly 0, the others mirror
@@ -141,7 +161,7 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
                     exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None,
                     baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None,
                     red_grid=None, t0_grid=None, outlier_frac: float = None, outlier_scale: float = None,
-                    red_baseline_order: int = None, red_baseline_sigma=None, red_kernel: str = None):
+                    red_baseline_order: int = None, red_baseline_sigma=None, red_kernel: str = None, white_grid=None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
     {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
     empty bins are dropped.
@@ -158,6 +178,8 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     red_baseline_order (None: no such key; >= 0): "red_baseline" = trend_columns(kept bins' times, red_baseline_order), the
     trend marginalised under the dataset's red_sigma / red_timescale, with red_baseline_sigma (a number or one per column;
     None: flat) passed through.
+    white_grid (white_noise_grid's result, or any list of (scale, jitter, weight)): candidates of the size of the white noise
+    to marginalise, passed through as the key "white_grid" when given.
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -188,4 +210,6 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
         out["red_baseline"] = trend_columns(tb, red_baseline_order)
     if red_baseline_sigma is not None:
         out["red_baseline_sigma"] = red_baseline_sigma
+    if white_grid is not None:
+        out["white_grid"] = white_grid
     return out

@@ -28,6 +28,7 @@ from . import _lib
 from ._numerics import _mc_errors, _normalize_probabilities
 from .constants import G, Msun, pi
 from .datasets import (Datasets, outliers as _outliers, red_baselines as _red_baselines, t0_grids as _t0_grids,
+                       white_grids as _white_grids,
                        validate as _validate_datasets)
 from .funcs import renorm_flux
 from .marginal_likelihoods import *  # noqa: F401,F403  (reference re-exports the lnZ_* names)
@@ -260,7 +261,8 @@ class target:
             if k in calc_probs_kwargs:
                 raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
         sets = _validate_datasets(datasets)
-        ds = Datasets(sets, _t0_grids(datasets, sets), _outliers(datasets, sets), _red_baselines(datasets, sets))
+        ds = Datasets(sets, _t0_grids(datasets, sets), _outliers(datasets, sets), _red_baselines(datasets, sets),
+                      white_grids=_white_grids(datasets, sets))
         n_samples = int(n_samples)
         if not 0 <= n_samples <= fused.POST_MAX_ROWS:
             raise ValueError("n_samples must lie in [0, %d]" % fused.POST_MAX_ROWS)
@@ -274,7 +276,7 @@ class target:
 
     def _datasets_pass(self, ds, P_orb, kw, verbose, evaluation, n_samples=0, **dataset_switches):
         """one pass of the datasets path over the target's work units: (units, rows, n_scen) for _finish.
-        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_OUTLIERS / DATASET_RED_BASELINES / DATASET_WARP_HIST for
+        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_OUTLIERS / DATASET_RED_BASELINES / DATASET_WHITE_NOISE / DATASET_WARP_HIST for
         the length of the pass."""
         from . import fused
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
@@ -289,6 +291,8 @@ class target:
                                       "evaluation='grid'")
         if ds.has_t0_grids and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a t0_grid dataset is not built: use evaluation='grid'")
+        if ds.has_white_grids and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with a white_grid dataset is not built: use evaluation='grid'")
         if ds.has_outliers and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with an outlier_frac dataset is not built: use evaluation='grid'")
         with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, **dataset_switches):
@@ -435,7 +439,29 @@ class target:
         that do not fit the kernel or an entry that is not finite and > 0 (tau = inf stays the one term's business) it is a
         ValueError.  Grid evaluation only: evaluation="fused" raises NotImplementedError.  Nothing new is reported per
         best draw.  Not built: these kernels next to a baseline, red_grid or the outlier keys, a quasi-periodic (SHO) term,
-        more than two exponential terms, the fused evaluation, the scalar calc_probs path."""
+        more than two exponential terms, the fused evaluation, the scalar calc_probs path.
+
+        Where the SIZE of a dataset's white noise is not known -- photon-noise errors from a differential-photometry
+        pipeline, binned errors that ignore what detrending left --, the dataset may carry "white_grid": 1 to 8 candidates
+        (scale k, jitter s, weight) -- lightcurve.white_noise_grid makes a product grid --, k finite and > 0, s finite and
+        >= 0 in flux units, the prior weights > 0 (normalised to sum 1; repeated pairs are allowed).  Candidate j has the
+        per-point variance v_j[t] = k_j^2 sigma_t^2 + s_j^2, and the pair is integrated out per draw, determinants included:
+        with w_j = 1 / v_j, h_j = 0.5 sum_t w_j[t] (flux_t - model_t)^2 and c_j proportional to weight_j prod_t w_j[t]^(1/2),
+        sum_j c_j = 1 (datasets.white_mix_system), the dataset's term of the log-weight is -ln sum_j c_j exp(-h_j), in one
+        pass over the model grid for all candidates (trxv_chi2_grid_white_mix).  The normaliser
+        sum_j weight_j prod_t w_j[t]^(1/2) depends on the dataset only (every s_j scales with the errors under
+        renormalisation and the k_j are pure numbers, so the c_j are the same for every star) and is dropped as det K is for
+        red_grid: `.probs`, `.FPP` and `.NFPP` are those of the full marginal.  One candidate (1, 0) of weight 1 gives the
+        bits of the dataset without the key.  sigma_bar and the secondary-eclipse rule use flux_err as given.  No condition
+        on the order of the stamps: a folded light curve may carry the key.  It stands alone or next to "t0_grid"; next to
+        offset_sigma, baseline, red_sigma / red_timescale, red_grid, red_kernel, red_baseline or the outlier keys on the
+        same dataset it is a ValueError.  Grid evaluation only.  `.dataset_white_noise` is then a list per scenario of a
+        list per dataset: None for a dataset without the key, else {"grid": the [J][3] candidates as validated (k, s,
+        normalised prior weight, in the units given), "weight": the [J] posterior weights of the candidates at the
+        scenario's best draw, softmax_j(ln c_j - h_j) (NaN without a finite lnZ; with a t0_grid on its node of largest
+        weight)}; the whole attribute is None when no dataset has the key.  Not built: the key next to an offset, a
+        baseline, red noise or the outlier keys, a continuous fit of k or s, per-draw candidate posteriors, the fused
+        evaluation, the scalar calc_probs path."""
         ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
         best_offsets = {} if ds.has_offsets else None
         best_baselines = {} if ds.has_baselines else None
@@ -443,10 +469,12 @@ class target:
         best_t0 = {} if ds.has_t0_grids else None
         best_outliers = {} if ds.has_outliers else None
         best_gls = {} if ds.has_red_baselines else None
+        best_white = {} if ds.has_white_grids else None
         units, rows, n_scen = self._datasets_pass(ds, P_orb, kw, verbose, evaluation, n_samples,
                                                   DATASET_OFFSETS=best_offsets, DATASET_BASELINES=best_baselines,
                                                   DATASET_RED_NOISE=best_red, DATASET_T0=best_t0,
-                                                  DATASET_OUTLIERS=best_outliers, DATASET_RED_BASELINES=best_gls)
+                                                  DATASET_OUTLIERS=best_outliers, DATASET_RED_BASELINES=best_gls,
+                                                  DATASET_WHITE_NOISE=best_white)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
@@ -519,6 +547,20 @@ class target:
                     if np.isfinite(self.lnZ[u.first_row + i]):
                         rows_[u.first_row + i] = [None if c is None else c * share[u.group[1]] for c in per]
             self.dataset_red_baselines = rows_
+        self.dataset_white_noise = None
+        if best_white is not None:
+            # (the weights are pure numbers: the same in every star's normalisation; the grid is as validated, in the units
+            # given)
+            def cand(g, w=None):
+                if g is None:
+                    return None
+                return {"grid": g.copy(), "weight": np.full(g.shape[0], np.nan) if w is None else w}
+            rows_ = [[cand(g) for g in ds.white_grids] for _ in range(n_scen)]
+            for k, u in enumerate(sharding.as_units(units)):
+                for i, per in enumerate(best_white.get(k, ())):
+                    if np.isfinite(self.lnZ[u.first_row + i]):
+                        rows_[u.first_row + i] = [cand(g, w) for g, w in zip(ds.white_grids, per)]
+            self.dataset_white_noise = rows_
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
@@ -617,7 +659,7 @@ class target:
         uniforms from the chi^2/2 values of that pass (trxw_hist_from_halfchi2, fused.DATASET_WARP_HIST) and refine
         the map; best-draw offsets and baselines are not computed in them.  The final pass is calc_probs_datasets under
         the maps the adaptation left: it fills `.probs`, `.FPP`, `.lnZ_err`, `.posterior` (n_samples > 0), `.sigma_ref`,
-        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise`, `.dataset_t0`, `.dataset_outliers` and `.dataset_red_baselines` as calc_probs_datasets does, and only it enters the result, so the
+        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise`, `.dataset_t0`, `.dataset_outliers`, `.dataset_red_baselines` and `.dataset_white_noise` as calc_probs_datasets does, and only it enters the result, so the
         estimate is unbiased.  `.refine_history` holds, per pass, the rows' lnZ, ess and w_max_frac.  n_adapt = 0 is
         calc_probs_datasets, bit for bit.  Both evaluations ("grid", "fused") feed the histogram the same way.
 
