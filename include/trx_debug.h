@@ -99,6 +99,16 @@ long trx_debug_cells_lds_one_row(void);
  * then zeroes them); the trips that cannot hold an in-window cell are in neither.  It waits for the device.  Device
  * counters of the testing library; they cannot change a result.  Either pointer may be NULL. */
 int trx_debug_whole_trips(long* whole, long* walked, int reset);
+/* 0: with full chunks (trx_set_full_chunks) every chunk of pass 2 runs the stencil tests of the chunk loop's body; 1
+ * (default, what the production library does): a chunk in the interior of a row's stencil zone -- 64 consecutive cells
+ * in step with the list before and behind them, every one planned for the stencil on the disc, the previous chunk's last
+ * 8 cells pending -- skips the stencil tests, whose outcome is known for it, and goes on with the centre values and the
+ * finalisation of the same body.  No output depends on it, bit for bit: the same terms in the same lanes and order. */
+int trx_set_zone_loop(int on);
+/* the chunks of pass 2 that skipped the stencil tests in this way on the current device since the library was loaded (or since the last call
+ * with reset != 0, which returns the count and then zeroes it).  It waits for the device.  A device counter of the testing
+ * library; it cannot change a result.  The pointer may be NULL. */
+int trx_debug_zone_chunks(long* chunks, int reset);
 /* what trx_star_enqueue has put into launch chains since the library was loaded (or since the last call with
  * reset != 0, which returns the counts and then zeroes them): chains, the calls in them, and those of these calls that
  * had post_rows > 0.  Host counters; they cannot change a result.  Any pointer may be NULL. */

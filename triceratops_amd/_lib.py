@@ -62,7 +62,8 @@ DEBUG_SYMBOLS = (
     "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison", "trx_set_debug_bug",
     "trx_set_probe_rows", "trx_set_star_chain", "trx_debug_capture_buffers", "trx_debug_chain_counts",
     "trx_set_row_order", "trx_debug_row_order", "trx_set_whole_trips", "trx_debug_whole_trips", "trx_set_one_sweep",
-    "trx_set_full_chunks", "trx_debug_cells_lds_one_row", "trx_debug_select_from_halfchi2",
+    "trx_set_full_chunks", "trx_debug_cells_lds_one_row", "trx_debug_select_from_halfchi2", "trx_set_zone_loop",
+    "trx_debug_zone_chunks",
 )
 
 
@@ -236,7 +237,8 @@ def _load(path, testing):
                      "trx_set_bounded_evaluation", "trx_set_debug_bounded_lnl", "trx_set_debug_poison",
                      "trx_set_debug_bug", "trx_set_star_chain", "trx_set_probe_rows", "trx_set_stencil",
                      "trx_set_supersample_tiers", "trx_set_debug_node_counts", "trx_set_cell_packing_below",
-                     "trx_set_row_order", "trx_set_whole_trips", "trx_set_one_sweep", "trx_set_full_chunks"):
+                     "trx_set_row_order", "trx_set_whole_trips", "trx_set_one_sweep", "trx_set_full_chunks",
+                     "trx_set_zone_loop"):
             fn = getattr(L, name)
             fn.restype = c_int
             fn.argtypes = [c_int]
@@ -248,6 +250,8 @@ def _load(path, testing):
         L.trx_debug_row_order.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long), _vp, _vp, _vp]
         L.trx_debug_whole_trips.restype = c_int
         L.trx_debug_whole_trips.argtypes = [ctypes.POINTER(c_long), ctypes.POINTER(c_long), c_int]
+        L.trx_debug_zone_chunks.restype = c_int
+        L.trx_debug_zone_chunks.argtypes = [ctypes.POINTER(c_long), c_int]
         L.trx_debug_select_from_halfchi2.restype = c_int
         L.trx_debug_select_from_halfchi2.argtypes = [_vp, _vp, _vp, _vp, c_long, c_long, c_long, c_int, c_int, c_int, c_int,
                                                      c_double, _vp, _vp, _vp, _vp]
@@ -472,6 +476,16 @@ def debug_whole_trips(reset=False):
     whole, walked = ctypes.c_long(0), ctypes.c_long(0)
     check(L.trx_debug_whole_trips(ctypes.byref(whole), ctypes.byref(walked), 1 if reset else 0))
     return whole.value, walked.value
+
+
+def debug_zone_chunks(reset=False):
+    """Testing library only (trx_debug_zone_chunks): the pass-2 chunks that the zone loop of the one-row stencil likelihood
+    kernels took on the current device since the last reset."""
+    L = lib()
+    assert L.trx_testing, "debug_zone_chunks needs use_testing_library()"
+    chunks = ctypes.c_long(0)
+    check(L.trx_debug_zone_chunks(ctypes.byref(chunks), 1 if reset else 0))
+    return chunks.value
 
 
 def lnl_batch_weighted(model, flags, time_d, flux_d, inv_var_d, params_d, exptime, nsamples, sec_limit=float("inf"),

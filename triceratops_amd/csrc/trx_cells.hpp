@@ -93,6 +93,7 @@ struct RowsArgs {
     int whole_trips;   // trx_set_whole_trips (read by the testing library's kernels only): see window_trips
     int one_sweep;     // trx_set_one_sweep (likewise): 0 two sweeps, 1 one in the likelihood kernels, 2 in the flux grid's too
     int full_chunks;   // trx_set_full_chunks (likewise): 0 one-sided halo, 1 full stencil chunks in the likelihood kernels, 2 in the flux grid's too
+                       // (+ 4: trx_set_zone_loop, the zone loop of the full chunks -- in the same field: the block does not grow)
     // Cost-ordered rows (one row per wave, full evaluation of a likelihood launch; null: rows as they come): rowc_kernel
     // files every row under its cost bucket, cells_kernel's position v takes the v-th row of that order (row_order_at)
     int* order;        // [kOrderSegs counters, kOrderStride ints apart | kOrderSegs lists of order_cap(n) row numbers]
@@ -204,18 +205,25 @@ __device__ __forceinline__ void add_row_stat(int which, unsigned count)
 // filed whole and those that were walked cell by cell; a wave adds its totals once, when it leaves.
 #ifdef TRX_TESTING
 __device__ unsigned long long g_trip_stats[2][kStatShards][kStatPad];      // [0] whole, [1] walked
+__device__ unsigned long long g_zone_stats[kStatShards][kStatPad];         // pass-2 chunks taken by the zone loop (trx_debug_zone_chunks)
 __device__ __forceinline__ void add_trip_stat(int which, unsigned count)
 {
     if (count) atomicAdd(&g_trip_stats[which][(blockIdx.x + 41u * blockIdx.y) & (kStatShards - 1)][0], (unsigned long long)count);
 }
+__device__ __forceinline__ void add_zone_stat(unsigned count)
+{
+    if (count) atomicAdd(&g_zone_stats[(blockIdx.x + 41u * blockIdx.y) & (kStatShards - 1)][0], (unsigned long long)count);
+}
 __device__ __forceinline__ bool whole_trips_on(const RowsArgs& a) { return a.whole_trips != 0; }
 __device__ __forceinline__ bool one_sweep_on(const RowsArgs& a, bool lnl) { return a.one_sweep >= (lnl ? 1 : 2); }
-__device__ __forceinline__ bool full_chunks_on(const RowsArgs& a, bool lnl) { return a.full_chunks >= (lnl ? 1 : 2); }
+__device__ __forceinline__ bool full_chunks_on(const RowsArgs& a, bool lnl) { return (a.full_chunks & 3) >= (lnl ? 1 : 2); }
+__device__ __forceinline__ bool zone_loop_on(const RowsArgs& a) { return (a.full_chunks & 4) != 0; }
 #define TRX_TRIP_STAT(var) ++var
 #else
 __device__ __forceinline__ bool whole_trips_on(const RowsArgs&) { return true; }
 __device__ __forceinline__ bool one_sweep_on(const RowsArgs&, bool lnl) { return lnl; }
 __device__ __forceinline__ bool full_chunks_on(const RowsArgs&, bool lnl) { return lnl; }
+__device__ __forceinline__ bool zone_loop_on(const RowsArgs&) { return true; }
 #define TRX_TRIP_STAT(var)
 #endif
 
@@ -1007,6 +1015,18 @@ struct CellState {
     };                                      // the pending cell of lane 64 - kStM + q, until the next chunk finalises it
 };
 // centre-value stencil (LONG only): the chunk's centre fluxes and the launch's weights
+// TRX_ST_DEFICITS (the one-row stencil likelihood instantiations): fc holds the centres' DEFICITS 1 - f, taken once where
+// a centre is written, instead of the fluxes f from which every stencil cell's sum took 1 - f again for each of its
+// 2 kStM + 1 neighbours -- 17 fp64 subtractions per lane and chunk in front of the 17 fmas.  1 - f is the same number
+// wherever it is taken (NaN stays NaN): same bits.  (0: fluxes, as in every other instantiation)
+#ifndef TRX_ST_DEFICITS
+#define TRX_ST_DEFICITS 1
+#endif
+// TRX_ZONE_LOOP (the same instantiations, full chunks): a chunk in the interior of a row's stencil zone skips the stencil
+// tests of the chunk loop's body, whose outcome is known for it -- cells_body, "zone loop".  (0: every chunk takes them)
+#ifndef TRX_ZONE_LOOP
+#define TRX_ZONE_LOOP 1
+#endif
 struct StencilState {
     double fc[64 + 2 * kStM];                               // [kFcB + h]: the centre flux of lane h; below: the previous chunk's last cells'
     double stw[2 * kStM + 1];                               // (halo: its last kStM owned cells' in [kStM, kFcB); full chunks: its last 2 kStM in [0, kFcB))
@@ -1267,6 +1287,10 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
     constexpr bool kCarry = TRX_CARRY_CELLS && STEP && !LONG;
     // (the stencil instantiation: tiers on demand, centres evaluated where they were planned -- plan_cell<LAZY>)
     constexpr bool kLazyTiers = TRX_LAZY_TIERS && ST && STEP && LONG && !PRUNE;
+    // (the one-row stencil likelihood instantiations, WT or not: centre deficits in ss.fc and the zone loop of pass 2)
+    constexpr bool kZoneInst = kLazyTiers && MODE == MODE_LNL;
+    constexpr bool kDeficits = TRX_ST_DEFICITS && kZoneInst;
+    constexpr bool kZone = TRX_ZONE_LOOP && kZoneInst;
     constexpr int W = cells_waves(LONG);
     const int wave = W > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;     // (scalar: so is all that follows from it)
     // shared by the workgroup's waves: node tables, atan constants, (short curves) the light curve
@@ -1400,6 +1424,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
     unsigned n_skipped = 0, n_pruned = 0;          // this wave's rows for trx_skipped_rows / trx_pruned_rows
 #ifdef TRX_TESTING
     unsigned n_whole = 0, n_walked = 0;            // ... and its pass-1 trips for trx_debug_whole_trips (ST)
+    unsigned n_zone = 0;                           // ... and its pass-2 chunks taken by the zone loop (trx_debug_zone_chunks)
 #endif
     for (long v = v0; v < 8 * positions; v += (long)gridDim.x * W) {
         RowsArgs a_again;
@@ -1762,6 +1787,29 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                         pl.anchored = true;
                     }
                 }
+                // Zone loop (full chunks): a chunk in the INTERIOR of the row's stencil zone.  Its 64 entries are
+                // consecutive cells that follow the previous chunk's last one in step, the list goes on behind it with kStM more
+                // in step, the previous chunk left centre values in its last 2 kStM lanes and all of its last kStM cells pending
+                // -- scalar tests on the list and on what crosses the back edge -- and every lane's plan passed the stencil's
+                // own test on the disc: one vote.  For such a chunk the stencil tests below reach, lane by lane, what is known
+                // here -- every cell takes the stencil and a centre value, none has nodes of its own, every lane left a value,
+                // the pending mask is full again -- so it skips them: no shuffles, no masks, no dilation, no votes, no look
+                // for a tier.  The `direct` block takes the centres and the finalisation adopts every pending cell (both
+                // pending masks full: its one scalar comparison).  The same terms in the same lanes and order: same bits.  A
+                // zone's first and last chunk, an epoch's jump, a pass's seam, the list's end and whatever lies near a contact
+                // fail a test and take the tests.  (Centre values in the last 2 kStM lanes, not kStM: the stencil tests' `left`
+                // field needs the last kStM, the adopted pending cells reach kStM further; a full pending mask implies both,
+                // the test is one scalar comparison and says so.)  (A body of its own for these chunks -- a second copy of the 17-term sum --
+                // does not fit 128 VGPRs: profiles/experiments/README.md.)
+                bool zone = false;
+                if (kZone && full && zone_loop_on(a) && w0 > 0 && w0 + 64 + kStM <= count && pendm == (1u << kStM) - 1u &&
+                    (carry_ok >> (64 - 2 * kStM)) == (1ull << (2 * kStM)) - 1ull) {
+                    const int r_first = __builtin_amdgcn_readlane(rel, 0), r_last = __builtin_amdgcn_readlane(rel, 63);
+                    const int r_next = __builtin_amdgcn_readfirstlane((int)winlist[w0 + 63 + kStM]);
+                    const int j_prev = __builtin_amdgcn_readlane(carry_j, 63);
+                    zone = r_last - r_first == 63 && win0 + r_first == j_prev + 1 && r_next - r_last == kStM &&
+                           __all(pl.st_ok && pl.n > 0);
+                }
                 // `planned`: a cell of this sweep that is no contact cell -- what counts as a neighbour for the stencil and
                 // may take a centre value.  One sweep: the contact cell stays `valid` (its owner evaluates and finalises it
                 // here, all S sub-exposures from the plan it has); two sweeps: it is filed for the second and leaves this one.
@@ -1783,8 +1831,14 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                 // side sit next to it in this chunk, all of them planned cells of this sweep, takes its
                 // exposure average from their centre values -- ONE pair, the centre, instead of its
                 // Gauss nodes; every cell within kStM of such a cell adds its centre to its own pairs.
-                bool st = false, centre = false;
-                if (ST && sweep == 0) {
+                bool st = zone, centre = zone;
+                if (zone) {
+                    nodes = 0;
+                    carry_j = j;
+                    carry_ok = ~0ull;
+                    TRX_TRIP_STAT(n_zone);
+                }
+                if (ST && sweep == 0 && !zone) {
                     // (the kStM cells to the left of this chunk's first: lanes 64 - 2 kStM .. 64 - kStM - 1 of the previous one)
                     // (both shuffles by every lane: a shuffle under a divergent mask reads 0 from the lanes that sit it out)
                     // (full chunks: they are the previous chunk's LAST kStM lanes)
@@ -1835,7 +1889,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                         if (__any(owes && !centre)) {
                             if (owes) {
                                 if (pl.n > 0) centre = true;                      // (a contact cell too: kCentreNode rides with its S pairs)
-                                else if (!centre) ss.fc[kFcB + lane] = 1.0;
+                                else if (!centre) ss.fc[kFcB + lane] = kDeficits ? 0.0 : 1.0;
                                 has_value = true;
                             }
                         }
@@ -1849,7 +1903,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                     const int kk = lane - (64 - 2 * kStM);
                     if (lend && !last_chunk && planned && !centre && kk >= 0 && kk < kStM && (mnext & ((2ull << kk) - 1ull)) != 0) {
                         if (pl.n > 0) centre = true;
-                        else ss.fc[kFcB + lane] = 1.0;
+                        else ss.fc[kFcB + lane] = kDeficits ? 0.0 : 1.0;
                     }
                     if (st) nodes = 0;
                     carry_j = j;
@@ -1875,7 +1929,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                 // were planned, lane = cell, straight from the plan's registers: no pair table, no cell state in LDS, no
                 // pair loop (its decode, its second look at the row, its Kepler step).  Same arithmetic on the same
                 // numbers: the same centre values, bit for bit.
-                const bool direct = kLazyTiers && ST && sweep == 0 && !__any(nodes > 0);
+                const bool direct = kLazyTiers && ST && sweep == 0 && (zone || !__any(nodes > 0));
                 if (direct) {
                     if (centre) {
                         const RowC& c = (LONG && !TRX_LONG_ROWS_IN_LDS) ? cu : rows[rr];
@@ -1892,7 +1946,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                         } else if (z2 != z2) {
                             f = z2;
                         }
-                        ss.fc[kFcB + lane] = f;
+                        ss.fc[kFcB + lane] = kDeficits ? 1.0 - f : f;
                     }
                     wave_sync();
                 }
@@ -2008,7 +2062,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                                 f = z2;
                             }
                             if (at_centre) {
-                                ss.fc[kFcB + h] = f;
+                                ss.fc[kFcB + h] = kDeficits ? 1.0 - f : f;
                             } else {
                                 const double term = (ht < 0) ? f : tier_xw[2 * (ht * kTierMaxNodes + s) + 1] * (1.0 - f);
                                 if (ht < 0 || term != 0.0)
@@ -2051,7 +2105,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                         const double* fcl = &ss.fc[kFcB + (adopt ? lq - kStM : lane)];
                         fsum = 0.0;
 #pragma unroll
-                        for (int i = -kStM; i <= kStM; ++i) fsum = fma(ss.stw[i + kStM], 1.0 - fcl[i], fsum);
+                        for (int i = -kStM; i <= kStM; ++i) fsum = fma(ss.stw[i + kStM], kDeficits ? fcl[i] : 1.0 - fcl[i], fsum);
                     }
                     // the cell's flux deficit: nothing, 1 - mean of the S sub-exposures, or the Gauss rule's weighted sum
                     // (a stencil cell's sum is one of deficits like a Gauss rule's -- and its tier may never have been looked for)
@@ -2091,7 +2145,8 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
                         const int jq = win0 + (int)winlist[w0] - kStM + q;
                         double fsum = 0.0;
 #pragma unroll
-                        for (int i = -kStM; i <= kStM; ++i) fsum = fma(ss.stw[i + kStM], 1.0 - ss.fc[kFcB - kStM + q + i], fsum);
+                        for (int i = -kStM; i <= kStM; ++i)
+                            fsum = fma(ss.stw[i + kStM], kDeficits ? ss.fc[kFcB - kStM + q + i] : 1.0 - ss.fc[kFcB - kStM + q + i], fsum);
                         const double m = fma(-fsum, rows[0].rdil, 1.0);
                         if (MODE == MODE_GRID) {
                             a.out[(size_t)base * n_time + jq] = m;
@@ -2211,7 +2266,7 @@ __device__ __forceinline__ void cells_body(const RowsArgs& a_in, const double st
         add_row_stat(0, n_skipped);
         add_row_stat(1, n_pruned);
 #ifdef TRX_TESTING
-        if (ST) { add_trip_stat(0, n_whole); add_trip_stat(1, n_walked); }
+        if (ST) { add_trip_stat(0, n_whole); add_trip_stat(1, n_walked); add_zone_stat(n_zone); }
 #endif
     }
 #ifdef TRX_TAIL_TIMERS

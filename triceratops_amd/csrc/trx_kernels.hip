@@ -380,7 +380,7 @@ int plan_cells(RowsArgs& a, bool long_rows, CellsPlan& P)
     a.debug_bug = knob_debug_bug();
     a.whole_trips = knob_whole_trips();
     a.one_sweep = knob_one_sweep();
-    a.full_chunks = knob_full_chunks();
+    a.full_chunks = knob_full_chunks() | (knob_zone_loop() ? 4 : 0);     // (one field for both: zone_loop_on, trx_cells.hpp)
     a.mark_unwritten = (MODE == MODE_LNL && !a.inv_var) ? 1 : 0;     // (a weighted launch may ADD to out[]: never marked)
     bool tiers_ok = false;
     if (tier_device(a.S, a.tiers, &a.tier_xw, &tiers_ok)) return fail(TRX_ERR_HIP, "tier table upload failed%s", "", 0);
@@ -1703,6 +1703,31 @@ int trx_set_full_chunks(int mode)
 {
     if (mode < 0 || mode > 2) return fail(TRX_ERR_ARG, "trx_set_full_chunks: mode must be 0, 1 or 2%s (got %ld)", "", (long)mode);
     g_knob_full_chunks = mode;
+    return TRX_OK;
+}
+
+/* (tests) 0: every chunk of the full chunks takes the chunk loop's body, the ones inside a stencil zone too */
+int trx_set_zone_loop(int on)
+{
+    g_knob_zone_loop = on ? 1 : 0;
+    return TRX_OK;
+}
+
+/* (tests) the pass-2 chunks the zone loop took on the current device since the last reset */
+int trx_debug_zone_chunks(long* chunks, int reset)
+{
+    static unsigned long long host[kStatShards][kStatPad];
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    TRX_HIP(hipDeviceSynchronize());
+    TRX_HIP(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_zone_stats), sizeof(host), 0));
+    long sum = 0;
+    for (int i = 0; i < kStatShards; ++i) sum += (long)host[i][0];
+    if (chunks) *chunks = sum;
+    if (reset) {
+        memset(host, 0, sizeof(host));
+        TRX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_zone_stats), host, sizeof(host), 0));
+    }
     return TRX_OK;
 }
 

@@ -64,6 +64,7 @@ TRX_KNOB(row_order, 1, nullptr)            // one row per wave, full evaluation:
 TRX_KNOB(whole_trips, 1, nullptr)          // stencil instantiation, pass 1: trips wholly inside a window filed untested (0: cell by cell)
 TRX_KNOB(one_sweep, 1, nullptr)            // one row per wave, likelihood: contact cells evaluated with their chunk (0: in a second sweep; 2: the flux grid too)
 TRX_KNOB(full_chunks, 1, nullptr)          // stencil instantiation, one sweep, likelihood: 64 new cells per chunk (0: the one-sided halo; 2: the flux grid too)
+TRX_KNOB(zone_loop, 1, nullptr)            // full chunks: the chunks inside a row's stencil zone skip the stencil tests (0: every chunk runs them)
 
 #undef TRX_KNOB
 
