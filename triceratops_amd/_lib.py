@@ -55,6 +55,9 @@ SS_SYMBOLS = ("trxs_chi2_grid_ss2",)
 # ... include/trx_mix.h as well (both libraries: the weighted row reduction over a grid of candidate white-noise models,
 # prefix trxv_)
 WHITE_SYMBOLS = ("trxv_chi2_grid_white_mix",)
+# ... include/trx_gls.h as well (both libraries: that reduction with baseline columns marginalised per candidate, prefix
+# trxb_)
+WLIN_SYMBOLS = ("trxb_chi2_grid_white_baseline",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -205,6 +208,9 @@ def _load(path, testing):
                                         _vp]
     L.trxv_chi2_grid_white_mix.restype = c_int
     L.trxv_chi2_grid_white_mix.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, c_int, _vp, _vp, _vp]
+    L.trxb_chi2_grid_white_baseline.restype = c_int
+    L.trxb_chi2_grid_white_baseline.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, c_int, c_int,
+                                                _vp, _vp, _vp, _vp, _vp]
     L.trxt_softmin_rows.restype = c_int
     L.trxt_softmin_rows.argtypes = [_vp, c_long, c_long, c_int, _vp, c_int, _vp, _vp]
     L.trxr_chi2_grid_robust.restype = c_int
@@ -702,6 +708,49 @@ def white_mix_blocks(n, n_time, n_cand):
     lds = (1 + n_cand) * ((n_time + 1) & ~1) * 8 if stage else 0
     per_cu = min((160 * 1024) // lds, 8) if lds else 8
     return min((n + 3) // 4, 256 * per_cu)
+
+
+def chi2_grid_white_baseline(flux_d, grid_d, w_d, basis_d, minv, lnc, secdepth=None, sec_limit=float("inf"), out=None,
+                             cand_out=None, coef_out=None):
+    """chi2_grid_white_mix with K baseline columns marginalised under every candidate (trxb_chi2_grid_white_baseline,
+    include/trx_gls.h): per row T = -ln sum_j exp(lnc[j] - h_j), h_j = 0.5 max(S2_j - b_j . Ainv_j b_j, 0) with
+    S2_j = sum_t w[j][t] d_t^2 and b_jk = sum_t w[j][t] basis[k][t] d_t, clamped at 0.  w_d: [J][n_time], basis_d: [K][n_time]
+    fp64 device tensors; minv: [J][K (K + 1) / 2] and lnc: [J] float64 on the host (datasets.white_baseline_system).
+    cand_out: an [n][J] fp64 device tensor that receives the h_j, coef_out: an [n][J][K] one that receives Ainv_j b_j, or
+    None.  The other arguments are chi2_grid_weighted's."""
+    n, nt = grid_d.shape
+    assert flux_d.dtype == torch.float64
+    lnc = np.ascontiguousarray(lnc, dtype=np.float64)
+    assert lnc.ndim == 1
+    j = int(lnc.size)
+    assert 1 <= j <= 8, "1 .. 8 candidates (got %d)" % j
+    assert w_d.shape == (j, nt) and w_d.dtype == torch.float64 and w_d.is_contiguous()
+    assert basis_d.dim() == 2 and basis_d.shape[1] == nt and basis_d.dtype == torch.float64 and basis_d.is_contiguous()
+    k = int(basis_d.shape[0])
+    assert 1 <= k <= 4, "1 .. 4 columns (got %d)" % k
+    minv = np.ascontiguousarray(minv, dtype=np.float64)
+    assert minv.shape == (j, k * (k + 1) // 2), "minv: per candidate the packed upper triangle of a %d x %d matrix" % (k, k)
+    assert cand_out is None or (cand_out.shape == (n, j) and cand_out.dtype == torch.float64 and cand_out.is_contiguous())
+    assert coef_out is None or (coef_out.shape == (n, j, k) and coef_out.dtype == torch.float64
+                                and coef_out.is_contiguous())
+    return _chi2_rows("trxb_chi2_grid_white_baseline", (flux_d,), grid_d, secdepth, sec_limit, out, w_d.data_ptr(),
+                      basis_d.data_ptr(), j, k, minv.ctypes.data, lnc.ctypes.data,
+                      cand_out.data_ptr() if cand_out is not None else None,
+                      coef_out.data_ptr() if coef_out is not None else None)
+
+
+def white_lin_blocks(n, n_time, n_cand, n_terms):
+    """the blocks trxb_chi2_grid_white_baseline launches for n rows of n_time stamps, n_cand candidates and n_terms columns
+    (its launcher's cap, for the tests): 4 rows a block; a CU holds 4 blocks up to 24 sums a row
+    (n_cand * (1 + n_terms) <= 24: at most 128 VGPRs), 3 up to 35 (at most 168) and 2 at 40 (at most 256) -- fewer where
+    the LDS of a block, the candidates' packed inverses and the staged [1 + n_cand + n_terms] vectors, fills the 160 KB -- on
+    256 CUs; staged up to ((2 * 2048) // (1 + n_cand + n_terms)) & ~1 stamps"""
+    vectors = 1 + n_cand + n_terms
+    sums = n_cand * (1 + n_terms)
+    stage = n_time <= (((2 * 2048) // vectors) & ~1)
+    lds = 8 * (((n_cand * (n_terms * (n_terms + 1) // 2) + 1) & ~1) + (vectors * ((n_time + 1) & ~1) if stage else 0))
+    by_regs = 4 if sums <= 24 else 3 if sums <= 35 else 2
+    return min((n + 3) // 4, 256 * min((160 * 1024) // lds, by_regs))
 
 
 def softmin_rows(cand_d, lnc, out=None):

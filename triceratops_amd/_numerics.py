@@ -274,6 +274,54 @@ def white_mix_halfchi2(y, w, lnc, dtype=np.float64, return_candidates=False):
     return (t, h) if return_candidates else t
 
 
+def white_baseline_halfchi2(y, system, dtype=np.float64, return_candidates=False, return_coef=False):
+    """A dataset's term of the log-weight with the size of its white noise marginalised over J candidates and K baseline
+    columns marginalised under every candidate, on the host: the statement of what
+    trxb_chi2_grid_white_baseline computes per row,
+        S2_j = sum_t w_j[t] y_t^2,   b_jk = sum_t w_j[t] B_k[t] y_t,   coef_j = A_j^-1 b_j,
+        h_j = 0.5 max(S2_j - b_j . coef_j, 0),   a_j = h_j - lnc_j,  m = min_j a_j,
+        T = m - ln sum_j exp(m - a_j) = -ln sum_j exp(lnc_j - h_j),   stored as 0 where rounding drives it below,
+    `system` from datasets.white_baseline_system (w [J][T], B [K][T], minv [J][K (K + 1) / 2] the packed A_j^-1, lnc [J]); the
+    terms are summed in ascending j.  y: [..., T] residuals.  In `dtype` (np.longdouble: the tests' reference).  minv = 0
+    gives white_mix_halfchi2 on (w, lnc).  Returns T, then with return_candidates h [..., J], then with return_coef
+    coef [..., J, K], the posterior-mean coefficients under each candidate."""
+    y = np.asarray(y, dtype=dtype)
+    w = np.atleast_2d(np.asarray(system.w, dtype=dtype))
+    B = np.atleast_2d(np.asarray(system.B, dtype=dtype))
+    lnc = np.asarray(system.lnc, dtype=dtype)
+    J, K = w.shape[0], B.shape[0]
+    packed = np.asarray(system.minv, dtype=dtype).reshape(J, -1)
+    iu = np.triu_indices(K)
+    hs, coefs = [], []
+    for j in range(J):
+        Ainv = np.zeros((K, K), dtype=dtype)
+        Ainv[iu] = packed[j]
+        Ainv = Ainv + np.triu(Ainv, 1).T
+        u = w[j] * y
+        S2 = np.sum(u * y, axis=-1)
+        b = u @ B.T
+        coef = b @ Ainv                                           # (A_j^-1 is symmetric)
+        with np.errstate(invalid="ignore"):
+            tot = S2 - np.sum(b * coef, axis=-1)
+            hs.append(np.where(tot < 0, dtype(0.0), tot) * dtype(0.5))        # (a NaN stays a NaN)
+        coefs.append(coef)
+    h = np.stack(hs, axis=-1)
+    a = h - lnc
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        m = np.fmin.reduce(a, axis=-1)
+        s = np.zeros(m.shape, dtype=dtype)
+        for j in range(J):
+            s = s + np.exp(m - a[..., j])
+        t = np.where(m < np.inf, m - np.log(s), m)                # (every candidate +inf, or a NaN row: no inf - inf)
+        t = np.where(t < 0, dtype(0.0), t)                        # (a NaN stays a NaN)
+    out = (np.asarray(t, dtype=dtype),)
+    if return_candidates:
+        out += (h,)
+    if return_coef:
+        out += (np.stack(coefs, axis=-2),)
+    return out if len(out) > 1 else out[0]
+
+
 def t0_mix_halfchi2(h, lnpi):
     """A dataset's term of the log-weight with a transit-time shift marginalised over J nodes, on the
     host: the statement of what trxt_softmin_rows computes per row,

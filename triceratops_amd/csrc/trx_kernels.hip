@@ -1,6 +1,6 @@
 // libtrx.so: the host side of the likelihood path and the C ABI (include/trx.h) for gfx950.
 //
-// The kernels live in ten headers that only this file includes:
+// The kernels live in eleven headers that only this file includes:
 //   trx_cells.hpp    rowc_kernel (per-row constants, 152 B per row of scratch; the EB rows' secondary-eclipse verdict),
 //                    sec_scan_kernel, cells_kernel<MODE, STEP, FP32, LONG, ST, PRUNE, WT> (the light-curve model and its
 //                    chi^2: one wavefront per row or per batch of rows, in-window cells filed in LDS, each lane plans a
@@ -21,6 +21,8 @@
 //                    exp and one log1p a value; chi2_robust_launch here; include/trx_robust.h)
 //   trx_white_mix.hpp  chi2_white_mix_kernel<STAGE, J> (the weighted row reduction for J candidate white-noise models in
 //                    one pass, their soft minimum per row; chi2_white_mix_launch here; include/trx_mix.h)
+//   trx_white_lin.hpp  chi2_white_lin_kernel<STAGE, J, K> (white_mix's reduction with K baseline columns marginalised per
+//                    candidate, the J (1 + K) sums of a row folded together; chi2_white_lin_launch here; include/trx_gls.h)
 //   trx_gls.hpp      OuColsFilter<K> (the OU filter with K baseline columns marginalised under the same noise;
 //                    include/trx_gls.h)
 //   trx_ss2.hpp      Ss2Filter (noise with a two-dimensional state: 2 x 2 affine maps in the scan; include/trx_ss.h)
@@ -85,6 +87,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 #include "trx_robust.hpp"
 #include "trx_white_mix.hpp"
 #include "trx_gls.hpp"
+#include "trx_white_lin.hpp"
 #include "trx_ss2.hpp"
 #include "trx_bands.hpp"
 
@@ -1140,6 +1143,33 @@ void chi2_white_mix_launch(const double* flux, const double* model_grid, int n_t
     });
 }
 
+// One launch of chi2_white_lin_kernel<STAGE, J, K> (trxb_chi2_grid_white_baseline), J = n_cand, K = n_terms: STAGE while
+// flux, the J weight vectors and the K columns fit the LDS budget of chi2_rows_kernel; the candidates' packed A^-1 sit in
+// front of them in either case.  The cap of blocks is what is
+// resident at once: a block is one wave a SIMD, a SIMD holds 512 / wlin_vgpr_bound(J, K) of them -- 4 up to 24 sums a row,
+// 3 up to 35, 2 at 40 --, fewer where the staged vectors fill the 160 KB of LDS, on 256 CUs.  The rows behind the
+// cap are a wave's further passes.
+void chi2_white_lin_launch(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                           double sec_limit, int accumulate, double* out, const WhiteLin& lin, int n_cand, int n_terms,
+                           hipStream_t st)
+{
+    dispatch_int<1, kWlinMaxCands>(n_cand, [&](auto j) {
+        dispatch_int<1, kWlinMaxTerms>(n_terms, [&](auto k) {
+            constexpr int J = decltype(j)::value, K = decltype(k)::value;
+            const bool stage = n_time <= wlin_stage_max(J, K);
+            const size_t lds = (wlin_minv_doubles(J, K) + (stage ? (1 + J + K) * (size_t)((n_time + 1) & ~1) : 0)) * sizeof(double);
+            constexpr long by_regs = 512 / wlin_vgpr_bound(J, K);
+            long per_cu = (long)((160u * 1024u) / lds);
+            per_cu = per_cu > by_regs ? by_regs : per_cu;
+            long blocks = (n + 3) / 4;
+            if (blocks > 256L * per_cu) blocks = 256L * per_cu;
+            const auto kernel = stage ? chi2_white_lin_kernel<true, J, K> : chi2_white_lin_kernel<false, J, K>;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, st, flux, model_grid, n_time, n, secdepth,
+                               sec_limit, accumulate, out, lin);
+        });
+    });
+}
+
 // One launch of softmin_rows_kernel<J> (trxt_softmin_rows), J = n_cand: one lane per row, and as many blocks as the draw
 // kernel's cap -- 16 of 256 threads a CU, on 256 CUs; the rows behind that cap are a lane's further trips.
 void softmin_launch(const double* cand, long stride, long n, int n_cand, const Lnc8& lnc, int accumulate, double* out,
@@ -1325,6 +1355,33 @@ int trxg_chi2_grid_ou_baseline(const double* flux, const double* model_grid, int
                          Filter{alpha, beta, omega, columns, {nullptr, M, coef_out}}, K < kGlsWideFrom ? 4 : 2,
                          static_cast<hipStream_t>(stream));
     });
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trxb_chi2_grid_white_baseline(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                                  double sec_limit, int accumulate, double* out_halfchi2, const double* weights,
+                                  const double* basis, int n_cand, int n_terms, const double* minv, const double* lnc,
+                                  double* cand_out, double* coef_out, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (n_cand < 1 || n_cand > TRXB_MAX_CANDIDATES) return fail(TRX_ERR_ARG, "n_cand outside 1 .. 8%s (n_cand=%ld)", "", n_cand);
+    if (n_terms < 1 || n_terms > TRXB_MAX_TERMS)
+        return fail(TRX_ERR_ARG, "n_terms must lie in [1, 4]%s (got %ld)", "", (long)n_terms);
+    if (!flux || !model_grid || !out_halfchi2 || !weights || !basis || !minv || !lnc)
+        return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    static_assert(TRXB_MAX_CANDIDATES == kWlinMaxCands && TRXB_MAX_TERMS == kWlinMaxTerms, "the header's limits are the kernel's");
+    WhiteLin lin{weights, basis, {}, {}, cand_out, coef_out};
+    if (int rc = pack_lnc(lnc, n_cand, "candidate", lin.lnc)) return rc;
+    const int packed = n_terms * (n_terms + 1) / 2;
+    for (int j = 0; j < n_cand; ++j) {
+        Chi2bM M;
+        if (int rc = pack_minv(minv + (size_t)j * packed, n_terms, M)) return rc;
+        for (int i = 0; i < packed; ++i) lin.minv[j][i] = M.m[i];
+    }
+    if (n == 0) return TRX_OK;
+    chi2_white_lin_launch(flux, model_grid, n_time, n, secdepth, sec_limit, accumulate, out_halfchi2, lin, n_cand, n_terms,
+                          static_cast<hipStream_t>(stream));
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

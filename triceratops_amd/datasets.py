@@ -14,7 +14,8 @@ correlated noise (red_baselines, ou_baseline_system); or, alone or next to `t0_g
 `outlier_frac` / `outlier_scale`: every point is with probability eps an outlier from a Gaussian kappa times wider than its
 error, the membership integrated out per point and per draw (outliers, robust_constants); or, alone or next to `t0_grid`,
 `white_grid`: up to MAX_WHITE_CANDIDATES weighted candidates (error scale k, jitter s) of the white noise's size,
-marginalised per draw (white_grids, white_mix_system).  This module is host side and numpy only:
+marginalised per draw (white_grids, white_mix_system), and next to it `white_baseline` / `white_baseline_sigma`: up to
+MAX_BASELINE_TERMS baseline columns marginalised under every candidate (white_baselines, white_baseline_system).  This module is host side and numpy only:
 validation, the reference noise sigma_bar and the per-star renormalisation.  A `Datasets` object is what the lnZ_*
 functions receive in place of `time` (with flux = None and sigma = sigma_bar); only the device sampling modes evaluate it
 (fused._Scenario).
@@ -388,7 +389,7 @@ def _white_grid(i, d):
     others = [k for k in WHITE_GRID_NEIGHBOURS if d.get(k) is not None]
     if others:
         raise ValueError("dataset %d: white_grid together with %s is not built: the candidates stand alone or next to t0_grid "
-                         "(a marginalised linear term would need its sums and its determinant per candidate)"
+                         "(baseline columns marginalised under every candidate go under white_baseline / white_baseline_sigma)"
                          % (i, ", ".join(others)))
     total = math.fsum(weight.tolist())
     if not (math.isfinite(total) and total > 0):
@@ -403,7 +404,7 @@ def white_grids(dicts, sets):
     finite and >= 0 in flux units, a prior weight finite and > 0, normalised to sum 1 (math.fsum); repeated pairs are
     allowed.  Candidate j has the per-point variance k_j^2 flux_err_t^2 + s_j^2, and the dataset's term of the log-weight
     becomes -ln sum_j c_j exp(-h_j) (_numerics.white_mix_halfchi2 on white_mix_system).  No condition on the order of the
-    stamps.  The key stands alone or next to t0_grid; next to offset_sigma, baseline, red_sigma / red_timescale, red_grid,
+    stamps.  The key stands alone, next to t0_grid or with white_baseline / white_baseline_sigma (white_baselines); next to offset_sigma, baseline, red_sigma / red_timescale, red_grid,
     red_kernel, red_baseline / red_baseline_sigma or the outlier keys it is a ValueError, as is a wrong shape, too many
     rows, a value that is not finite, a scale <= 0, a jitter < 0, a weight <= 0, a bool or a string.  Dataset itself has no
     field for the key: the grids travel in Datasets.white_grids."""
@@ -437,6 +438,113 @@ def white_mix_system(dataset, grid):
     norm = math.log(math.fsum(math.exp(v) for v in diff))
     lnc = np.array([v - norm for v in diff])
     return np.ascontiguousarray(np.stack(w)), lnc
+
+
+WHITE_BASELINE_KEYS = ("white_baseline", "white_baseline_sigma")
+
+
+class WhiteBaselineSystem(NamedTuple):
+    """the candidates' weights of a dataset's white_grid and, per candidate, the linear system of its baseline columns
+    under those weights (white_baseline_system)"""
+    w: np.ndarray             # [J][T] w_j[t] = 1 / (k_j^2 flux_err_t^2 + s_j^2), as white_mix_system forms them
+    B: np.ndarray             # [K][T] the columns as given
+    minv: np.ndarray          # [J][K (K + 1) / 2] A_j^-1, upper triangle packed by rows, in the units of b_jk = sum w_j B_k y
+    lnc: np.ndarray           # [J] ln pi_j + 0.5 sum_t ln w_j[t] - 0.5 ln det A_j, less their log-sum-exp
+    lambda_min: np.ndarray    # [J] smallest eigenvalue of the unit-diagonal scaling A~_j of A_j
+    D: np.ndarray             # [J][K] D_jk = sum_t w_j[t] B_k[t]^2
+    M: tuple                  # per candidate [K][K] A~_j^-1 (None where A~_j is singular)
+
+
+def white_baseline_system(dataset, grid, B, sigmas):
+    """WhiteBaselineSystem of the columns B [K][T] with prior sigmas [K] (inf: flat) under every candidate (k_j, s_j, pi_j)
+    of a dataset's white_grid [J][3] -- the one place that forms them, for the device path (fused._Dataset) and for the
+    numpy statement (_numerics.white_baseline_halfchi2).  Per candidate linear_system(w_j, B, sigmas) gives D_j, the
+    unit-diagonal A~_j = D_j^(-1/2) A_j D_j^(-1/2), A_j = B^T W_j B + diag(1 / s_k^2), and M_j = A~_j^-1; then
+        A_j^-1 = D_j^(-1/2) M_j D_j^(-1/2),      ln det A_j = ln det A~_j + sum_k ln D_jk,
+        lnc_j = ln pi_j + 0.5 sum_t ln w_j[t] - 0.5 ln det A_j - logsumexp_j(the same),
+    so that the dataset's term of the log-weight is -ln sum_j exp(lnc_j - h_j), h_j = 0.5 max(S2_j - b_j^T A_j^-1 b_j, 0).  For
+    finite priors that is -ln sum_j pi_j N(y; 0, diag(1 / w_j) + B diag(s^2) B^T) up to a constant of the dataset: det(I +
+    diag(s^2) B^T W_j B) = det A_j prod_k s_k^2.  The lnc are formed as white_mix_system forms them: the difference to the
+    largest is one math.fsum over both candidates' terms.  ValueError for a column whose D_jk is 0 (or not finite); a
+    singular A~_j gives lambda_min[j] <= 0, M[j] = None and NaN in minv[j] and lnc."""
+    B = np.ascontiguousarray(np.atleast_2d(np.asarray(B, dtype=np.float64)))
+    K = B.shape[0]
+    w, _ = white_mix_system(dataset, grid)
+    grid = np.asarray(grid, dtype=np.float64)
+    iu = np.triu_indices(K)
+    minv, lam, Ds, Ms, terms = [], [], [], [], []
+    for w_j, (_, _, weight) in zip(w, grid):
+        system = linear_system(w_j, B, sigmas)
+        lam.append(system.lambda_min)
+        Ds.append(system.D)
+        Ms.append(system.M)
+        if system.M is None:
+            minv.append(np.full(iu[0].size, np.nan))
+            terms.append([math.nan])
+            continue
+        rs = 1.0 / np.sqrt(system.D)
+        minv.append((system.M * rs[:, None] * rs[None, :])[iu])
+        sign, lndet = np.linalg.slogdet(system.A)
+        terms.append([math.log(weight)] + (0.5 * np.log(w_j)).tolist() + [-0.5 * float(lndet)]
+                     + (-0.5 * np.log(system.D)).tolist())
+    if any(M is None for M in Ms):
+        lnc = np.full(len(terms), np.nan)
+    else:
+        top = [-v for v in max(terms, key=math.fsum)]
+        diff = [math.fsum(t + top) for t in terms]
+        norm = math.log(math.fsum(math.exp(v) for v in diff))
+        lnc = np.array([v - norm for v in diff])
+    return WhiteBaselineSystem(w, B, np.ascontiguousarray(np.stack(minv)), lnc, np.array(lam), np.stack(Ds), tuple(Ms))
+
+
+def _white_baseline(i, d, dataset):
+    """a dataset's "white_baseline" and "white_baseline_sigma" -> ([K_b][T kept] columns, [K_b] sigmas), or None; dataset:
+    the validated Dataset of the same dict (its errors)"""
+    value, sigma = d.get("white_baseline"), d.get("white_baseline_sigma")
+    if isinstance(value, (bool, np.bool_, str, bytes)):
+        raise ValueError("dataset %d: white_baseline must be an array [K][len(time)] or [len(time)] (got %r)" % (i, value))
+    time = np.atleast_1d(np.asarray(d["time"], dtype=np.float64))
+    keep = ~np.isnan(time) & ~np.isnan(np.atleast_1d(np.asarray(d["flux"], dtype=np.float64)))
+    B, s = _baseline(i, value, sigma, time.size, keep, name="white_baseline")
+    if B is None:
+        return None
+    if B.shape[0] > MAX_BASELINE_TERMS:
+        raise ValueError("dataset %d: at most %d white_baseline columns (got %d)" % (i, MAX_BASELINE_TERMS, B.shape[0]))
+    others = [k for k in WHITE_GRID_NEIGHBOURS if d.get(k) is not None]
+    if others:
+        raise ValueError("dataset %d: white_baseline together with %s is not built: the columns stand next to white_grid (and "
+                         "t0_grid) alone; a column of ones is the constant" % (i, ", ".join(others)))
+    grid = _white_grid(i, d)
+    if grid is None:
+        raise ValueError("dataset %d: white_baseline needs white_grid: with the errors as given give the columns as "
+                         "baseline" % i)
+    try:
+        system = white_baseline_system(dataset, grid, B, s)
+    except ValueError as e:
+        raise ValueError("dataset %d: white_baseline term %s" % (i, e)) from None
+    if not np.all(system.lambda_min >= MIN_BASELINE_EIGENVALUE):
+        raise ValueError("dataset %d: the white_baseline terms are collinear under a candidate's weights (smallest "
+                         "eigenvalue of the scaled system %.3g < %g): drop a column, or give finite priors"
+                         % (i, float(np.min(system.lambda_min)), MIN_BASELINE_EIGENVALUE))
+    return B, s
+
+
+def white_baselines(dicts, sets):
+    """The "white_baseline" / "white_baseline_sigma" keys of the dicts that validate() turned into `sets`: per dataset None,
+    or the pair (B, sigmas) -- B a contiguous float64 [K_b][kept points] array of K_b = 1 ... MAX_BASELINE_TERMS columns of a
+    linear baseline model sum_k c_k B_k[t], aligned with `time` (entries of NaN-dropped points dropped with them, every
+    kept entry finite), sigmas [K_b] the prior sigmas of c_k ~ N(0, s_k^2), each > 0 or inf (absent: flat) -- marginalised
+    per draw under every candidate of the dataset's white_grid, determinants included: its term of the log-weight becomes
+    -ln sum_j exp(lnc_j - h_j), h_j = 0.5 [S2_j - b_j^T A_j^-1 b_j] (_numerics.white_baseline_halfchi2 on
+    white_baseline_system).  A column of ones is how the constant is given.  The keys stand only next to white_grid, and may
+    stand next to t0_grid (the columns follow the points); ValueError without white_grid, next to offset_sigma, baseline,
+    any red key or outlier_frac / outlier_scale, for a sigma without columns, a wrong shape, more than MAX_BASELINE_TERMS
+    columns, a kept entry that is not finite, a zero column, a bool or a string, or columns that are collinear under a
+    candidate's weights (smallest eigenvalue of a scaled system < MIN_BASELINE_EIGENVALUE).  Dataset itself has no field
+    for the keys: the pairs travel in Datasets.white_baselines."""
+    if len(dicts) != len(sets):
+        raise ValueError("white_baselines: %d dicts for %d datasets" % (len(dicts), len(sets)))
+    return [_white_baseline(i, d, s) for i, (d, s) in enumerate(zip(dicts, sets))]
 
 
 RED_BASELINE_KEYS = ("red_baseline", "red_baseline_sigma")
@@ -664,7 +772,7 @@ def _check_baseline(i, dataset):
 def validate(datasets):
     """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
     baseline_sigma, red_sigma, red_timescale, red_kernel, red_grid, t0_grid, outlier_frac, outlier_scale, red_baseline,
-    red_baseline_sigma, white_grid]} -> a list of Dataset ("red_kernel" = "matern32" / "ou2" gives a Matern32Dataset / an Ou2Dataset: the
+    red_baseline_sigma, white_grid, white_baseline, white_baseline_sigma]} -> a list of Dataset ("red_kernel" = "matern32" / "ou2" gives a Matern32Dataset / an Ou2Dataset: the
     same fields, red_sigma and red_timescale two finite numbers / two arrays of two finite entries, all > 0; "t0_grid"
     is allowed here and read by t0_grids, "outlier_frac" / "outlier_scale" are checked here and returned by outliers,
     "red_baseline" / "red_baseline_sigma" are checked here and returned by red_baselines, "white_grid" is checked here and
@@ -682,7 +790,7 @@ def validate(datasets):
     offset_sigma, baseline, red_sigma / red_timescale or red_grid; for a red_kernel that is not None, "ou", "matern32" or
     "ou2", and with the last two for a red_sigma or red_timescale of the wrong shape or with an entry that is not finite and
     > 0, for stamps out of order, or for offset_sigma, baseline, red_grid, red_baseline or the outlier keys next to them; and
-    for what red_baselines and white_grids list."""
+    for what red_baselines, white_grids and white_baselines list."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -693,7 +801,7 @@ def validate(datasets):
     for i, d in enumerate(datasets):
         unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma",
                             "red_sigma", "red_timescale", "red_grid", "t0_grid", "outlier_frac", "outlier_scale",
-                            "red_baseline", "red_baseline_sigma", "red_kernel", "white_grid"}
+                            "red_baseline", "red_baseline_sigma", "red_kernel", "white_grid"} - set(WHITE_BASELINE_KEYS)
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -740,6 +848,7 @@ def validate(datasets):
         _red_baseline(i, d, out[-1])
         _outliers(i, d, out[-1])
         _white_grid(i, d)
+        _white_baseline(i, d, out[-1])
     return out
 
 
@@ -763,9 +872,10 @@ def sigma_bar(errs):
 class Datasets:
     """validated datasets in one star's normalisation, their sigma_bar, and per dataset None or its transit-time shift
     grid (t0_grids), None or its outlier pair (frac, scale) (outliers), None or the pair (columns, sigmas) of its
-    baseline under correlated noise (red_baselines) and None or its grid of white-noise candidates (white_grids)"""
+    baseline under correlated noise (red_baselines), None or its grid of white-noise candidates (white_grids) and None or
+    the pair (columns, sigmas) of its baseline under those candidates (white_baselines)"""
 
-    def __init__(self, sets, t0_grids=None, outliers=None, red_baselines=None, white_grids=None):
+    def __init__(self, sets, t0_grids=None, outliers=None, red_baselines=None, white_grids=None, white_baselines=None):
         self.sets = tuple(sets)
         self.sigma_ref = sigma_ref(self.sets)
         self.t0_grids = (None,) * len(self.sets) if t0_grids is None else tuple(t0_grids)
@@ -780,6 +890,9 @@ class Datasets:
         self.white_grids = (None,) * len(self.sets) if white_grids is None else tuple(white_grids)
         if len(self.white_grids) != len(self.sets):
             raise ValueError("white_grids: %d grids for %d datasets" % (len(self.white_grids), len(self.sets)))
+        self.white_baselines = (None,) * len(self.sets) if white_baselines is None else tuple(white_baselines)
+        if len(self.white_baselines) != len(self.sets):
+            raise ValueError("white_baselines: %d pairs for %d datasets" % (len(self.white_baselines), len(self.sets)))
 
     def __len__(self):
         return len(self.sets)
@@ -813,6 +926,10 @@ class Datasets:
         return any(g is not None for g in self.white_grids)
 
     @property
+    def has_white_baselines(self):
+        return any(b is not None for b in self.white_baselines)
+
+    @property
     def size(self):
         """points of all datasets together"""
         return sum(s.time.size for s in self.sets)
@@ -832,7 +949,9 @@ class Datasets:
         ou_baseline_system scales with the square of the flux ratio, s_k^2 D_k and the scaled system matrix are the same
         for every star, and so is the determinant that the evidence drops.  The jitter column of a white_grids grid is in
         flux units and is divided by the flux ratio, the scales are pure numbers: every candidate's weights gain the
-        square of the flux ratio, so the lnc of white_mix_system do not change."""
+        square of the flux ratio, so the lnc of white_mix_system do not change.  A finite sigma of a white_baselines pair is
+        divided by the flux ratio as a red_baselines pair's is: every A_j of white_baseline_system gains the square of the
+        flux ratio, det A_j its K-th power for every candidate alike, and the lnc do not change."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
@@ -859,4 +978,6 @@ class Datasets:
                 g = g.copy()
                 g[:, 1] = g[:, 1] / star_fluxratio
             white.append(g)
-        return Datasets(out, self.t0_grids, self.outliers, red, white)
+        lin = [None if p is None else (p[0], np.where(np.isfinite(p[1]), p[1] / star_fluxratio, p[1]))
+               for p in self.white_baselines]
+        return Datasets(out, self.t0_grids, self.outliers, red, white, lin)

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib, funcs
 from .datasets import (Datasets, baseline_system, ou_baseline_system, ou_mix_system, ou_system, robust_constants, white_mix_system,
-                       ss2_system)
+                       ss2_system, white_baseline_system)
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
@@ -258,6 +258,12 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # datasets.white_mix_system (grid evaluation only).  DATASET_WHITE_NOISE = {}: every such call leaves {work unit: [per branch, a
 # list per dataset: None or the [J] posterior weights of the candidates at the branch's best draw, softmax_j(lnc_j - h_j)
 # (with a t0_grid on its heaviest node)]} there (target.dataset_white_noise).
+# A dataset with `white_baseline` columns next to its white_grid (Datasets.white_baselines) has them marginalised under every
+# candidate: its reduction is trxb_chi2_grid_white_baseline on the tables of datasets.white_baseline_system (grid evaluation
+# only).  DATASET_WHITE_BASELINES = {}: every such call leaves {work unit: [per branch, a list per dataset: None or
+# {"coef": the [J][K] posterior-mean coefficients under each candidate at the branch's best draw, in the call's
+# normalisation, "mean": [K] their average under the candidates' posterior weights} (with a t0_grid on its heaviest
+# node)]} there (target.dataset_white_baselines).
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
@@ -268,6 +274,7 @@ DATASET_T0 = None
 DATASET_OUTLIERS = None
 DATASET_RED_BASELINES = None
 DATASET_WHITE_NOISE = None
+DATASET_WHITE_BASELINES = None
 # An importance map (WARP_GRIDS) applies to a datasets call as to any other: its draws are trx_draw_scenario's.  The weight
 # histogram of the library's own chain (WARP_HIST) does not exist here -- chi^2/2 is computed outside that chain -- so
 # DATASET_WARP_HIST = {}: every datasets call leaves {work unit: [branches][WARP_BRANCH] uint64 words} there, one
@@ -278,7 +285,7 @@ DATASET_WARP_HIST = None
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_OUTLIERS, DATASET_RED_BASELINES, DATASET_WHITE_NOISE, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_OUTLIERS, DATASET_RED_BASELINES, DATASET_WHITE_NOISE, DATASET_WHITE_BASELINES, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -808,6 +815,32 @@ def _white_on_device(d, grid, device):
     return _cached(_white_cache, key, 32, build)
 
 
+class _WhiteLin(NamedTuple):
+    """what the `white` slot of a _Dataset holds for a dataset with white_baseline columns next to its white_grid
+    (datasets.white_baseline_system); the first two fields are the pair a white_grid alone leaves there"""
+    w: torch.Tensor              # the candidates' weights [J][T], on the device
+    lnc: np.ndarray              # [J] on the host, the determinants of the candidates' systems included
+    basis: torch.Tensor          # the columns [K][T] as given, on the device
+    minv: np.ndarray             # [J][K (K + 1) / 2] on the host: A_j^-1, packed upper triangle
+
+
+_white_lin_cache = {}
+
+
+def _white_lin_on_device(d, grid, pair, device):
+    """the _WhiteLin record of a dataset with a white_grid [J][3] and white_baseline columns (datasets.white_baseline_system):
+    formed once per content of its errors, candidates, columns and prior sigmas -- J eigenproblems of K x K -- for the
+    lnZ_* calls of a star (a cache of its own, as _white_on_device's)"""
+    B, sigmas = pair
+    key = (tuple(hash(np.ascontiguousarray(a).tobytes()) for a in (d.flux_err, grid, B, sigmas)), d.flux_err.shape,
+           grid.shape, B.shape, device.index)
+
+    def build():
+        system = white_baseline_system(d, grid, B, sigmas)
+        return _WhiteLin(_lib.dev(system.w, device), system.lnc, _lib.dev(system.B, device), system.minv)
+    return _cached(_white_lin_cache, key, 32, build)
+
+
 _ss2_cache = {}
 
 
@@ -875,7 +908,7 @@ class _Dataset(NamedTuple):
     or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then --, or correlated
     noise -- one exponential term alone (`ou`) or with baseline columns under it (`gls`: `ou` is None then), or a term with
     a two-dimensional state (`ss2`: `ou` is None then) --, or the outlier mixture of its
-    points, or white noise whose size is marginalised over candidates (`white`); and, next to any of these, the nodes of a transit-time shift (`shift`: the
+    points, or white noise whose size is marginalised over candidates (`white`: a pair, or a _WhiteLin where baseline columns are marginalised under every candidate); and, next to any of these, the nodes of a transit-time shift (`shift`: the
     reduction then runs once per node)"""
     time: torch.Tensor
     flux: torch.Tensor
@@ -890,10 +923,10 @@ class _Dataset(NamedTuple):
     robust: Optional[tuple] = None           # (c0, c1, k2): the outlier mixture of the points (datasets.robust_constants)
     gls: Optional[_Gls] = None               # baseline columns under correlated noise (datasets.ou_baseline_system)
     ss2: Optional[tuple] = None              # (A, g, omega) on the device: red_kernel matern32 / ou2 (datasets.ss2_system)
-    white: Optional[tuple] = None            # (w [J][T] on the device, lnc [J] on the host): datasets.white_mix_system
+    white: Optional[tuple] = None            # (w [J][T] on the device, lnc [J] on the host): datasets.white_mix_system; or a _WhiteLin
 
     @classmethod
-    def upload(cls, d, dev, t0_grid=None, outliers=None, red_baseline=None, white_grid=None):
+    def upload(cls, d, dev, t0_grid=None, outliers=None, red_baseline=None, white_grid=None, white_baseline=None):
         inv_var = 1.0 / (d.flux_err * d.flux_err)
         rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
         if outliers is not None:
@@ -904,6 +937,8 @@ class _Dataset(NamedTuple):
             rec = rec._replace(shift=_shift_on_device(d, t0_grid, dev))
         if white_grid is not None:
             # (validate refuses anything but a t0_grid next to it)
+            if white_baseline is not None:
+                return rec._replace(white=_white_lin_on_device(d, white_grid, white_baseline, dev))
             return rec._replace(white=_white_on_device(d, white_grid, dev))
         if d.red_grid is not None:
             # (validate refuses anything else next to it)
@@ -935,9 +970,15 @@ class _Dataset(NamedTuple):
         trxn_chi2_grid_ou for correlated noise, trxm_chi2_grid_ou_mix for a grid of its candidates (cand_out: the rows'
         per-candidate chi^2/2), trxg_chi2_grid_ou_baseline for baseline columns under correlated noise (coef_out likewise),
         trxs_chi2_grid_ss2 for correlated noise with a two-dimensional state, trxr_chi2_grid_robust for the outlier mixture,
-        trxv_chi2_grid_white_mix for a grid of white-noise candidates (cand_out likewise), else trx_chi2_grid_weighted."""
+        trxv_chi2_grid_white_mix for a grid of white-noise candidates (cand_out likewise), trxb_chi2_grid_white_baseline for
+        baseline columns under such a grid (cand_out likewise, coef_out: the rows' [J][K] coefficients), else
+        trx_chi2_grid_weighted."""
         if self.robust is not None:
             return _lib.chi2_grid_robust(self.flux, self.inv_var, grid, *self.robust, secdepth, sec_limit, out=out)
+        if isinstance(self.white, _WhiteLin):
+            return _lib.chi2_grid_white_baseline(self.flux, grid, self.white.w, self.white.basis, self.white.minv,
+                                                 self.white.lnc, secdepth, sec_limit, out=out, cand_out=cand_out,
+                                                 coef_out=coef_out)
         if self.white is not None:
             return _lib.chi2_grid_white_mix(self.flux, grid, *self.white, secdepth, sec_limit, out=out, cand_out=cand_out)
         if self.mix is not None:
@@ -967,9 +1008,9 @@ class _Scenario:
         self.datasets = None
         if isinstance(time, Datasets):
             # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
-            self.datasets = [_Dataset.upload(d, self.dev, g, o, b, w)
-                             for d, g, o, b, w in zip(time.sets, time.t0_grids, time.outliers, time.red_baselines,
-                                                      time.white_grids)]
+            self.datasets = [_Dataset.upload(d, self.dev, g, o, b, w, wb)
+                             for d, g, o, b, w, wb in zip(time.sets, time.t0_grids, time.outliers, time.red_baselines,
+                                                          time.white_grids, time.white_baselines)]
             sigma = time.sigma_ref
             self.time, self.flux = self.datasets[0].time, self.datasets[0].flux
         else:
@@ -1261,7 +1302,8 @@ class _Scenario:
             best = self._best(h, idx, n)
             if self.datasets is not None and ((DATASET_OFFSETS is not None and any(d.offset is not None for d in self.datasets))
                                               or self._any_baseline() or self._any_mix() or self._any_shift()
-                                              or self._any_robust() or self._any_gls() or self._any_white()):
+                                              or self._any_robust() or self._any_gls() or self._any_white()
+                                              or self._any_white_lin()):
                 o, c, hc, hn, mr = (self._best_offsets(model, flags, cols, best, twin, nblk) if n
                                     else (None, None, None, None, None))
                 offsets.append(o)
@@ -1318,6 +1360,10 @@ class _Scenario:
         """whether a white_grid dataset's candidate weights are wanted back (DATASET_WHITE_NOISE)"""
         return DATASET_WHITE_NOISE is not None and any(d.white is not None for d in self.datasets)
 
+    def _any_white_lin(self):
+        """whether a white_baseline dataset's coefficients are wanted back (DATASET_WHITE_BASELINES)"""
+        return DATASET_WHITE_BASELINES is not None and any(isinstance(d.white, _WhiteLin) for d in self.datasets)
+
     def _any_gls(self):
         """whether a red_baseline dataset's coefficients are wanted back (DATASET_RED_BASELINES)"""
         return DATASET_RED_BASELINES is not None and any(d.gls is not None for d in self.datasets)
@@ -1330,9 +1376,30 @@ class _Scenario:
         probabilities of a robust dataset's points at that draw, _numerics.robust_responsibility on the draw's model row, to
         DATASET_OUTLIERS (likewise); and the coefficients of a red_baseline dataset's columns at that draw,
         c_k = c~_k / sqrt(D_k), to DATASET_RED_BASELINES (likewise); and the posterior weights of a white_grid dataset's
-        candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_WHITE_NOISE (likewise)"""
+        candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_WHITE_NOISE (likewise); and the coefficients of a
+        white_baseline dataset's columns under each candidate at that draw with their average under those weights, to
+        DATASET_WHITE_BASELINES (likewise)"""
         L = len(self.datasets)
         unit = getattr(_tls, "unit", None)
+        if DATASET_WHITE_BASELINES is not None:
+            out = []
+            for c, hc in zip(coefs, cands):
+                per = [None] * L
+                for l, d in enumerate(self.datasets):
+                    if not isinstance(d.white, _WhiteLin):
+                        continue
+                    J, K = int(d.white.lnc.size), int(d.white.basis.shape[0])
+                    if c is None or hc is None:
+                        per[l] = {"coef": np.full((J, K), np.nan), "mean": np.full(K, np.nan)}
+                        continue
+                    coef = c[l].cpu().numpy().reshape(J, K)
+                    x = d.white.lnc - hc[l].cpu().numpy().reshape(-1)
+                    w = np.exp(x - np.max(x))
+                    w = w / w.sum()
+                    # (a candidate of weight 0 -- switched off, or far below -- does not enter, whatever its coefficients)
+                    per[l] = {"coef": coef, "mean": np.sum(np.where(w[:, None] > 0, w[:, None] * coef, 0.0), axis=0)}
+                out.append(per)
+            DATASET_WHITE_BASELINES[unit] = out
         if DATASET_WHITE_NOISE is not None:
             white = []
             for hc in cands:
@@ -1429,7 +1496,8 @@ class _Scenario:
         """([L] device tensor and four lists per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
         S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
         baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them; likewise for a
-        red_baseline dataset under DATASET_RED_BASELINES); and None or the
+        red_baseline dataset under DATASET_RED_BASELINES; for a white_baseline dataset under DATASET_WHITE_BASELINES the
+        [1][J][K] coefficients under each candidate); and None or the
         [1][J] device tensor of a red_grid or white_grid dataset's per-candidate chi^2/2.  The one row is evaluated again -- trx_flux_grid
         on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out, coef_out or cand_out -- so nothing of
         size n x L is kept.  A t0_grid dataset has the row evaluated on every node: the fourth list holds None or the [J]
@@ -1450,7 +1518,8 @@ class _Scenario:
             if (d.offset is None and d.baseline is None and (d.mix is None or DATASET_RED_NOISE is None)
                     and (d.shift is None or DATASET_T0 is None) and (d.robust is None or DATASET_OUTLIERS is None)
                     and (d.gls is None or DATASET_RED_BASELINES is None)
-                    and (d.white is None or DATASET_WHITE_NOISE is None)):
+                    and (d.white is None or DATASET_WHITE_NOISE is None)
+                    and (not isinstance(d.white, _WhiteLin) or DATASET_WHITE_BASELINES is None)):
                 continue
             keep = d.robust is not None and DATASET_OUTLIERS is not None
             grids = []
@@ -1465,6 +1534,8 @@ class _Scenario:
                 cands[l] = torch.empty((J, int(d.mix[3].size)), dtype=F64, device=self.dev)
             if d.white is not None:
                 cands[l] = torch.empty((J, int(d.white[1].size)), dtype=F64, device=self.dev)
+            if isinstance(d.white, _WhiteLin) and DATASET_WHITE_BASELINES is not None:
+                coefs[l] = torch.empty((J, int(d.white.lnc.size), int(d.white.basis.shape[0])), dtype=F64, device=self.dev)
             hs = []
             for j, t in enumerate(stamps):
                 grid, _ = _lib.flux_grid(model, flags, t, row, d.exptime, d.nsamples, want_secdepth=False)

@@ -161,7 +161,8 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
                     exptime: float = 0.00139, nsamples: int = 20, offset_sigma: float = None,
                     baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None,
                     red_grid=None, t0_grid=None, outlier_frac: float = None, outlier_scale: float = None,
-                    red_baseline_order: int = None, red_baseline_sigma=None, red_kernel: str = None, white_grid=None):
+                    red_baseline_order: int = None, red_baseline_sigma=None, red_kernel: str = None, white_grid=None,
+                    white_baseline_order: int = None, white_baseline_sigma=None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
     {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
     empty bins are dropped.
@@ -180,6 +181,9 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     None: flat) passed through.
     white_grid (white_noise_grid's result, or any list of (scale, jitter, weight)): candidates of the size of the white noise
     to marginalise, passed through as the key "white_grid" when given.
+    white_baseline_order (None: no such key; >= 0): "white_baseline" = trend_columns(kept bins' times, white_baseline_order),
+    the trend marginalised under every candidate of white_grid, with white_baseline_sigma (a number or one per column;
+    None: flat) passed through.
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -212,4 +216,8 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
         out["red_baseline_sigma"] = red_baseline_sigma
     if white_grid is not None:
         out["white_grid"] = white_grid
+    if white_baseline_order is not None:
+        out["white_baseline"] = trend_columns(tb, white_baseline_order)
+    if white_baseline_sigma is not None:
+        out["white_baseline_sigma"] = white_baseline_sigma
     return out

@@ -28,7 +28,7 @@ from . import _lib
 from ._numerics import _mc_errors, _normalize_probabilities
 from .constants import G, Msun, pi
 from .datasets import (Datasets, outliers as _outliers, red_baselines as _red_baselines, t0_grids as _t0_grids,
-                       white_grids as _white_grids,
+                       white_grids as _white_grids, white_baselines as _white_baselines,
                        validate as _validate_datasets)
 from .funcs import renorm_flux
 from .marginal_likelihoods import *  # noqa: F401,F403  (reference re-exports the lnZ_* names)
@@ -262,7 +262,7 @@ class target:
                 raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
         sets = _validate_datasets(datasets)
         ds = Datasets(sets, _t0_grids(datasets, sets), _outliers(datasets, sets), _red_baselines(datasets, sets),
-                      white_grids=_white_grids(datasets, sets))
+                      white_grids=_white_grids(datasets, sets), white_baselines=_white_baselines(datasets, sets))
         n_samples = int(n_samples)
         if not 0 <= n_samples <= fused.POST_MAX_ROWS:
             raise ValueError("n_samples must lie in [0, %d]" % fused.POST_MAX_ROWS)
@@ -276,7 +276,7 @@ class target:
 
     def _datasets_pass(self, ds, P_orb, kw, verbose, evaluation, n_samples=0, **dataset_switches):
         """one pass of the datasets path over the target's work units: (units, rows, n_scen) for _finish.
-        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_OUTLIERS / DATASET_RED_BASELINES / DATASET_WHITE_NOISE / DATASET_WARP_HIST for
+        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_OUTLIERS / DATASET_RED_BASELINES / DATASET_WHITE_NOISE / DATASET_WHITE_BASELINES / DATASET_WARP_HIST for
         the length of the pass."""
         from . import fused
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
@@ -293,6 +293,8 @@ class target:
             raise NotImplementedError("evaluation='fused' with a t0_grid dataset is not built: use evaluation='grid'")
         if ds.has_white_grids and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a white_grid dataset is not built: use evaluation='grid'")
+        if ds.has_white_baselines and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with a white_baseline dataset is not built: use evaluation='grid'")
         if ds.has_outliers and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with an outlier_frac dataset is not built: use evaluation='grid'")
         with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, **dataset_switches):
@@ -461,7 +463,27 @@ class target:
         scenario's best draw, softmax_j(ln c_j - h_j) (NaN without a finite lnZ; with a t0_grid on its node of largest
         weight)}; the whole attribute is None when no dataset has the key.  Not built: the key next to an offset, a
         baseline, red noise or the outlier keys, a continuous fit of k or s, per-draw candidate posteriors, the fused
-        evaluation, the scalar calc_probs path."""
+        evaluation, the scalar calc_probs path.
+
+        A dataset with "white_grid" whose normalisation or trend is not known either -- a single-night ground-based curve --
+        may carry next to it "white_baseline": an array [K][len(time)] (or [len(time)]) of K <= 4 columns B_k[t] of a linear
+        baseline model sum_k c_k B_k[t] -- lightcurve.trend_columns makes them; a column of ones is the constant --, and
+        "white_baseline_sigma": the prior sigmas of c_k ~ N(0, s_k^2), a number or one per column, > 0 or inf (absent:
+        flat).  The coefficients are integrated out per draw under every candidate, determinants included: with
+        A_j = B^T W_j B + diag(1 / s_k^2), b_j = B^T W_j (flux - model) and h_j = 0.5 max(S2_j - b_j^T A_j^-1 b_j, 0) the
+        dataset's term is -ln sum_j c_j exp(-h_j), c_j proportional to weight_j prod_t w_j[t]^(1/2) det(A_j)^(-1/2)
+        (datasets.white_baseline_system), in one pass over the model grid for all candidates and columns
+        (trxb_chi2_grid_white_baseline).  Every finite sigma is in flux units per unit of its column and is renormalised
+        with the errors, so det A_j gains the same factor for every candidate and the c_j are the same for every star.  The
+        keys stand only next to white_grid (and t0_grid): without it, or next to offset_sigma, baseline, any red key or
+        the outlier keys they are a ValueError, as are a sigma without columns, a wrong shape, more than four columns, a
+        kept entry that is not finite, a zero column, a bool or a string, or columns that are collinear under a
+        candidate's weights.  Grid evaluation only.  `.dataset_white_baselines` is then a list per scenario of a list per
+        dataset: None for a dataset without the keys, else {"coef": the [J][K] posterior-mean coefficients under each
+        candidate at the scenario's best draw, in the units of the given flux, "mean": [K] their average under the
+        candidates' posterior weights (`.dataset_white_noise`'s "weight")} (NaN without a finite lnZ; with a t0_grid on
+        its node of largest weight); the whole attribute is None when no dataset has the keys.  Not built: white_grid next
+        to the plain offset_sigma / baseline keys, red_grid next to a baseline, the fused evaluation."""
         ds, n_samples, kw, verbose = self._datasets_args(datasets, n_samples, evaluation, calc_probs_kwargs)
         best_offsets = {} if ds.has_offsets else None
         best_baselines = {} if ds.has_baselines else None
@@ -470,11 +492,12 @@ class target:
         best_outliers = {} if ds.has_outliers else None
         best_gls = {} if ds.has_red_baselines else None
         best_white = {} if ds.has_white_grids else None
+        best_lin = {} if ds.has_white_baselines else None
         units, rows, n_scen = self._datasets_pass(ds, P_orb, kw, verbose, evaluation, n_samples,
                                                   DATASET_OFFSETS=best_offsets, DATASET_BASELINES=best_baselines,
                                                   DATASET_RED_NOISE=best_red, DATASET_T0=best_t0,
                                                   DATASET_OUTLIERS=best_outliers, DATASET_RED_BASELINES=best_gls,
-                                                  DATASET_WHITE_NOISE=best_white)
+                                                  DATASET_WHITE_NOISE=best_white, DATASET_WHITE_BASELINES=best_lin)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
@@ -561,6 +584,23 @@ class target:
                     if np.isfinite(self.lnZ[u.first_row + i]):
                         rows_[u.first_row + i] = [cand(g, w) for g, w in zip(ds.white_grids, per)]
             self.dataset_white_noise = rows_
+        self.dataset_white_baselines = None
+        if best_lin is not None:
+            # (as dataset_baselines: c_k multiplies a column that is left alone, so c = fr c')
+            def terms(g, p, c=None, fr=1.0):
+                if p is None:
+                    return None
+                J, K = g.shape[0], p[0].shape[0]
+                if c is None:
+                    return {"coef": np.full((J, K), np.nan), "mean": np.full(K, np.nan)}
+                return {"coef": c["coef"] * fr, "mean": c["mean"] * fr}
+            pairs = list(zip(ds.white_grids, ds.white_baselines))
+            rows_ = [[terms(g, p) for g, p in pairs] for _ in range(n_scen)]
+            for k, u in enumerate(sharding.as_units(units)):
+                for i, per in enumerate(best_lin.get(k, ())):
+                    if np.isfinite(self.lnZ[u.first_row + i]):
+                        rows_[u.first_row + i] = [terms(g, p, c, share[u.group[1]]) for (g, p), c in zip(pairs, per)]
+            self.dataset_white_baselines = rows_
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
@@ -659,7 +699,7 @@ class target:
         uniforms from the chi^2/2 values of that pass (trxw_hist_from_halfchi2, fused.DATASET_WARP_HIST) and refine
         the map; best-draw offsets and baselines are not computed in them.  The final pass is calc_probs_datasets under
         the maps the adaptation left: it fills `.probs`, `.FPP`, `.lnZ_err`, `.posterior` (n_samples > 0), `.sigma_ref`,
-        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise`, `.dataset_t0`, `.dataset_outliers`, `.dataset_red_baselines` and `.dataset_white_noise` as calc_probs_datasets does, and only it enters the result, so the
+        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise`, `.dataset_t0`, `.dataset_outliers`, `.dataset_red_baselines`, `.dataset_white_noise` and `.dataset_white_baselines` as calc_probs_datasets does, and only it enters the result, so the
         estimate is unbiased.  `.refine_history` holds, per pass, the rows' lnZ, ess and w_max_frac.  n_adapt = 0 is
         calc_probs_datasets, bit for bit.  Both evaluations ("grid", "fused") feed the histogram the same way.
 
