@@ -58,6 +58,9 @@ WHITE_SYMBOLS = ("trxv_chi2_grid_white_mix",)
 # ... include/trx_gls.h as well (both libraries: that reduction with baseline columns marginalised per candidate, prefix
 # trxb_)
 WLIN_SYMBOLS = ("trxb_chi2_grid_white_baseline",)
+# ... include/trx_ss.h as well (both libraries: the two-state reduction with baseline columns marginalised under the same
+# noise, prefix trxk_)
+SSGLS_SYMBOLS = ("trxk_chi2_grid_ss2_baseline",)
 # ... and include/trx_debug.h: the testing library only
 DEBUG_SYMBOLS = (
     "trx_set_rows_per_wave", "trx_set_cell_packing_below", "trx_debug_batch_plan", "trx_set_supersample_tiers",
@@ -221,6 +224,9 @@ def _load(path, testing):
                                              _vp, _vp, _vp]
     L.trxs_chi2_grid_ss2.restype = c_int
     L.trxs_chi2_grid_ss2.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, _vp]
+    L.trxk_chi2_grid_ss2_baseline.restype = c_int
+    L.trxk_chi2_grid_ss2_baseline.argtypes = [_vp, _vp, c_int, c_long, _vp, c_double, c_int, _vp, _vp, _vp, _vp, _vp, c_int,
+                                              _vp, _vp, _vp]
     L.trx_grid_quantiles.restype = c_int
     L.trx_grid_quantiles.argtypes = [_vp, c_long, c_int, _vp, _vp, c_long, _vp, c_int, _vp, _vp]
     L.trx_lnl_batch_host.restype = c_int
@@ -662,6 +668,40 @@ def chi2_grid_ou_baseline(flux_d, grid_d, alpha_d, beta_d, omega_d, cols_d, minv
     return _chi2_rows("trxg_chi2_grid_ou_baseline", (flux_d,), grid_d, secdepth, sec_limit, out, alpha_d.data_ptr(),
                       beta_d.data_ptr(), omega_d.data_ptr(), cols_d.data_ptr(), k, minv.ctypes.data,
                       coef_out.data_ptr() if coef_out is not None else None)
+
+
+def chi2_grid_ss2_baseline(flux_d, grid_d, A_d, g_d, omega_d, cols_d, minv, secdepth=None, sec_limit=float("inf"),
+                           out=None, coef_out=None):
+    """chi2_grid_ss2 with a linear baseline sum_k c_k B_k[t] of the light curve marginalised per row under the same noise
+    (trxk_chi2_grid_ss2_baseline, include/trx_ss.h): 0.5 * max(S2 - sum_ij M_ij b_i b_j, 0), S2 what chi2_grid_ss2 sums and
+    b_k = sum_n cols[k][n] z_n over the same innovations z.  cols_d: [K][n_time] fp64 device tensor, the whitened scaled
+    columns; minv: the K (K + 1) / 2 entries of the upper triangle of M by rows, on the host (datasets.ss2_baseline_system);
+    K = 1 .. 4.  coef_out: an [n][K] fp64 device tensor that receives the scaled posterior-mean coefficients M b, or None.
+    The other arguments are chi2_grid_ss2's."""
+    n, nt = grid_d.shape
+    for v, per in ((flux_d, 1), (A_d, 4), (g_d, 2), (omega_d, 1)):
+        assert v.numel() == per * nt and v.dtype == torch.float64 and v.is_contiguous()
+    assert cols_d.dim() == 2 and cols_d.shape[1] == nt and cols_d.dtype == torch.float64 and cols_d.is_contiguous()
+    k = int(cols_d.shape[0])
+    assert 1 <= k <= 4, "1 .. 4 columns (got %d)" % k
+    minv = np.ascontiguousarray(minv, dtype=np.float64).reshape(-1)
+    assert minv.size == k * (k + 1) // 2, "minv: the packed upper triangle of a %d x %d matrix" % (k, k)
+    assert coef_out is None or (coef_out.shape == (n, k) and coef_out.dtype == torch.float64 and coef_out.is_contiguous())
+    return _chi2_rows("trxk_chi2_grid_ss2_baseline", (flux_d,), grid_d, secdepth, sec_limit, out, A_d.data_ptr(),
+                      g_d.data_ptr(), omega_d.data_ptr(), cols_d.data_ptr(), k, minv.ctypes.data,
+                      coef_out.data_ptr() if coef_out is not None else None)
+
+
+# blocks of 256 threads a CU of scan_rows_kernel<ONE, Ss2ColsFilter<K>>, [ONE][K - 1]: kSs2ColsBlocksPerCu of
+# csrc/trx_ss2_cols.hpp (tests/test_build_resources_ss2_cols.py holds the two against each other and the code object)
+SS2_COLS_BLOCKS_PER_CU = ((3, 3, 3, 3), (4, 3, 4, 3))
+
+
+def ss2_baseline_blocks(n, n_time, K):
+    """the blocks trxk_chi2_grid_ss2_baseline launches for n rows of n_time stamps and K columns (its launcher's cap, for
+    the tests): 4 rows a block, on 256 CUs as many blocks a CU as the registers of the instantiation -- a single trip up to
+    128 stamps, or trips -- leave resident"""
+    return min((n + 3) // 4, 256 * SS2_COLS_BLOCKS_PER_CU[1 if n_time <= 128 else 0][K - 1])
 
 
 def chi2_grid_ou_mix(flux_d, grid_d, alpha_d, beta_d, omega_d, lnc, secdepth=None, sec_limit=float("inf"), out=None,

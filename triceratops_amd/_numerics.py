@@ -227,6 +227,53 @@ def ou_baseline_halfchi2(y, system, dtype=np.float64, return_coef=False):
     return (h, coef) if return_coef else h
 
 
+def ss2_innovations(x, A, g, dtype=np.float64):
+    """The innovations of x [..., T] under the Kalman recurrence of datasets.ss2_system: z_n = x_n - u_(n-1)[0], u_(-1) = 0,
+    u_n = A_n u_(n-1) + g_n x_n -- what ss2_halfchi2 squares, and what whitens a baseline column as it whitens the
+    residuals: x^T K^-1 x' = sum_n omega_n z[x]_n z[x']_n.  In `dtype`, the operations of ss2_halfchi2 in its order."""
+    x = np.asarray(x, dtype=dtype)
+    T = x.shape[-1]
+    A = np.asarray(A, dtype=dtype).reshape(T, 2, 2)
+    g = np.asarray(g, dtype=dtype).reshape(T, 2)
+    z = np.empty(x.shape, dtype=dtype)
+    u0 = np.zeros(x.shape[:-1], dtype=dtype)
+    u1 = np.zeros(x.shape[:-1], dtype=dtype)
+    for n in range(T):
+        xn = x[..., n]
+        z[..., n] = xn - u0
+        u0, u1 = (A[n, 0, 0] * u0 + A[n, 0, 1] * u1 + g[n, 0] * xn,
+                  A[n, 1, 0] * u0 + A[n, 1, 1] * u1 + g[n, 1] * xn)
+    return z
+
+
+def ss2_baseline_halfchi2(y, system, dtype=np.float64, return_coef=False):
+    """ou_baseline_halfchi2 for noise with a two-dimensional state -- a Matern-3/2 term, two exponential terms -- (DESIGN.md
+    section 14), on the host: the statement of what trxk_chi2_grid_ss2_baseline computes per row,
+        h = 0.5 [y^T K^-1 y - b^T A^-1 b],   b = B^T K^-1 y,   A = B^T K^-1 B + diag(1 / s_k^2),
+    (for finite priors 0.5 y^T (K + B diag(s^2) B^T)^-1 y) in the innovations z = ss2_innovations(y) and the scaled form of
+    `system` (datasets.ss2_baseline_system: A, g, omega, c, M):
+        S2 = sum_n omega_n z_n^2,   b~_k = sum_n c_k[n] z_n,   h = 0.5 max(S2 - b~^T M b~, 0).
+    The factors det K and det(I + diag(s^2) B^T K^-1 B) depend on the dataset alone and are dropped.  y: [..., T]
+    residuals; in `dtype` (np.longdouble: the tests' reference).  S2 is summed as ss2_halfchi2 sums it: M = 0 gives its
+    bits.  return_coef: (h, coef~ [..., K]), coef~ = M b~ the scaled posterior-mean coefficients, c_k = coef~_k / sqrt(D_k)."""
+    z = ss2_innovations(y, system.A, system.g, dtype)
+    omega = np.asarray(system.omega, dtype=dtype).reshape(-1)
+    c = np.asarray(system.c, dtype=dtype)
+    M = np.asarray(system.M, dtype=dtype)
+    S2 = np.zeros(z.shape[:-1], dtype=dtype)
+    for n in range(z.shape[-1]):                                  # (ss2_halfchi2's order: its bits at M = 0)
+        zn = z[..., n]
+        S2 = S2 + omega[n] * zn * zn
+    b = z @ c.T
+    coef = b @ M                                                  # (M is symmetric)
+    q = np.sum(b * coef, axis=-1)
+    with np.errstate(invalid="ignore"):
+        tot = S2 - q
+        h = np.where(tot < 0, dtype(0.0), tot) * dtype(0.5)       # (a NaN stays a NaN)
+    h = np.asarray(h, dtype=dtype)
+    return (h, coef) if return_coef else h
+
+
 def ou_mix_halfchi2(y, alpha, beta, omega, lnc, dtype=np.float64, return_candidates=False):
     """A dataset's term of the log-weight with the amplitude and time scale of its correlated noise marginalised over J
     candidates, on the host: the statement of what trxm_chi2_grid_ou_mix computes per row,

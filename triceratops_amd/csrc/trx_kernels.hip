@@ -26,6 +26,8 @@
 //   trx_gls.hpp      OuColsFilter<K> (the OU filter with K baseline columns marginalised under the same noise;
 //                    include/trx_gls.h)
 //   trx_ss2.hpp      Ss2Filter (noise with a two-dimensional state: 2 x 2 affine maps in the scan; include/trx_ss.h)
+//   trx_ss2_cols.hpp Ss2ColsFilter<K> (that filter with K baseline columns marginalised under the same noise, and the
+//                    blocks a CU of each instantiation; include/trx_ss.h)
 //   (+ trx_device.hpp: the fp64 device math; trx_draw.hip / trx_scenario.hip: the per-draw kernel and the scenario calls)
 // Here: the launch plan (plan_cells; probe_pass: what its probe pass changes), the launchers (launch_cells for one call,
 // lnl_lme_chain for a chain's branches; launch_cells_kernel is the one place that names cells_kernel instantiations), the
@@ -89,6 +91,7 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0)
 #include "trx_gls.hpp"
 #include "trx_white_lin.hpp"
 #include "trx_ss2.hpp"
+#include "trx_ss2_cols.hpp"
 #include "trx_bands.hpp"
 
 namespace {
@@ -1050,7 +1053,8 @@ void chi2_rows_launch(const double* flux, const double* inv_var, const double* m
 // One launch of the red-noise row reductions (trxn_chi2_grid_ou, trxs_chi2_grid_ss2, trxg_chi2_grid_ou_baseline,
 // trxm_chi2_grid_ou_mix): `one` -- scan_rows_kernel<true, Filter>, ou_mix_kernel<true, J> -- while a row is a single trip
 // of kOuTrip stamps, `trips` past that; p: the filter, or ou_mix_kernel's OuMix.  No dynamic LDS, so the registers bound
-// what stays resident: blocks_per_cu = 4 blocks of 256 threads a CU at up to 128 VGPRs, 2 at up to 256 (two waves a SIMD;
+// what stays resident: blocks_per_cu = 4 blocks of 256 threads a CU at up to 128 VGPRs, 3 at up to 168
+// (trxk_chi2_grid_ss2_baseline alone asks for that step), 2 at up to 256 (two waves a SIMD;
 // ou_mix_kernel's up to 52 KB of LDS a block fit as well), on 256 CUs.  The rows behind that cap are the second row of a
 // wave's pass and its further passes.
 template <class P>
@@ -1396,6 +1400,33 @@ int trxs_chi2_grid_ss2(const double* flux, const double* model_grid, int n_time,
     scan_rows_launch(scan_rows_kernel<true, Ss2Filter>, scan_rows_kernel<false, Ss2Filter>, flux, model_grid, n_time, n,
                      secdepth, sec_limit, accumulate, out_halfchi2, Ss2Filter{A, g, omega}, 4,
                      static_cast<hipStream_t>(stream));
+    TRX_HIP(hipGetLastError());
+    return TRX_OK;
+}
+
+int trxk_chi2_grid_ss2_baseline(const double* flux, const double* model_grid, int n_time, long n, const double* secdepth,
+                                double sec_limit, int accumulate, double* out_halfchi2, const double* A, const double* g,
+                                const double* omega, const double* columns, int n_terms, const double* minv,
+                                double* coef_out, void* stream)
+{
+    if (n < 0 || n_time < 1) return fail(TRX_ERR_ARG, "n < 0 or n_time < 1%s (n=%ld)", "", n);
+    if (n_terms < 1 || n_terms > TRXK_MAX_TERMS)
+        return fail(TRX_ERR_ARG, "n_terms must lie in [1, 4]%s (got %ld)", "", (long)n_terms);
+    if (!flux || !model_grid || !out_halfchi2 || !A || !g || !omega || !columns || !minv)
+        return fail(TRX_ERR_ARG, "null pointer%s", "", 0);
+    static_assert(TRXK_MAX_TERMS == kChi2bMaxTerms, "the header's limit is the kernel's");
+    Chi2bM M;
+    if (int rc = pack_minv(minv, n_terms, M)) return rc;
+    if (n == 0) return TRX_OK;
+    // (the registers of an instantiation decide how many blocks a CU are resident: kSs2ColsBlocksPerCu, trx_ss2_cols.hpp)
+    dispatch_int<1, kChi2bMaxTerms>(n_terms, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        using Filter = Ss2ColsFilter<K>;
+        scan_rows_launch(scan_rows_kernel<true, Filter>, scan_rows_kernel<false, Filter>, flux, model_grid, n_time, n,
+                         secdepth, sec_limit, accumulate, out_halfchi2,
+                         Filter{A, g, omega, columns, {nullptr, M, coef_out}}, ss2_cols_blocks_per_cu(n_time <= kOuTrip, K),
+                         static_cast<hipStream_t>(stream));
+    });
     TRX_HIP(hipGetLastError());
     return TRX_OK;
 }

@@ -20,8 +20,8 @@
 //   Row                                a row's running state, its carry and sums: value-initialised at the row's start
 //   row_trip(t, m0, m1, row, lane)     one trip of one row from the lane's two grid values
 //   wave_sums(row), store(row, r, ..)  the wave reduction, and what lane 0 makes of it
-// OuFilter (trx_noise.hpp), OuColsFilter<K> (trx_gls.hpp), Ss2Filter (trx_ss2.hpp).  ou_mix_kernel (trx_noise_mix.hpp) is
-// a kernel of its own over the same pieces.
+// OuFilter (trx_noise.hpp), OuColsFilter<K> (trx_gls.hpp), Ss2Filter (trx_ss2.hpp), Ss2ColsFilter<K> (trx_ss2_cols.hpp).
+// ou_mix_kernel (trx_noise_mix.hpp) is a kernel of its own over the same pieces.
 #pragma once
 #include "trx_reduce.hpp"
 

@@ -126,6 +126,25 @@ __device__ __forceinline__ Ss2Trip ss2_trip(const double* __restrict__ flux, con
 }
 
 
+// One trip of one row up to its innovations z0, z1 (carry: u before the trip's first stamp).  Returns the lane's u after
+// its second stamp: the last lane's is the next trip's carry.  Ss2Filter and Ss2ColsFilter<K> (trx_ss2_cols.hpp) both go
+// through here, so their z0, z1 are the same bits.
+__device__ __forceinline__ Ss2Vec ss2_innovations(const Ss2Trip& t, double m0, double m1, const Ss2Vec& carry, int lane,
+                                                  double& z0, double& z1)
+{
+    const double y0 = t.f0 - m0, y1 = t.f1 - m1;
+    Ss2Vec v;
+    v.x = fma(t.h.x, y0, t.g1.x * y1);
+    v.y = fma(t.h.y, y0, t.g1.y * y1);
+    ss2_scan_v<0>(t.m, v);
+    const Ss2Vec uinc = ss2_apply(t.minc, carry, v);               // u after the lane's second stamp
+    const double uin0 = ou_shift_up1(uinc.x, carry.x, lane);       // ... and before its first
+    const double uin1 = ou_shift_up1(uinc.y, carry.y, lane);
+    z0 = y0 - uin0;
+    z1 = y1 - fma(t.a00, uin0, fma(t.a01, uin1, t.g00 * y0));
+    return uinc;
+}
+
 struct Ss2Row {
     Ss2Vec carry = {0.0, 0.0};        // u before the trip's first stamp
     double acc = 0.0;                 // the lane's share of sum omega z^2
@@ -141,16 +160,8 @@ struct Ss2Filter {
     }
     static __device__ __forceinline__ void row_trip(const Ss2Trip& t, double m0, double m1, Ss2Row& s, int lane)
     {
-        const double y0 = t.f0 - m0, y1 = t.f1 - m1;
-        Ss2Vec v;
-        v.x = fma(t.h.x, y0, t.g1.x * y1);
-        v.y = fma(t.h.y, y0, t.g1.y * y1);
-        ss2_scan_v<0>(t.m, v);
-        const Ss2Vec uinc = ss2_apply(t.minc, s.carry, v);             // u after the lane's second stamp
-        const double uin0 = ou_shift_up1(uinc.x, s.carry.x, lane);     // ... and before its first
-        const double uin1 = ou_shift_up1(uinc.y, s.carry.y, lane);
-        const double z0 = y0 - uin0;
-        const double z1 = y1 - fma(t.a00, uin0, fma(t.a01, uin1, t.g00 * y0));
+        double z0, z1;
+        const Ss2Vec uinc = ss2_innovations(t, m0, m1, s.carry, lane, z0, z1);
         s.acc = fma(t.w0 * z0, z0, s.acc);
         s.acc = fma(t.w1 * z1, z1, s.acc);
         s.carry.x = wave_read_lane<63>(uinc.x);                        // the last lane's u, to every lane

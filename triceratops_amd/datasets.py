@@ -10,7 +10,9 @@ kernel, with "ou2" two exponential terms (ss2_system) --, or `red_grid`: up to M
 weighted candidates (s_r, tau) of that noise, marginalised per draw (ou_mix_system); and next to any of these `t0_grid`: up
 to MAX_T0_NODES weighted shifts of its stamps, marginalised per draw (t0_grids); next to `red_sigma` / `red_timescale` (and
 `t0_grid`) alone `red_baseline` / `red_baseline_sigma`: up to MAX_BASELINE_TERMS baseline columns marginalised under that
-correlated noise (red_baselines, ou_baseline_system); or, alone or next to `t0_grid`,
+correlated noise (red_baselines, ou_baseline_system), next to `red_kernel` = "matern32" / "ou2" (and `t0_grid`) alone
+`red_kernel_baseline` / `red_kernel_baseline_sigma`: the same under that kernel's noise (red_kernel_baselines,
+ss2_baseline_system); or, alone or next to `t0_grid`,
 `outlier_frac` / `outlier_scale`: every point is with probability eps an outlier from a Gaussian kappa times wider than its
 error, the membership integrated out per point and per draw (outliers, robust_constants); or, alone or next to `t0_grid`,
 `white_grid`: up to MAX_WHITE_CANDIDATES weighted candidates (error scale k, jitter s) of the white noise's size,
@@ -237,7 +239,8 @@ def _red_terms(i, kernel, sigma, timescale, time, others):
         out.append(np.ascontiguousarray(v) if n else float(v))
     if others:
         raise ValueError("dataset %d: red_kernel = %r together with %s is not built: the kernel stands next to red_sigma / "
-                         "red_timescale and t0_grid alone" % (i, kernel, ", ".join(others)))
+                         "red_timescale and t0_grid alone (baseline columns marginalised under it go under "
+                         "red_kernel_baseline / red_kernel_baseline_sigma)" % (i, kernel, ", ".join(others)))
     if np.any(np.diff(time) < 0):
         raise ValueError("dataset %d: red_sigma needs time in non-decreasing order: the noise model is a process in "
                          "time and follows the stamps as given (a folded light curve is not sorted silently)" % i)
@@ -628,6 +631,94 @@ def red_baselines(dicts, sets):
     return [_red_baseline(i, d, s) for i, (d, s) in enumerate(zip(dicts, sets))]
 
 
+RED_KERNEL_BASELINE_KEYS = ("red_kernel_baseline", "red_kernel_baseline_sigma")
+
+
+class Ss2BaselineSystem(NamedTuple):
+    """the noise tables of a dataset with red_kernel "matern32" or "ou2" and the linear system of its baseline columns
+    under that noise (ss2_baseline_system)"""
+    A: np.ndarray             # [T][2][2] of ss2_system
+    g: np.ndarray             # [T][2]
+    omega: np.ndarray         # [T]
+    c: np.ndarray             # [K][T] c_k[n] = omega_n z[B_k]_n / sqrt(D_k), z[x] the innovations of x
+    D: np.ndarray             # [K] D_k = sum_n omega_n z[B_k]_n^2 = B_k^T K^-1 B_k
+    Atilde: np.ndarray        # [K][K] A~ = D^(-1/2) (B^T K^-1 B + diag(1 / s_k^2)) D^(-1/2)
+    M: np.ndarray             # [K][K] A~^(-1), symmetric; None where A~ is singular
+    lambda_min: float         # smallest eigenvalue of A~
+
+    @property
+    def minv(self):
+        """M's upper triangle packed by rows: the `minv` of trxk_chi2_grid_ss2_baseline"""
+        return np.ascontiguousarray(self.M[np.triu_indices(self.M.shape[0])])
+
+
+def ss2_baseline_system(dataset, B, sigmas):
+    """Ss2BaselineSystem of the columns B [K][T] with prior sigmas [K] (inf: flat) under the noise of a Dataset with
+    red_kernel "matern32" or "ou2" -- the one place that forms them, for the device path (fused._Dataset) and for the numpy
+    statement (_numerics.ss2_baseline_halfchi2).  The two-state filter of ss2_system whitens the columns exactly as the
+    recurrence of ou_system does: with z[x]_n = x_n - u_(n-1)[0] (_numerics.ss2_innovations), which is linear in x,
+    B_k^T K^-1 B_l = sum_n omega_n z[B_k]_n z[B_l]_n, so the scaled system is linear_system's on the weights omega and the
+    columns z[B_k].  ValueError for a column whose D_k is 0 (or not finite); a singular A~ gives lambda_min <= 0 and
+    M = None."""
+    from ._numerics import ss2_innovations
+    A, g, omega = ss2_system(dataset)
+    Z = ss2_innovations(np.atleast_2d(np.asarray(B, dtype=np.float64)), A, g, np.float64)
+    system = linear_system(omega, Z, sigmas)
+    return Ss2BaselineSystem(A, g, omega, system.g, system.D, system.A, system.M, system.lambda_min)
+
+
+def _red_kernel_baseline(i, d, dataset):
+    """a dataset's "red_kernel_baseline" and "red_kernel_baseline_sigma" -> ([K_b][T kept] columns, [K_b] sigmas), or None;
+    dataset: the validated Dataset of the same dict (its noise, and what else it marginalises)"""
+    value, sigma = d.get("red_kernel_baseline"), d.get("red_kernel_baseline_sigma")
+    if isinstance(value, (bool, np.bool_, str, bytes)):
+        raise ValueError("dataset %d: red_kernel_baseline must be an array [K][len(time)] or [len(time)] (got %r)"
+                         % (i, value))
+    time = np.atleast_1d(np.asarray(d["time"], dtype=np.float64))
+    keep = ~np.isnan(time) & ~np.isnan(np.atleast_1d(np.asarray(d["flux"], dtype=np.float64)))
+    B, s = _baseline(i, value, sigma, time.size, keep, name="red_kernel_baseline")
+    if B is None:
+        return None
+    if B.shape[0] > MAX_BASELINE_TERMS:
+        raise ValueError("dataset %d: at most %d red_kernel_baseline columns (got %d)" % (i, MAX_BASELINE_TERMS, B.shape[0]))
+    others = [k for k in ("offset_sigma", "baseline", "baseline_sigma", "red_baseline", "red_baseline_sigma", "red_grid",
+                          "white_grid") + WHITE_BASELINE_KEYS + OUTLIER_KEYS if d.get(k) is not None]
+    if others:
+        raise ValueError("dataset %d: red_kernel_baseline together with %s is not built: the columns stand next to "
+                         "red_kernel = 'matern32' or 'ou2' with its red_sigma / red_timescale (and t0_grid) alone; a column "
+                         "of ones is the constant" % (i, ", ".join(others)))
+    if dataset.red_kernel not in RED_KERNELS:
+        raise ValueError("dataset %d: red_kernel_baseline needs red_kernel = 'matern32' or 'ou2': under the one exponential "
+                         "term give the columns as red_baseline, under white noise as baseline" % i)
+    try:
+        system = ss2_baseline_system(dataset, B, s)
+    except ValueError as e:
+        raise ValueError("dataset %d: red_kernel_baseline term %s" % (i, e)) from None
+    if not system.lambda_min >= MIN_BASELINE_EIGENVALUE:
+        raise ValueError("dataset %d: the red_kernel_baseline terms are collinear under the dataset's noise (smallest "
+                         "eigenvalue of the scaled system %.3g < %g): drop a column, or give finite priors"
+                         % (i, system.lambda_min, MIN_BASELINE_EIGENVALUE))
+    return B, s
+
+
+def red_kernel_baselines(dicts, sets):
+    """The "red_kernel_baseline" / "red_kernel_baseline_sigma" keys of the dicts that validate() turned into `sets`: per
+    dataset None, or the pair (B, sigmas) -- B a contiguous float64 [K_b][kept points] array of K_b = 1 ...
+    MAX_BASELINE_TERMS columns of a linear baseline model sum_k c_k B_k[t], aligned with `time` (entries of NaN-dropped
+    points dropped with them, every kept entry finite), sigmas [K_b] the prior sigmas of c_k ~ N(0, s_k^2), each > 0 or inf
+    (absent: flat) -- marginalised per draw under the dataset's Matern-3/2 or two-term noise: its term of the log-weight
+    becomes 0.5 [y^T K^-1 y - b^T A^-1 b] (_numerics.ss2_baseline_halfchi2 on ss2_baseline_system).  A column of ones is
+    how the constant is given.  The keys stand only next to red_kernel = "matern32" or "ou2", and may stand next to t0_grid
+    (the columns follow the points); ValueError next to offset_sigma, baseline, red_baseline, red_grid, white_grid or
+    outlier_frac / outlier_scale, without such a red_kernel, for a sigma without columns, a wrong shape, more than
+    MAX_BASELINE_TERMS columns, a kept entry that is not finite, a zero column, a bool or a string, or columns that are
+    collinear under the noise (smallest eigenvalue of the scaled system < MIN_BASELINE_EIGENVALUE).  Dataset itself has no
+    field for the keys: the pairs travel in Datasets.red_kernel_baselines."""
+    if len(dicts) != len(sets):
+        raise ValueError("red_kernel_baselines: %d dicts for %d datasets" % (len(dicts), len(sets)))
+    return [_red_kernel_baseline(i, d, s) for i, (d, s) in enumerate(zip(dicts, sets))]
+
+
 def robust_constants(frac, scale):
     """(c0, c1, k2) of a dataset's outlier mixture: c0 = -log1p(-eps) >= 0, c1 = ln kappa - ln eps > 0, k2 = 1 / kappa^2 --
     the one place that forms them, for the device path (fused._Dataset) and for the numpy statement
@@ -772,7 +863,7 @@ def _check_baseline(i, dataset):
 def validate(datasets):
     """A list of 1 ... MAX_DATASETS dicts {time, flux, flux_err[, exptime, nsamples, offset_sigma, baseline,
     baseline_sigma, red_sigma, red_timescale, red_kernel, red_grid, t0_grid, outlier_frac, outlier_scale, red_baseline,
-    red_baseline_sigma, white_grid, white_baseline, white_baseline_sigma]} -> a list of Dataset ("red_kernel" = "matern32" / "ou2" gives a Matern32Dataset / an Ou2Dataset: the
+    red_baseline_sigma, white_grid, white_baseline, white_baseline_sigma, red_kernel_baseline, red_kernel_baseline_sigma]} -> a list of Dataset ("red_kernel" = "matern32" / "ou2" gives a Matern32Dataset / an Ou2Dataset: the
     same fields, red_sigma and red_timescale two finite numbers / two arrays of two finite entries, all > 0; "t0_grid"
     is allowed here and read by t0_grids, "outlier_frac" / "outlier_scale" are checked here and returned by outliers,
     "red_baseline" / "red_baseline_sigma" are checked here and returned by red_baselines, "white_grid" is checked here and
@@ -790,7 +881,8 @@ def validate(datasets):
     offset_sigma, baseline, red_sigma / red_timescale or red_grid; for a red_kernel that is not None, "ou", "matern32" or
     "ou2", and with the last two for a red_sigma or red_timescale of the wrong shape or with an entry that is not finite and
     > 0, for stamps out of order, or for offset_sigma, baseline, red_grid, red_baseline or the outlier keys next to them; and
-    for what red_baselines, white_grids and white_baselines list."""
+    for what red_baselines, white_grids, white_baselines and red_kernel_baselines list ("red_kernel_baseline" /
+    "red_kernel_baseline_sigma" are checked here and returned by red_kernel_baselines)."""
     if isinstance(datasets, dict) or not hasattr(datasets, "__len__"):
         raise ValueError("datasets must be a list of dicts with the keys time, flux, flux_err")
     if len(datasets) == 0:
@@ -801,7 +893,8 @@ def validate(datasets):
     for i, d in enumerate(datasets):
         unknown = set(d) - {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma",
                             "red_sigma", "red_timescale", "red_grid", "t0_grid", "outlier_frac", "outlier_scale",
-                            "red_baseline", "red_baseline_sigma", "red_kernel", "white_grid"} - set(WHITE_BASELINE_KEYS)
+                            "red_baseline", "red_baseline_sigma", "red_kernel", "white_grid"} - set(WHITE_BASELINE_KEYS) \
+            - set(RED_KERNEL_BASELINE_KEYS)
         if unknown:
             raise ValueError("dataset %d: unknown key(s) %s" % (i, sorted(unknown)))
         for k in ("time", "flux", "flux_err"):
@@ -846,6 +939,7 @@ def validate(datasets):
                           offset_sigma, baseline, baseline_sigma, red_grid, red_sigma, red_timescale))
         _check_baseline(i, out[-1])
         _red_baseline(i, d, out[-1])
+        _red_kernel_baseline(i, d, out[-1])
         _outliers(i, d, out[-1])
         _white_grid(i, d)
         _white_baseline(i, d, out[-1])
@@ -873,9 +967,11 @@ class Datasets:
     """validated datasets in one star's normalisation, their sigma_bar, and per dataset None or its transit-time shift
     grid (t0_grids), None or its outlier pair (frac, scale) (outliers), None or the pair (columns, sigmas) of its
     baseline under correlated noise (red_baselines), None or its grid of white-noise candidates (white_grids) and None or
-    the pair (columns, sigmas) of its baseline under those candidates (white_baselines)"""
+    the pair (columns, sigmas) of its baseline under those candidates (white_baselines), and None or the pair (columns,
+    sigmas) of its baseline under Matern-3/2 or two-term noise (red_kernel_baselines: a keyword)"""
 
-    def __init__(self, sets, t0_grids=None, outliers=None, red_baselines=None, white_grids=None, white_baselines=None):
+    def __init__(self, sets, t0_grids=None, outliers=None, red_baselines=None, white_grids=None, red_kernel_baselines=None,
+                 white_baselines=None):
         self.sets = tuple(sets)
         self.sigma_ref = sigma_ref(self.sets)
         self.t0_grids = (None,) * len(self.sets) if t0_grids is None else tuple(t0_grids)
@@ -893,6 +989,11 @@ class Datasets:
         self.white_baselines = (None,) * len(self.sets) if white_baselines is None else tuple(white_baselines)
         if len(self.white_baselines) != len(self.sets):
             raise ValueError("white_baselines: %d pairs for %d datasets" % (len(self.white_baselines), len(self.sets)))
+        self.red_kernel_baselines = ((None,) * len(self.sets) if red_kernel_baselines is None
+                                     else tuple(red_kernel_baselines))
+        if len(self.red_kernel_baselines) != len(self.sets):
+            raise ValueError("red_kernel_baselines: %d pairs for %d datasets"
+                             % (len(self.red_kernel_baselines), len(self.sets)))
 
     def __len__(self):
         return len(self.sets)
@@ -930,6 +1031,10 @@ class Datasets:
         return any(b is not None for b in self.white_baselines)
 
     @property
+    def has_red_kernel_baselines(self):
+        return any(b is not None for b in self.red_kernel_baselines)
+
+    @property
     def size(self):
         """points of all datasets together"""
         return sum(s.time.size for s in self.sets)
@@ -951,7 +1056,10 @@ class Datasets:
         flux units and is divided by the flux ratio, the scales are pure numbers: every candidate's weights gain the
         square of the flux ratio, so the lnc of white_mix_system do not change.  A finite sigma of a white_baselines pair is
         divided by the flux ratio as a red_baselines pair's is: every A_j of white_baseline_system gains the square of the
-        flux ratio, det A_j its K-th power for every candidate alike, and the lnc do not change."""
+        flux ratio, det A_j its K-th power for every candidate alike, and the lnc do not change.  A finite sigma of a
+        red_kernel_baselines pair is divided by the flux ratio as well: A and g of ss2_system do not change, omega and D_k of
+        ss2_baseline_system scale with the square of the flux ratio, so s_k^2 D_k, the scaled system matrix and the
+        determinant that the evidence drops are the same for every star."""
         out = []
         for s in self.sets:
             flux, err = renorm_flux(s.flux, s.flux_err, star_fluxratio)
@@ -980,4 +1088,6 @@ class Datasets:
             white.append(g)
         lin = [None if p is None else (p[0], np.where(np.isfinite(p[1]), p[1] / star_fluxratio, p[1]))
                for p in self.white_baselines]
-        return Datasets(out, self.t0_grids, self.outliers, red, white, lin)
+        ss2 = [None if p is None else (p[0], np.where(np.isfinite(p[1]), p[1] / star_fluxratio, p[1]))
+               for p in self.red_kernel_baselines]
+        return Datasets(out, self.t0_grids, self.outliers, red, white, white_baselines=lin, red_kernel_baselines=ss2)

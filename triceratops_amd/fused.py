@@ -22,7 +22,7 @@ import torch
 
 from . import _lib, funcs
 from .datasets import (Datasets, baseline_system, ou_baseline_system, ou_mix_system, ou_system, robust_constants, white_mix_system,
-                       ss2_system, white_baseline_system)
+                       ss2_baseline_system, ss2_system, white_baseline_system)
 from . import device_pipeline as dp
 from . import marginal_likelihoods as ml
 from ._lib import FLAG_COMPANION_IS_HOST, FLAG_SCALAR_K, MODEL_EB, MODEL_EB_TWIN, MODEL_TP
@@ -264,6 +264,11 @@ WARP_BRANCH = _lib.WARP_BRANCH
 # {"coef": the [J][K] posterior-mean coefficients under each candidate at the branch's best draw, in the call's
 # normalisation, "mean": [K] their average under the candidates' posterior weights} (with a t0_grid on its heaviest
 # node)]} there (target.dataset_white_baselines).
+# A dataset with `red_kernel_baseline` columns (Datasets.red_kernel_baselines) has their coefficients marginalised per draw
+# under its Matern-3/2 or two-term noise: its reduction is trxk_chi2_grid_ss2_baseline on the tables of
+# datasets.ss2_baseline_system (grid evaluation only).  DATASET_RED_KERNEL_BASELINES = {}: every such call leaves {work unit:
+# [per branch, a list per dataset: None or the [K_b] posterior-mean coefficients at the branch's best draw, in the call's
+# normalisation (with a t0_grid on its heaviest node)]} there (target.dataset_red_kernel_baselines).
 DATASET_GRID_BYTES = 512 << 20
 DATASET_EVALUATIONS = ("grid", "fused")
 DATASET_EVALUATION = "grid"
@@ -275,6 +280,7 @@ DATASET_OUTLIERS = None
 DATASET_RED_BASELINES = None
 DATASET_WHITE_NOISE = None
 DATASET_WHITE_BASELINES = None
+DATASET_RED_KERNEL_BASELINES = None
 # An importance map (WARP_GRIDS) applies to a datasets call as to any other: its draws are trx_draw_scenario's.  The weight
 # histogram of the library's own chain (WARP_HIST) does not exist here -- chi^2/2 is computed outside that chain -- so
 # DATASET_WARP_HIST = {}: every datasets call leaves {work unit: [branches][WARP_BRANCH] uint64 words} there, one
@@ -285,7 +291,7 @@ DATASET_WARP_HIST = None
 
 @contextlib.contextmanager
 def switches(**values):
-    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_OUTLIERS, DATASET_RED_BASELINES, DATASET_WHITE_NOISE, DATASET_WHITE_BASELINES, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
+    """POSTERIOR_ROWS, POSTERIOR_SUMMARY, WARP_GRIDS, WARP_HIST, DATASET_GRID_BYTES, DATASET_EVALUATION, DATASET_OFFSETS, DATASET_BASELINES, DATASET_RED_NOISE, DATASET_T0, DATASET_OUTLIERS, DATASET_RED_BASELINES, DATASET_WHITE_NOISE, DATASET_WHITE_BASELINES, DATASET_RED_KERNEL_BASELINES, DATASET_WARP_HIST = ... for the length of a `with` block: what they were
     before -- a user's own setting included -- comes back on exit, also on an error"""
     saved = {name: globals()[name] for name in values}
     globals().update(values)
@@ -853,6 +859,25 @@ def _ss2_on_device(d, device):
     return _cached(_ss2_cache, key, 32, lambda: tuple(_lib.dev(np.ascontiguousarray(v), device) for v in ss2_system(d)))
 
 
+_ss2gls_cache = {}
+
+
+def _ss2gls_on_device(d, pair, device):
+    """the _Ss2Gls record of a dataset with red_kernel_baseline columns (datasets.ss2_baseline_system): formed once per
+    content of its stamps, errors, noise keys, columns and prior sigmas -- (1 + K) * T steps of a Python loop and a K x K
+    eigenproblem -- for the lnZ_* calls of a star (a cache of its own, as _gls_on_device's)"""
+    B, sigmas = pair
+    terms = tuple(tuple(np.ravel(np.asarray(v, dtype=np.float64)).tolist()) for v in (d.red_sigma, d.red_timescale))
+    key = (tuple(hash(np.ascontiguousarray(a).tobytes()) for a in (d.time, d.flux_err, B, sigmas)), B.shape, d.red_kernel,
+           terms, device.index)
+
+    def build():
+        system = ss2_baseline_system(d, B, sigmas)
+        return _Ss2Gls(tuple(_lib.dev(np.ascontiguousarray(v), device) for v in (system.A, system.g, system.omega)),
+                       _lib.dev(system.c, device), system.minv, np.sqrt(system.D))
+    return _cached(_ss2gls_cache, key, 32, build)
+
+
 _gls_cache = {}
 
 
@@ -903,11 +928,21 @@ class _Gls(NamedTuple):
     sqrt_d: np.ndarray           # sqrt(D): c_k = c~_k / sqrt(D_k)
 
 
+class _Ss2Gls(NamedTuple):
+    """the system of a dataset with red_kernel_baseline columns (datasets.ss2_baseline_system); it travels in
+    _Dataset.ss2, where the kernel's tables alone are a plain tuple"""
+    tables: tuple                # (A, g, omega) on the device
+    c: torch.Tensor              # the whitened scaled columns [K][T], on the device
+    minv: np.ndarray             # M's packed upper triangle
+    sqrt_d: np.ndarray           # sqrt(D): c_k = c~_k / sqrt(D_k)
+
+
 class _Dataset(NamedTuple):
     """one light curve of a Datasets call on the device, and what its reduction marginalises: nothing, a constant offset,
     or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then --, or correlated
     noise -- one exponential term alone (`ou`) or with baseline columns under it (`gls`: `ou` is None then), or a term with
-    a two-dimensional state (`ss2`: `ou` is None then) --, or the outlier mixture of its
+    a two-dimensional state (`ss2`: `ou` is None then; a _Ss2Gls where baseline columns are marginalised under it:
+    `ss2gls`) --, or the outlier mixture of its
     points, or white noise whose size is marginalised over candidates (`white`: a pair, or a _WhiteLin where baseline columns are marginalised under every candidate); and, next to any of these, the nodes of a transit-time shift (`shift`: the
     reduction then runs once per node)"""
     time: torch.Tensor
@@ -922,11 +957,17 @@ class _Dataset(NamedTuple):
     shift: Optional[tuple] = None            # (J device tensors time + shift_j, ln pi [J] on the host, ln pi on the device)
     robust: Optional[tuple] = None           # (c0, c1, k2): the outlier mixture of the points (datasets.robust_constants)
     gls: Optional[_Gls] = None               # baseline columns under correlated noise (datasets.ou_baseline_system)
-    ss2: Optional[tuple] = None              # (A, g, omega) on the device: red_kernel matern32 / ou2 (datasets.ss2_system)
+    ss2: Optional[tuple] = None              # (A, g, omega) on the device: red_kernel matern32 / ou2 (datasets.ss2_system); or a _Ss2Gls
     white: Optional[tuple] = None            # (w [J][T] on the device, lnc [J] on the host): datasets.white_mix_system; or a _WhiteLin
 
+    @property
+    def ss2gls(self):
+        """the _Ss2Gls record of a dataset with red_kernel_baseline columns, or None"""
+        return self.ss2 if isinstance(self.ss2, _Ss2Gls) else None
+
     @classmethod
-    def upload(cls, d, dev, t0_grid=None, outliers=None, red_baseline=None, white_grid=None, white_baseline=None):
+    def upload(cls, d, dev, t0_grid=None, outliers=None, red_baseline=None, white_grid=None, white_baseline=None,
+               red_kernel_baseline=None):
         inv_var = 1.0 / (d.flux_err * d.flux_err)
         rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
         if outliers is not None:
@@ -946,8 +987,11 @@ class _Dataset(NamedTuple):
         if red_baseline is not None:
             # (validate wants red_sigma / red_timescale next to it and refuses an offset, a baseline or a red_grid)
             return rec._replace(gls=_gls_on_device(d, red_baseline, dev))
+        if red_kernel_baseline is not None:
+            # (validate wants red_kernel matern32 / ou2 next to it and refuses anything else but a t0_grid)
+            return rec._replace(ss2=_ss2gls_on_device(d, red_kernel_baseline, dev))
         if d.red_kernel is not None:
-            # (validate refuses anything but a t0_grid next to it)
+            # (validate refuses anything but a t0_grid or those columns next to it)
             return rec._replace(ss2=_ss2_on_device(d, dev))
         if d.red_sigma is not None:
             # (validate refuses an offset or a baseline next to it)
@@ -969,7 +1013,8 @@ class _Dataset(NamedTuple):
         the rows' scaled coefficients), trx_chi2_grid_offset for an offset alone (offset_out: the rows' offsets),
         trxn_chi2_grid_ou for correlated noise, trxm_chi2_grid_ou_mix for a grid of its candidates (cand_out: the rows'
         per-candidate chi^2/2), trxg_chi2_grid_ou_baseline for baseline columns under correlated noise (coef_out likewise),
-        trxs_chi2_grid_ss2 for correlated noise with a two-dimensional state, trxr_chi2_grid_robust for the outlier mixture,
+        trxs_chi2_grid_ss2 for correlated noise with a two-dimensional state, trxk_chi2_grid_ss2_baseline for baseline columns
+        under it (coef_out likewise), trxr_chi2_grid_robust for the outlier mixture,
         trxv_chi2_grid_white_mix for a grid of white-noise candidates (cand_out likewise), trxb_chi2_grid_white_baseline for
         baseline columns under such a grid (cand_out likewise, coef_out: the rows' [J][K] coefficients), else
         trx_chi2_grid_weighted."""
@@ -986,6 +1031,9 @@ class _Dataset(NamedTuple):
         if self.gls is not None:
             return _lib.chi2_grid_ou_baseline(self.flux, grid, *self.gls.ou, self.gls.c, self.gls.minv, secdepth, sec_limit,
                                               out=out, coef_out=coef_out)
+        if self.ss2gls is not None:
+            return _lib.chi2_grid_ss2_baseline(self.flux, grid, *self.ss2.tables, self.ss2.c, self.ss2.minv, secdepth,
+                                               sec_limit, out=out, coef_out=coef_out)
         if self.ss2 is not None:
             return _lib.chi2_grid_ss2(self.flux, grid, *self.ss2, secdepth, sec_limit, out=out)
         if self.ou is not None:
@@ -1008,9 +1056,10 @@ class _Scenario:
         self.datasets = None
         if isinstance(time, Datasets):
             # (several light curves: sigma is their sigma_bar; exptime / nsamples are each dataset's own)
-            self.datasets = [_Dataset.upload(d, self.dev, g, o, b, w, wb)
-                             for d, g, o, b, w, wb in zip(time.sets, time.t0_grids, time.outliers, time.red_baselines,
-                                                          time.white_grids, time.white_baselines)]
+            self.datasets = [_Dataset.upload(d, self.dev, g, o, b, w, wb, kb)
+                             for d, g, o, b, w, wb, kb in zip(time.sets, time.t0_grids, time.outliers, time.red_baselines,
+                                                              time.white_grids, time.white_baselines,
+                                                              time.red_kernel_baselines)]
             sigma = time.sigma_ref
             self.time, self.flux = self.datasets[0].time, self.datasets[0].flux
         else:
@@ -1302,7 +1351,8 @@ class _Scenario:
             best = self._best(h, idx, n)
             if self.datasets is not None and ((DATASET_OFFSETS is not None and any(d.offset is not None for d in self.datasets))
                                               or self._any_baseline() or self._any_mix() or self._any_shift()
-                                              or self._any_robust() or self._any_gls() or self._any_white()
+                                              or self._any_robust() or self._any_gls() or self._any_ss2gls()
+                                              or self._any_white()
                                               or self._any_white_lin()):
                 o, c, hc, hn, mr = (self._best_offsets(model, flags, cols, best, twin, nblk) if n
                                     else (None, None, None, None, None))
@@ -1368,6 +1418,10 @@ class _Scenario:
         """whether a red_baseline dataset's coefficients are wanted back (DATASET_RED_BASELINES)"""
         return DATASET_RED_BASELINES is not None and any(d.gls is not None for d in self.datasets)
 
+    def _any_ss2gls(self):
+        """whether a red_kernel_baseline dataset's coefficients are wanted back (DATASET_RED_KERNEL_BASELINES)"""
+        return DATASET_RED_KERNEL_BASELINES is not None and any(d.ss2gls is not None for d in self.datasets)
+
     def _leave_best_terms(self, offsets, coefs, cands, nodes, probs):
         """the branches' best-draw offsets and baseline coefficients, from the device to DATASET_OFFSETS / DATASET_BASELINES
         under this thread's work unit, in the call's normalisation: c_k = c~_k / sqrt(D_k); and the posterior weights of a
@@ -1378,9 +1432,20 @@ class _Scenario:
         c_k = c~_k / sqrt(D_k), to DATASET_RED_BASELINES (likewise); and the posterior weights of a white_grid dataset's
         candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_WHITE_NOISE (likewise); and the coefficients of a
         white_baseline dataset's columns under each candidate at that draw with their average under those weights, to
-        DATASET_WHITE_BASELINES (likewise)"""
+        DATASET_WHITE_BASELINES (likewise); and the coefficients of a red_kernel_baseline dataset's columns at that draw,
+        c_k = c~_k / sqrt(D_k), to DATASET_RED_KERNEL_BASELINES (likewise)"""
         L = len(self.datasets)
         unit = getattr(_tls, "unit", None)
+        if DATASET_RED_KERNEL_BASELINES is not None:
+            out = []
+            for c in coefs:
+                per = [None] * L
+                for l, d in enumerate(self.datasets):
+                    if d.ss2gls is not None:
+                        per[l] = (np.full(d.ss2.sqrt_d.size, np.nan) if c is None
+                                  else c[l].cpu().numpy().reshape(-1) / d.ss2.sqrt_d)
+                out.append(per)
+            DATASET_RED_KERNEL_BASELINES[unit] = out
         if DATASET_WHITE_BASELINES is not None:
             out = []
             for c, hc in zip(coefs, cands):
@@ -1496,7 +1561,8 @@ class _Scenario:
         """([L] device tensor and four lists per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
         S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
         baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them; likewise for a
-        red_baseline dataset under DATASET_RED_BASELINES; for a white_baseline dataset under DATASET_WHITE_BASELINES the
+        red_baseline dataset under DATASET_RED_BASELINES and a red_kernel_baseline dataset under
+        DATASET_RED_KERNEL_BASELINES; for a white_baseline dataset under DATASET_WHITE_BASELINES the
         [1][J][K] coefficients under each candidate); and None or the
         [1][J] device tensor of a red_grid or white_grid dataset's per-candidate chi^2/2.  The one row is evaluated again -- trx_flux_grid
         on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out, coef_out or cand_out -- so nothing of
@@ -1518,6 +1584,7 @@ class _Scenario:
             if (d.offset is None and d.baseline is None and (d.mix is None or DATASET_RED_NOISE is None)
                     and (d.shift is None or DATASET_T0 is None) and (d.robust is None or DATASET_OUTLIERS is None)
                     and (d.gls is None or DATASET_RED_BASELINES is None)
+                    and (d.ss2gls is None or DATASET_RED_KERNEL_BASELINES is None)
                     and (d.white is None or DATASET_WHITE_NOISE is None)
                     and (not isinstance(d.white, _WhiteLin) or DATASET_WHITE_BASELINES is None)):
                 continue
@@ -1530,6 +1597,8 @@ class _Scenario:
                 coefs[l] = torch.empty((J, int(d.baseline.g.shape[0])), dtype=F64, device=self.dev)
             if d.gls is not None and DATASET_RED_BASELINES is not None:
                 coefs[l] = torch.empty((J, int(d.gls.c.shape[0])), dtype=F64, device=self.dev)
+            if d.ss2gls is not None and DATASET_RED_KERNEL_BASELINES is not None:
+                coefs[l] = torch.empty((J, int(d.ss2.c.shape[0])), dtype=F64, device=self.dev)
             if d.mix is not None:
                 cands[l] = torch.empty((J, int(d.mix[3].size)), dtype=F64, device=self.dev)
             if d.white is not None:
@@ -1576,6 +1645,9 @@ class _Scenario:
                                       "carries no sums of basis * residual; use evaluation='grid'")
         if DATASET_EVALUATION == "fused" and any(d.gls is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a red_baseline dataset is not built: the fused kernel "
+                                      "carries no recurrence along the row; use evaluation='grid'")
+        if DATASET_EVALUATION == "fused" and any(d.ss2gls is not None for d in self.datasets):
+            raise NotImplementedError("evaluation='fused' with a red_kernel_baseline dataset is not built: the fused kernel "
                                       "carries no recurrence along the row; use evaluation='grid'")
         if DATASET_EVALUATION == "fused" and any(d.ou is not None for d in self.datasets):
             raise NotImplementedError("evaluation='fused' with a red_sigma dataset is not built: the fused kernel "

@@ -162,6 +162,7 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
                     baseline_order: int = 0, baseline_sigma=None, red_sigma: float = None, red_timescale: float = None,
                     red_grid=None, t0_grid=None, outlier_frac: float = None, outlier_scale: float = None,
                     red_baseline_order: int = None, red_baseline_sigma=None, red_kernel: str = None, white_grid=None,
+                    red_kernel_baseline_order: int = None, red_kernel_baseline_sigma=None,
                     white_baseline_order: int = None, white_baseline_sigma=None):
     """prepare() for target.calc_probs_datasets: the same trimming and binning, but one error per bin.  Returns the dict
     {"time", "flux", "flux_err", "exptime", "nsamples", "offset_sigma", "baseline", "baseline_sigma"} of one dataset;
@@ -184,6 +185,10 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
     white_baseline_order (None: no such key; >= 0): "white_baseline" = trend_columns(kept bins' times, white_baseline_order),
     the trend marginalised under every candidate of white_grid, with white_baseline_sigma (a number or one per column;
     None: flat) passed through.
+    red_kernel_baseline_order (None: no such key; >= 0): "red_kernel_baseline" = trend_columns(kept bins' times,
+    red_kernel_baseline_order), the trend marginalised under the dataset's red_kernel = "matern32" or "ou2" noise, with
+    red_kernel_baseline_sigma (a number or one per column; None: flat) passed through (keywords: they stand before the
+    white_baseline pair in the signature).
 
     flux_err of a bin = s / sqrt(points in the bin), s the per-point scatter: s^2 is the mean over the first `n_sigma`
     (out-of-transit) bins of count x (bin flux - their mean)^2 -- a bin mean of c points scatters with s^2 / c.  With
@@ -214,6 +219,10 @@ def prepare_dataset(time, flux, half_width: float = 0.4, n_bins: int = 200, n_si
         out["red_baseline"] = trend_columns(tb, red_baseline_order)
     if red_baseline_sigma is not None:
         out["red_baseline_sigma"] = red_baseline_sigma
+    if red_kernel_baseline_order is not None:
+        out["red_kernel_baseline"] = trend_columns(tb, red_kernel_baseline_order)
+    if red_kernel_baseline_sigma is not None:
+        out["red_kernel_baseline_sigma"] = red_kernel_baseline_sigma
     if white_grid is not None:
         out["white_grid"] = white_grid
     if white_baseline_order is not None:

@@ -29,6 +29,7 @@ from ._numerics import _mc_errors, _normalize_probabilities
 from .constants import G, Msun, pi
 from .datasets import (Datasets, outliers as _outliers, red_baselines as _red_baselines, t0_grids as _t0_grids,
                        white_grids as _white_grids, white_baselines as _white_baselines,
+                       red_kernel_baselines as _red_kernel_baselines,
                        validate as _validate_datasets)
 from .funcs import renorm_flux
 from .marginal_likelihoods import *  # noqa: F401,F403  (reference re-exports the lnZ_* names)
@@ -262,7 +263,8 @@ class target:
                 raise TypeError("calc_probs_datasets() got the keyword '%s': every dataset carries its own" % k)
         sets = _validate_datasets(datasets)
         ds = Datasets(sets, _t0_grids(datasets, sets), _outliers(datasets, sets), _red_baselines(datasets, sets),
-                      white_grids=_white_grids(datasets, sets), white_baselines=_white_baselines(datasets, sets))
+                      white_grids=_white_grids(datasets, sets), white_baselines=_white_baselines(datasets, sets),
+                      red_kernel_baselines=_red_kernel_baselines(datasets, sets))
         n_samples = int(n_samples)
         if not 0 <= n_samples <= fused.POST_MAX_ROWS:
             raise ValueError("n_samples must lie in [0, %d]" % fused.POST_MAX_ROWS)
@@ -276,7 +278,7 @@ class target:
 
     def _datasets_pass(self, ds, P_orb, kw, verbose, evaluation, n_samples=0, **dataset_switches):
         """one pass of the datasets path over the target's work units: (units, rows, n_scen) for _finish.
-        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_OUTLIERS / DATASET_RED_BASELINES / DATASET_WHITE_NOISE / DATASET_WHITE_BASELINES / DATASET_WARP_HIST for
+        dataset_switches: fused.DATASET_OFFSETS / DATASET_BASELINES / DATASET_RED_NOISE / DATASET_T0 / DATASET_OUTLIERS / DATASET_RED_BASELINES / DATASET_WHITE_NOISE / DATASET_WHITE_BASELINES / DATASET_RED_KERNEL_BASELINES / DATASET_WARP_HIST for
         the length of the pass."""
         from . import fused
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
@@ -286,6 +288,9 @@ class target:
             raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: use evaluation='grid'")
         if ds.has_red_baselines and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a red_baseline dataset is not built: use evaluation='grid'")
+        if ds.has_red_kernel_baselines and evaluation == "fused":
+            raise NotImplementedError("evaluation='fused' with a red_kernel_baseline dataset is not built: use "
+                                      "evaluation='grid'")
         if ds.has_red_noise and evaluation == "fused":
             raise NotImplementedError("evaluation='fused' with a red_sigma or red_grid dataset is not built: use "
                                       "evaluation='grid'")
@@ -424,7 +429,7 @@ class target:
         else the [K_b] posterior-mean coefficients at the scenario's best draw, in flux units per unit of the column (NaN
         without a finite lnZ; with a t0_grid on its node of largest weight); the whole attribute is None when no dataset
         has the keys.  Not built: red_grid next to a baseline, the outlier keys next to any marginalised term, the fused
-        evaluation, the columns under another kernel than the one exponential term, the scalar calc_probs path.
+        evaluation, the scalar calc_probs path (under the other kernels the columns go under red_kernel_baseline).
 
         A dataset with red_sigma / red_timescale may name the kernel of that noise: "red_kernel": "ou", None or absent is
         the one exponential term above, with its calls and its bits.  "matern32": red_sigma = s and red_timescale = l, both
@@ -440,8 +445,27 @@ class target:
         baseline, red_grid, red_baseline or the outlier keys, for a red_kernel that is none of the four values, for shapes
         that do not fit the kernel or an entry that is not finite and > 0 (tau = inf stays the one term's business) it is a
         ValueError.  Grid evaluation only: evaluation="fused" raises NotImplementedError.  Nothing new is reported per
-        best draw.  Not built: these kernels next to a baseline, red_grid or the outlier keys, a quasi-periodic (SHO) term,
+        best draw.  Not built: these kernels next to red_grid or the outlier keys, a quasi-periodic (SHO) term,
         more than two exponential terms, the fused evaluation, the scalar calc_probs path.
+
+        A dataset with such a red_kernel may carry a trend as well: "red_kernel_baseline": 1 ... 4 columns B_k
+        [K_b][len(time)] (or [len(time)]) aligned with `time`, finite at the kept points -- lightcurve.trend_columns makes
+        them; a column of ones is the constant --, and "red_kernel_baseline_sigma": the prior sigmas of their coefficients
+        c_k ~ N(0, s_k^2), a number or [K_b], each > 0 or inf (absent: flat).  The coefficients are marginalised per draw
+        under the kernel's noise K exactly as red_baseline's are under the one exponential term: the dataset's term of the
+        log-weight is 0.5 [y^T K^-1 y - b^T A^-1 b], b = B^T K^-1 y, A = B^T K^-1 B + diag(1 / s_k^2) -- for finite priors
+        0.5 y^T (K + B diag(s^2) B^T)^-1 y --, the two-state filter of ss2_system whitening residuals and columns alike
+        (datasets.ss2_baseline_system, _numerics.ss2_baseline_halfchi2, trxk_chi2_grid_ss2_baseline).  The dropped factors
+        det K and det(I + diag(s^2) B^T K^-1 B) depend on the dataset alone and are the same for every star.  The keys
+        stand only next to red_kernel = "matern32" or "ou2" and may stand next to "t0_grid"; next to offset_sigma,
+        baseline, red_baseline, red_grid, white_grid or the outlier keys, without such a red_kernel ("red_baseline" next to
+        red_kernel stays a ValueError: these are its keys there), with a zero column or with columns that are collinear
+        under the noise they are a ValueError.  Grid evaluation only.  `.dataset_red_kernel_baselines` is then a list per
+        scenario of a list per dataset: None for a dataset without the keys, else the [K_b] posterior-mean coefficients at
+        the scenario's best draw, in flux units per unit of the column (NaN without a finite lnZ; with a t0_grid on its
+        node of largest weight); the whole attribute is None when no dataset has the keys.  Not built: red_grid next to a
+        baseline, an SHO term, the fused evaluation, the keys next to any other marginalised term, the scalar calc_probs
+        path.
 
         Where the SIZE of a dataset's white noise is not known -- photon-noise errors from a differential-photometry
         pipeline, binned errors that ignore what detrending left --, the dataset may carry "white_grid": 1 to 8 candidates
@@ -493,11 +517,13 @@ class target:
         best_gls = {} if ds.has_red_baselines else None
         best_white = {} if ds.has_white_grids else None
         best_lin = {} if ds.has_white_baselines else None
+        best_ss2gls = {} if ds.has_red_kernel_baselines else None
         units, rows, n_scen = self._datasets_pass(ds, P_orb, kw, verbose, evaluation, n_samples,
                                                   DATASET_OFFSETS=best_offsets, DATASET_BASELINES=best_baselines,
                                                   DATASET_RED_NOISE=best_red, DATASET_T0=best_t0,
                                                   DATASET_OUTLIERS=best_outliers, DATASET_RED_BASELINES=best_gls,
-                                                  DATASET_WHITE_NOISE=best_white, DATASET_WHITE_BASELINES=best_lin)
+                                                  DATASET_WHITE_NOISE=best_white, DATASET_WHITE_BASELINES=best_lin,
+                                                  DATASET_RED_KERNEL_BASELINES=best_ss2gls)
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
@@ -601,6 +627,16 @@ class target:
                     if np.isfinite(self.lnZ[u.first_row + i]):
                         rows_[u.first_row + i] = [terms(g, p, c, share[u.group[1]]) for (g, p), c in zip(pairs, per)]
             self.dataset_white_baselines = rows_
+        self.dataset_red_kernel_baselines = None
+        if best_ss2gls is not None:
+            # (as dataset_red_baselines: c_k multiplies a column that is left alone, so c = fr c')
+            sizes = [None if p is None else p[0].shape[0] for p in ds.red_kernel_baselines]
+            rows_ = [[None if m is None else np.full(m, np.nan) for m in sizes] for _ in range(n_scen)]
+            for k, u in enumerate(sharding.as_units(units)):
+                for i, per in enumerate(best_ss2gls.get(k, ())):
+                    if np.isfinite(self.lnZ[u.first_row + i]):
+                        rows_[u.first_row + i] = [None if c is None else c * share[u.group[1]] for c in per]
+            self.dataset_red_kernel_baselines = rows_
         return
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
@@ -699,7 +735,7 @@ class target:
         uniforms from the chi^2/2 values of that pass (trxw_hist_from_halfchi2, fused.DATASET_WARP_HIST) and refine
         the map; best-draw offsets and baselines are not computed in them.  The final pass is calc_probs_datasets under
         the maps the adaptation left: it fills `.probs`, `.FPP`, `.lnZ_err`, `.posterior` (n_samples > 0), `.sigma_ref`,
-        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise`, `.dataset_t0`, `.dataset_outliers`, `.dataset_red_baselines`, `.dataset_white_noise` and `.dataset_white_baselines` as calc_probs_datasets does, and only it enters the result, so the
+        `.dataset_offsets`, `.dataset_baselines`, `.dataset_red_noise`, `.dataset_t0`, `.dataset_outliers`, `.dataset_red_baselines`, `.dataset_white_noise`, `.dataset_white_baselines` and `.dataset_red_kernel_baselines` as calc_probs_datasets does, and only it enters the result, so the
         estimate is unbiased.  `.refine_history` holds, per pass, the rows' lnZ, ess and w_max_frac.  n_adapt = 0 is
         calc_probs_datasets, bit for bit.  Both evaluations ("grid", "fused") feed the histogram the same way.
 
