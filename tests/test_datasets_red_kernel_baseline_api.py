@@ -266,11 +266,14 @@ def test_the_switch_and_the_record():
     with fused.switches(DATASET_RED_KERNEL_BASELINES=box):
         assert fused.DATASET_RED_KERNEL_BASELINES is box
     assert fused.DATASET_RED_KERNEL_BASELINES is None
-    assert fused._Ss2Gls._fields == ("tables", "c", "minv", "sqrt_d")
-    assert fused._Dataset(None, None, None, 0.0, 1).ss2gls is None
-    assert fused._Dataset(None, None, None, 0.0, 1, ss2=(1, 2, 3)).ss2gls is None          # the kernel's tables alone
-    rec = fused._Ss2Gls((1, 2, 3), None, None, None)
-    assert fused._Dataset(None, None, None, 0.0, 1, ss2=rec).ss2gls is rec
+    assert fused._Ss2Lin._fields == ("tables", "c", "minv", "sqrt_d") and fused._Ss2._fields == ("A", "g", "omega")
+    assert fused._Dataset._fields == ("time", "flux", "inv_var", "exptime", "nsamples", "term", "shift")
+    assert fused._Dataset(None, None, None, 0.0, 1).term is None and fused._Dataset(None, None, None, 0.0, 1).shift is None
+    alone = fused._Dataset(None, None, None, 0.0, 1, term=fused._Ss2(1, 2, 3))             # the kernel's tables alone
+    rec = fused._Ss2Lin((1, 2, 3), None, None, None)
+    cols = fused._Dataset(None, None, None, 0.0, 1, term=rec)
+    assert cols.term is rec and type(alone.term) is fused._Ss2 and type(cols.term) is fused._Ss2Lin
+    assert not isinstance(alone.term, fused._Ss2Lin) and not isinstance(cols.term, fused._Ss2)
 
 
 # ---------------------------------------------------------------------------------------

@@ -223,8 +223,11 @@ def test_the_switch_is_listed_with_the_others():
     with fused.switches(DATASET_WHITE_BASELINES=box):
         assert fused.DATASET_WHITE_BASELINES is box
     assert fused.DATASET_WHITE_BASELINES is None
-    assert fused._Dataset._fields[-1] == "white" and fused._Dataset._field_defaults["white"] is None
-    assert fused._WhiteLin._fields[:2] == ("w", "lnc")                   # (where a white_grid's pair keeps them)
+    assert fused._Dataset._fields == ("time", "flux", "inv_var", "exptime", "nsamples", "term", "shift")
+    assert fused._Dataset._field_defaults == {"term": None, "shift": None}
+    assert fused._WhiteLin._fields == ("w", "lnc", "basis", "minv")
+    assert fused._WhiteLin._fields[:2] == fused._WhiteMix._fields        # (a type of its own, not a white_grid's pair grown)
+    assert not issubclass(fused._WhiteLin, fused._WhiteMix) and not issubclass(fused._WhiteMix, fused._WhiteLin)
 
 
 # ---------------------------------------------------------------------------------------

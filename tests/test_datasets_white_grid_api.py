@@ -201,7 +201,9 @@ def test_the_switch_is_listed_with_the_others():
     with fused.switches(DATASET_WHITE_NOISE=box):
         assert fused.DATASET_WHITE_NOISE is box
     assert fused.DATASET_WHITE_NOISE is None
-    assert fused._Dataset._fields[-1] == "white" and fused._Dataset._field_defaults["white"] is None
+    assert fused._Dataset._fields == ("time", "flux", "inv_var", "exptime", "nsamples", "term", "shift")
+    assert fused._Dataset._field_defaults == {"term": None, "shift": None}
+    assert fused._WhiteMix._fields == ("w", "lnc")
 
 
 # ---------------------------------------------------------------------------------------

@@ -78,7 +78,7 @@ class _Spy:
             h = real_h(scen, model, flags, block)
             if replay:
                 kept = scen.datasets
-                scen.datasets = [d._replace(offset=None, baseline=None, ou=None, gls=None) for d in scen.datasets]
+                scen.datasets = [d._replace(term=None) for d in scen.datasets]
                 try:
                     spy.plain.append(real_h(scen, model, flags, block).cpu().numpy())
                 finally:

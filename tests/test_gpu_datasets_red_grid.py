@@ -180,7 +180,7 @@ def test_candidate_weights_at_the_best_draw(device_mode, monkeypatch):
             continue
         assert (w >= 0).all() and abs(math.fsum(w) - 1.0) <= 8 * EPS * 2
         d, grid = best[j]
-        alpha, beta, omega, lnc = d.mix
+        alpha, beta, omega, lnc = d.term
         h = np.array([float(_lib.chi2_grid_ou(d.flux, grid, alpha[k], beta[k], omega[k]).cpu()[0]) for k in range(2)])
         x = lnc - h
         want = np.exp(x - x.max())

@@ -49,7 +49,7 @@ class _Spy:
         def halfchi2(scen, model, flags, block):
             h = real_h(scen, model, flags, block)
             if replay:
-                kept, scen.datasets = scen.datasets, [d._replace(offset=None, ou=None) for d in scen.datasets]
+                kept, scen.datasets = scen.datasets, [d._replace(term=None) for d in scen.datasets]
                 try:
                     spy.plain.append(real_h(scen, model, flags, block).cpu().numpy())
                 finally:

@@ -205,7 +205,7 @@ def test_coefficients_at_the_best_draw(device_mode, monkeypatch):
         if not np.isfinite(m["lnZ"][j]):
             continue
         y = (d.flux - grid[0]).cpu().numpy()
-        system = _system(_inputs(white_grid=AB, **LIN))._replace(w=d.white.w.cpu().numpy(), minv=d.white.minv, lnc=d.white.lnc)
+        system = _system(_inputs(white_grid=AB, **LIN))._replace(w=d.term.w.cpu().numpy(), minv=d.term.minv, lnc=d.term.lnc)
         _, _, coef = _numerics.white_baseline_halfchi2(y, system, return_candidates=True, return_coef=True)
         got = tg.dataset_white_baselines[j][1]["coef"]
         share = got[0, 0] / coef[0, 0]

@@ -213,7 +213,7 @@ def _check_weights(m, data):
             continue
         assert (w >= 0).all() and abs(math.fsum(w) - 1.0) <= 8 * EPS * J
         d, grid = best[j]
-        w_d, lnc = d.white
+        w_d, lnc = d.term
         h = np.array([float(_lib.chi2_grid_weighted(d.flux, w_d[k].contiguous(), grid).cpu()[0]) for k in range(J)])
         x = lnc - h
         want = np.exp(x - x.max())

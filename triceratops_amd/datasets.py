@@ -974,26 +974,14 @@ class Datasets:
                  white_baselines=None):
         self.sets = tuple(sets)
         self.sigma_ref = sigma_ref(self.sets)
-        self.t0_grids = (None,) * len(self.sets) if t0_grids is None else tuple(t0_grids)
-        if len(self.t0_grids) != len(self.sets):
-            raise ValueError("t0_grids: %d grids for %d datasets" % (len(self.t0_grids), len(self.sets)))
-        self.outliers = (None,) * len(self.sets) if outliers is None else tuple(outliers)
-        if len(self.outliers) != len(self.sets):
-            raise ValueError("outliers: %d pairs for %d datasets" % (len(self.outliers), len(self.sets)))
-        self.red_baselines = (None,) * len(self.sets) if red_baselines is None else tuple(red_baselines)
-        if len(self.red_baselines) != len(self.sets):
-            raise ValueError("red_baselines: %d pairs for %d datasets" % (len(self.red_baselines), len(self.sets)))
-        self.white_grids = (None,) * len(self.sets) if white_grids is None else tuple(white_grids)
-        if len(self.white_grids) != len(self.sets):
-            raise ValueError("white_grids: %d grids for %d datasets" % (len(self.white_grids), len(self.sets)))
-        self.white_baselines = (None,) * len(self.sets) if white_baselines is None else tuple(white_baselines)
-        if len(self.white_baselines) != len(self.sets):
-            raise ValueError("white_baselines: %d pairs for %d datasets" % (len(self.white_baselines), len(self.sets)))
-        self.red_kernel_baselines = ((None,) * len(self.sets) if red_kernel_baselines is None
-                                     else tuple(red_kernel_baselines))
-        if len(self.red_kernel_baselines) != len(self.sets):
-            raise ValueError("red_kernel_baselines: %d pairs for %d datasets"
-                             % (len(self.red_kernel_baselines), len(self.sets)))
+        for name, what, seq in (("t0_grids", "grids", t0_grids), ("outliers", "pairs", outliers),
+                                ("red_baselines", "pairs", red_baselines), ("white_grids", "grids", white_grids),
+                                ("white_baselines", "pairs", white_baselines),
+                                ("red_kernel_baselines", "pairs", red_kernel_baselines)):
+            seq = (None,) * len(self.sets) if seq is None else tuple(seq)
+            if len(seq) != len(self.sets):
+                raise ValueError("%s: %d %s for %d datasets" % (name, len(seq), what, len(self.sets)))
+            setattr(self, name, seq)
 
     def __len__(self):
         return len(self.sets)
@@ -1078,16 +1066,15 @@ class Datasets:
                 grid[:, 0] = grid[:, 0] / star_fluxratio
             out.append(s._replace(flux=np.ascontiguousarray(flux), flux_err=np.ascontiguousarray(err), offset_sigma=off,
                                   baseline_sigma=bsig, red_sigma=red, red_grid=grid))
-        red = [None if p is None else (p[0], np.where(np.isfinite(p[1]), p[1] / star_fluxratio, p[1]))
-               for p in self.red_baselines]
+
+        def pairs(seq):
+            """the finite sigmas of (columns, sigmas) pairs divided by the flux ratio"""
+            return [None if p is None else (p[0], np.where(np.isfinite(p[1]), p[1] / star_fluxratio, p[1])) for p in seq]
         white = []
         for g in self.white_grids:
             if g is not None:
                 g = g.copy()
                 g[:, 1] = g[:, 1] / star_fluxratio
             white.append(g)
-        lin = [None if p is None else (p[0], np.where(np.isfinite(p[1]), p[1] / star_fluxratio, p[1]))
-               for p in self.white_baselines]
-        ss2 = [None if p is None else (p[0], np.where(np.isfinite(p[1]), p[1] / star_fluxratio, p[1]))
-               for p in self.red_kernel_baselines]
-        return Datasets(out, self.t0_grids, self.outliers, red, white, white_baselines=lin, red_kernel_baselines=ss2)
+        return Datasets(out, self.t0_grids, self.outliers, pairs(self.red_baselines), white,
+                        white_baselines=pairs(self.white_baselines), red_kernel_baselines=pairs(self.red_kernel_baselines))

@@ -15,6 +15,7 @@ import ctypes
 import math
 import os
 import threading
+from collections import namedtuple
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -791,260 +792,416 @@ def _on_device(a, device):
     return _cached(_lc_cache, (a.shape, hash(a.tobytes()), device.index), 32, lambda: _lib.dev(a, device))
 
 
+# What a dataset's reduction marginalises is one `term` record on its _Dataset -- one type per kind, below -- and, next to
+# any of them, the nodes of a transit-time shift (`shift`, a _Shift).  A record holds its kind's tables and answers what
+# the callers ask (the defaults are _Term's):
+#   reduce(d, grid, ...)   the one _lib.chi2_grid_* call of its kind (_Dataset.halfchi2)
+#   coef_shape, lnc        the per-node shape of its coef_out buffer, and the host log-weights of its candidates
+#                          (cand_out is [J] per node), or None (_Scenario._best_offsets)
+#   refusal                its place in, and its sentence of, the fused evaluation's refusals (_Scenario._datasets_halfchi2)
+#   reports, entry(...)    the DATASET_* switches it feeds, by name, and what it leaves in each for the best draw of a
+#                          branch, NaN-filled without one (_Scenario._leave_best_terms)
+# The kinds with tables that take a loop or an eigenproblem to form keep them in a cache of their own, by content, for the
+# lnZ_* calls of a star (not in _lc_cache: its entries decide where a star's launch chain splits).
+class _Best(NamedTuple):
+    """what evaluating a branch's best draw again leaves for one dataset (on the heaviest node of a t0_grid): the [1] +
+    coef_shape coefficients, the [1][J] per-candidate chi^2/2, the [J] per-node terms, the [1][T] model row -- each None
+    where nobody asked, all None without a draw.  Device tensors from _best_offsets; a term's entry() reads host copies"""
+    coef: Optional[torch.Tensor] = None
+    cand: Optional[torch.Tensor] = None
+    nodes: Optional[torch.Tensor] = None
+    row: Optional[torch.Tensor] = None
+
+
+def _weights(lnc, h):
+    """softmax_j(lnc_j - h_j): the posterior weights of candidates (or nodes) of log-weights lnc at a draw whose
+    per-candidate chi^2/2 is h; NaN without a draw"""
+    if h is None:
+        return np.full(lnc.size, np.nan)
+    x = lnc - h.reshape(-1)
+    w = np.exp(x - np.max(x))
+    return w / w.sum()
+
+
+def _unscaled(coef, sqrt_d):
+    """c_k = c~_k / sqrt(D_k): a draw's scaled coefficients in the call's normalisation; NaN without a
+    draw"""
+    return np.full(sqrt_d.size, np.nan) if coef is None else coef.reshape(-1) / sqrt_d
+
+
+def _refusal(rank, what, why):
+    return rank, "evaluation='fused' with %s dataset is not built: %s; use evaluation='grid'" % (what, why)
+
+
+_NO_RECURRENCE = "the fused kernel carries no recurrence along the row"
+
+
+def _noise_terms(d):
+    return tuple(tuple(np.ravel(np.asarray(v, dtype=np.float64)).tolist()) for v in (d.red_sigma, d.red_timescale))
+
+
+def _hashes(*arrays):
+    return tuple(hash(np.ascontiguousarray(a).tobytes()) for a in arrays)
+
+
+class _Term:
+    """the answers of a kind that has nothing to give back"""
+    always = False           # the best row is evaluated again whichever switch is open
+    coef_shape = None
+    coef_switch = None       # the switch under which coef_out is read (`always`: under any)
+    lnc = None
+    wants_row = False        # entry() reads the best draw's model row
+    reports = ()
+
+    def entry(self, switch, d, off, best):
+        raise NotImplementedError(switch)
+
+
+class _Offset(namedtuple("_Offset", "sum_w inv_s2"), _Term):
+    """offset_sigma: the sum of the weights and 1 / s^2.  DATASET_OFFSETS: the posterior-mean offset S1 / (S0 + 1 / s^2)"""
+    always = True
+    refusal = _refusal(0, "an offset_sigma", "the fused kernel carries no sum of w * residual")
+    reports = ("DATASET_OFFSETS",)
+
+    @classmethod
+    def on_device(cls, d, inv_var):
+        # (sum_w is the correctly rounded sum of the weights the device holds)
+        return cls(math.fsum(inv_var.tolist()), 0.0 if math.isinf(d.offset_sigma) else 1.0 / (d.offset_sigma * d.offset_sigma))
+
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_offset(d.flux, d.inv_var, grid, *self, secdepth, sec_limit, out=out, offset_out=offset_out)
+
+    def entry(self, switch, d, off, best):
+        return off
+
+
+class _Baseline(namedtuple("_Baseline", "g minv sqrt_d has_offset"), _Term):
+    """baseline (datasets.baseline_system): the scaled columns [K][T] on the device, M's packed upper triangle, sqrt(D),
+    and whether term 0 is the dataset's offset.  DATASET_BASELINES: the coefficients c_k = c~_k / sqrt(D_k) of the columns;
+    DATASET_OFFSETS: term 0, if it is the offset"""
+    always = True
+    refusal = _refusal(1, "a baseline", "the fused kernel carries no sums of basis * residual")
+    reports = ("DATASET_BASELINES", "DATASET_OFFSETS")
+
+    @classmethod
+    def on_device(cls, d, device):
+        system = baseline_system(d)
+        return cls(_on_device(system.g, device), system.minv, np.sqrt(system.D), d.offset_sigma is not None)
+
+    @property
+    def coef_shape(self):
+        return (int(self.g.shape[0]),)
+
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_baseline(d.flux, d.inv_var, grid, self.g, self.minv, secdepth, sec_limit, out=out,
+                                       coef_out=coef_out)
+
+    def entry(self, switch, d, off, best):
+        ck = _unscaled(best.coef, self.sqrt_d)
+        if switch == "DATASET_OFFSETS":
+            return ck[0] if self.has_offset else off
+        return ck[1:] if self.has_offset else ck
+
+
+class _Ou(namedtuple("_Ou", "alpha beta omega"), _Term):
+    """red_sigma / red_timescale (datasets.ou_system): the three [T] tables on the device"""
+    refusal = _refusal(4, "a red_sigma", _NO_RECURRENCE)
+
+    @classmethod
+    def on_device(cls, d, device):
+        return cls(*(_on_device(v, device) for v in ou_system(d)))
+
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_ou(d.flux, grid, *self, secdepth, sec_limit, out=out)
+
+
 _mix_cache = {}
 
 
-def _mix_on_device(d, device):
-    """(alpha, beta, omega [J][T] on the device, lnc [J] on the host) of a red_grid dataset (datasets.ou_mix_system): formed
-    once per content of its stamps, errors and candidates -- J * T steps of a Python loop -- for the lnZ_* calls of a star
-    (a cache of its own: _lc_cache's entries decide where a star's launch chain splits)"""
-    key = (tuple(hash(a.tobytes()) for a in (d.time, d.flux_err, d.red_grid)), d.red_grid.shape, device.index)
+class _OuMix(namedtuple("_OuMix", "alpha beta omega lnc"), _Term):
+    """red_grid (datasets.ou_mix_system): alpha, beta, omega [J][T] on the device and lnc [J] on the host, formed once per
+    content of stamps, errors and candidates -- J * T steps of a Python loop.  DATASET_RED_NOISE: the candidates' weights"""
+    refusal = _refusal(6, "a red_grid", _NO_RECURRENCE)
+    reports = ("DATASET_RED_NOISE",)
 
-    def build():
-        alpha, beta, omega, lnc = ou_mix_system(d)
-        return _lib.dev(alpha, device), _lib.dev(beta, device), _lib.dev(omega, device), lnc
-    return _cached(_mix_cache, key, 32, build)
+    @classmethod
+    def on_device(cls, d, device):
+        key = (tuple(hash(a.tobytes()) for a in (d.time, d.flux_err, d.red_grid)), d.red_grid.shape, device.index)
 
+        def build():
+            alpha, beta, omega, lnc = ou_mix_system(d)
+            return cls(_lib.dev(alpha, device), _lib.dev(beta, device), _lib.dev(omega, device), lnc)
+        return _cached(_mix_cache, key, 32, build)
 
-_white_cache = {}
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_ou_mix(d.flux, grid, *self, secdepth, sec_limit, out=out, cand_out=cand_out)
 
-
-def _white_on_device(d, grid, device):
-    """(w [J][T] on the device, lnc [J] on the host) of a dataset with a white_grid [J][3] (datasets.white_mix_system):
-    formed once per content of its errors and candidates for the lnZ_* calls of a star (a cache of its own, as
-    _mix_on_device's)"""
-    key = (hash(d.flux_err.tobytes()), hash(grid.tobytes()), d.flux_err.shape, grid.shape, device.index)
-
-    def build():
-        w, lnc = white_mix_system(d, grid)
-        return _lib.dev(w, device), lnc
-    return _cached(_white_cache, key, 32, build)
-
-
-class _WhiteLin(NamedTuple):
-    """what the `white` slot of a _Dataset holds for a dataset with white_baseline columns next to its white_grid
-    (datasets.white_baseline_system); the first two fields are the pair a white_grid alone leaves there"""
-    w: torch.Tensor              # the candidates' weights [J][T], on the device
-    lnc: np.ndarray              # [J] on the host, the determinants of the candidates' systems included
-    basis: torch.Tensor          # the columns [K][T] as given, on the device
-    minv: np.ndarray             # [J][K (K + 1) / 2] on the host: A_j^-1, packed upper triangle
-
-
-_white_lin_cache = {}
-
-
-def _white_lin_on_device(d, grid, pair, device):
-    """the _WhiteLin record of a dataset with a white_grid [J][3] and white_baseline columns (datasets.white_baseline_system):
-    formed once per content of its errors, candidates, columns and prior sigmas -- J eigenproblems of K x K -- for the
-    lnZ_* calls of a star (a cache of its own, as _white_on_device's)"""
-    B, sigmas = pair
-    key = (tuple(hash(np.ascontiguousarray(a).tobytes()) for a in (d.flux_err, grid, B, sigmas)), d.flux_err.shape,
-           grid.shape, B.shape, device.index)
-
-    def build():
-        system = white_baseline_system(d, grid, B, sigmas)
-        return _WhiteLin(_lib.dev(system.w, device), system.lnc, _lib.dev(system.B, device), system.minv)
-    return _cached(_white_lin_cache, key, 32, build)
-
-
-_ss2_cache = {}
-
-
-def _ss2_on_device(d, device):
-    """(A [T][2][2], g [T][2], omega [T]) on the device of a dataset with red_kernel "matern32" or "ou2"
-    (datasets.ss2_system): formed once per content of its stamps, errors and noise keys -- T steps of a Python loop -- for
-    the lnZ_* calls of a star (a cache of its own, as _mix_on_device's)"""
-    terms = tuple(tuple(np.ravel(np.asarray(v, dtype=np.float64)).tolist()) for v in (d.red_sigma, d.red_timescale))
-    key = (tuple(hash(a.tobytes()) for a in (d.time, d.flux_err)), d.time.shape, d.red_kernel, terms, device.index)
-    return _cached(_ss2_cache, key, 32, lambda: tuple(_lib.dev(np.ascontiguousarray(v), device) for v in ss2_system(d)))
-
-
-_ss2gls_cache = {}
-
-
-def _ss2gls_on_device(d, pair, device):
-    """the _Ss2Gls record of a dataset with red_kernel_baseline columns (datasets.ss2_baseline_system): formed once per
-    content of its stamps, errors, noise keys, columns and prior sigmas -- (1 + K) * T steps of a Python loop and a K x K
-    eigenproblem -- for the lnZ_* calls of a star (a cache of its own, as _gls_on_device's)"""
-    B, sigmas = pair
-    terms = tuple(tuple(np.ravel(np.asarray(v, dtype=np.float64)).tolist()) for v in (d.red_sigma, d.red_timescale))
-    key = (tuple(hash(np.ascontiguousarray(a).tobytes()) for a in (d.time, d.flux_err, B, sigmas)), B.shape, d.red_kernel,
-           terms, device.index)
-
-    def build():
-        system = ss2_baseline_system(d, B, sigmas)
-        return _Ss2Gls(tuple(_lib.dev(np.ascontiguousarray(v), device) for v in (system.A, system.g, system.omega)),
-                       _lib.dev(system.c, device), system.minv, np.sqrt(system.D))
-    return _cached(_ss2gls_cache, key, 32, build)
+    def entry(self, switch, d, off, best):
+        return _weights(self.lnc, best.cand)
 
 
 _gls_cache = {}
 
 
-def _gls_on_device(d, pair, device):
-    """the _Gls record of a dataset with red_baseline columns (datasets.ou_baseline_system): formed once per content of its
-    stamps, errors, noise keys, columns and prior sigmas -- (1 + K) * T steps of a Python loop and a K x K eigenproblem --
-    for the lnZ_* calls of a star (a cache of its own, as _mix_on_device's)"""
-    B, sigmas = pair
-    key = (tuple(hash(np.ascontiguousarray(a).tobytes()) for a in (d.time, d.flux_err, B, sigmas)), B.shape,
-           float(d.red_sigma), float(d.red_timescale), device.index)
+class _OuLin(namedtuple("_OuLin", "ou c minv sqrt_d"), _Term):
+    """red_baseline (datasets.ou_baseline_system): (alpha, beta, omega) and the whitened scaled columns [K][T] on the device,
+    M's packed upper triangle, sqrt(D) -- formed once per content of stamps, errors, noise keys, columns and prior sigmas:
+    (1 + K) * T steps of a Python loop and a K x K eigenproblem.  DATASET_RED_BASELINES: c_k = c~_k / sqrt(D_k)"""
+    refusal = _refusal(2, "a red_baseline", _NO_RECURRENCE)
+    reports = ("DATASET_RED_BASELINES",)
+    coef_switch = "DATASET_RED_BASELINES"
 
-    def build():
-        system = ou_baseline_system(d, B, sigmas)
-        return _Gls(tuple(_lib.dev(v, device) for v in (system.alpha, system.beta, system.omega)),
-                    _lib.dev(system.c, device), system.minv, np.sqrt(system.D))
-    return _cached(_gls_cache, key, 32, build)
+    @classmethod
+    def on_device(cls, d, pair, device):
+        B, sigmas = pair
+        key = (_hashes(d.time, d.flux_err, B, sigmas), B.shape, float(d.red_sigma), float(d.red_timescale), device.index)
+
+        def build():
+            system = ou_baseline_system(d, B, sigmas)
+            return cls(tuple(_lib.dev(v, device) for v in (system.alpha, system.beta, system.omega)),
+                       _lib.dev(system.c, device), system.minv, np.sqrt(system.D))
+        return _cached(_gls_cache, key, 32, build)
+
+    @property
+    def coef_shape(self):
+        return (int(self.c.shape[0]),)
+
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_ou_baseline(d.flux, grid, *self.ou, self.c, self.minv, secdepth, sec_limit, out=out,
+                                          coef_out=coef_out)
+
+    def entry(self, switch, d, off, best):
+        return _unscaled(best.coef, self.sqrt_d)
+
+
+_ss2_cache = {}
+
+
+class _Ss2(namedtuple("_Ss2", "A g omega"), _Term):
+    """red_kernel "matern32" or "ou2" (datasets.ss2_system): A [T][2][2], g [T][2], omega [T] on the device, formed once per
+    content of stamps, errors and noise keys -- T steps of a Python loop"""
+    refusal = _refusal(5, "a red_kernel", _NO_RECURRENCE)
+
+    @classmethod
+    def on_device(cls, d, device):
+        key = (tuple(hash(a.tobytes()) for a in (d.time, d.flux_err)), d.time.shape, d.red_kernel, _noise_terms(d), device.index)
+        return _cached(_ss2_cache, key, 32, lambda: cls(*(_lib.dev(np.ascontiguousarray(v), device) for v in ss2_system(d))))
+
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_ss2(d.flux, grid, *self, secdepth, sec_limit, out=out)
+
+
+_ss2gls_cache = {}
+
+
+class _Ss2Lin(namedtuple("_Ss2Lin", "tables c minv sqrt_d"), _Term):
+    """red_kernel_baseline (datasets.ss2_baseline_system): (A, g, omega) and the whitened scaled columns [K][T] on the
+    device, M's packed upper triangle, sqrt(D) -- formed once per content of stamps, errors, noise keys, columns and prior
+    sigmas, as _OuLin's.  DATASET_RED_KERNEL_BASELINES: c_k = c~_k / sqrt(D_k)"""
+    refusal = _refusal(3, "a red_kernel_baseline", _NO_RECURRENCE)
+    reports = ("DATASET_RED_KERNEL_BASELINES",)
+    coef_switch = "DATASET_RED_KERNEL_BASELINES"
+
+    @classmethod
+    def on_device(cls, d, pair, device):
+        B, sigmas = pair
+        key = (_hashes(d.time, d.flux_err, B, sigmas), B.shape, d.red_kernel, _noise_terms(d), device.index)
+
+        def build():
+            system = ss2_baseline_system(d, B, sigmas)
+            return cls(tuple(_lib.dev(np.ascontiguousarray(v), device) for v in (system.A, system.g, system.omega)),
+                       _lib.dev(system.c, device), system.minv, np.sqrt(system.D))
+        return _cached(_ss2gls_cache, key, 32, build)
+
+    coef_shape = _OuLin.coef_shape
+    entry = _OuLin.entry
+
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_ss2_baseline(d.flux, grid, *self.tables, self.c, self.minv, secdepth, sec_limit, out=out,
+                                           coef_out=coef_out)
+
+
+class _Robust(namedtuple("_Robust", "c0 c1 k2"), _Term):
+    """outlier_frac / outlier_scale (datasets.robust_constants).  DATASET_OUTLIERS: the [T] posterior outlier probabilities
+    of the points, _numerics.robust_responsibility on the draw's model row, formed on the host"""
+    refusal = _refusal(9, "an outlier_frac", "the fused kernel carries no exp and log1p per point")
+    reports = ("DATASET_OUTLIERS",)
+    wants_row = True
+
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_robust(d.flux, d.inv_var, grid, *self, secdepth, sec_limit, out=out)
+
+    def entry(self, switch, d, off, best):
+        from ._numerics import robust_responsibility
+        if best.row is None:
+            return np.full(int(d.flux.numel()), np.nan)
+        resid = d.flux.cpu().numpy() - best.row.reshape(-1)
+        return robust_responsibility(resid, d.inv_var.cpu().numpy(), *self)
+
+
+_white_cache = {}
+
+
+class _WhiteMix(namedtuple("_WhiteMix", "w lnc"), _Term):
+    """white_grid [J][3] (datasets.white_mix_system): the candidates' weights [J][T] on the device and lnc [J] on the host,
+    formed once per content of errors and candidates.  DATASET_WHITE_NOISE: the candidates' weights"""
+    refusal = _refusal(7, "a white_grid", "the fused kernel carries one sum per row, not one per candidate")
+    reports = ("DATASET_WHITE_NOISE",)
+
+    @classmethod
+    def on_device(cls, d, grid, device):
+        key = (hash(d.flux_err.tobytes()), hash(grid.tobytes()), d.flux_err.shape, grid.shape, device.index)
+
+        def build():
+            w, lnc = white_mix_system(d, grid)
+            return cls(_lib.dev(w, device), lnc)
+        return _cached(_white_cache, key, 32, build)
+
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_white_mix(d.flux, grid, *self, secdepth, sec_limit, out=out, cand_out=cand_out)
+
+    def entry(self, switch, d, off, best):
+        return _weights(self.lnc, best.cand)
+
+
+_white_lin_cache = {}
+
+
+class _WhiteLin(namedtuple("_WhiteLin", "w lnc basis minv"), _Term):
+    """white_baseline columns next to a white_grid (datasets.white_baseline_system): w and lnc as _WhiteMix's (lnc with the
+    determinants of the candidates' systems), the columns [K][T] as given on the device, and A_j^-1 [J][K (K + 1) / 2],
+    packed upper triangles, on the host -- formed once per content of errors, candidates, columns and prior sigmas: J
+    eigenproblems of K x K.  DATASET_WHITE_NOISE: the candidates' weights; DATASET_WHITE_BASELINES: {"coef": the [J][K]
+    coefficients under each candidate, "mean": [K] their average under those weights}"""
+    refusal = _WhiteMix.refusal
+    reports = ("DATASET_WHITE_NOISE", "DATASET_WHITE_BASELINES")
+    coef_switch = "DATASET_WHITE_BASELINES"
+
+    @classmethod
+    def on_device(cls, d, grid, pair, device):
+        B, sigmas = pair
+        key = (_hashes(d.flux_err, grid, B, sigmas), d.flux_err.shape, grid.shape, B.shape, device.index)
+
+        def build():
+            system = white_baseline_system(d, grid, B, sigmas)
+            return cls(_lib.dev(system.w, device), system.lnc, _lib.dev(system.B, device), system.minv)
+        return _cached(_white_lin_cache, key, 32, build)
+
+    @property
+    def coef_shape(self):
+        return int(self.lnc.size), int(self.basis.shape[0])
+
+    def reduce(self, d, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out):
+        return _lib.chi2_grid_white_baseline(d.flux, grid, self.w, self.basis, self.minv, self.lnc, secdepth, sec_limit,
+                                             out=out, cand_out=cand_out, coef_out=coef_out)
+
+    def entry(self, switch, d, off, best):
+        w = _weights(self.lnc, best.cand)
+        if switch == "DATASET_WHITE_NOISE":
+            return w
+        J, K = self.coef_shape
+        if best.coef is None or best.cand is None:
+            return {"coef": np.full((J, K), np.nan), "mean": np.full(K, np.nan)}
+        coef = best.coef.reshape(J, K)
+        # (a candidate of weight 0 -- switched off, or far below -- does not enter, whatever its coefficients)
+        return {"coef": coef, "mean": np.sum(np.where(w[:, None] > 0, w[:, None] * coef, 0.0), axis=0)}
 
 
 _shift_cache = {}
 
 
-def _shift_on_device(d, grid, device):
-    """(the J device tensors time + shift_j, ln pi [J] on the host, the same on the device) of a dataset with a t0_grid
-    [J][2]: the sums are float64, formed once on the host per content of the stamps and the grid (a cache of its own, as
-    _mix_on_device's).  The device copy of ln pi serves the best draw's choice of a node: an upload per branch would make
-    the host wait for the device there."""
-    key = (hash(d.time.tobytes()), hash(grid.tobytes()), d.time.shape, grid.shape, device.index)
+class _Shift(namedtuple("_Shift", "stamps lnpi lnpi_dev"), _Term):
+    """t0_grid [J][2]: the J device tensors time + shift_j, ln pi [J] on the host and the same on the device.  The sums are
+    float64, formed once on the host per content of the stamps and the grid.  The device copy of ln pi serves the best
+    draw's choice of a node: an upload per branch would make the host wait for the device there.  DATASET_T0: the nodes'
+    weights softmax_j(ln pi_j - h_j)"""
+    refusal = _refusal(8, "a t0_grid", "the nodes' terms are folded from the grid reductions")
+    reports = ("DATASET_T0",)
 
-    def build():
-        lnpi = np.log(grid[:, 1])
-        return [_lib.dev(np.ascontiguousarray(d.time + shift), device) for shift in grid[:, 0]], lnpi, _lib.dev(lnpi, device)
-    return _cached(_shift_cache, key, 32, build)
+    @classmethod
+    def on_device(cls, d, grid, device):
+        key = (hash(d.time.tobytes()), hash(grid.tobytes()), d.time.shape, grid.shape, device.index)
 
+        def build():
+            lnpi = np.log(grid[:, 1])
+            return cls([_lib.dev(np.ascontiguousarray(d.time + shift), device) for shift in grid[:, 0]], lnpi,
+                       _lib.dev(lnpi, device))
+        return _cached(_shift_cache, key, 32, build)
 
-class _Baseline(NamedTuple):
-    """the system of a dataset with baseline columns (datasets.baseline_system)"""
-    g: torch.Tensor              # the scaled columns [K][T], on the device
-    minv: np.ndarray             # M's packed upper triangle
-    sqrt_d: np.ndarray           # sqrt(D): c_k = c~_k / sqrt(D_k)
-    has_offset: bool             # term 0 is the dataset's offset
-
-
-class _Gls(NamedTuple):
-    """the system of a dataset with red_baseline columns (datasets.ou_baseline_system)"""
-    ou: tuple                    # (alpha, beta, omega) on the device
-    c: torch.Tensor              # the whitened scaled columns [K][T], on the device
-    minv: np.ndarray             # M's packed upper triangle
-    sqrt_d: np.ndarray           # sqrt(D): c_k = c~_k / sqrt(D_k)
+    def entry(self, switch, d, off, best):
+        return _weights(self.lnpi, best.nodes)
 
 
-class _Ss2Gls(NamedTuple):
-    """the system of a dataset with red_kernel_baseline columns (datasets.ss2_baseline_system); it travels in
-    _Dataset.ss2, where the kernel's tables alone are a plain tuple"""
-    tables: tuple                # (A, g, omega) on the device
-    c: torch.Tensor              # the whitened scaled columns [K][T], on the device
-    minv: np.ndarray             # M's packed upper triangle
-    sqrt_d: np.ndarray           # sqrt(D): c_k = c~_k / sqrt(D_k)
+# (DATASET_OFFSETS is an [L] array per branch, NaN where the others hold None)
+_TERM_SWITCHES = ("DATASET_OFFSETS", "DATASET_BASELINES", "DATASET_RED_NOISE", "DATASET_T0", "DATASET_OUTLIERS",
+                  "DATASET_RED_BASELINES", "DATASET_WHITE_NOISE", "DATASET_WHITE_BASELINES", "DATASET_RED_KERNEL_BASELINES")
+
+
+def _open(switch):
+    return switch is not None and globals()[switch] is not None
 
 
 class _Dataset(NamedTuple):
-    """one light curve of a Datasets call on the device, and what its reduction marginalises: nothing, a constant offset,
-    or a baseline system -- whose term 0 is the offset, if the dataset has one: `offset` is None then --, or correlated
-    noise -- one exponential term alone (`ou`) or with baseline columns under it (`gls`: `ou` is None then), or a term with
-    a two-dimensional state (`ss2`: `ou` is None then; a _Ss2Gls where baseline columns are marginalised under it:
-    `ss2gls`) --, or the outlier mixture of its
-    points, or white noise whose size is marginalised over candidates (`white`: a pair, or a _WhiteLin where baseline columns are marginalised under every candidate); and, next to any of these, the nodes of a transit-time shift (`shift`: the
-    reduction then runs once per node)"""
+    """one light curve of a Datasets call on the device; what its reduction marginalises (`term`: None for nothing, else
+    one of the records above); and, next to any term, the nodes of a transit-time shift (`shift`: the reduction then runs
+    once per node)"""
     time: torch.Tensor
     flux: torch.Tensor
     inv_var: torch.Tensor
     exptime: float
     nsamples: int
-    offset: Optional[tuple] = None           # (sum_w, 1 / s^2)
-    baseline: Optional[_Baseline] = None
-    ou: Optional[tuple] = None               # (alpha, beta, omega) on the device: correlated noise (datasets.ou_system)
-    mix: Optional[tuple] = None              # (alpha, beta, omega [J][T] on the device, lnc [J] on the host): ou_mix_system
-    shift: Optional[tuple] = None            # (J device tensors time + shift_j, ln pi [J] on the host, ln pi on the device)
-    robust: Optional[tuple] = None           # (c0, c1, k2): the outlier mixture of the points (datasets.robust_constants)
-    gls: Optional[_Gls] = None               # baseline columns under correlated noise (datasets.ou_baseline_system)
-    ss2: Optional[tuple] = None              # (A, g, omega) on the device: red_kernel matern32 / ou2 (datasets.ss2_system); or a _Ss2Gls
-    white: Optional[tuple] = None            # (w [J][T] on the device, lnc [J] on the host): datasets.white_mix_system; or a _WhiteLin
-
-    @property
-    def ss2gls(self):
-        """the _Ss2Gls record of a dataset with red_kernel_baseline columns, or None"""
-        return self.ss2 if isinstance(self.ss2, _Ss2Gls) else None
+    term: Optional[_Term] = None
+    shift: Optional[_Shift] = None
 
     @classmethod
     def upload(cls, d, dev, t0_grid=None, outliers=None, red_baseline=None, white_grid=None, white_baseline=None,
                red_kernel_baseline=None):
+        """the record of a validated dataset: the one place that picks its term from its keys"""
         inv_var = 1.0 / (d.flux_err * d.flux_err)
         rec = cls(_on_device(d.time, dev), _on_device(d.flux, dev), _on_device(inv_var, dev), d.exptime, d.nsamples)
-        if outliers is not None:
-            # (validate refuses anything but a t0_grid next to it)
-            rec = rec._replace(robust=robust_constants(*outliers))
         if t0_grid is not None:
             # (next to whatever else the dataset marginalises: a shift leaves all of that as it is)
-            rec = rec._replace(shift=_shift_on_device(d, t0_grid, dev))
-        if white_grid is not None:
+            rec = rec._replace(shift=_Shift.on_device(d, t0_grid, dev))
+        term = None
+        if outliers is not None:
             # (validate refuses anything but a t0_grid next to it)
-            if white_baseline is not None:
-                return rec._replace(white=_white_lin_on_device(d, white_grid, white_baseline, dev))
-            return rec._replace(white=_white_on_device(d, white_grid, dev))
-        if d.red_grid is not None:
+            term = _Robust(*robust_constants(*outliers))
+        elif white_grid is not None:
+            # (validate refuses anything but a t0_grid, or these columns, next to it)
+            term = (_WhiteMix.on_device(d, white_grid, dev) if white_baseline is None
+                    else _WhiteLin.on_device(d, white_grid, white_baseline, dev))
+        elif d.red_grid is not None:
             # (validate refuses anything else next to it)
-            return rec._replace(mix=_mix_on_device(d, dev))
-        if red_baseline is not None:
+            term = _OuMix.on_device(d, dev)
+        elif red_baseline is not None:
             # (validate wants red_sigma / red_timescale next to it and refuses an offset, a baseline or a red_grid)
-            return rec._replace(gls=_gls_on_device(d, red_baseline, dev))
-        if red_kernel_baseline is not None:
+            term = _OuLin.on_device(d, red_baseline, dev)
+        elif red_kernel_baseline is not None:
             # (validate wants red_kernel matern32 / ou2 next to it and refuses anything else but a t0_grid)
-            return rec._replace(ss2=_ss2gls_on_device(d, red_kernel_baseline, dev))
-        if d.red_kernel is not None:
+            term = _Ss2Lin.on_device(d, red_kernel_baseline, dev)
+        elif d.red_kernel is not None:
             # (validate refuses anything but a t0_grid or those columns next to it)
-            return rec._replace(ss2=_ss2_on_device(d, dev))
-        if d.red_sigma is not None:
+            term = _Ss2.on_device(d, dev)
+        elif d.red_sigma is not None:
             # (validate refuses an offset or a baseline next to it)
-            return rec._replace(ou=tuple(_on_device(v, dev) for v in ou_system(d)))
-        if d.baseline is not None:
-            system = baseline_system(d)
-            return rec._replace(baseline=_Baseline(_on_device(system.g, dev), system.minv, np.sqrt(system.D),
-                                                    d.offset_sigma is not None))
-        if d.offset_sigma is not None:
-            # (sum_w is the correctly rounded sum of the weights the device holds)
-            return rec._replace(offset=(math.fsum(inv_var.tolist()),
-                                         0.0 if math.isinf(d.offset_sigma) else 1.0 / (d.offset_sigma * d.offset_sigma)))
-        return rec
+            term = _Ou.on_device(d, dev)
+        elif d.baseline is not None:
+            # (its offset, if it has offset_sigma, is term 0 of the same system)
+            term = _Baseline.on_device(d, dev)
+        elif d.offset_sigma is not None:
+            term = _Offset.on_device(d, inv_var)
+        return rec._replace(term=term)
 
     def halfchi2(self, grid, secdepth=None, sec_limit=float("inf"), out=None, offset_out=None, coef_out=None,
                  cand_out=None):
         """this dataset's weighted chi^2/2 of every row of a model grid [n][T], written or added to `out`; +inf where
-        secdepth >= sec_limit.  The one place that picks the reduction: trx_chi2_grid_baseline for baseline columns (coef_out:
-        the rows' scaled coefficients), trx_chi2_grid_offset for an offset alone (offset_out: the rows' offsets),
-        trxn_chi2_grid_ou for correlated noise, trxm_chi2_grid_ou_mix for a grid of its candidates (cand_out: the rows'
-        per-candidate chi^2/2), trxg_chi2_grid_ou_baseline for baseline columns under correlated noise (coef_out likewise),
-        trxs_chi2_grid_ss2 for correlated noise with a two-dimensional state, trxk_chi2_grid_ss2_baseline for baseline columns
-        under it (coef_out likewise), trxr_chi2_grid_robust for the outlier mixture,
-        trxv_chi2_grid_white_mix for a grid of white-noise candidates (cand_out likewise), trxb_chi2_grid_white_baseline for
-        baseline columns under such a grid (cand_out likewise, coef_out: the rows' [J][K] coefficients), else
-        trx_chi2_grid_weighted."""
-        if self.robust is not None:
-            return _lib.chi2_grid_robust(self.flux, self.inv_var, grid, *self.robust, secdepth, sec_limit, out=out)
-        if isinstance(self.white, _WhiteLin):
-            return _lib.chi2_grid_white_baseline(self.flux, grid, self.white.w, self.white.basis, self.white.minv,
-                                                 self.white.lnc, secdepth, sec_limit, out=out, cand_out=cand_out,
-                                                 coef_out=coef_out)
-        if self.white is not None:
-            return _lib.chi2_grid_white_mix(self.flux, grid, *self.white, secdepth, sec_limit, out=out, cand_out=cand_out)
-        if self.mix is not None:
-            return _lib.chi2_grid_ou_mix(self.flux, grid, *self.mix, secdepth, sec_limit, out=out, cand_out=cand_out)
-        if self.gls is not None:
-            return _lib.chi2_grid_ou_baseline(self.flux, grid, *self.gls.ou, self.gls.c, self.gls.minv, secdepth, sec_limit,
-                                              out=out, coef_out=coef_out)
-        if self.ss2gls is not None:
-            return _lib.chi2_grid_ss2_baseline(self.flux, grid, *self.ss2.tables, self.ss2.c, self.ss2.minv, secdepth,
-                                               sec_limit, out=out, coef_out=coef_out)
-        if self.ss2 is not None:
-            return _lib.chi2_grid_ss2(self.flux, grid, *self.ss2, secdepth, sec_limit, out=out)
-        if self.ou is not None:
-            return _lib.chi2_grid_ou(self.flux, grid, *self.ou, secdepth, sec_limit, out=out)
-        if self.baseline is not None:
-            return _lib.chi2_grid_baseline(self.flux, self.inv_var, grid, self.baseline.g, self.baseline.minv, secdepth,
-                                           sec_limit, out=out, coef_out=coef_out)
-        if self.offset is not None:
-            return _lib.chi2_grid_offset(self.flux, self.inv_var, grid, *self.offset, secdepth, sec_limit, out=out,
-                                         offset_out=offset_out)
+        secdepth >= sec_limit: its term's reduction (offset_out: the rows' offsets; coef_out: the rows' scaled
+        coefficients; cand_out: the rows' per-candidate chi^2/2 -- each for the kinds that have them), else
+        trx_chi2_grid_weighted"""
+        if self.term is not None:
+            return self.term.reduce(self, grid, secdepth, sec_limit, out, offset_out, coef_out, cand_out)
         return _lib.chi2_grid_weighted(self.flux, self.inv_var, grid, secdepth, sec_limit, out=out)
+
 
 
 # ---------------------------------------------------------------------------------------
@@ -1315,11 +1472,11 @@ class _Scenario:
         moments = MOMENTS and (_lib.moments_wanted() or self.want_moments)
         self.moments = [] if moments else None
         flags = self._flags(is_host)
-        offsets = []       # (DATASET_OFFSETS: per branch the best draw's offsets, still on the device)
-        coefs = []         # (DATASET_BASELINES: per branch and dataset the best draw's scaled coefficients, likewise)
-        cands = []         # (DATASET_RED_NOISE, DATASET_WHITE_NOISE: per branch and dataset the best draw's per-candidate chi^2/2, likewise)
-        nodes = []         # (DATASET_T0: per branch and dataset the best draw's per-node terms, likewise)
-        probs = []         # (DATASET_OUTLIERS: per branch and dataset the best draw's model row, likewise)
+        # (the DATASET_* switches of the terms: per branch the best draw's offsets and what else its datasets' terms give
+        # back, still on the device -- wanted where an open switch is fed by a dataset of the call)
+        offsets, bests = [], []
+        want_terms = self.datasets is not None and any(_open(s) for d in self.datasets for t in (d.term, d.shift)
+                                                       if t is not None for s in t.reports)
         hists = None       # (DATASET_WARP_HIST: per branch the weight histogram of its evidence, likewise)
         if self.datasets is not None and DATASET_WARP_HIST is not None:
             if not self.philox:
@@ -1349,18 +1506,10 @@ class _Scenario:
                 self.moments.append((float(mom[1]), float(mom[2])))
                 _lib.moments_emit(mom[1], mom[2])
             best = self._best(h, idx, n)
-            if self.datasets is not None and ((DATASET_OFFSETS is not None and any(d.offset is not None for d in self.datasets))
-                                              or self._any_baseline() or self._any_mix() or self._any_shift()
-                                              or self._any_robust() or self._any_gls() or self._any_ss2gls()
-                                              or self._any_white()
-                                              or self._any_white_lin()):
-                o, c, hc, hn, mr = (self._best_offsets(model, flags, cols, best, twin, nblk) if n
-                                    else (None, None, None, None, None))
+            if want_terms:
+                o, b = self._best_offsets(model,flags, cols, best, twin, nblk) if n else (None, None)
                 offsets.append(o)
-                coefs.append(c)
-                cands.append(hc)
-                nodes.append(hn)
-                probs.append(mr)
+                bests.append(b)
             post = None
             if POSTERIOR_ROWS:
                 # the same selection on this chain's chi^2/2 values (trx_posterior_from_halfchi2; the twin branch draws
@@ -1384,289 +1533,109 @@ class _Scenario:
             if POSTERIOR_ROWS:
                 res[-1]["posterior"] = None if post is None else self._posterior_dict(post.cpu().numpy(), ncol, twin)
         if offsets:
-            self._leave_best_terms(offsets, coefs, cands, nodes, probs)
+            self._leave_best_terms(offsets, bests)
         if hists is not None:
             DATASET_WARP_HIST[getattr(_tls, "unit", None)] = torch.stack(hists).cpu().numpy().view(np.uint64)
         return res[0] if a.planet else (res[0], res[1])
 
-    def _any_baseline(self):
-        """whether a dataset's baseline terms are wanted back (DATASET_BASELINES or, for their term 0, DATASET_OFFSETS)"""
-        return ((DATASET_BASELINES is not None or DATASET_OFFSETS is not None)
-                and any(d.baseline is not None for d in self.datasets))
-
-    def _any_mix(self):
-        """whether a red_grid dataset's candidate weights are wanted back (DATASET_RED_NOISE)"""
-        return DATASET_RED_NOISE is not None and any(d.mix is not None for d in self.datasets)
-
-    def _any_shift(self):
-        """whether a t0_grid dataset's node weights are wanted back (DATASET_T0)"""
-        return DATASET_T0 is not None and any(d.shift is not None for d in self.datasets)
-
-    def _any_robust(self):
-        """whether a robust dataset's outlier probabilities are wanted back (DATASET_OUTLIERS)"""
-        return DATASET_OUTLIERS is not None and any(d.robust is not None for d in self.datasets)
-
-    def _any_white(self):
-        """whether a white_grid dataset's candidate weights are wanted back (DATASET_WHITE_NOISE)"""
-        return DATASET_WHITE_NOISE is not None and any(d.white is not None for d in self.datasets)
-
-    def _any_white_lin(self):
-        """whether a white_baseline dataset's coefficients are wanted back (DATASET_WHITE_BASELINES)"""
-        return DATASET_WHITE_BASELINES is not None and any(isinstance(d.white, _WhiteLin) for d in self.datasets)
-
-    def _any_gls(self):
-        """whether a red_baseline dataset's coefficients are wanted back (DATASET_RED_BASELINES)"""
-        return DATASET_RED_BASELINES is not None and any(d.gls is not None for d in self.datasets)
-
-    def _any_ss2gls(self):
-        """whether a red_kernel_baseline dataset's coefficients are wanted back (DATASET_RED_KERNEL_BASELINES)"""
-        return DATASET_RED_KERNEL_BASELINES is not None and any(d.ss2gls is not None for d in self.datasets)
-
-    def _leave_best_terms(self, offsets, coefs, cands, nodes, probs):
-        """the branches' best-draw offsets and baseline coefficients, from the device to DATASET_OFFSETS / DATASET_BASELINES
-        under this thread's work unit, in the call's normalisation: c_k = c~_k / sqrt(D_k); and the posterior weights of a
-        red_grid dataset's candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_RED_NOISE (NaN without a draw); and
-        those of a t0_grid dataset's nodes, softmax_j(ln pi_j - h_j), to DATASET_T0 (likewise); and the posterior outlier
-        probabilities of a robust dataset's points at that draw, _numerics.robust_responsibility on the draw's model row, to
-        DATASET_OUTLIERS (likewise); and the coefficients of a red_baseline dataset's columns at that draw,
-        c_k = c~_k / sqrt(D_k), to DATASET_RED_BASELINES (likewise); and the posterior weights of a white_grid dataset's
-        candidates at that draw, softmax_j(lnc_j - h_j), to DATASET_WHITE_NOISE (likewise); and the coefficients of a
-        white_baseline dataset's columns under each candidate at that draw with their average under those weights, to
-        DATASET_WHITE_BASELINES (likewise); and the coefficients of a red_kernel_baseline dataset's columns at that draw,
-        c_k = c~_k / sqrt(D_k), to DATASET_RED_KERNEL_BASELINES (likewise)"""
-        L = len(self.datasets)
+    def _leave_best_terms(self, offsets, bests):
+        """what the branches' best draws give back, from the device to every open DATASET_* switch of the terms under this
+        thread's work unit: per branch a list per dataset -- None, or the entry of the dataset's term (of its shift, for
+        DATASET_T0) if that feeds the switch; NaN-filled for a branch without a draw -- and for DATASET_OFFSETS an [L]
+        array, NaN in place of None"""
         unit = getattr(_tls, "unit", None)
-        if DATASET_RED_KERNEL_BASELINES is not None:
-            out = []
-            for c in coefs:
-                per = [None] * L
+        offsets = [np.full(len(self.datasets), np.nan) if o is None else o.cpu().numpy() for o in offsets]
+        # (one copy to the host of what a dataset's best draw left, whichever switches read it)
+        bests = [per if per is None else [_Best(*(v if v is None else v.cpu().numpy() for v in b)) for b in per]
+                 for per in bests]
+        for switch in _TERM_SWITCHES:
+            if not _open(switch):
+                continue
+            rows = []
+            for o, per in zip(offsets, bests):
+                row = [None] * len(self.datasets)
                 for l, d in enumerate(self.datasets):
-                    if d.ss2gls is not None:
-                        per[l] = (np.full(d.ss2.sqrt_d.size, np.nan) if c is None
-                                  else c[l].cpu().numpy().reshape(-1) / d.ss2.sqrt_d)
-                out.append(per)
-            DATASET_RED_KERNEL_BASELINES[unit] = out
-        if DATASET_WHITE_BASELINES is not None:
-            out = []
-            for c, hc in zip(coefs, cands):
-                per = [None] * L
-                for l, d in enumerate(self.datasets):
-                    if not isinstance(d.white, _WhiteLin):
-                        continue
-                    J, K = int(d.white.lnc.size), int(d.white.basis.shape[0])
-                    if c is None or hc is None:
-                        per[l] = {"coef": np.full((J, K), np.nan), "mean": np.full(K, np.nan)}
-                        continue
-                    coef = c[l].cpu().numpy().reshape(J, K)
-                    x = d.white.lnc - hc[l].cpu().numpy().reshape(-1)
-                    w = np.exp(x - np.max(x))
-                    w = w / w.sum()
-                    # (a candidate of weight 0 -- switched off, or far below -- does not enter, whatever its coefficients)
-                    per[l] = {"coef": coef, "mean": np.sum(np.where(w[:, None] > 0, w[:, None] * coef, 0.0), axis=0)}
-                out.append(per)
-            DATASET_WHITE_BASELINES[unit] = out
-        if DATASET_WHITE_NOISE is not None:
-            white = []
-            for hc in cands:
-                per = [None] * L
-                for l, d in enumerate(self.datasets):
-                    if d.white is None:
-                        continue
-                    lnc = d.white[1]
-                    if hc is None:
-                        per[l] = np.full(lnc.size, np.nan)
-                        continue
-                    x = lnc - hc[l].cpu().numpy().reshape(-1)
-                    w = np.exp(x - np.max(x))
-                    per[l] = w / w.sum()
-                white.append(per)
-            DATASET_WHITE_NOISE[unit] = white
-        if DATASET_RED_BASELINES is not None:
-            out = []
-            for c in coefs:
-                per = [None] * L
-                for l, d in enumerate(self.datasets):
-                    if d.gls is not None:
-                        per[l] = (np.full(d.gls.sqrt_d.size, np.nan) if c is None
-                                  else c[l].cpu().numpy().reshape(-1) / d.gls.sqrt_d)
-                out.append(per)
-            DATASET_RED_BASELINES[unit] = out
-        if DATASET_OUTLIERS is not None:
-            from ._numerics import robust_responsibility
-            out = []
-            for mr in probs:
-                per = [None] * L
-                for l, d in enumerate(self.datasets):
-                    if d.robust is None:
-                        continue
-                    if mr is None:
-                        per[l] = np.full(int(d.flux.numel()), np.nan)
-                        continue
-                    resid = d.flux.cpu().numpy() - mr[l].cpu().numpy().reshape(-1)
-                    per[l] = robust_responsibility(resid, d.inv_var.cpu().numpy(), *d.robust)
-                out.append(per)
-            DATASET_OUTLIERS[unit] = out
-        if DATASET_T0 is not None:
-            t0 = []
-            for hn in nodes:
-                per = [None] * L
-                for l, d in enumerate(self.datasets):
-                    if d.shift is None:
-                        continue
-                    lnpi = d.shift[1]
-                    if hn is None:
-                        per[l] = np.full(lnpi.size, np.nan)
-                        continue
-                    x = lnpi - hn[l].cpu().numpy().reshape(-1)
-                    w = np.exp(x - np.max(x))
-                    per[l] = w / w.sum()
-                t0.append(per)
-            DATASET_T0[unit] = t0
-        if DATASET_RED_NOISE is not None:
-            red = []
-            for hc in cands:
-                per = [None] * L
-                for l, d in enumerate(self.datasets):
-                    if d.mix is None:
-                        continue
-                    lnc = d.mix[3]
-                    if hc is None:
-                        per[l] = np.full(lnc.size, np.nan)
-                        continue
-                    x = lnc - hc[l].cpu().numpy().reshape(-1)
-                    w = np.exp(x - np.max(x))
-                    per[l] = w / w.sum()
-                red.append(per)
-            DATASET_RED_NOISE[unit] = red
-        offs, base = [], []
-        for o, c in zip(offsets, coefs):
-            o = np.full(L, np.nan) if o is None else o.cpu().numpy()
-            per = [None] * L
-            for l, d in enumerate(self.datasets):
-                b = d.baseline
-                if b is None:
-                    continue
-                ck = np.full(b.sqrt_d.size, np.nan) if c is None else c[l].cpu().numpy().reshape(-1) / b.sqrt_d
-                if b.has_offset:
-                    o[l] = ck[0]
-                per[l] = ck[1:] if b.has_offset else ck
-            offs.append(o)
-            base.append(per)
-        if DATASET_OFFSETS is not None:
-            DATASET_OFFSETS[unit] = offs
-        if DATASET_BASELINES is not None:
-            DATASET_BASELINES[unit] = base
+                    for t in (d.term, d.shift):
+                        if t is not None and switch in t.reports:
+                            row[l] = t.entry(switch, d, o[l], _Best() if per is None else per[l])
+                rows.append(row)
+            if switch == "DATASET_OFFSETS":
+                rows = [np.array([np.nan if v is None else v for v in row]) for row in rows]
+            globals()[switch][unit] = rows
+
+    @staticmethod
+    def _fed(t):
+        """whether a best draw is evaluated again for this term (or shift) of a dataset"""
+        return t is not None and (t.always or any(_open(s) for s in t.reports))
 
     def _best_offsets(self, model, flags, cols, best, twin, nblk):
-        """([L] device tensor and four lists per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
-        S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and None or the [1][K] device tensor of a
-        baseline dataset's scaled posterior-mean coefficients M b~ (its offset, if any, is term 0 of them; likewise for a
-        red_baseline dataset under DATASET_RED_BASELINES and a red_kernel_baseline dataset under
-        DATASET_RED_KERNEL_BASELINES; for a white_baseline dataset under DATASET_WHITE_BASELINES the
-        [1][J][K] coefficients under each candidate); and None or the
-        [1][J] device tensor of a red_grid or white_grid dataset's per-candidate chi^2/2.  The one row is evaluated again -- trx_flux_grid
-        on one row, then the dataset's reduction (_Dataset.halfchi2) with offset_out, coef_out or cand_out -- so nothing of
-        size n x L is kept.  A t0_grid dataset has the row evaluated on every node: the fourth list holds None or the [J]
-        device tensor of its per-node terms h_j, and its offset, coefficients and candidates are those of the node of
-        largest ln pi_j - h_j (on a tie the first), picked on the device.  The fifth list holds None or, for a robust
-        dataset under DATASET_OUTLIERS, the [1][T] device tensor of the draw's model row (on that node)."""
+        """([L] device tensor, a _Best per dataset) of the branch's best draw: per dataset the posterior-mean baseline offset
+        S1 / (S0 + 1 / s^2), NaN for a dataset without an offset of its own; and what its term writes through coef_out and
+        cand_out -- the coefficients only where they are read: always for a term that is always evaluated, else under the
+        term's coef_switch.  The one row is evaluated again -- trx_flux_grid on one row, then the dataset's reduction
+        (_Dataset.halfchi2) -- so nothing of size n x L is kept: always for an offset or a baseline, else where the term or the
+        shift feeds an open switch.  A t0_grid dataset has the row evaluated on every node: `nodes` holds its per-node terms
+        h_j, and its offset, coefficients and candidates are those of the node of largest ln pi_j - h_j (on a tie the first),
+        picked on the device.  `row` holds the draw's model row (on that node) where the term's entry reads it."""
         out = torch.full((len(self.datasets),), float("nan"), dtype=F64, device=self.dev)
-        coefs = [None] * len(self.datasets)
-        cands = [None] * len(self.datasets)
-        nodes = [None] * len(self.datasets)
-        rows = [None] * len(self.datasets)
+        bests = [_Best()] * len(self.datasets)
         row = cols[:nblk].index_select(1, best[:1]).contiguous()
         if twin:
             row[2] *= 2.0
             row[4] = cols[11].index_select(0, best[:1])
         flags |= _lib.EXTRA_FLAGS & _lib.FLAG_FP32_MODEL
         for l, d in enumerate(self.datasets):
-            if (d.offset is None and d.baseline is None and (d.mix is None or DATASET_RED_NOISE is None)
-                    and (d.shift is None or DATASET_T0 is None) and (d.robust is None or DATASET_OUTLIERS is None)
-                    and (d.gls is None or DATASET_RED_BASELINES is None)
-                    and (d.ss2gls is None or DATASET_RED_KERNEL_BASELINES is None)
-                    and (d.white is None or DATASET_WHITE_NOISE is None)
-                    and (not isinstance(d.white, _WhiteLin) or DATASET_WHITE_BASELINES is None)):
+            term, shift = d.term, d.shift
+            if not (self._fed(term) or self._fed(shift)):
                 continue
-            keep = d.robust is not None and DATASET_OUTLIERS is not None
+            keep = self._fed(term) and term.wants_row
             grids = []
-            stamps = [d.time] if d.shift is None else d.shift[0]
+            stamps = [d.time] if shift is None else shift.stamps
             J = len(stamps)
-            off = out[l:l + 1] if d.shift is None else torch.full((J,), float("nan"), dtype=F64, device=self.dev)
-            if d.baseline is not None:
-                coefs[l] = torch.empty((J, int(d.baseline.g.shape[0])), dtype=F64, device=self.dev)
-            if d.gls is not None and DATASET_RED_BASELINES is not None:
-                coefs[l] = torch.empty((J, int(d.gls.c.shape[0])), dtype=F64, device=self.dev)
-            if d.ss2gls is not None and DATASET_RED_KERNEL_BASELINES is not None:
-                coefs[l] = torch.empty((J, int(d.ss2.c.shape[0])), dtype=F64, device=self.dev)
-            if d.mix is not None:
-                cands[l] = torch.empty((J, int(d.mix[3].size)), dtype=F64, device=self.dev)
-            if d.white is not None:
-                cands[l] = torch.empty((J, int(d.white[1].size)), dtype=F64, device=self.dev)
-            if isinstance(d.white, _WhiteLin) and DATASET_WHITE_BASELINES is not None:
-                coefs[l] = torch.empty((J, int(d.white.lnc.size), int(d.white.basis.shape[0])), dtype=F64, device=self.dev)
+            off = out[l:l + 1] if shift is None else torch.full((J,), float("nan"), dtype=F64, device=self.dev)
+            coefs = cands = nodes = kept = None
+            if term is not None and term.coef_shape is not None and (term.always or _open(term.coef_switch)):
+                coefs = torch.empty((J,) + tuple(term.coef_shape), dtype=F64, device=self.dev)
+            if term is not None and term.lnc is not None:
+                cands = torch.empty((J, int(term.lnc.size)), dtype=F64, device=self.dev)
             hs = []
             for j, t in enumerate(stamps):
                 grid, _ = _lib.flux_grid(model, flags, t, row, d.exptime, d.nsamples, want_secdepth=False)
                 if keep:
                     grids.append(grid)
-                hs.append(d.halfchi2(grid, offset_out=off[j:j + 1], coef_out=None if coefs[l] is None else coefs[l][j:j + 1],
-                                     cand_out=None if cands[l] is None else cands[l][j:j + 1]))
-            if d.shift is not None:
-                nodes[l] = torch.cat(hs)
-                top = torch.argmax(d.shift[2] - nodes[l]).reshape(1)   # (the first of equal maxima)
+                hs.append(d.halfchi2(grid, offset_out=off[j:j + 1], coef_out=None if coefs is None else coefs[j:j + 1],
+                                     cand_out=None if cands is None else cands[j:j + 1]))
+            if shift is not None:
+                nodes = torch.cat(hs)
+                top = torch.argmax(shift.lnpi_dev - nodes).reshape(1)   # (the first of equal maxima)
                 out[l:l + 1] = off.index_select(0, top)
-                coefs[l] = None if coefs[l] is None else coefs[l].index_select(0, top)
-                cands[l] = None if cands[l] is None else cands[l].index_select(0, top)
+                coefs = None if coefs is None else coefs.index_select(0, top)
+                cands = None if cands is None else cands.index_select(0, top)
                 if keep:
-                    rows[l] = torch.cat(grids).index_select(0, top)
+                    kept = torch.cat(grids).index_select(0, top)
             elif keep:
-                rows[l] = grids[0]
-        return out, coefs, cands, nodes, rows
+                kept = grids[0]
+            bests[l] = _Best(coefs, cands, nodes, kept)
+        return out, bests
 
     def _datasets_halfchi2(self, model, flags, block):
         """sum over the datasets of the weighted chi^2/2 of every row of `block` ([n_param][n], the masked draws of one
         branch): per chunk of rows and per dataset one trx_flux_grid and the dataset's accumulating reduction
-        (_Dataset.halfchi2: trx_chi2_grid_weighted, or what marginalises its offset or baseline columns); for a dataset
+        (_Dataset.halfchi2: trx_chi2_grid_weighted, or its term's); for a dataset
         with a t0_grid, J of each on the stamps time + shift_j into a zeroed [J][rows] buffer, then one trxt_softmin_rows that
         adds -ln sum_j pi_j exp(-h_j).  The EB
         branch's secondary-eclipse rule (secdepth >= 1.5 sigma_bar -> +inf) rides in the first dataset's reduction: the
         depth does not depend on the time stamps (asked for once; with a t0_grid on the first dataset it rides every node's
         reduction: all nodes +inf give +inf).  A row's value does not depend on the chunk it falls in.
         DATASET_EVALUATION = "fused": one trx_lnl_batch_weighted per dataset over the whole block instead -- no grid, no
-        chunks; the rule rides in the first dataset's call as its sec_limit.  It has no offset form."""
+        chunks; the rule rides in the first dataset's call as its sec_limit.  It has no form for any term, nor for a shift: each
+        is refused with its own sentence."""
         if DATASET_EVALUATION not in DATASET_EVALUATIONS:
             raise ValueError("fused.DATASET_EVALUATION must be one of %s (got %r)" % (DATASET_EVALUATIONS, DATASET_EVALUATION))
-        if DATASET_EVALUATION == "fused" and any(d.offset is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: the fused kernel "
-                                      "carries no sum of w * residual; use evaluation='grid'")
-        if DATASET_EVALUATION == "fused" and any(d.baseline is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: the fused kernel "
-                                      "carries no sums of basis * residual; use evaluation='grid'")
-        if DATASET_EVALUATION == "fused" and any(d.gls is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with a red_baseline dataset is not built: the fused kernel "
-                                      "carries no recurrence along the row; use evaluation='grid'")
-        if DATASET_EVALUATION == "fused" and any(d.ss2gls is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with a red_kernel_baseline dataset is not built: the fused kernel "
-                                      "carries no recurrence along the row; use evaluation='grid'")
-        if DATASET_EVALUATION == "fused" and any(d.ou is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with a red_sigma dataset is not built: the fused kernel "
-                                      "carries no recurrence along the row; use evaluation='grid'")
-        if DATASET_EVALUATION == "fused" and any(d.ss2 is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with a red_kernel dataset is not built: the fused kernel "
-                                      "carries no recurrence along the row; use evaluation='grid'")
-        if DATASET_EVALUATION == "fused" and any(d.mix is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with a red_grid dataset is not built: the fused kernel "
-                                      "carries no recurrence along the row; use evaluation='grid'")
-        if DATASET_EVALUATION == "fused" and any(d.white is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with a white_grid dataset is not built: the fused kernel "
-                                      "carries one sum per row, not one per candidate; use evaluation='grid'")
-        if DATASET_EVALUATION == "fused" and any(d.shift is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with a t0_grid dataset is not built: the nodes' terms are folded "
-                                      "from the grid reductions; use evaluation='grid'")
-        if DATASET_EVALUATION == "fused" and any(d.robust is not None for d in self.datasets):
-            raise NotImplementedError("evaluation='fused' with an outlier_frac dataset is not built: the fused kernel "
-                                      "carries no exp and log1p per point; use evaluation='grid'")
+        refused = [t.refusal for d in self.datasets for t in (d.term, d.shift) if t is not None]
+        if DATASET_EVALUATION == "fused" and refused:
+            # (every term is a grid reduction; of several kinds in a list, the sentence of the first in the terms' ranking)
+            raise NotImplementedError(min(refused)[1])
         n = int(block.shape[1])
         h = torch.zeros(n, dtype=F64, device=self.dev)         # (0 + x = x: every reduction accumulates)
         if n == 0:
@@ -1689,7 +1658,7 @@ class _Scenario:
                 for l, d in enumerate(self.datasets):
                     nt = int(d.time.numel())
                     if d.shift is not None:
-                        stamps, lnpi = d.shift[:2]
+                        stamps, lnpi = d.shift.stamps, d.shift.lnpi
                         cand = torch.zeros((len(stamps), r1 - r0), dtype=F64, device=self.dev)
                         sec = None
                         for j, t in enumerate(stamps):
@@ -1706,7 +1675,7 @@ class _Scenario:
         with _stats_lock:
             # (the masked draws once, every (draw, time stamp) cell of every dataset)
             _lib.STATS["rows"] += n
-            nodes = [1 if d.shift is None else len(d.shift[0]) for d in self.datasets]
+            nodes = [1 if d.shift is None else len(d.shift.stamps) for d in self.datasets]
             _lib.STATS["cells"] += n * sum(j * int(d.time.numel()) for j, d in zip(nodes, self.datasets))
             _lib.STATS["launches"] += sum(nodes) * chunks
         return h

@@ -51,6 +51,14 @@ _TARGET_CALLS = (
     ("BTP", ("BTP",), 12, 2), ("BEB", ("BEB", "BEBx2P"), 13, 2),
 )
 
+# (Datasets flag, wording) of what evaluation="fused" refuses, in the order in which a list of several kinds is answered
+_FUSED_REFUSALS = (
+    ("has_offsets", "an offset_sigma"), ("has_baselines", "a baseline"), ("has_red_baselines", "a red_baseline"),
+    ("has_red_kernel_baselines", "a red_kernel_baseline"), ("has_red_noise", "a red_sigma or red_grid"),
+    ("has_t0_grids", "a t0_grid"), ("has_white_grids", "a white_grid"), ("has_white_baselines", "a white_baseline"),
+    ("has_outliers", "an outlier_frac"),
+)
+
 
 def _model_block(is_tp, comp, c):
     """(model, flags, [n_param][n] host block) of the light curves of n parameter sets of one kind -- is_tp: planets
@@ -282,26 +290,9 @@ class target:
         the length of the pass."""
         from . import fused
         units, n_scen = self._prepare(ds, None, None, P_orb, **kw)
-        if ds.has_offsets and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with an offset_sigma dataset is not built: use evaluation='grid'")
-        if ds.has_baselines and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with a baseline dataset is not built: use evaluation='grid'")
-        if ds.has_red_baselines and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with a red_baseline dataset is not built: use evaluation='grid'")
-        if ds.has_red_kernel_baselines and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with a red_kernel_baseline dataset is not built: use "
-                                      "evaluation='grid'")
-        if ds.has_red_noise and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with a red_sigma or red_grid dataset is not built: use "
-                                      "evaluation='grid'")
-        if ds.has_t0_grids and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with a t0_grid dataset is not built: use evaluation='grid'")
-        if ds.has_white_grids and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with a white_grid dataset is not built: use evaluation='grid'")
-        if ds.has_white_baselines and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with a white_baseline dataset is not built: use evaluation='grid'")
-        if ds.has_outliers and evaluation == "fused":
-            raise NotImplementedError("evaluation='fused' with an outlier_frac dataset is not built: use evaluation='grid'")
+        for flag, what in _FUSED_REFUSALS:
+            if getattr(ds, flag) and evaluation == "fused":
+                raise NotImplementedError("evaluation='fused' with %s dataset is not built: use evaluation='grid'" % what)
         with fused.switches(POSTERIOR_ROWS=n_samples, DATASET_EVALUATION=evaluation, **dataset_switches):
             rows = sharding.run_units(units, verbose=verbose, as_rows=True)
         return units, rows, n_scen
@@ -527,117 +518,81 @@ class target:
         self._finish(units, rows, n_scen, layout=sharding.last_layout)
         share = self.stars["fluxratio"].to_numpy()[self.stars["tdepth"].to_numpy() > 0]
         self.sigma_ref = ds.renorm(share[0]).sigma_ref if share.size else ds.sigma_ref
-        self.dataset_offsets = None
-        if best_offsets is not None:
-            # (a call's offsets are in its star's normalisation: flux' = (flux - (1 - fr)) / fr, so c = fr c')
-            table = np.full((n_scen, len(ds)), np.nan)
-            for k, u in enumerate(sharding.as_units(units)):
-                for i, c in enumerate(best_offsets.get(k, ())):
-                    table[u.first_row + i] = c * share[u.group[1]]
-            table[~np.isfinite(self.lnZ)] = np.nan
-            self.dataset_offsets = table
-        self.dataset_baselines = None
-        if best_baselines is not None:
-            # (c_k multiplies a column that is left alone, so it scales as the flux does: c = fr c')
-            sizes = [None if s.baseline is None else s.baseline.shape[0] for s in ds.sets]
-            rows_ = [[None if m is None else np.full(m, np.nan) for m in sizes] for _ in range(n_scen)]
-            for k, u in enumerate(sharding.as_units(units)):
-                for i, per in enumerate(best_baselines.get(k, ())):
-                    if np.isfinite(self.lnZ[u.first_row + i]):
-                        rows_[u.first_row + i] = [None if c is None else c * share[u.group[1]] for c in per]
-            self.dataset_baselines = rows_
-        self.dataset_red_noise = None
-        if best_red is not None:
-            # (the weights are pure numbers: the same in every star's normalisation)
-            def entry(s, w=None):
-                if s.red_grid is None:
-                    return None
-                return {"grid": s.red_grid.copy(), "weight": np.full(s.red_grid.shape[0], np.nan) if w is None else w}
-            rows_ = [[entry(s) for s in ds.sets] for _ in range(n_scen)]
-            for k, u in enumerate(sharding.as_units(units)):
-                for i, per in enumerate(best_red.get(k, ())):
-                    if np.isfinite(self.lnZ[u.first_row + i]):
-                        rows_[u.first_row + i] = [entry(s, w) for s, w in zip(ds.sets, per)]
-            self.dataset_red_noise = rows_
-        self.dataset_t0 = None
-        if best_t0 is not None:
-            # (shifts are times and the weights pure numbers: the same in every star's normalisation)
-            def node(g, w=None):
-                if g is None:
-                    return None
-                w = np.full(g.shape[0], np.nan) if w is None else w
-                return {"shift": g[:, 0].copy(), "weight": w, "mean": float(np.sum(w * g[:, 0]))}
-            rows_ = [[node(g) for g in ds.t0_grids] for _ in range(n_scen)]
-            for k, u in enumerate(sharding.as_units(units)):
-                for i, per in enumerate(best_t0.get(k, ())):
-                    if np.isfinite(self.lnZ[u.first_row + i]):
-                        rows_[u.first_row + i] = [node(g, w) for g, w in zip(ds.t0_grids, per)]
-            self.dataset_t0 = rows_
-        self.dataset_outliers = None
-        if best_outliers is not None:
-            # (only (flux - model) / sigma enters: the same in every star's normalisation)
-            def points(s, o, p=None):
-                if o is None:
-                    return None
-                return {"frac": o[0], "scale": o[1], "prob": np.full(s.time.size, np.nan) if p is None else p}
-            rows_ = [[points(s, o) for s, o in zip(ds.sets, ds.outliers)] for _ in range(n_scen)]
-            for k, u in enumerate(sharding.as_units(units)):
-                for i, per in enumerate(best_outliers.get(k, ())):
-                    if np.isfinite(self.lnZ[u.first_row + i]):
-                        rows_[u.first_row + i] = [points(s, o, p) for s, o, p in zip(ds.sets, ds.outliers, per)]
-            self.dataset_outliers = rows_
-        self.dataset_red_baselines = None
-        if best_gls is not None:
-            # (as dataset_baselines: c_k multiplies a column that is left alone, so c = fr c')
-            sizes = [None if p is None else p[0].shape[0] for p in ds.red_baselines]
-            rows_ = [[None if m is None else np.full(m, np.nan) for m in sizes] for _ in range(n_scen)]
-            for k, u in enumerate(sharding.as_units(units)):
-                for i, per in enumerate(best_gls.get(k, ())):
-                    if np.isfinite(self.lnZ[u.first_row + i]):
-                        rows_[u.first_row + i] = [None if c is None else c * share[u.group[1]] for c in per]
-            self.dataset_red_baselines = rows_
-        self.dataset_white_noise = None
-        if best_white is not None:
-            # (the weights are pure numbers: the same in every star's normalisation; the grid is as validated, in the units
-            # given)
-            def cand(g, w=None):
-                if g is None:
-                    return None
-                return {"grid": g.copy(), "weight": np.full(g.shape[0], np.nan) if w is None else w}
-            rows_ = [[cand(g) for g in ds.white_grids] for _ in range(n_scen)]
-            for k, u in enumerate(sharding.as_units(units)):
-                for i, per in enumerate(best_white.get(k, ())):
-                    if np.isfinite(self.lnZ[u.first_row + i]):
-                        rows_[u.first_row + i] = [cand(g, w) for g, w in zip(ds.white_grids, per)]
-            self.dataset_white_noise = rows_
-        self.dataset_white_baselines = None
-        if best_lin is not None:
-            # (as dataset_baselines: c_k multiplies a column that is left alone, so c = fr c')
-            def terms(g, p, c=None, fr=1.0):
-                if p is None:
-                    return None
-                J, K = g.shape[0], p[0].shape[0]
-                if c is None:
-                    return {"coef": np.full((J, K), np.nan), "mean": np.full(K, np.nan)}
-                return {"coef": c["coef"] * fr, "mean": c["mean"] * fr}
-            pairs = list(zip(ds.white_grids, ds.white_baselines))
-            rows_ = [[terms(g, p) for g, p in pairs] for _ in range(n_scen)]
-            for k, u in enumerate(sharding.as_units(units)):
-                for i, per in enumerate(best_lin.get(k, ())):
-                    if np.isfinite(self.lnZ[u.first_row + i]):
-                        rows_[u.first_row + i] = [terms(g, p, c, share[u.group[1]]) for (g, p), c in zip(pairs, per)]
-            self.dataset_white_baselines = rows_
-        self.dataset_red_kernel_baselines = None
-        if best_ss2gls is not None:
-            # (as dataset_red_baselines: c_k multiplies a column that is left alone, so c = fr c')
-            sizes = [None if p is None else p[0].shape[0] for p in ds.red_kernel_baselines]
-            rows_ = [[None if m is None else np.full(m, np.nan) for m in sizes] for _ in range(n_scen)]
-            for k, u in enumerate(sharding.as_units(units)):
-                for i, per in enumerate(best_ss2gls.get(k, ())):
-                    if np.isfinite(self.lnZ[u.first_row + i]):
-                        rows_[u.first_row + i] = [None if c is None else c * share[u.group[1]] for c in per]
-            self.dataset_red_kernel_baselines = rows_
+
+        # (a call's offsets are in its star's normalisation: flux' = (flux - (1 - fr)) / fr, so c = fr c'; and c_k multiplies
+        # a column that is left alone, so it scales as the flux does: c = fr c')
+        def scaled(u, per):
+            return [None if c is None else c * share[u.group[1]] for c in per]
+
+        def blank_coefs(sizes):
+            return lambda: [None if m is None else np.full(m, np.nan) for m in sizes]
+
+        table = self._scatter_best(units, best_offsets, lambda: np.full(len(ds), np.nan),
+                                   lambda u, c: c * share[u.group[1]])
+        self.dataset_offsets = None if table is None else np.array(table).reshape(n_scen, len(ds))
+        self.dataset_baselines = self._scatter_best(
+            units, best_baselines, blank_coefs([None if s.baseline is None else s.baseline.shape[0] for s in ds.sets]), scaled)
+        self.dataset_red_baselines = self._scatter_best(
+            units, best_gls, blank_coefs([None if p is None else p[0].shape[0] for p in ds.red_baselines]), scaled)
+        self.dataset_red_kernel_baselines = self._scatter_best(
+            units, best_ss2gls, blank_coefs([None if p is None else p[0].shape[0] for p in ds.red_kernel_baselines]), scaled)
+
+        # (the weights are pure numbers: the same in every star's normalisation; a white_grid is as validated, in the units
+        # given)
+        def cand(g, w=None):
+            if g is None:
+                return None
+            return {"grid": g.copy(), "weight": np.full(g.shape[0], np.nan) if w is None else w}
+        red_grids = [s.red_grid for s in ds.sets]
+        self.dataset_red_noise = self._scatter_best(units, best_red, lambda: [cand(g) for g in red_grids],
+                                                    lambda u, per: [cand(g, w) for g, w in zip(red_grids, per)])
+        self.dataset_white_noise = self._scatter_best(units, best_white, lambda: [cand(g) for g in ds.white_grids],
+                                                      lambda u, per: [cand(g, w) for g, w in zip(ds.white_grids, per)])
+
+        # (shifts are times and the weights pure numbers: the same in every star's normalisation)
+        def node(g, w=None):
+            if g is None:
+                return None
+            w = np.full(g.shape[0], np.nan) if w is None else w
+            return {"shift": g[:, 0].copy(), "weight": w, "mean": float(np.sum(w * g[:, 0]))}
+        self.dataset_t0 = self._scatter_best(units, best_t0, lambda: [node(g) for g in ds.t0_grids],
+                                             lambda u, per: [node(g, w) for g, w in zip(ds.t0_grids, per)])
+
+        # (only (flux - model) / sigma enters: the same in every star's normalisation)
+        def points(s, o, p=None):
+            if o is None:
+                return None
+            return {"frac": o[0], "scale": o[1], "prob": np.full(s.time.size, np.nan) if p is None else p}
+        robust = list(zip(ds.sets, ds.outliers))
+        self.dataset_outliers = self._scatter_best(units, best_outliers, lambda: [points(s, o) for s, o in robust],
+                                                   lambda u, per: [points(s, o, p) for (s, o), p in zip(robust, per)])
+
+        # (as dataset_baselines: c = fr c')
+        def terms(g, p, c=None, fr=1.0):
+            if p is None:
+                return None
+            J, K = g.shape[0], p[0].shape[0]
+            if c is None:
+                return {"coef": np.full((J, K), np.nan), "mean": np.full(K, np.nan)}
+            return {"coef": c["coef"] * fr, "mean": c["mean"] * fr}
+        pairs = list(zip(ds.white_grids, ds.white_baselines))
+        self.dataset_white_baselines = self._scatter_best(
+            units, best_lin, lambda: [terms(g, p) for g, p in pairs],
+            lambda u, per: [terms(g, p, c, share[u.group[1]]) for (g, p), c in zip(pairs, per)])
         return
+
+    def _scatter_best(self, units, best, blank, fill):
+        """what a DATASET_* switch collected (`best`: {work unit: per branch, what the datasets' terms left}) as a list per
+        scenario row: blank() for a row whose unit left nothing or whose lnZ is not finite, else fill(unit, the branch's
+        entries); None for a switch that was not opened"""
+        if best is None:
+            return None
+        rows = [blank() for _ in range(len(self.lnZ))]
+        for k, u in enumerate(sharding.as_units(units)):
+            for i, per in enumerate(best.get(k, ())):
+                if np.isfinite(self.lnZ[u.first_row + i]):
+                    rows[u.first_row + i] = fill(u, per)
+        return rows
 
     def calc_probs_refined(self, time, flux_0, flux_err_0: float, P_orb, n_adapt: int = 2, N_adapt: int = None,
                            n_samples: int = 0, alpha: float = 0.5, floor: float = 0.1, **calc_probs_kwargs):
